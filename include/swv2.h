@@ -93,7 +93,8 @@ typedef struct swv2_attn_args {
                                  the two-phase backward with the softmax statistics read from LDS instead of riding in the
                                  MFMA operands; SWV2_ATTN_BWD_TWO_PHASE = the barrier-separated two-phase backward of csrc/attn.hip
                                  (statistics in the operands) where csrc/attn_bwd_stream.hip would run (176-row layout, 16-wide
-                                 head slots, no table): same arithmetic, bit-identical d(qkv) */
+                                 head slots, no table): same arithmetic, bit-identical d(qkv).  None applies at head_dim 256:
+                                 csrc/attn_d256.hip is the only kernel pair there */
     void* dbias_ws;           /* bwd, optional scratch of dbias_ws_bytes >= swv2_attn_dbias_ws_bytes(heads, L, max_chunks): the
                                  workgroups store their d bias tables there and one more launch sums them into dbias (in a
                                  fixed order); NULL / too small = 31 K float atomics per workgroup instead */

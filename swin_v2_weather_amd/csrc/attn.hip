@@ -1228,7 +1228,12 @@ extern "C" int swv2_attn_geometry(int L, int head_dim, int* Lp, int* DP) {
     // head dims are padded to 16, 32, 64, 96 or 128 columns (the yaml default 768 / 8 = 96 runs unpadded)
     if (head_dim <= 16) DK = 1; else if (head_dim <= 32) DK = 2; else if (head_dim <= 64) DK = 4; else if (head_dim <= 96) DK = 6;
     else if (head_dim <= 128) DK = 8;
-    SWV2_CHECK_ARG(LT && DK, "attention: unsupported window area L=%d (<=176) or head_dim=%d (<=128)", L, head_dim);
+    // 256-channel heads (embed 2048 / 8 heads): exactly 256, unpadded, in the 176-row window layout only (attn_d256.hip)
+    else if (head_dim == 256) {
+        SWV2_CHECK_ARG(LT == 11, "attention: head_dim=256 needs a window of 65 - 176 tokens (window area L=%d)", L);
+        DK = 16;
+    }
+    SWV2_CHECK_ARG(LT && DK, "attention: unsupported window area L=%d (<=176) or head_dim=%d (<=128, or 256)", L, head_dim);
     if (Lp) *Lp = 16 * LT;
     if (DP) *DP = 16 * DK;
     return SWV2_OK;
@@ -1305,6 +1310,10 @@ int swv2_attn2_fwd(const swv2_attn_args* a, int Lp, int DP, void* stream);
 int swv2_attn_fwd_wide(const swv2_attn_args* a, int Lp, int DP, void* stream);
 int swv2_attn_bwd_wide(const swv2_attn_args* a, int Lp, int DP, void* stream);
 
+// the kernel pair for 256-channel heads of attn_d256.hip: 0 / negative = handled (ok / error), 1 = another layout
+int swv2_attn_fwd_d256(const swv2_attn_args* a, int Lp, int DP, void* stream);
+int swv2_attn_bwd_d256(const swv2_attn_args* a, int Lp, int DP, void* stream);
+
 // the streamed-dQ backward of attn_bwd_stream.hip (176-row layout, 16-wide head slots, no table): 0 / negative = handled, 1 = not covered
 int swv2_attn_bwd_stream(const swv2_attn_args* a, int Lp, int DP, void* stream);
 
@@ -1324,14 +1333,18 @@ extern "C" int swv2_attn_fwd_regime(int L, int head_dim, int has_bias, int dbg) 
 extern "C" int swv2_attn_fwd(const swv2_attn_args* a, void* stream) {
     int rc0 = check_args(a, false);
     if (rc0) return rc0;
-    if (!(a->dbg & SWV2_ATTN_FIRST_GEN)) {
+    {
         int Lp2, DP2;
         int rc2 = swv2_attn_geometry(a->L, a->head_dim, &Lp2, &DP2);
         if (rc2) return rc2;
-        rc2 = swv2_attn2_fwd(a, Lp2, DP2, stream);
+        rc2 = swv2_attn_fwd_d256(a, Lp2, DP2, stream);           // the only kernel at this width: SWV2_ATTN_FIRST_GEN does not apply
         if (rc2 <= 0) return rc2;
-        rc2 = swv2_attn_fwd_wide(a, Lp2, DP2, stream);
-        if (rc2 <= 0) return rc2;
+        if (!(a->dbg & SWV2_ATTN_FIRST_GEN)) {
+            rc2 = swv2_attn2_fwd(a, Lp2, DP2, stream);
+            if (rc2 <= 0) return rc2;
+            rc2 = swv2_attn_fwd_wide(a, Lp2, DP2, stream);
+            if (rc2 <= 0) return rc2;
+        }
     }
     SWV2_ATTN_DISPATCH(launch_fwd)
 }
@@ -1343,6 +1356,8 @@ extern "C" int swv2_attn_bwd(const swv2_attn_args* a, void* stream) {
         int Lp2, DP2;
         int rc2 = swv2_attn_geometry(a->L, a->head_dim, &Lp2, &DP2);
         if (rc2) return rc2;
+        rc2 = swv2_attn_bwd_d256(a, Lp2, DP2, stream);
+        if (rc2 <= 0) return rc2;
         rc2 = swv2_attn_bwd_wide(a, Lp2, DP2, stream);
         if (rc2 <= 0) return rc2;
         rc2 = swv2_attn_bwd_stream(a, Lp2, DP2, stream);

@@ -197,9 +197,10 @@ __device__ __forceinline__ void heads_item(const EpiDesc& d, const float* st, in
         }
     }
 }
-// DP = 96 / 128 (head dims 65 .. 128): a wave's 64-column sub-tile is PART of a head, so the squared norm cannot be finished
-// here.  Each half adds its partial sum of squares into rnorm (zeroed by the caller; two addends -> order-independent)
-// and writes the UN-normalised bf16 values; swv2_qk_normalize then turns the sums into 1 / |.| and rescales q, k in
+// DP = 96 / 128 / 256 (head dims 65 .. 128, 256): a wave's 64-column sub-tile is PART of a head, so the squared norm cannot be finished
+// here.  Each 64-column piece adds its partial sum of squares into rnorm (zeroed by the caller) by a float atomic: two
+// addends per row at DP = 128 (order-independent, so bit-reproducible), up to six at 96 and four at 256 (the order, and so the
+// last bit of the sum and of q^ / k^, varies from run to run).  It writes the UN-normalised bf16 values; swv2_qk_normalize then turns the sums into 1 / |.| and rescales q, k in
 // place (one extra bf16 rounding of q^, k^ compared with the narrow-head epilogue).  lane = (row, 16-column quarter).
 // PB: the lane's 16 bias values were loaded by the caller (once per tile: the wide kernels; a load inside this function sits
 // under a condition and makes the compiler wait for every earlier store with s_waitcnt vmcnt(0)); zeros without a bias
@@ -225,7 +226,8 @@ __device__ __forceinline__ void heads_item_wide(const EpiDesc& d, const float* s
         }
     }
     if (NORM) {
-        if (DPv == 128) {                 // the wave's 64 columns lie in ONE head: one addend per row
+        if (DPv >= 128) {                 // the wave's 64 columns lie in ONE head: one addend per row (four per row at DP = 256:
+                                          // their order, and so the last bit of the sum, is not fixed)
             ss += __shfl_xor(ss, 16);
             ss += __shfl_xor(ss, 32);
             if (in && qd == 0 && part < 2 && valid) atomicAdd(d.aux_out + (((long)bw * h + hd) * 2 + part) * Lp + t, ss);
@@ -1613,8 +1615,8 @@ extern "C" int swv2_linear(const swv2_operand* a, const void* w_bf16, const swv2
     if (e->kind == SWV2_EPI_F32 || e->kind == SWV2_EPI_F32_ACC)
         SWV2_CHECK_ARG(e->ld % 4 == 0 && e->ld >= N, "swv2_linear: output pitch %ld must be a multiple of 4 and >= N", e->ld);
     if (e->kind == SWV2_EPI_QKV_HEADS || e->kind == SWV2_EPI_HEADS)
-        SWV2_CHECK_ARG((e->p[3] == 16 || e->p[3] == 32 || e->p[3] == 64 || e->p[3] == 96 || e->p[3] == 128) && N % e->p[3] == 0 && e->p[0] > 0 && e->p[2] > 0,
-                       "swv2_linear: head-split epilogue needs DP in {16,32,64,96,128} and N a multiple of DP (DP=%d N=%d)", e->p[3], N);
+        SWV2_CHECK_ARG((e->p[3] == 16 || e->p[3] == 32 || e->p[3] == 64 || e->p[3] == 96 || e->p[3] == 128 || e->p[3] == 256) && N % e->p[3] == 0 && e->p[0] > 0 && e->p[2] > 0,
+                       "swv2_linear: head-split epilogue needs DP in {16,32,64,96,128,256} and N a multiple of DP (DP=%d N=%d)", e->p[3], N);
     if (e->kind == SWV2_EPI_UNPATCH || e->kind == SWV2_EPI_UNPATCH_LOSS)
         SWV2_CHECK_ARG(N == e->p[0] * 16, "swv2_linear: un-patchify needs N == Cout*16");
     if (e->kind == SWV2_EPI_UNPATCH_LOSS) {

@@ -260,7 +260,7 @@ template <> struct ALoad<A_BF16_GELU> {
     __device__ __forceinline__ uint4 chunk(int m, int k0) const { return cvt(raw(m, k0)); }
 };
 // head-major window layout [Bw][h][S][Lp][DP] -> logical row m = bw*Lp + t, logical k = (part*h + head)*DP + j
-// (head dim padded to DP in {16, 32, 64, 96, 128}; the matching weights are padded by swv2_prep_weight).
+// (head dim padded to DP in {16, 32, 64, 96, 128}, or exactly 256; the matching weights are padded by swv2_prep_weight).
 // p0 = heads, p2 = Lp, p3 = DP ; ld = number of parts S (1 for oh, 3 for dqkvh)
 template <> struct ALoad<A_HEADS> {
     static constexpr bool ROW_FASTEST = false;
@@ -382,7 +382,7 @@ ALoad<AK> make_loader(const swv2_operand* o) {
     l.d.mg0 = l.d.mg1 = l.d.mg2 = 0;
     if (AK == A_HEADS) {
         l.d.mg0 = fdiv_magic(o->p[2]); l.d.mg1 = fdiv_magic(o->p[0]);
-        l.d.p1 = o->p[3] == 16 ? 4 : o->p[3] == 32 ? 5 : o->p[3] == 64 ? 6 : o->p[3] == 128 ? 7 : -1;
+        l.d.p1 = o->p[3] == 16 ? 4 : o->p[3] == 32 ? 5 : o->p[3] == 64 ? 6 : o->p[3] == 128 ? 7 : o->p[3] == 256 ? 8 : -1;
         l.d.mg2 = fdiv_magic(o->p[3]);
     }
     if (AK == A_PATCH) { l.d.mg0 = fdiv_magic((o->p[1] / 4) * (o->p[2] / 4)); l.d.mg1 = fdiv_magic(o->p[2] / 4); }
@@ -403,7 +403,7 @@ int check_operand(const swv2_operand* o, const char* who) {
         SWV2_CHECK_ARG(o->aux0 && o->p[0] > 0 && o->p[2] * 16 >= o->cols && o->cols % 16 == 0 && !o->rowidx,
                        "%s: scaled operand needs aux0, rows per sample p[0] > 0, p[2] >= cols / 16 groups, no gather", who);
     if (o->kind == SWV2_OP_HEADS)
-        SWV2_CHECK_ARG(o->p[3] == 16 || o->p[3] == 32 || o->p[3] == 64 || o->p[3] == 96 || o->p[3] == 128, "%s: head pad %d not in {16,32,64,96,128}", who, o->p[3]);
+        SWV2_CHECK_ARG(o->p[3] == 16 || o->p[3] == 32 || o->p[3] == 64 || o->p[3] == 96 || o->p[3] == 128 || o->p[3] == 256, "%s: head pad %d not in {16,32,64,96,128,256}", who, o->p[3]);
     if (o->kind == SWV2_OP_PATCH)
         SWV2_CHECK_ARG(o->p[1] % 4 == 0 && o->p[2] % 4 == 0 && o->cols == o->p[0] * 16, "%s: bad patch geometry", who);
     if (o->kind == SWV2_OP_MERGE_LN)

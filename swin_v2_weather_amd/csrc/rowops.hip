@@ -563,7 +563,7 @@ void launch_ln_bwd(const swv2_ln_args* a, hipStream_t st) {
 
 int ln_check(const swv2_ln_args* a, bool bwd) {
     SWV2_CHECK_ARG(a && a->a && a->gamma && a->mean && a->rstd, "ln_residual: null pointer");
-    SWV2_CHECK_ARG(a->M > 0 && a->C > 0 && a->C % 8 == 0 && a->C <= 1024, "ln_residual: C=%d must be a multiple of 8, <= 1024", a->C);
+    SWV2_CHECK_ARG(a->M > 0 && a->C > 0 && a->C % 8 == 0 && a->C <= 2048, "ln_residual: C=%d must be a multiple of 8, <= 2048", a->C);
     SWV2_CHECK_ARG(a->rows_per_sample > 0, "ln_residual: rows_per_sample must be positive");
     if (bwd) SWV2_CHECK_ARG(a->dy && a->da && a->dgamma && a->dbeta && a->ws, "ln_residual_bwd: null gradient / workspace pointer");
     else SWV2_CHECK_ARG(a->y && a->beta, "ln_residual_fwd: null output pointer");
@@ -589,7 +589,8 @@ void swv2_launch_ln_partials_reduce(const float* ws, float* dgamma, float* dbeta
     if (chunks <= 16) FN<16, 1>(a, st);                              \
     else if (chunks <= 32) FN<32, 1>(a, st);                         \
     else if (chunks <= 64) FN<64, 1>(a, st);                         \
-    else FN<64, 2>(a, st);
+    else if (chunks <= 128) FN<64, 2>(a, st);                        \
+    else FN<64, 4>(a, st);
 
 extern "C" int swv2_ln_residual_fwd(const swv2_ln_args* a, void* stream) {
     int rc = ln_check(a, false);
@@ -610,7 +611,7 @@ extern "C" int swv2_ln_residual_bwd(const swv2_ln_args* a, void* stream) {
 }
 
 // ------------------------------------------------------------------------------------------------
-// second half of the q / k normalisation for 128-wide padded heads (the GEMM epilogue leaves the squared norms in rnorm
+// second half of the q / k normalisation for the 96- / 128- / 256-wide head layouts (the GEMM epilogue leaves the squared norms in rnorm
 // and the un-normalised values in qkvh, see heads_item_wide in gemm.hip): rn = 1 / max(|.|, 1e-12) (F.normalize's eps,
 // swinv2_global.py:300-304), q, k rows rescaled in place, rnorm <- rn (0 on padded rows).  16 lanes per 128-wide row.
 // ------------------------------------------------------------------------------------------------
@@ -618,7 +619,7 @@ namespace {
 __global__ __launch_bounds__(256) void qk_normalize_kernel(uint16_t* __restrict__ qkvh, float* __restrict__ rnorm, long rows,
                                                            int h, int Lp, int L, int DP) {
     const long i = (long)blockIdx.x * 16 + (threadIdx.x >> 4);        // row index over [Bw][h][2][Lp]
-    const int c = threadIdx.x & 15;                                   // 16-byte chunk of the row (DP / 8 of them: 12 or 16)
+    const int c = threadIdx.x & 15;                                   // 16-byte chunk of the row (DP / 8 of them: 12, 16 or 32)
     if (i >= rows) return;
     const int t = (int)(i % Lp);
     const long bh2 = i / Lp;
@@ -626,8 +627,8 @@ __global__ __launch_bounds__(256) void qk_normalize_kernel(uint16_t* __restrict_
     const long bh = bh2 >> 1;
     const float ss = rnorm[i];
     const float rn = (t < L) ? 1.f / fmaxf(sqrtf(ss), 1e-12f) : 0.f;
-    if (c * 8 < DP) {
-        uint16_t* row = qkvh + ((bh * 3 + part) * Lp + t) * DP + c * 8;
+    for (int cc = c; cc * 8 < DP; cc += 16) {                       // one chunk per lane at DP <= 128, two at 256
+        uint16_t* row = qkvh + ((bh * 3 + part) * Lp + t) * DP + cc * 8;
         float v[8];
         unpack8f(*(const uint4*)row, v);
 #pragma unroll
@@ -640,7 +641,7 @@ __global__ __launch_bounds__(256) void qk_normalize_kernel(uint16_t* __restrict_
 
 extern "C" int swv2_qk_normalize(void* qkvh, float* rnorm, int Bw, int heads, int Lp, int L, int DP, void* stream) {
     SWV2_CHECK_ARG(qkvh && rnorm && Bw > 0 && heads > 0 && Lp > 0 && L > 0 && L <= Lp, "swv2_qk_normalize: bad argument");
-    SWV2_CHECK_ARG(DP == 96 || DP == 128, "swv2_qk_normalize: only the 96- and 128-wide head layouts need this pass (DP=%d)", DP);
+    SWV2_CHECK_ARG(DP == 96 || DP == 128 || DP == 256, "swv2_qk_normalize: only the 96-, 128- and 256-wide head layouts need this pass (DP=%d)", DP);
     const long rows = (long)Bw * heads * 2 * Lp;
     hipLaunchKernelGGL(qk_normalize_kernel, dim3((unsigned)cdiv(rows, 16)), dim3(256), 0, (hipStream_t)stream, (uint16_t*)qkvh,
                        rnorm, rows, heads, Lp, L, DP);
