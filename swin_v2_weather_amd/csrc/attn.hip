@@ -274,12 +274,8 @@ __global__ __launch_bounds__(64 * LT) void attn_fwd_kernel(
 }
 
 // Issue priority that falls with a wave's progress through phase 1 (see attn_bwd_stream.hip: the SIMD arbiter serves its oldest wave first, the
-// youngest then finishes the phase alone with nothing to cover its latencies); reset to 0 behind the phase.  -DSWV2_ATTN1_NO_PRIO: A/B builds.
-#ifndef SWV2_ATTN1_NO_PRIO
+// youngest then finishes the phase alone with nothing to cover its latencies); reset to 0 behind the phase.
 #define SWV2_P1PRIO(n) __builtin_amdgcn_s_setprio(n)
-#else
-#define SWV2_P1PRIO(n) do {} while (0)
-#endif
 #ifdef SWV2_ATTN1_STAMPS          // diagnostic build (tools/probe_attn1_stamps.py): per-phase s_memtime sums of every wave 0
 __device__ unsigned long long attn1_stamps[512 * 8];
 __device__ unsigned long long attn1_win[64 * 128];        // wave 8 of the first 64 workgroups of head 0: s_memtime at the end of every window
@@ -305,10 +301,8 @@ __device__ unsigned long long attn1_win[64 * 128];        // wave 8 of the first
 //            no cross-wave reduction -- then the normalisation backward and a coalesced store.
 // The CPB bias (log2 domain, bf16, [key][q]) of the workgroup's head sits in LDS when it fits (BIAS_LDS), its
 // gradient accumulates in registers (wave = key tile owns 16 x Lp entries) across all windows of the workgroup.
-// TPW = key / query tiles per wave.  TPW = 2 (used without bias): 6 waves own 11 tiles, the Q / dO / statistics
-// fragments of a step are read once for both key tiles, and the dcos image is kept compact ([L rounded up to 4 (+ one
-// zero block)][Lp + 4]) so that TWO workgroups fit one CU's LDS (2 x 77 KB): 12 waves = 3 per SIMD, and one workgroup's
-// barriers / staging overlap the other's MFMA + softmax work.  TPW = 1 is the one-tile-per-wave layout (11 waves).
+// One wave per key tile in phase 1 and per query tile in phase 2 (11 waves at the 176-token window).  The loops over a wave's tiles
+// (TPW = 1) run once; they stay loops because the compiler schedules the flattened form differently.
 // AUGP (16- and 32-wide heads, no bias, one key tile per wave; described for 16, the 32-wide variant at `QP` below): the softmax statistics, the padded-key flag and the shift mask ride in
 // the unused half of K = 32 MFMA operands, so phase 1 reads no lse / delta rows and has no per-element selects: two LDS reads and
 // ~6 vector instructions less per 16 x 16 tile in the kernel's LDS-bound phase.  Construction (head dim 16 fills k = 0 .. 15 of
@@ -322,8 +316,8 @@ __device__ unsigned long long attn1_win[64 * 128];        // wave 8 of the first
 //   so  S' = Q_aug K_aug^T = cos - lse / (sigma log2 e) + [pad] + [mask]  and  dP' = dO_aug V_aug^T = dP - delta  come out of the
 //   matrix pipe, and the softmax backward is  p = exp2(S' sigma log2 e),  dS = p dP'.  The reference's mask (-100 where the query's
 //   and the key's regions differ, swinv2_global.py:403-424) is bilinear in the two region flags, hence two slots.
-template <int LT, int DK, bool HAS_BIAS, int LFIX, int TPW, bool AUGP = false>
-__global__ __launch_bounds__(64 * ((LT + TPW - 1) / TPW)) void attn_bwd_kernel(
+template <int LT, int DK, bool HAS_BIAS, int LFIX, bool AUGP = false>
+__global__ __launch_bounds__(64 * LT) void attn_bwd_kernel(
     const uint16_t* __restrict__ qkvh, const float* __restrict__ logit_scale, const float* __restrict__ bias,
     const uint16_t* __restrict__ bimg,     // swv2_attn_pack_bias backward part ([h][Lp][Lp + 4] bf16) or null
     const uint16_t* __restrict__ oh, const uint16_t* __restrict__ doh, const float* __restrict__ lse,
@@ -334,15 +328,9 @@ __global__ __launch_bounds__(64 * ((LT + TPW - 1) / TPW)) void attn_bwd_kernel(
     int Bw, int h, int L, int nW, int nww, int nwh, int mask_thr,
     float* __restrict__ dbws) {          // [gridDim.x][h][L][L] partial d bias tables (summed by dbias_reduce_kernel) or null
     using C = AttnCfg<LT, DK>;
-    static_assert(TPW == 1 || !HAS_BIAS, "the bias-gradient rows are sized for one key tile per wave");
     constexpr int Lp = C::Lp, DP = C::DP, SLAB = C::SLAB;
-    constexpr int WAVES = (LT + TPW - 1) / TPW, NT = 64 * WAVES;
+    constexpr int TPW = 1, WAVES = LT, NT = 64 * WAVES;
     constexpr int DSP = Lp + 4;                              // row pitch (elements) of the [key][q] bf16 images
-    // rows of the dcos image: all Lp keys, or (compile-time L, no bias) the real keys rounded up to a 4-row block plus
-    // one block of zeros that stands in for every padded-key block in phase 2
-    constexpr bool COMPACT = (LFIX > 0) && !HAS_BIAS && TPW > 1;
-    constexpr int IREAL = COMPACT ? (LFIX + 3) / 4 * 4 : Lp;
-    constexpr int IROWS = COMPACT ? IREAL + 4 : Lp;
     constexpr bool BIAS_LDS = HAS_BIAS && (LT * DK <= 11);   // 145 KB at LT=11, DK=1
     constexpr int CH = SLAB / 8;                             // 16-byte chunks per slab
     constexpr int CPT = (CH + NT - 1) / NT;                  // chunks per thread
@@ -353,8 +341,8 @@ __global__ __launch_bounds__(64 * ((LT + TPW - 1) / TPW)) void attn_bwd_kernel(
     // QG: the q / dO slabs do not fit beside K, V and the dcos image (head dim padded to 128 at the 176-token window:
     // 4 x 45 KB + 63 KB) -- their fragments are then read from global memory / L2 (the slab layout in memory is the LDS
     // image), the transposed ones as four 2-byte loads.  A coverage path for wide heads, not a tuned one.
-    constexpr bool QG = (4 * SLAB * 2 + IROWS * DSP * 2 + Lp * 8 + 256 > 160 * 1024);
-    constexpr bool AUG = AUGP && DK <= 2 && TPW == 1 && !QG && (!HAS_BIAS || (DK == 1 && BIAS_LDS && LFIX > 0));
+    constexpr bool QG = (4 * SLAB * 2 + Lp * DSP * 2 + Lp * 8 + 256 > 160 * 1024);
+    constexpr bool AUG = AUGP && DK <= 2 && !QG && (!HAS_BIAS || (DK == 1 && BIAS_LDS && LFIX > 0));
     // bias image rows (keys): with AUG the padded keys are switched off inside the operand, so the image ends at the last real key
     // (rounded up to 4) and the last wave reads a clamped row -- 5 KB that the 80-byte Q / dO rows need
     constexpr int BROWS = (HAS_BIAS && AUG) ? (LFIX + 3) / 4 * 4 : Lp;
@@ -366,7 +354,7 @@ __global__ __launch_bounds__(64 * ((LT + TPW - 1) / TPW)) void attn_bwd_kernel(
     constexpr int QSTAT = AUG ? (DK == 1 ? 16 : 32) : 0;       // first statistics slot of a row
     constexpr int OFF_Q = 0, OFF_DO = OFF_Q + (QG ? 0 : Lp * QP * 2), OFF_LSE = OFF_DO + (QG ? 0 : Lp * QP * 2), OFF_DL = OFF_LSE + Lp * 4,
                   OFF_K = OFF_DL + Lp * 4, OFF_V = OFF_K + SLAB * 2, OFF_DS = OFF_V + SLAB * 2,
-                  OFF_BIAS = OFF_DS + IROWS * DSP * 2, OFF_RED = OFF_BIAS + (BIAS_LDS ? BROWS * DSP * 2 : 16),
+                  OFF_BIAS = OFF_DS + Lp * DSP * 2, OFF_RED = OFF_BIAS + (BIAS_LDS ? BROWS * DSP * 2 : 16),
                   OFF_DLP = OFF_RED + ((WAVES * 4 + 15) / 16) * 16,
                   // chunks per row not a power of two (96 columns = 12 chunks): the per-chunk parts of delta go through LDS
                   LDS_BYTES = OFF_DLP + (((CPR & (CPR - 1)) != 0) ? CH * 4 : 0);
@@ -407,10 +395,7 @@ __global__ __launch_bounds__(64 * ((LT + TPW - 1) / TPW)) void attn_bwd_kernel(
     const float inv_sc2 = 1.f / sc2;
     (void)inv_sc2;
 
-    if (COMPACT)
-        for (int i = tid; i < 4 * DSP; i += NT) dSb[IREAL * DSP + i] = 0;      // the zero block
-
-    // bias rows: registers (fallback) or LDS image biasS[key][q]; gradient rows always in registers (TPW = 1)
+    // bias rows: registers (fallback) or LDS image biasS[key][q]; gradient rows always in registers
     f32x4 biasr[BIAS_LDS ? 1 : LT];
     f32x4 dbr[HAS_BIAS ? LT : 1];
     if (HAS_BIAS) {
@@ -573,7 +558,7 @@ __global__ __launch_bounds__(64 * ((LT + TPW - 1) / TPW)) void attn_bwd_kernel(
         f32x4 dk[TPW][DK], dv[TPW][DK];
 #pragma unroll
         for (int i = 0; i < TPW; ++i) {
-            const int key = 16 * min(tw * TPW + i, LT - 1) + fr;      // a wave's surplus tile repeats the last one (unused)
+            const int key = 16 * min(tw * TPW + i, LT - 1) + fr;
 #pragma unroll
             for (int kk = 0; kk < DK; ++kk) {
                 kf[i][kk] = *(const bf16x4*)(Ks + key * DP + 16 * kk + 4 * g);
@@ -583,7 +568,7 @@ __global__ __launch_bounds__(64 * ((LT + TPW - 1) / TPW)) void attn_bwd_kernel(
             }
         }
         const bool do_mask = (mask_thr > 0) && (((bw % nW) / nww) == nwh - 1);
-        // one q-tile step; `br` / `dbrow`: this lane's bias row / bias-gradient row of the tile (TPW = 1 only)
+        // one q-tile step; `br` / `dbrow`: this lane's bias row / bias-gradient row of the tile
         // MASKED / PADT (shift-mask window / a key tile with padded keys) are wave-uniform and loop-invariant: separate
         // instantiations, so the common case carries no per-element selects
         auto step = [&](const int qt, const f32x4 br, f32x4& dbrow, auto masked_c, auto pad_c) {
@@ -601,7 +586,6 @@ __global__ __launch_bounds__(64 * ((LT + TPW - 1) / TPW)) void attn_bwd_kernel(
 #pragma unroll
             for (int i = 0; i < TPW; ++i) {
                 const int kt = tw * TPW + i;
-                if (TPW > 1 && kt >= LT) continue;                      // wave-uniform
                 const int key = 16 * kt + fr;
                 const bool kid = key >= mask_thr;
                 const bool key_ok = key < Lc;
@@ -633,7 +617,7 @@ __global__ __launch_bounds__(64 * ((LT + TPW - 1) / TPW)) void attn_bwd_kernel(
                 const uint32_t pk2[2] = {f2bf2(p[0], p[1]), f2bf2(p[2], p[3])};      // explicit pairs: one cvt_pk each
                 const bf16x4 pb = __builtin_bit_cast(bf16x4, pk2);
                 const bf16x4 dsb = f2bf4(ds);
-                if (!COMPACT || key < IREAL) *(bf16x4*)(dSb + key * DSP + 16 * qt + 4 * g) = dsb;   // image [key][q] for phase 2
+                *(bf16x4*)(dSb + key * DSP + 16 * qt + 4 * g) = dsb;                            // image [key][q] for phase 2
                 // dV^T += dO^T P ; dK^T += Q^T dcos     (A operands: transposed reads of the staged dO / Q tiles)
 #pragma unroll
                 for (int dt = 0; dt < DK; ++dt) {
@@ -665,12 +649,11 @@ __global__ __launch_bounds__(64 * ((LT + TPW - 1) / TPW)) void attn_bwd_kernel(
             }
             const uint16_t* const Qa = (const uint16_t*)(lds + OFF_Q);
             const uint16_t* const Da = (const uint16_t*)(lds + OFF_DO);
-#ifndef SWV2_BIAS_BWD_ROLLED
             // The two-stage software pipeline of the kernel without bias, FULLY UNROLLED so that the d bias rows are statically indexed
             // registers, with a scheduling fence after every pair of steps: the fence keeps the scheduler from hoisting the LDS reads
             // of all eleven steps to the top (which is what made earlier unrolled forms spill), and inside a pair stage A of the next
-            // step interleaves with stage B of the current one.  The rolled form below needs a scalar switch to pick the row; the
-            // compiler turns it into ~24 64-bit register copies per step.
+            // step interleaves with stage B of the current one.  (A rolled form needs a scalar switch to pick the row; the compiler
+            // turns it into ~24 64-bit register copies per step.)
             struct St { f32x4 s, dp; bf16x4 tq, td, b4; };
             auto stageA = [&](const int qt, St& o) {
                 const bf16x8 qa = *(const bf16x8*)(Qa + (16 * qt + fr) * QP + 8 * g);
@@ -711,32 +694,6 @@ __global__ __launch_bounds__(64 * ((LT + TPW - 1) / TPW)) void attn_bwd_kernel(
             }
             if (LT & 1) stageB(LT - 1, sa, dbr[LT - 1]);
             SWV2_P1PRIO(0);
-#else
-#pragma unroll 1
-            for (int qt = 0; qt < LT; ++qt) {
-                const bf16x8 qa = *(const bf16x8*)(Qa + (16 * qt + fr) * QP + 8 * g);
-                const bf16x8 da = *(const bf16x8*)(Da + (16 * qt + fr) * QP + 8 * g);
-                const bf16x4 td = lds_tr_read(Da + (16 * qt + 4 * g + (fr >> 2)) * QP + (fr & 3) * 4);
-                const bf16x4 tq = lds_tr_read(Qa + (16 * qt + 4 * g + (fr >> 2)) * QP + (fr & 3) * 4);
-                const bf16x4 b4 = *(const bf16x4*)(biasS + min(key, BROWS - 1) * DSP + 16 * qt + 4 * g);
-                const f32x4 sv = mfma32(qa, kf8, (f32x4){0.f, 0.f, 0.f, 0.f});
-                const f32x4 dpv = mfma32(da, vf8, (f32x4){0.f, 0.f, 0.f, 0.f});
-                f32x4 p, ds;
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    p[r] = __builtin_amdgcn_exp2f(fmaf(sv[r], sc2, bf2f(b4[r])));
-                    ds[r] = p[r] * dpv[r];
-                }
-                const bf16x4 pb = f2bf4(p), dsb = f2bf4(ds);
-                *(bf16x4*)(dSb + key * DSP + 16 * qt + 4 * g) = dsb;
-                dv[0][0] = mfma16(td, pb, dv[0][0]);
-                dk[0][0] = mfma16(tq, dsb, dk[0][0]);
-#define SWV2_CASE(I) case I: if (I < LT) dbr[I < LT ? I : 0] += ds; break;
-                switch (qt) { SWV2_CASE(0) SWV2_CASE(1) SWV2_CASE(2) SWV2_CASE(3) SWV2_CASE(4) SWV2_CASE(5)
-                              SWV2_CASE(6) SWV2_CASE(7) SWV2_CASE(8) SWV2_CASE(9) SWV2_CASE(10) }
-#undef SWV2_CASE
-            }
-#endif
         } else if constexpr (HAS_BIAS) {
             const int key = 16 * tw + fr;
             // rolled loop; the bias-gradient rows stay statically indexed registers through a (scalar, wave-uniform)
@@ -898,7 +855,7 @@ __global__ __launch_bounds__(64 * ((LT + TPW - 1) / TPW)) void attn_bwd_kernel(
                 if (LT & 1) stageB(LT - 1, sa);
                 SWV2_P1PRIO(0);
             }
-        } else if constexpr (TPW == 1) {
+        } else {
             // software-pipelined over the q tiles (two register sets used alternately): stage A of step qt + 1 (fragment
             // reads, S and dP MFMAs) is issued before stage B of step qt (softmax backward on the vector ALU, dV / dK
             // MFMAs), so a wave has independent work while its MFMA results and LDS reads are in flight.  A plain
@@ -962,22 +919,12 @@ __global__ __launch_bounds__(64 * ((LT + TPW - 1) / TPW)) void attn_bwd_kernel(
             if (do_mask) run(std::true_type{}, std::true_type{});
             else if (pad_wave) run(std::false_type{}, std::true_type{});
             else run(std::false_type{}, std::false_type{});
-        } else {
-            f32x4 dummy = {0.f, 0.f, 0.f, 0.f};
-            if (do_mask) {
-#pragma unroll 1
-                for (int qt = 0; qt < LT; ++qt) step(qt, dummy, dummy, std::true_type{}, std::true_type{});
-            } else {
-#pragma unroll 1
-                for (int qt = 0; qt < LT; ++qt) step(qt, dummy, dummy, std::false_type{}, std::true_type{});
-            }
         }
         GSTAMP(1);                      // phase 1 loop
         // ---- dK (through the L2-normalisation) and dV of this wave's key tile(s)
 #pragma unroll
         for (int i = 0; i < TPW; ++i) {
             const int kt = tw * TPW + i;
-            if (TPW > 1 && kt >= LT) continue;
             const int key = 16 * kt + fr;
             const float rk = rnorm[(((size_t)bw * h + hd) * 2 + 1) * Lp + key];
             float dot = 0.f;
@@ -1014,14 +961,12 @@ __global__ __launch_bounds__(64 * ((LT + TPW - 1) / TPW)) void attn_bwd_kernel(
             // both sides), which halves the MFMA count and the length of the dependent accumulation chain
             auto frag = [&](int t, bf16x4 (&kt_)[DK], bf16x4 (&ds_)[TPW]) {
                 const int row = 16 * t + 4 * g + (fr >> 2);
-                // padded-key blocks of the compact image read the zero block
-                const int irow = (COMPACT && 16 * t + 4 * g >= IREAL) ? IREAL + (fr >> 2) : row;
 #pragma unroll
                 for (int dt = 0; dt < DK; ++dt) kt_[dt] = lds_tr_read(Ks + row * DP + 16 * dt + (fr & 3) * 4);   // rows d, col key
 #pragma unroll
                 for (int i = 0; i < TPW; ++i) {
                     const int qt = min(tw * TPW + i, LT - 1);
-                    ds_[i] = lds_tr_read(dSb + irow * DSP + 16 * qt + (fr & 3) * 4);                // B[k = key][n = q]
+                    ds_[i] = lds_tr_read(dSb + row * DSP + 16 * qt + (fr & 3) * 4);                // B[k = key][n = q]
                 }
             };
 #pragma unroll
@@ -1052,7 +997,6 @@ __global__ __launch_bounds__(64 * ((LT + TPW - 1) / TPW)) void attn_bwd_kernel(
 #pragma unroll
             for (int i = 0; i < TPW; ++i) {
                 const int qt = tw * TPW + i;
-                if (TPW > 1 && qt >= LT) continue;
                 const int q = 16 * qt + fr;
                 const float rq = rnorm[(((size_t)bw * h + hd) * 2 + 0) * Lp + q] * sigma;
                 bf16x4 qn[DK];
@@ -1171,12 +1115,12 @@ int launch_bwd(const swv2_attn_args* a, hipStream_t st) {
         if (a->dbias_partials) SWV2_CHECK_ARG(dbws != nullptr, "attn_bwd: dbias_partials needs a workspace of %zu bytes", need);
         // 16-wide heads with the bias image in LDS: statistics / mask inside the MFMA operands here too
         if (DK == 1 && !(a->dbg & SWV2_ATTN_PLAIN_STATS))
-            hipLaunchKernelGGL((attn_bwd_kernel<LT, DK, true, LFIX, 1, true>), grid, block, 0, st, (const uint16_t*)a->qkvh, a->logit_scale,
+            hipLaunchKernelGGL((attn_bwd_kernel<LT, DK, true, LFIX, true>), grid, block, 0, st, (const uint16_t*)a->qkvh, a->logit_scale,
                                a->bias, bimg, (const uint16_t*)a->oh, (const uint16_t*)a->doh, a->lse, a->rnorm,
                                (uint16_t*)a->dqkvh, a->dlogit_scale, a->dbias, a->Bw, a->heads, a->L, nW, a->nww, a->nwh,
                                a->mask_thr, dbws);
         else
-        hipLaunchKernelGGL((attn_bwd_kernel<LT, DK, true, LFIX, 1>), grid, block, 0, st, (const uint16_t*)a->qkvh, a->logit_scale,
+        hipLaunchKernelGGL((attn_bwd_kernel<LT, DK, true, LFIX>), grid, block, 0, st, (const uint16_t*)a->qkvh, a->logit_scale,
                            a->bias, bimg, (const uint16_t*)a->oh, (const uint16_t*)a->doh, a->lse, a->rnorm,
                            (uint16_t*)a->dqkvh, a->dlogit_scale, a->dbias, a->Bw, a->heads, a->L, nW, a->nww, a->nwh,
                            a->mask_thr, dbws);
@@ -1185,18 +1129,15 @@ int launch_bwd(const swv2_attn_args* a, hipStream_t st) {
             hipLaunchKernelGGL(dbias_reduce_kernel, dim3((n + 255) / 256), dim3(256), 0, st, (const float*)dbws, a->dbias, n, nchunk);
         }
     } else {
-        // TPW = 2 (6 waves x 2 tiles, two workgroups per CU) measured SLOWER than 11 waves x 1 tile at the benchmark shape
-        // (224 us vs 178 us): kept as a template option, not used
-        constexpr int TPW = 1;
-        dim3 grid(nchunk, a->heads), block(64 * ((LT + TPW - 1) / TPW));
+        dim3 grid(nchunk, a->heads), block(64 * LT);
         // 16-wide heads: statistics / mask inside the MFMA operands (SWV2_ATTN_PLAIN_STATS keeps the kernel that reads them from LDS)
         if (DK <= 2 && !(a->dbg & SWV2_ATTN_PLAIN_STATS))
-            hipLaunchKernelGGL((attn_bwd_kernel<LT, DK, false, LFIX, TPW, true>), grid, block, 0, st, (const uint16_t*)a->qkvh,
+            hipLaunchKernelGGL((attn_bwd_kernel<LT, DK, false, LFIX, true>), grid, block, 0, st, (const uint16_t*)a->qkvh,
                                a->logit_scale, a->bias, (const uint16_t*)nullptr, (const uint16_t*)a->oh, (const uint16_t*)a->doh, a->lse,
                                a->rnorm, (uint16_t*)a->dqkvh, a->dlogit_scale, a->dbias, a->Bw, a->heads, a->L, nW, a->nww, a->nwh,
                                a->mask_thr, (float*)nullptr);
         else
-        hipLaunchKernelGGL((attn_bwd_kernel<LT, DK, false, LFIX, TPW>), grid, block, 0, st, (const uint16_t*)a->qkvh,
+        hipLaunchKernelGGL((attn_bwd_kernel<LT, DK, false, LFIX>), grid, block, 0, st, (const uint16_t*)a->qkvh,
                            a->logit_scale, a->bias, (const uint16_t*)nullptr, (const uint16_t*)a->oh, (const uint16_t*)a->doh, a->lse, a->rnorm,
                            (uint16_t*)a->dqkvh, a->dlogit_scale, a->dbias, a->Bw, a->heads, a->L, nW, a->nww, a->nwh,
                            a->mask_thr, (float*)nullptr);
@@ -1242,9 +1183,6 @@ extern "C" int swv2_attn_geometry(int L, int head_dim, int* Lp, int* DP) {
 // kernels are specialised for the window areas of the reference configurations (9x18 = 162 at 720x1440 / ratio 80,
 // 6x9 = 54 at 192x288 / ratio 32); any other area <= 176 runs the generic (runtime-L) instantiation
 #define SWV2_ATTN_DISPATCH(FN)                                                         \
-    int Lp, DP;                                                                        \
-    int rc = swv2_attn_geometry(a->L, a->head_dim, &Lp, &DP);                          \
-    if (rc) return rc;                                                                 \
     hipStream_t st = (hipStream_t)stream;                                              \
     if (Lp == 176 && DP == 16 && a->L == 162) return FN<11, 1, 162>(a, st);            \
     if (Lp == 64 && DP == 16 && a->L == 54) return FN<4, 1, 54>(a, st);                \
@@ -1303,65 +1241,93 @@ extern "C" int swv2_attn_pack_bias(const float* bias, int heads, int L, void* ou
 // workgroups per head of the attention backward with a CPB table (= d bias tables per head it leaves in swv2_attn_args.dbias_ws)
 extern "C" int swv2_attn_bias_chunks(int Bw) { return Bw < 32 ? Bw : 32; }
 
-// the small-workgroup forward of attn2.hip: 0 / negative = handled (ok / error), 1 = shape not covered
-int swv2_attn2_fwd(const swv2_attn_args* a, int Lp, int DP, void* stream);
+// the launchers of the other attention files (0 = ok, negative = error); attn_fwd_kernel_for / attn_bwd_kernel_for pick the one that runs
+int swv2_attn_fwd3(const swv2_attn_args* a, void* stream);                      // attn2.hip
+int swv2_attn_fwd3w(const swv2_attn_args* a, void* stream);
+int swv2_attn_fwd3b(const swv2_attn_args* a, void* stream);
+int swv2_attn_fwd_wide(const swv2_attn_args* a, int DP, void* stream);          // attn_wide.hip
+int swv2_attn_bwd_wide(const swv2_attn_args* a, int DP, void* stream);
+int swv2_attn_fwd_d256(const swv2_attn_args* a, int Lp, void* stream);          // attn_d256.hip
+int swv2_attn_bwd_d256(const swv2_attn_args* a, int Lp, void* stream);
+int swv2_attn_bwd_stream(const swv2_attn_args* a, void* stream);                // attn_bwd_stream.hip
 
-// the kernels for 65 .. 96-channel heads of attn_wide.hip: 0 / negative = handled (ok / error), 1 = shape not covered
-int swv2_attn_fwd_wide(const swv2_attn_args* a, int Lp, int DP, void* stream);
-int swv2_attn_bwd_wide(const swv2_attn_args* a, int Lp, int DP, void* stream);
+namespace {
 
-// the kernel pair for 256-channel heads of attn_d256.hip: 0 / negative = handled (ok / error), 1 = another layout
-int swv2_attn_fwd_d256(const swv2_attn_args* a, int Lp, int DP, void* stream);
-int swv2_attn_bwd_d256(const swv2_attn_args* a, int Lp, int DP, void* stream);
+enum class AttnKernel { D256, FWD3, FWD3W, FWD3B, WIDE, STREAM, FIRST_GEN };
 
-// the streamed-dQ backward of attn_bwd_stream.hip (176-row layout, 16-wide head slots, no table): 0 / negative = handled, 1 = not covered
-int swv2_attn_bwd_stream(const swv2_attn_args* a, int Lp, int DP, void* stream);
+// 65 .. 96-channel heads in the 176-row layout without a table: attn_wide.hip
+bool wide_shape(int head_dim, int Lp, int DP, bool bias) {
+    return !bias && Lp == 176 && (DP == 96 || DP == 128) && head_dim > 64 && head_dim <= 96;
+}
+
+// The forward kernel of a geometry (Lp, DP from swv2_attn_geometry).  256-channel heads: attn_d256.hip, the only kernel at that width
+// (SWV2_ATTN_FIRST_GEN does not apply).  attn2.hip: the 176-row layout with 16- or 32-wide head slots; its kernels start only the LAST
+// key tile's accumulators at -1e30 for padded keys, so every other key tile must hold real keys only -- L >= 16 (LT - 1) = 160 (ADVICE
+// r4: at 65 .. 159 tokens the zero K rows of the padded keys in tiles 4 .. 9 entered the row sum with weight exp2(-sigma')).  With a
+// CPB table only the packed form (swv2_attn_pack_bias) at 16-wide slots runs there; a raw table runs attn.hip.  Everything else runs
+// the first-generation kernel of attn.hip.
+AttnKernel attn_fwd_kernel_for(int L, int head_dim, int Lp, int DP, bool bias, bool bias_pack, int dbg) {
+    if (DP == 256) return AttnKernel::D256;
+    if (dbg & SWV2_ATTN_FIRST_GEN) return AttnKernel::FIRST_GEN;
+    if (Lp == 176 && L >= 160 && (DP == 16 || DP == 32)) {
+        if (!bias) return DP == 16 ? AttnKernel::FWD3 : AttnKernel::FWD3W;
+        if (bias_pack && DP == 16) return AttnKernel::FWD3B;
+    }
+    if (wide_shape(head_dim, Lp, DP, bias)) return AttnKernel::WIDE;
+    return AttnKernel::FIRST_GEN;
+}
+
+// The backward kernel: attn_d256.hip at 256 channels; attn_wide.hip (unless SWV2_ATTN_FIRST_GEN); the streamed-dQ backward of
+// attn_bwd_stream.hip in the 176-row layout with 16-wide head slots and no table (unless SWV2_ATTN_PLAIN_STATS or
+// SWV2_ATTN_BWD_TWO_PHASE); otherwise the two-phase kernel of attn.hip.
+AttnKernel attn_bwd_kernel_for(int head_dim, int Lp, int DP, bool bias, int dbg) {
+    if (DP == 256) return AttnKernel::D256;
+    if (wide_shape(head_dim, Lp, DP, bias) && !(dbg & SWV2_ATTN_FIRST_GEN)) return AttnKernel::WIDE;
+    if (Lp == 176 && DP == 16 && !bias && !(dbg & (SWV2_ATTN_PLAIN_STATS | SWV2_ATTN_BWD_TWO_PHASE))) return AttnKernel::STREAM;
+    return AttnKernel::FIRST_GEN;
+}
+
+}  // namespace
 
 // which forward kernel family serves a geometry (pure host function, no launch): 1 = the operand-folded softmax of attn2.hip, 0 = row
-// maximum + exact sum (attn.hip, attn_wide.hip); negative: geometry not covered.  The parity tests declare the regime their oracle
-// emulates and check it against this.
+// maximum + exact sum (attn.hip, attn_wide.hip, attn_d256.hip); negative: geometry not covered.  The parity tests declare the regime
+// their oracle emulates and check it against this.  (has_bias: a table in its PACKED form, as the model always passes it.)
 extern "C" int swv2_attn_fwd_regime(int L, int head_dim, int has_bias, int dbg) {
     int Lp, DP;
     const int rc = swv2_attn_geometry(L, head_dim, &Lp, &DP);
     if (rc) return rc;
-    // (has_bias: a table in its PACKED form, as the model always passes it; a raw table without swv2_attn_pack_bias runs attn.hip)
-    static const int fwd3b = getenv("SWV2_ATTN_FWD3B") ? atoi(getenv("SWV2_ATTN_FWD3B")) : 1;
-    const bool shape = Lp == 176 && L >= 160 && !(dbg & SWV2_ATTN_FIRST_GEN);
-    return (shape && (has_bias ? (DP == 16 && fwd3b) : (DP == 16 || DP == 32))) ? 1 : 0;
+    switch (attn_fwd_kernel_for(L, head_dim, Lp, DP, has_bias, has_bias, dbg)) {
+        case AttnKernel::FWD3: case AttnKernel::FWD3W: case AttnKernel::FWD3B: return 1;
+        default: return 0;
+    }
 }
 
 extern "C" int swv2_attn_fwd(const swv2_attn_args* a, void* stream) {
-    int rc0 = check_args(a, false);
-    if (rc0) return rc0;
-    {
-        int Lp2, DP2;
-        int rc2 = swv2_attn_geometry(a->L, a->head_dim, &Lp2, &DP2);
-        if (rc2) return rc2;
-        rc2 = swv2_attn_fwd_d256(a, Lp2, DP2, stream);           // the only kernel at this width: SWV2_ATTN_FIRST_GEN does not apply
-        if (rc2 <= 0) return rc2;
-        if (!(a->dbg & SWV2_ATTN_FIRST_GEN)) {
-            rc2 = swv2_attn2_fwd(a, Lp2, DP2, stream);
-            if (rc2 <= 0) return rc2;
-            rc2 = swv2_attn_fwd_wide(a, Lp2, DP2, stream);
-            if (rc2 <= 0) return rc2;
-        }
+    int Lp, DP;
+    int rc = check_args(a, false);
+    if (!rc) rc = swv2_attn_geometry(a->L, a->head_dim, &Lp, &DP);
+    if (rc) return rc;
+    switch (attn_fwd_kernel_for(a->L, a->head_dim, Lp, DP, a->bias, a->bias_pack, a->dbg)) {
+        case AttnKernel::D256: return swv2_attn_fwd_d256(a, Lp, stream);
+        case AttnKernel::FWD3: return swv2_attn_fwd3(a, stream);
+        case AttnKernel::FWD3W: return swv2_attn_fwd3w(a, stream);
+        case AttnKernel::FWD3B: return swv2_attn_fwd3b(a, stream);
+        case AttnKernel::WIDE: return swv2_attn_fwd_wide(a, DP, stream);
+        default: break;
     }
     SWV2_ATTN_DISPATCH(launch_fwd)
 }
 
 extern "C" int swv2_attn_bwd(const swv2_attn_args* a, void* stream) {
-    int rc0 = check_args(a, true);
-    if (rc0) return rc0;
-    {
-        int Lp2, DP2;
-        int rc2 = swv2_attn_geometry(a->L, a->head_dim, &Lp2, &DP2);
-        if (rc2) return rc2;
-        rc2 = swv2_attn_bwd_d256(a, Lp2, DP2, stream);
-        if (rc2 <= 0) return rc2;
-        rc2 = swv2_attn_bwd_wide(a, Lp2, DP2, stream);
-        if (rc2 <= 0) return rc2;
-        rc2 = swv2_attn_bwd_stream(a, Lp2, DP2, stream);
-        if (rc2 <= 0) return rc2;
+    int Lp, DP;
+    int rc = check_args(a, true);
+    if (!rc) rc = swv2_attn_geometry(a->L, a->head_dim, &Lp, &DP);
+    if (rc) return rc;
+    switch (attn_bwd_kernel_for(a->head_dim, Lp, DP, a->bias, a->dbg)) {
+        case AttnKernel::D256: return swv2_attn_bwd_d256(a, Lp, stream);
+        case AttnKernel::WIDE: return swv2_attn_bwd_wide(a, DP, stream);
+        case AttnKernel::STREAM: return swv2_attn_bwd_stream(a, stream);
+        default: break;
     }
     SWV2_ATTN_DISPATCH(launch_bwd)
 }

@@ -51,12 +51,7 @@ __device__ unsigned long long fwd3_span[2048 * 2];
 //     The normaliser is then the sum of the bf16-rounded P -- exactly the values that multiply V.
 // Measured before (tools/probe_attn_stamps.py): ~259 vector instructions per 16-query row at ~5.7 SIMD cycles each.
 // ------------------------------------------------------------------------------------------------
-// KREG: the wave keeps the K (A operand of S^T) and V^T (A operand of O^T) fragments of the whole item in registers (66
-// VGPRs), read from LDS once per item and pinned there (an empty asm makes the values opaque: the compiler otherwise sinks the
-// loop-invariant reads back into the row loop, where -- double-buffered in 8 registers -- every QK MFMA waits a full LDS
-// round trip: 11 x ~80 cycles per row against 11 x 16 for back-to-back MFMAs; measured on one wave per SIMD: ~2000 cycles
-// per row of pure compute).
-template <int LT, int LFIX, int WAVES, int OCC, bool KREG>
+template <int LT, int LFIX, int WAVES, int OCC>
 __global__ __launch_bounds__(64 * WAVES, OCC) void attn_fwd3_kernel(
     const uint16_t* __restrict__ qkvh, const float* __restrict__ logit_scale, uint16_t* __restrict__ oh, float* __restrict__ lse,
     int Bw, int h, int L, int nW, int nww, int nwh, int mask_thr, int dbg) {
@@ -159,37 +154,16 @@ __global__ __launch_bounds__(64 * WAVES, OCC) void attn_fwd3_kernel(
 #pragma unroll
         for (int r = 0; r < 4; ++r) cpad[r] = (16 * (LT - 1) + 4 * g + r < Lc) ? c0 : SWV2_NEG_BIG;
 
-        bf16x8 kreg[KREG ? LT : 1], vreg[KREG ? LT / 2 : 1];
-        bf16x4 vtail = {0, 0, 0, 0};
-        if constexpr (KREG) {
-#pragma unroll
-            for (int t = 0; t < LT; ++t) kreg[t] = *(const bf16x8*)(Ki + (16 * t + fr) * 32 + 8 * g);
-#pragma unroll
-            for (int t = 0; t + 1 < LT; t += 2) {
-                const bf16x4 v0 = lds_tr_read(Vs + (16 * t + 4 * g + (fr >> 2)) * DP + (fr & 3) * 4);
-                const bf16x4 v1 = lds_tr_read(Vs + (16 * (t + 1) + 4 * g + (fr >> 2)) * DP + (fr & 3) * 4);
-                vreg[t / 2] = __builtin_shufflevector(v0, v1, 0, 1, 2, 3, 4, 5, 6, 7);
-            }
-            if (LT & 1) vtail = lds_tr_read(Vs + (16 * (LT - 1) + 4 * g + (fr >> 2)) * DP + (fr & 3) * 4);
-#pragma unroll
-            for (int t = 0; t < LT; ++t) asm volatile("" : "+v"(kreg[t]));
-#pragma unroll
-            for (int t = 0; t < LT / 2; ++t) asm volatile("" : "+v"(vreg[t]));
-            asm volatile("" : "+v"(vtail));
-        }
-
         STAMP(5, cpad[0]);
 #pragma unroll 1
         for (int qt = wave; qt < LT; qt += WAVES) {                   // wave-uniform trip count
             const int q = 16 * qt + fr;
-#ifndef SWV2_FWD3_NO_PRIO
             // Issue priority falls with the wave's progress through its item.  The three waves of a SIMD belong to the CU's three workgroups and
             // the arbiter serves the oldest first: spans of the item loop (s_memtime, -DSWV2_FWD3_SPAN, tools/probe_attn_fwd.py) mean 78 K cycles,
             // max 104 K without this, 80.5 K / 96 K with it -- the launch ends with the slowest workgroup.
             if (qt < WAVES) __builtin_amdgcn_s_setprio(2);
             else if (qt < 2 * WAVES) __builtin_amdgcn_s_setprio(1);
             else __builtin_amdgcn_s_setprio(0);
-#endif
             // the next item's slabs go to the other LDS buffer before the LAST row's stores are issued: its wait (in-order
             // vmcnt) then covers only loads issued rows ago and the earlier rows' stores
             if (qt + WAVES >= LT && bw_next < Bw) write_stage(buf ^ 1);
@@ -215,9 +189,7 @@ __global__ __launch_bounds__(64 * WAVES, OCC) void attn_fwd3_kernel(
             f32x4 acc[LT];
 #pragma unroll
             for (int t = 0; t < LT; ++t) {
-                bf16x8 kA;
-                if constexpr (KREG) kA = kreg[t];
-                else kA = *(const bf16x8*)(Ki + (16 * t + fr) * 32 + 8 * g);
+                const bf16x8 kA = *(const bf16x8*)(Ki + (16 * t + fr) * 32 + 8 * g);
                 const f32x4 c = (t == LT - 1) ? cpad : (f32x4){c0, c0, c0, c0};
                 acc[t] = mfma32(kA, qB, c);
             }
@@ -256,21 +228,15 @@ __global__ __launch_bounds__(64 * WAVES, OCC) void attn_fwd3_kernel(
             for (int t = 0; t + 1 < LT; t += 2) {
                 const bf16x4 p0 = f2bf4(acc[t]), p1 = f2bf4(acc[t + 1]);
                 const bf16x8 pb = __builtin_shufflevector(p0, p1, 0, 1, 2, 3, 4, 5, 6, 7);
-                bf16x8 vA;
-                if constexpr (KREG) vA = vreg[t / 2];
-                else {
-                    const bf16x4 v0 = lds_tr_read(Vs + (16 * t + 4 * g + (fr >> 2)) * DP + (fr & 3) * 4);
-                    const bf16x4 v1 = lds_tr_read(Vs + (16 * (t + 1) + 4 * g + (fr >> 2)) * DP + (fr & 3) * 4);
-                    vA = __builtin_shufflevector(v0, v1, 0, 1, 2, 3, 4, 5, 6, 7);
-                }
+                const bf16x4 v0 = lds_tr_read(Vs + (16 * t + 4 * g + (fr >> 2)) * DP + (fr & 3) * 4);
+                const bf16x4 v1 = lds_tr_read(Vs + (16 * (t + 1) + 4 * g + (fr >> 2)) * DP + (fr & 3) * 4);
+                const bf16x8 vA = __builtin_shufflevector(v0, v1, 0, 1, 2, 3, 4, 5, 6, 7);
                 o = mfma32(vA, pb, o);
                 rs = mfma32(ones8, pb, rs);
             }
             if (LT & 1) {
                 const bf16x4 pb = f2bf4(acc[LT - 1]);
-                bf16x4 vf;
-                if constexpr (KREG) vf = vtail;
-                else vf = lds_tr_read(Vs + (16 * (LT - 1) + 4 * g + (fr >> 2)) * DP + (fr & 3) * 4);
+                const bf16x4 vf = lds_tr_read(Vs + (16 * (LT - 1) + 4 * g + (fr >> 2)) * DP + (fr & 3) * 4);
                 // own accumulators for the K = 16 tail (see attn.hip: chaining it onto the K = 32 accumulator was wrong)
                 const f32x4 to = mfma16(vf, pb, (f32x4){0.f, 0.f, 0.f, 0.f});
                 const f32x4 ts = mfma16(ones4, pb, (f32x4){0.f, 0.f, 0.f, 0.f});
@@ -317,7 +283,7 @@ __global__ __launch_bounds__(64 * WAVES, OCC) void attn_fwd3_kernel(
 // slabs go to the other LDS buffer during the wave's last row (one barrier per item, 2 x 33 KB: two workgroups per CU);
 // NBUF = 1: one buffer, rewritten between two barriers (three workgroups per CU).
 // ------------------------------------------------------------------------------------------------
-template <int LT, int LFIX, int WAVES, int OCC, int NBUF, bool KREG = false>
+template <int LT, int LFIX, int WAVES, int OCC, int NBUF>
 __global__ __launch_bounds__(64 * WAVES, OCC) void attn_fwd3w_kernel(
     const uint16_t* __restrict__ qkvh, const float* __restrict__ logit_scale, uint16_t* __restrict__ oh, float* __restrict__ lse,
     int Bw, int h, int L, int nW, int nww, int nwh, int mask_thr) {
@@ -378,23 +344,23 @@ __global__ __launch_bounds__(64 * WAVES, OCC) void attn_fwd3w_kernel(
 #pragma unroll
         for (int r = 0; r < 4; ++r) cpad[r] = (16 * (LT - 1) + 4 * g + r < Lc) ? c0 : SWV2_NEG_BIG;
         auto vfrag = [&](int t, int dt) { return lds_tr_read(Vs + (16 * t + 4 * g + (fr >> 2)) * DP + 16 * dt + (fr & 3) * 4); };
-        // KREG: the item's K and V^T fragments in registers, read once per item and wave and pinned (see attn_fwd3_kernel)
-        bf16x8 kreg[KREG ? LT : 1], vreg[KREG ? LT / 2 : 1][2];
+        // the item's K and V^T fragments in registers, read from LDS once per item and wave and pinned there (an empty asm makes the
+        // values opaque: the compiler otherwise sinks the loop-invariant reads back into the row loop, where every QK MFMA waits a full
+        // LDS round trip: 11 x ~80 cycles per row against 11 x 16 for back-to-back MFMAs)
+        bf16x8 kreg[LT], vreg[LT / 2][2];
         bf16x4 vtail[2] = {{0, 0, 0, 0}, {0, 0, 0, 0}};
-        if constexpr (KREG) {
 #pragma unroll
-            for (int t = 0; t < LT; ++t) kreg[t] = *(const bf16x8*)(Ks + (16 * t + fr) * DP + 8 * g);
+        for (int t = 0; t < LT; ++t) kreg[t] = *(const bf16x8*)(Ks + (16 * t + fr) * DP + 8 * g);
 #pragma unroll
-            for (int t = 0; t + 1 < LT; t += 2)
+        for (int t = 0; t + 1 < LT; t += 2)
 #pragma unroll
-                for (int dt = 0; dt < 2; ++dt) vreg[t / 2][dt] = __builtin_shufflevector(vfrag(t, dt), vfrag(t + 1, dt), 0, 1, 2, 3, 4, 5, 6, 7);
-            if (LT & 1) { vtail[0] = vfrag(LT - 1, 0); vtail[1] = vfrag(LT - 1, 1); }
+            for (int dt = 0; dt < 2; ++dt) vreg[t / 2][dt] = __builtin_shufflevector(vfrag(t, dt), vfrag(t + 1, dt), 0, 1, 2, 3, 4, 5, 6, 7);
+        if (LT & 1) { vtail[0] = vfrag(LT - 1, 0); vtail[1] = vfrag(LT - 1, 1); }
 #pragma unroll
-            for (int t = 0; t < LT; ++t) asm volatile("" : "+v"(kreg[t]));
+        for (int t = 0; t < LT; ++t) asm volatile("" : "+v"(kreg[t]));
 #pragma unroll
-            for (int t = 0; t < LT / 2; ++t) asm volatile("" : "+v"(vreg[t][0]), "+v"(vreg[t][1]));
-            asm volatile("" : "+v"(vtail[0]), "+v"(vtail[1]));
-        }
+        for (int t = 0; t < LT / 2; ++t) asm volatile("" : "+v"(vreg[t][0]), "+v"(vreg[t][1]));
+        asm volatile("" : "+v"(vtail[0]), "+v"(vtail[1]));
 
 #pragma unroll 1
         for (int qt = wave; qt < LT; qt += WAVES) {                   // wave-uniform trip count
@@ -418,9 +384,7 @@ __global__ __launch_bounds__(64 * WAVES, OCC) void attn_fwd3w_kernel(
             f32x4 acc[LT];
 #pragma unroll
             for (int t = 0; t < LT; ++t) {
-                bf16x8 kA;
-                if constexpr (KREG) kA = kreg[t];
-                else kA = *(const bf16x8*)(Ks + (16 * t + fr) * DP + 8 * g);
+                const bf16x8 kA = kreg[t];
                 const f32x4 c = (t == LT - 1) ? cpad : (f32x4){c0, c0, c0, c0};
                 acc[t] = mfma32(kA, qlo, c);
                 acc[t] = mfma32(kA, qhi, acc[t]);
@@ -456,21 +420,15 @@ __global__ __launch_bounds__(64 * WAVES, OCC) void attn_fwd3w_kernel(
             for (int t = 0; t + 1 < LT; t += 2) {
                 const bf16x4 p0 = f2bf4(acc[t]), p1 = f2bf4(acc[t + 1]);
                 const bf16x8 pb = __builtin_shufflevector(p0, p1, 0, 1, 2, 3, 4, 5, 6, 7);
-                bf16x8 vA0, vA1;
-                if constexpr (KREG) { vA0 = vreg[t / 2][0]; vA1 = vreg[t / 2][1]; }
-                else {
-                    vA0 = __builtin_shufflevector(vfrag(t, 0), vfrag(t + 1, 0), 0, 1, 2, 3, 4, 5, 6, 7);
-                    vA1 = __builtin_shufflevector(vfrag(t, 1), vfrag(t + 1, 1), 0, 1, 2, 3, 4, 5, 6, 7);
-                }
-                o0 = mfma32(vA0, pb, o0);
-                o1 = mfma32(vA1, pb, o1);
+                o0 = mfma32(vreg[t / 2][0], pb, o0);
+                o1 = mfma32(vreg[t / 2][1], pb, o1);
                 rs = mfma32(ones8, pb, rs);
             }
             if (LT & 1) {
                 const bf16x4 pb = f2bf4(acc[LT - 1]);
                 // own accumulators for the K = 16 tail (see attn.hip)
-                o0 += mfma16(KREG ? vtail[0] : vfrag(LT - 1, 0), pb, (f32x4){0.f, 0.f, 0.f, 0.f});
-                o1 += mfma16(KREG ? vtail[1] : vfrag(LT - 1, 1), pb, (f32x4){0.f, 0.f, 0.f, 0.f});
+                o0 += mfma16(vtail[0], pb, (f32x4){0.f, 0.f, 0.f, 0.f});
+                o1 += mfma16(vtail[1], pb, (f32x4){0.f, 0.f, 0.f, 0.f});
                 rs += mfma16(ones4, pb, (f32x4){0.f, 0.f, 0.f, 0.f});
             }
             const float sum = rs[0];                                  // every row of the ones product holds the column sums
@@ -499,7 +457,7 @@ __global__ __launch_bounds__(64 * WAVES, OCC) void attn_fwd3w_kernel(
 // sigma' + max(bias') of the head (the (max, min) part of the packed buffer), valid while 2 sigma' + (max - min) <= 80.
 // 66 registers of bias per wave (3 q-tiles) on top of the 145 of the kernel without bias: two workgroups per CU instead of three.
 // ------------------------------------------------------------------------------------------------
-template <int LT, int LFIX, int WAVES, int OCC, bool KREG>
+template <int LT, int LFIX, int WAVES, int OCC>
 __global__ __launch_bounds__(64 * WAVES, OCC) void attn_fwd3b_kernel(
     const uint16_t* __restrict__ qkvh, const float* __restrict__ logit_scale, const uint32_t* __restrict__ bpack,
     const float* __restrict__ brange, uint16_t* __restrict__ oh, float* __restrict__ lse, int Bw, int h, int L, int nW, int nww, int nwh,
@@ -602,15 +560,6 @@ __global__ __launch_bounds__(64 * WAVES, OCC) void attn_fwd3b_kernel(
         const bool fixed = bounded && !do_mask;                       // wave-uniform
         const float c0 = fixed ? -(sc2 + bmax) : 0.f;
         const f32x4 cinit = {c0, c0, c0, c0};
-        // KREG: the item's K fragments (A operands of S^T) in registers, read once per item and wave and pinned (see attn_fwd3_kernel)
-        bf16x8 kreg[KREG ? LT : 1];
-        if constexpr (KREG) {
-#pragma unroll
-            for (int t = 0; t < LT; ++t) kreg[t] = *(const bf16x8*)(Ki + (16 * t + fr) * 32 + 8 * g);
-#pragma unroll
-            for (int t = 0; t < LT; ++t) asm volatile("" : "+v"(kreg[t]));
-        }
-
         // rolled loop (unrolled, the compiler interleaves the rows and spills: 256 registers + 94 in scratch); the wave's i-th bias
         // register set is picked by a scalar switch around the identity products only
 #pragma unroll 1
@@ -618,12 +567,10 @@ __global__ __launch_bounds__(64 * WAVES, OCC) void attn_fwd3b_kernel(
             const int qt = wave + i * WAVES;
             if (qt >= LT) break;                                      // wave-uniform
             const int q = 16 * qt + fr;
-#ifndef SWV2_FWD3_NO_PRIO
             // (issue priority falls with the wave's progress through its item, see attn_fwd3_kernel: 62.4 -> 57.7 - 58.0 us in situ, same box)
             if (i == 0) __builtin_amdgcn_s_setprio(2);
             else if (i == 1) __builtin_amdgcn_s_setprio(1);
             else __builtin_amdgcn_s_setprio(0);
-#endif
             if (qt + WAVES >= LT && bw_next < Bw) write_stage(buf ^ 1);
             const bf16x4 qraw = *(const bf16x4*)(Qs + (size_t)q * DP + 4 * g);
             bf16x8 qB;
@@ -665,9 +612,7 @@ __global__ __launch_bounds__(64 * WAVES, OCC) void attn_fwd3b_kernel(
 #undef SWV2_BIAS_TILES
 #pragma unroll
             for (int t = 0; t < LT; ++t) {
-                bf16x8 kA;
-                if constexpr (KREG) kA = kreg[t];
-                else kA = *(const bf16x8*)(Ki + (16 * t + fr) * 32 + 8 * g);
+                const bf16x8 kA = *(const bf16x8*)(Ki + (16 * t + fr) * 32 + 8 * g);
                 acc[t] = mfma32(kA, qB, acc[t]);
             }
             float mx = sc2 + bmax;
@@ -726,35 +671,35 @@ __global__ __launch_bounds__(64 * WAVES, OCC) void attn_fwd3b_kernel(
     }
 }
 
-template <int LT, int LFIX, int WAVES, int OCC, bool KREG>
+template <int LT, int LFIX, int WAVES, int OCC>
 int launch_fwd3b(const swv2_attn_args* a, const uint32_t* bpack, const float* brange, hipStream_t st) {
     int nchunk = (OCC * 256 + a->heads - 1) / a->heads;
     if (nchunk > a->Bw) nchunk = a->Bw;
     dim3 grid(nchunk, a->heads), block(64 * WAVES);
-    hipLaunchKernelGGL((attn_fwd3b_kernel<LT, LFIX, WAVES, OCC, KREG>), grid, block, 0, st, (const uint16_t*)a->qkvh, a->logit_scale, bpack, brange,
+    hipLaunchKernelGGL((attn_fwd3b_kernel<LT, LFIX, WAVES, OCC>), grid, block, 0, st, (const uint16_t*)a->qkvh, a->logit_scale, bpack, brange,
                        (uint16_t*)a->oh, a->lse, a->Bw, a->heads, a->L, a->nwh * a->nww, a->nww, a->nwh, a->mask_thr);
     SWV2_CHECK_LAUNCH("swv2_attn_fwd");
     return SWV2_OK;
 }
 
-template <int LT, int LFIX, int WAVES, int OCC, int NBUF, bool KREG = false>
+template <int LT, int LFIX, int WAVES, int OCC, int NBUF>
 int launch_fwd3w(const swv2_attn_args* a, hipStream_t st) {
     int nchunk = (OCC * 256 + a->heads - 1) / a->heads;
     if (nchunk > a->Bw) nchunk = a->Bw;
     dim3 grid(nchunk, a->heads), block(64 * WAVES);
-    hipLaunchKernelGGL((attn_fwd3w_kernel<LT, LFIX, WAVES, OCC, NBUF, KREG>), grid, block, 0, st, (const uint16_t*)a->qkvh, a->logit_scale,
+    hipLaunchKernelGGL((attn_fwd3w_kernel<LT, LFIX, WAVES, OCC, NBUF>), grid, block, 0, st, (const uint16_t*)a->qkvh, a->logit_scale,
                        (uint16_t*)a->oh, a->lse, a->Bw, a->heads, a->L, a->nwh * a->nww, a->nww, a->nwh, a->mask_thr);
     SWV2_CHECK_LAUNCH("swv2_attn_fwd");
     return SWV2_OK;
 }
 
-template <int LT, int LFIX, int WAVES, int OCC, bool KREG>
+template <int LT, int LFIX, int WAVES, int OCC>
 int launch_fwd3(const swv2_attn_args* a, hipStream_t st) {
     // OCC workgroups per CU on 256 CUs, every workgroup loops over windows
     int nchunk = (OCC * 256 + a->heads - 1) / a->heads;
     if (nchunk > a->Bw) nchunk = a->Bw;
     dim3 grid(nchunk, a->heads), block(64 * WAVES);
-    hipLaunchKernelGGL((attn_fwd3_kernel<LT, LFIX, WAVES, OCC, KREG>), grid, block, 0, st, (const uint16_t*)a->qkvh, a->logit_scale,
+    hipLaunchKernelGGL((attn_fwd3_kernel<LT, LFIX, WAVES, OCC>), grid, block, 0, st, (const uint16_t*)a->qkvh, a->logit_scale,
                        (uint16_t*)a->oh, a->lse, a->Bw, a->heads, a->L, a->nwh * a->nww, a->nww, a->nwh, a->mask_thr, a->dbg);
     SWV2_CHECK_LAUNCH("swv2_attn_fwd");
     return SWV2_OK;
@@ -768,33 +713,27 @@ extern "C" int swv2_debug_fwd3_span(void* out) {
 }
 #endif
 
-// called by swv2_attn_fwd (attn.hip); returns 1 when this kernel does not cover the shape (the caller then runs the
-// first-generation kernel).  Window areas: only the LAST key tile's accumulators start at -1e30 for padded keys, so every other key tile
-// must hold real keys only -- L >= 16 (LT - 1) = 160 (at 65 .. 159 tokens the zero K rows of the padded keys in tiles 4 .. 9
-// entered the row sum with weight exp2(-sigma')); smaller areas run the first-generation kernel.  With a CPB table: the packed form (swv2_attn_pack_bias)
-// is required -- its forward part is the register image, its (max, min) part bounds the fixed-maximum softmax.
-int swv2_attn2_fwd(const swv2_attn_args* a, int Lp, int DP, void* stream) {
+// The launchers of the three forwards, called by swv2_attn_fwd (attn.hip) for the shapes attn_fwd_kernel_for gives them: the 176-row
+// layout, 16- or 32-wide head slots, L >= 160.
+int swv2_attn_fwd3(const swv2_attn_args* a, void* stream) {
     hipStream_t st = (hipStream_t)stream;
-    if (Lp != 176 || a->L < 160 || (DP != 16 && DP != 32)) return 1;
-    if (a->bias) {
-        static const int fwd3b = getenv("SWV2_ATTN_FWD3B") ? atoi(getenv("SWV2_ATTN_FWD3B")) : 1;
-        if (!fwd3b || !a->bias_pack || DP != 16 || a->heads <= 0) return 1;
-        const uint32_t* bpack = (const uint32_t*)a->bias_pack;
-        const float* brange = (const float*)((const char*)a->bias_pack + swv2_attn_bias_range_offset(a->heads, a->L));
-        static const int kreg = getenv("SWV2_ATTN_FWD3B_KREG") ? atoi(getenv("SWV2_ATTN_FWD3B_KREG")) : 0;
-        if (kreg) return a->L == 162 ? launch_fwd3b<11, 162, 4, 2, true>(a, bpack, brange, st) : launch_fwd3b<11, 0, 4, 2, true>(a, bpack, brange, st);
-        static const int stream = getenv("SWV2_ATTN_FWD3B_STREAM") ? atoi(getenv("SWV2_ATTN_FWD3B_STREAM")) : 1;
-        if (stream && a->L == 162) return launch_fwd3b<11, 162, 4, 3, false>(a, bpack, brange, st);
-        return a->L == 162 ? launch_fwd3b<11, 162, 4, 2, false>(a, bpack, brange, st) : launch_fwd3b<11, 0, 4, 2, false>(a, bpack, brange, st);
-    }
-    if (DP == 32) {
-        // measured at B = 2 (800 windows x 8 heads, 24-wide heads): 4 waves x 2 workgroups per CU, two LDS buffers: 90 us with the K / V^T
-        // fragments read per row, 80 us with them in registers (227 VGPRs); one buffer at 3 workgroups per CU (spills): 99; 6 waves x 2
-        // workgroups (SIMDs loaded 4 / 4 / 2 / 2): 112; first generation: 203
-        static const int kreg = getenv("SWV2_ATTN_FWD3W_KREG") ? atoi(getenv("SWV2_ATTN_FWD3W_KREG")) : 1;
-        if (!kreg) return a->L == 162 ? launch_fwd3w<11, 162, 4, 2, 2, false>(a, st) : launch_fwd3w<11, 0, 4, 2, 2, false>(a, st);
-        return a->L == 162 ? launch_fwd3w<11, 162, 4, 2, 2, true>(a, st) : launch_fwd3w<11, 0, 4, 2, 2, true>(a, st);
-    }
-    if (a->L == 162) return launch_fwd3<11, 162, 4, 3, false>(a, st);          // measured best: 49 us at B = 2 (first generation: 72)
-    return launch_fwd3<11, 0, 4, 3, false>(a, st);
+    if (a->L == 162) return launch_fwd3<11, 162, 4, 3>(a, st);          // measured best: 49 us at B = 2 (first generation: 72)
+    return launch_fwd3<11, 0, 4, 3>(a, st);
+}
+
+// measured at B = 2 (800 windows x 8 heads, 24-wide heads): 4 waves x 2 workgroups per CU, two LDS buffers: 90 us with the K / V^T
+// fragments read per row, 80 us with them in registers (227 VGPRs); one buffer at 3 workgroups per CU (spills): 99; 6 waves x 2
+// workgroups (SIMDs loaded 4 / 4 / 2 / 2): 112; first generation: 203
+int swv2_attn_fwd3w(const swv2_attn_args* a, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    return a->L == 162 ? launch_fwd3w<11, 162, 4, 2, 2>(a, st) : launch_fwd3w<11, 0, 4, 2, 2>(a, st);
+}
+
+// with a CPB table in its packed form (swv2_attn_pack_bias): its forward part is the register image, its (max, min) part bounds the
+// fixed-maximum softmax
+int swv2_attn_fwd3b(const swv2_attn_args* a, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    const uint32_t* bpack = (const uint32_t*)a->bias_pack;
+    const float* brange = (const float*)((const char*)a->bias_pack + swv2_attn_bias_range_offset(a->heads, a->L));
+    return a->L == 162 ? launch_fwd3b<11, 162, 4, 3>(a, bpack, brange, st) : launch_fwd3b<11, 0, 4, 2>(a, bpack, brange, st);
 }

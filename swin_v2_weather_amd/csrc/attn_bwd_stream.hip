@@ -62,11 +62,7 @@ __device__ unsigned long long attns_clock[512 * 2];       // per wave: s_memtime
 #define SSTAMP(k) do {} while (0)
 #endif
 
-#ifndef SWV2_ATTNS_NO_PRIO          // (A/B builds)
 #define SWV2_PRIO(n) __builtin_amdgcn_s_setprio(n)
-#else
-#define SWV2_PRIO(n) do {} while (0)
-#endif
 
 template <int LFIX>
 __global__ __launch_bounds__(1024) void attn_bwd_stream_kernel(
@@ -487,12 +483,9 @@ extern "C" int swv2_debug_attns_clock(void* out) {
 }
 #endif
 
-// called by swv2_attn_bwd (attn.hip); returns 1 when this kernel does not cover the shape or is switched off (the caller then runs
-// the two-phase kernel): the 176-row layout with 16-wide head slots, no CPB table.  Window areas: any L <= 176 of the layout (padded
-// keys are switched off inside the operand, padded query rows carry lse = 1e30).
-int swv2_attn_bwd_stream(const swv2_attn_args* a, int Lp, int DP, void* stream) {
-    static const int on = getenv("SWV2_ATTN_BWD_STREAM") ? atoi(getenv("SWV2_ATTN_BWD_STREAM")) : 1;
-    if (!on || Lp != 176 || DP != 16 || a->bias || (a->dbg & (SWV2_ATTN_PLAIN_STATS | SWV2_ATTN_BWD_TWO_PHASE))) return 1;
+// called by swv2_attn_bwd (attn.hip) for the shapes attn_bwd_kernel_for gives it: the 176-row layout with 16-wide head slots, no CPB
+// table.  Window areas: any L <= 176 of the layout (padded keys are switched off inside the operand, padded query rows carry lse = 1e30).
+int swv2_attn_bwd_stream(const swv2_attn_args* a, void* stream) {
     hipStream_t st = (hipStream_t)stream;
     const int nchunk = a->Bw < a->max_chunks ? a->Bw : a->max_chunks;
     dim3 grid(nchunk, a->heads), block(1024);

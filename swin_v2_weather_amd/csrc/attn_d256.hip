@@ -410,9 +410,8 @@ __global__ __launch_bounds__(D256_NT) void attn_bwd_d256_kernel(
     }
 }
 
-// 1 = not the 256-column layout (the caller goes on), 0 = launch, negative = error
-int d256_check(const swv2_attn_args* a, int Lp, int DP) {
-    if (DP != D256_DP) return 1;
+// 0 = launch, negative = error
+int d256_check(const swv2_attn_args* a, int Lp) {
     if (a->bias) {
         swv2_set_error("attention: no CPB bias at head_dim=%d (the 256-column kernels have no table)", a->head_dim);
         return SWV2_ERR_UNSUPPORTED;
@@ -431,9 +430,9 @@ dim3 d256_grid(const swv2_attn_args* a) {
 
 }  // namespace
 
-// the kernel pair for 256-channel heads: 1 = another layout (the caller goes on), 0 = launched, negative = error
-int swv2_attn_fwd_d256(const swv2_attn_args* a, int Lp, int DP, void* stream) {
-    const int rc = d256_check(a, Lp, DP);
+// the kernel pair for 256-channel heads, called by swv2_attn_fwd / swv2_attn_bwd (attn.hip) at DP = 256: 0 = launched, negative = error
+int swv2_attn_fwd_d256(const swv2_attn_args* a, int Lp, void* stream) {
+    const int rc = d256_check(a, Lp);
     if (rc) return rc;
     hipStream_t st = (hipStream_t)stream;
     const int nW = a->nwh * a->nww;
@@ -446,8 +445,8 @@ int swv2_attn_fwd_d256(const swv2_attn_args* a, int Lp, int DP, void* stream) {
     return SWV2_OK;
 }
 
-int swv2_attn_bwd_d256(const swv2_attn_args* a, int Lp, int DP, void* stream) {
-    const int rc = d256_check(a, Lp, DP);
+int swv2_attn_bwd_d256(const swv2_attn_args* a, int Lp, void* stream) {
+    const int rc = d256_check(a, Lp);
     if (rc) return rc;
     hipStream_t st = (hipStream_t)stream;
     const int nW = a->nwh * a->nww;

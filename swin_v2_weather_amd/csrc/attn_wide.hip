@@ -413,16 +413,9 @@ __global__ __launch_bounds__(64 * LT) void attn_fwd_wide_kernel(
 
 }  // namespace
 
-// 0 = launched, 1 = shape not covered (the caller falls back to attn_bwd_kernel), negative = error
-static bool wide_off() { const char* e = getenv("SWV2_ATTN_WIDE"); return e && atoi(e) == 0; }      // (read per call: A/B and tests)
-
-static bool wide_shape(const swv2_attn_args* a, int Lp, int DP) {
-    return !wide_off() && !a->bias && Lp == 176 && (DP == 96 || DP == 128) && a->head_dim > 64 && a->head_dim <= 96 &&
-           !(a->dbg & SWV2_ATTN_FIRST_GEN);
-}
-
-int swv2_attn_bwd_wide(const swv2_attn_args* a, int Lp, int DP, void* stream) {
-    if (!wide_shape(a, Lp, DP)) return 1;
+// the launchers, called by swv2_attn_bwd / swv2_attn_fwd (attn.hip) for the shapes attn_bwd_kernel_for / attn_fwd_kernel_for give them:
+// the 176-row layout, 65 .. 96-channel heads, no CPB table
+int swv2_attn_bwd_wide(const swv2_attn_args* a, int DP, void* stream) {
     hipStream_t st = (hipStream_t)stream;
     const int nW = a->nwh * a->nww;
     // one workgroup (11 waves, 141 KB of LDS) per CU: persistent over the windows of its head
@@ -441,9 +434,7 @@ int swv2_attn_bwd_wide(const swv2_attn_args* a, int Lp, int DP, void* stream) {
     return SWV2_OK;
 }
 
-// the matching forward: same return convention
-int swv2_attn_fwd_wide(const swv2_attn_args* a, int Lp, int DP, void* stream) {
-    if (!wide_shape(a, Lp, DP)) return 1;
+int swv2_attn_fwd_wide(const swv2_attn_args* a, int DP, void* stream) {
     hipStream_t st = (hipStream_t)stream;
     const int nW = a->nwh * a->nww;
     int chunks = 256 / a->heads;            // 79 KB of LDS: one workgroup of 11 waves per CU (two would leave 85 registers per wave)

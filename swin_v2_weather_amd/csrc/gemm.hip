@@ -365,11 +365,7 @@ template <> struct Epi<E_UNPATCH_LOSS> {
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             const uint32_t c = (uint32_t)min((n0 >> 4) + k, Cout - 1);
-#ifdef SWV2_HEAD_ABL_NO_TAR
-            o.t[k] = (f32x4){0.f, 0.f, 0.f, 0.f};
-#else
             o.t[k] = *(const f32x4*)(d.loss_tar + ((rw.tbase + c) * plane + rw.pix));
-#endif
         }
     }
     // The same step on the accumulators of the TRANSPOSED product (D^T = W X^T: lane (token fr, image row p = g) holds the four
@@ -397,12 +393,10 @@ template <> struct Epi<E_UNPATCH_LOSS> {
             const bool ok = rw.ok && c < Cout;
             f32x4 v = acc[k];
             if constexpr (HAS_SKIP) v += *(const f32x4*)((const float*)d.aux + ((rw.sbase + min(c, Cout - 1)) * plane + rw.pix));
-#ifndef SWV2_HEAD_ABL_NO_Y       // (timing ablation: what materialising the prediction costs the loss epilogue)
             *(f32x4*)(outp + (ok ? (rw.ybase + c) * plane + rw.pix : ydump)) = v;
             // rollouts: the next step's input buffer gets the prediction from the same registers (wave-uniform branch around stores
             // only: the counted waits of the common path are unaffected)
             if (d.aux_out) *(f32x4*)(d.aux_out + (ok ? (rw.nbase + c) * plane + rw.pix : ndump)) = v;
-#endif
             const f32x4 dd = v - in.t[k];
             const float e0 = q * (dd[0] * dd[0] + dd[1] * dd[1] + dd[2] * dd[2] + dd[3] * dd[3]);
             const float e1 = q * (in.t[k][0] * in.t[k][0] + in.t[k][1] * in.t[k][1] + in.t[k][2] * in.t[k][2] + in.t[k][3] * in.t[k][3]);
@@ -417,12 +411,8 @@ template <> struct Epi<E_UNPATCH_LOSS> {
         const int r2 = lane >> 2, c0 = (lane & 3) * 16, m2 = m0 + r2, n = n0 + c0;
         const uint4 w0 = *(const uint4*)(st16 + r2 * RP + c0), w1 = *(const uint4*)(st16 + r2 * RP + c0 + 8);
         uint16_t* o = d.loss_resid + ((m2 < d.M && n < d.N) ? (uint32_t)m2 * RPITCH + n : rdump);
-#ifndef SWV2_HEAD_ABL_NO_RESID
         *(uint4*)o = w0;
         *(uint4*)(o + 8) = w1;
-#else
-        if (w0.x == 0x12345678u) { *(uint4*)o = w0; *(uint4*)(o + 8) = w1; }
-#endif
     }
     // loss_part[group][slot][Cout][2]: slot 0 = rows of the sample of the group's first row, slot 1 = rows of the following
     // sample (zero unless the group straddles a boundary).  Lane 63 holds the DPP sums and stores 8 floats per slot.
@@ -487,11 +477,8 @@ template <> struct Epi<E_UNPATCH_LOSS_SKIP> : Epi<E_UNPATCH_LOSS> {};
 // grid quantisation: at 3 workgroups per CU the chip holds 768; 1013 row tiles of 128 (local batch 2) run as 1 full + 1
 // third-full round (66 % of the slots busy on average, measured 12 - 16 us of batch-independent time per launch), 2026
 // tiles of 64 as 2.64 of 3 rounds.
-#ifndef SWV2_HEAD_OCC
-#define SWV2_HEAD_OCC 2
-#endif
 template <int AK, int EK, int BMT = BM>
-__global__ __launch_bounds__(NTHREADS, ((EK == E_UNPATCH_LOSS || EK == E_UNPATCH_LOSS_SKIP) && BMT == 64) ? SWV2_HEAD_OCC : 2) void gemm_nt_kernel(ALoad<AK> al, const uint16_t* __restrict__ Wb, Epi<EK> ep,
+__global__ __launch_bounds__(NTHREADS, 2) void gemm_nt_kernel(ALoad<AK> al, const uint16_t* __restrict__ Wb, Epi<EK> ep,
                                                               int M, int N, int K) {
     // one A|B tile buffer (32 KB) + wave-private epilogue staging (17 KB): 49 KB -> 3 workgroups (12 waves) per CU.
     // Latency hiding comes from the co-resident workgroups plus the register prefetch of the next step's tiles.
@@ -873,13 +860,8 @@ __global__ __launch_bounds__(WTH) void gemm_nt_wide_dma_kernel(ALoad<AK> al, con
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
             const int row = drow + 16 * i;
-#ifdef SWV2_WIDE_SAME_TILE          // (timing ablation: every workgroup streams the first tile's operands -- all L2 hits; wrong results)
-            t.boff[i] = 2u * (uint32_t)(row * K + dkc[i] * 8);
-            t.aoff[i] = AK == A_BF16 ? 2u * (uint32_t)(row * (int)al.d.ld + dkc[i] * 8) : 0u;
-#else
             t.boff[i] = 2u * (uint32_t)(min(t.n_base + row, N - 1) * K + dkc[i] * 8);      // (N = 192, one partial column tile: rows past N re-read the last one, their columns are never stored)
             t.aoff[i] = AK == A_BF16 ? 2u * (uint32_t)(min(t.m_base + row, M - 1) * (int)al.d.ld + dkc[i] * 8) : 0u;
-#endif
         }
         return t;
     };
@@ -917,10 +899,8 @@ __global__ __launch_bounds__(WTH) void gemm_nt_wide_dma_kernel(ALoad<AK> al, con
             for (int j = 0; j < 4; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
         for (int t = 0; t < stages; ++t) {
             // ---- LOAD(t)
-#ifndef SWV2_WIDE_NO_DMA            // (timing ablations, tools/ab_build.sh: wrong results)
             if (t + 3 < stages) issue(cur, t + 3, (t + 3) & 3);
             else issue(nxt, has_next ? t + 3 - stages : stages - 1, (t + 3) & 3);
-#endif
             const uint16_t* As = smem + (t & 3) * WSTG;
             const uint16_t* Bs = As + WBM * 32;
             bf16x8 af[8], bf[4];
@@ -935,15 +915,10 @@ __global__ __launch_bounds__(WTH) void gemm_nt_wide_dma_kernel(ALoad<AK> al, con
             __builtin_amdgcn_sched_barrier(0);
             // ---- MFMA(t)
             __builtin_amdgcn_s_setprio(1);
-#ifdef SWV2_WIDE_NO_MMA
-#pragma unroll
-            for (int i = 0; i < 8; ++i) asm volatile("" :: "v"(af[i]), "v"(bf[i & 3]));
-#else
 #pragma unroll
             for (int i = 0; i < 8; ++i)
 #pragma unroll
                 for (int j = 0; j < 4; ++j) acc[i][j] = mfma32(af[i], bf[j], acc[i][j]);
-#endif
             __builtin_amdgcn_s_setprio(0);
             __builtin_amdgcn_sched_barrier(0);
             __builtin_amdgcn_s_barrier();
@@ -954,11 +929,7 @@ __global__ __launch_bounds__(WTH) void gemm_nt_wide_dma_kernel(ALoad<AK> al, con
         __builtin_amdgcn_sched_barrier(0);
         {
             float* st = (float*)(smem + 3 * WSTG) + wave * 16 * EP;
-#ifndef SWV2_WIDE_NO_EPI            // (timing ablation)
             if (cur.n_base + wc * 64 < N) wide_epilogue<EK>(ep, acc, st, cur.m_base + wr * 128, cur.n_base + wc * 64, lane);      // (N: a multiple of 64)
-#else
-            for (int i = 0; i < 8; ++i) asm volatile("" :: "v"(acc[i][0]), "v"(acc[i][1]), "v"(acc[i][2]), "v"(acc[i][3]));
-#endif
         }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");     // the staging reads are done before slot 3 is handed back
         __builtin_amdgcn_sched_barrier(0);
@@ -1466,9 +1437,8 @@ int launch_nt2(const swv2_operand* a, const void* w, const swv2_epilogue* e, int
         ep.d.q3 = (int)(nb * e->ld * plane);
     }
     // the two per-block products at the benchmark width: resident-weight persistent kernel
-    static const int rw = getenv("SWV2_GEMM_RW") ? atoi(getenv("SWV2_GEMM_RW")) : 1;
     if constexpr (AK == A_F32 && EK == E_QKV_HEADS) {
-        if (rw && N == 384 && K == 128 && M >= 256 * 128 && e->p[3] == 16 && a->rowidx) {
+        if (N == 384 && K == 128 && M >= 256 * 128 && e->p[3] == 16 && a->rowidx) {
             Epi<EK> ep1 = ep;
             ep1.d.p1 = 0;                                 // (first part of the launch's columns; p[1] is not a parameter of this epilogue)
             hipLaunchKernelGGL((gemm_rw_kernel<AK, EK, 384, 128, 128>), dim3(256), dim3(512), 0, st, make_loader<AK>(a),
@@ -1479,7 +1449,7 @@ int launch_nt2(const swv2_operand* a, const void* w, const swv2_epilogue* e, int
         // BASELINE configs[4] (192 channels, 8 heads in 32-wide slots): the 768 x 192 weight does not fit LDS beside an A tile, one
         // of its q / k / v parts (256 x 192 = 96 KB) does: three launches, each over all rows (the gathered fp32 rows are read three
         // times, 3 x 108 MB, against the generic kernel's re-read of the weight per 64-row tile: 207 -> 3 x ~45 us)
-        if (rw && N == 768 && K == 192 && M >= 256 * 128 && e->p[3] == 32 && e->p[0] == 8 && a->rowidx) {
+        if (N == 768 && K == 192 && M >= 256 * 128 && e->p[3] == 32 && e->p[0] == 8 && a->rowidx) {
             for (int part = 0; part < 3; ++part) {
                 Epi<EK> ep2 = ep;
                 ep2.d.N = 256;
@@ -1493,7 +1463,7 @@ int launch_nt2(const swv2_operand* a, const void* w, const swv2_epilogue* e, int
         }
     }
     if constexpr (AK == A_HEADS && EK == E_F32) {
-        if (rw && N == 128 && K == 384 && M >= 256 * 64 && e->rowidx && e->aux && !a->rowidx) {
+        if (N == 128 && K == 384 && M >= 256 * 64 && e->rowidx && e->aux && !a->rowidx) {
             hipLaunchKernelGGL((gemm_rw_kernel<AK, EK, 128, 384, 64>), dim3(256), dim3(512), 0, st, make_loader<AK>(a),
                                (const uint16_t*)w, ep, M);
             SWV2_CHECK_LAUNCH("swv2_linear");
@@ -1535,8 +1505,7 @@ int launch_nt2(const swv2_operand* a, const void* w, const swv2_epilogue* e, int
     if constexpr ((AK == A_F32 && EK == E_QKV_HEADS) || (AK == A_HEADS && EK == E_F32)) {
         const double w1 = cdiv(M, BM), w2 = cdiv(M, BM / 2), slots = 768.0;
         const double e1 = w1 / (std::ceil(w1 / slots) * slots), e2 = w2 / (std::ceil(w2 / slots) * slots);
-        static const int force = getenv("SWV2_GEMM_BM") ? atoi(getenv("SWV2_GEMM_BM")) : 0;
-        half = force ? force == 64 : (e2 > e1 + 0.08);
+        half = e2 > e1 + 0.08;
         if (half)
             hipLaunchKernelGGL((gemm_nt_kernel<AK, EK, BM / 2>), dim3(cdiv(M, BM / 2)), dim3(NTHREADS), 0, st, make_loader<AK>(a),
                                (const uint16_t*)w, ep, M, N, K);

@@ -586,14 +586,11 @@ int swv2_block_wgrad_ln(const swv2_wgrad_item* it, int slices, void* ws, size_t 
         tt += cdiv(it[i].dy.cols, BN) * cdiv(it[i].x.cols, BN);
     }
     g.first[4] = tt;
-    // second-generation kernel (gemm_tn_slab.hip: operands fetched once, by LDS-DMA) for the shapes it covers; SWV2_WGRAD_SLAB=0
-    // and an explicit slice count select the 128 x 128 tile kernel below
-    {
-        static const int use_slab = getenv("SWV2_WGRAD_SLAB") ? atoi(getenv("SWV2_WGRAD_SLAB")) : 1;
-        if (use_slab && slices <= 0) {
-            const int rc = swv2_tn_slab_launch(it, ws, ws_bytes, ln, (hipStream_t)stream);
-            if (rc <= 0) return rc;
-        }
+    // second-generation kernel (gemm_tn_slab.hip: operands fetched once, by LDS-DMA) for the shapes it covers; an explicit slice
+    // count selects the 128 x 128 tile kernel below
+    if (slices <= 0) {
+        const int rc = swv2_tn_slab_launch(it, ws, ws_bytes, ln, (hipStream_t)stream);
+        if (rc <= 0) return rc;
     }
     const int S = group_slices(tt, slices);
     SWV2_CHECK_ARG(ws_bytes >= (size_t)S * tt * BN * BN * sizeof(float), "swv2_block_wgrad: workspace of %zu bytes, %zu needed",

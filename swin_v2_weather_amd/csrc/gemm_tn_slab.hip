@@ -308,10 +308,6 @@ __device__ __forceinline__ void slab_job(const SlProd& P, const int j, unsigned 
                 }
                 __syncthreads();
             }
-#if defined(SWV2_SLAB_ABL) && (SWV2_SLAB_ABL & 1)      // timing ablation (tools/build_variant.sh): pure streaming, wrong results
-            issue(ti_n, slot_n);
-            continue;
-#endif
             if constexpr (XF32) {                     // fp32 slab -> bf16 slab (row-major, swizzled), 8 elements per thread and pass
                 constexpr int NCH = SR * TK / 8, NPASS = (NCH + SL_TH - 1) / SL_TH;
                 uint16_t* const xdst = INPLACE ? (uint16_t*)(sb + YB) : xbs;
@@ -363,7 +359,6 @@ __device__ __forceinline__ void slab_job(const SlProd& P, const int j, unsigned 
                         b1 = tr_row(Xs, std::integral_constant<int, TK>{}, 32 * kk + 16, k_w + 16 * jj);
                     }
                     bf16x8 b = __builtin_shufflevector(b0, b1, 0, 1, 2, 3, 4, 5, 6, 7);
-#if !defined(SWV2_SLAB_ABL) || !(SWV2_SLAB_ABL & 2)    // (& 2: timing ablation without the GELU lookups, wrong results)
                     if constexpr (FX == F_ROWG) {
                         const uint4 raw = __builtin_bit_cast(uint4, b);
                         bool bad;
@@ -371,7 +366,6 @@ __device__ __forceinline__ void slab_job(const SlProd& P, const int j, unsigned 
                         if (__builtin_expect(__any((int)bad), 0)) gv = glf.cvt(raw);       // formula (no table set on glf)
                         b = __builtin_bit_cast(bf16x8, gv);
                     }
-#endif
                     [&]<int... KK>(std::integer_sequence<int, KK...>) {          // (kk is a run-time loop variable of an unrolled loop)
                         ((kk == KK ? issue_point(ti_n, slot_n, std::integral_constant<int, 1 + KK * JB + jj>{}) : (void)0), ...);
                     }(std::make_integer_sequence<int, KS>{});
@@ -430,9 +424,6 @@ __device__ __forceinline__ void slab_job(const SlProd& P, const int j, unsigned 
     // every store instruction writes 1 KB of contiguous memory with no LDS staging and no wait between the stores (through a row-major
     // staging tile the 54 MB of partials took 20 us of the launch).  Chunk c = (wave IA + i) JB + jj of tile `tile`; the S slices of one
     // chunk lie next to each other ([chunk][slice][256]) so that the reduction reads S contiguous KB per chunk.
-#if defined(SWV2_SLAB_ABL) && (SWV2_SLAB_ABL & 4)      // timing ablation: no partial stores, wrong results
-    if (M < 0)
-#endif
     {
         constexpr int CPT = 8 * IA * JB;             // chunks per tile
         sl_part_t* out = P.part + ((size_t)(tile * CPT + wave * IA * JB) * S + slice) * 256 + lane * 4;
@@ -466,16 +457,13 @@ __device__ __forceinline__ void slab_job(const SlProd& P, const int j, unsigned 
 }
 
 // shape set 0: C = 128, hidden = 512, 8 heads x 16 columns (the BASELINE cfg 2 / 3 / 5 block)
-#ifndef SWV2_SLAB_NS
-#define SWV2_SLAB_NS 3
-#endif
 __global__ __launch_bounds__(SL_TH) void gemm_tn_slab_c128_kernel(SlArgs a) {
     __shared__ __attribute__((aligned(1024))) unsigned char smem[SL_SMEM];
     const int b = blockIdx.x;
-    if (b < a.p[1].first) slab_job<F_ROW, F_ROWG, 128, 512, 1, 8, 32, SWV2_SLAB_NS>(a.p[0], b - a.p[0].first, smem, a.stamps);          // fc2: d(a2)^T GELU(hpre)
-    else if (b < a.p[2].first) slab_job<F_ROW, F_F32, 512, 128, 8, 1, 32, SWV2_SLAB_NS>(a.p[1], b - a.p[1].first, smem, a.stamps);      // fc1: d(h)^T x1
-    else if (b < a.p[3].first) slab_job<F_ROW, F_HEAD, 128, 128, 2, 4, 64, SWV2_SLAB_NS + 1>(a.p[2], b - a.p[2].first, smem, a.stamps); // proj: d(a1)^T merge(oh)
-    else slab_job<F_HEAD, F_F32G, 384, 128, 8, 1, 32, SWV2_SLAB_NS>(a.p[3], b - a.p[3].first, smem, a.stamps);                          // qkv: d(qkv)^T gather(x)
+    if (b < a.p[1].first) slab_job<F_ROW, F_ROWG, 128, 512, 1, 8, 32, 3>(a.p[0], b - a.p[0].first, smem, a.stamps);          // fc2: d(a2)^T GELU(hpre)
+    else if (b < a.p[2].first) slab_job<F_ROW, F_F32, 512, 128, 8, 1, 32, 3>(a.p[1], b - a.p[1].first, smem, a.stamps);      // fc1: d(h)^T x1
+    else if (b < a.p[3].first) slab_job<F_ROW, F_HEAD, 128, 128, 2, 4, 64, 4>(a.p[2], b - a.p[2].first, smem, a.stamps); // proj: d(a1)^T merge(oh)
+    else slab_job<F_HEAD, F_F32G, 384, 128, 8, 1, 32, 3>(a.p[3], b - a.p[3].first, smem, a.stamps);                          // qkv: d(qkv)^T gather(x)
 }
 // shape set 1: C = 192, hidden = 768, 8 heads x 32 columns (head dim 24 padded: the BASELINE cfg 4 block).  The outputs of fc2 / fc1 /
 // qkv (192 x 768) do not fit one workgroup's registers: two column tiles each (the narrow operand is read twice).
@@ -582,9 +570,6 @@ __global__ __launch_bounds__(512) void tn_slab_reduce_kernel(SlRedArgs a) {
 #endif
     f32x4 s0 = {0.f, 0.f, 0.f, 0.f}, s1 = s0, s2 = s0, s3 = s0;
     int s = sl0;
-#if defined(SWV2_SLAB_ABL) && (SWV2_SLAB_ABL & 8)      // timing ablation: one slice only (fixed cost of the reduction launch)
-    s = p.S;
-#endif
     for (; s + 3 * NG < p.S; s += 4 * NG) {
         s0 += ld(src + (size_t)s * 256);
         s1 += ld(src + (size_t)(s + NG) * 256);
@@ -649,10 +634,9 @@ SlPlan sl_plan(const swv2_wgrad_item* it, int cus) {
     if (cus < 16 || cus > 1024) return p;
     // bytes per row of each product; rows in proportion so that every workgroup streams about the same number of bytes
     double cost[4], tot = 0;
-    // measured weights on top of the byte counts (tools/probe_wgrad_slab.py, SWV2_SLAB_WEIGHTS sweep): the fc2 workgroups carry the
-    // GELU lookups (LDS gathers) and need ~1.5 x the time per byte of the others; the optimum is flat (+- 2 us from 1.4 to 1.7)
-    double wgt[4] = {1.55, 1.0, 1.0, 1.1};
-    if (const char* e = getenv("SWV2_SLAB_WEIGHTS")) sscanf(e, "%lf,%lf,%lf,%lf", &wgt[0], &wgt[1], &wgt[2], &wgt[3]);
+    // measured weights on top of the byte counts (a sweep of the four weights): the fc2 workgroups carry the GELU lookups (LDS
+    // gathers) and need ~1.5 x the time per byte of the others; the optimum is flat (+- 2 us from 1.4 to 1.7)
+    const double wgt[4] = {1.55, 1.0, 1.0, 1.1};
     for (int i = 0; i < 4; ++i) {
         const double xb = it[i].x.kind == SWV2_OP_F32 ? 4.0 : 2.0;
         p.ntile[i] = (N[i] / sh.TN[i]) * (K[i] / sh.TK[i]);
@@ -739,9 +723,6 @@ int swv2_tn_slab_launch(const swv2_wgrad_item* it, void* ws, size_t ws_bytes, co
     int cpw = 2;
     for (int i = 0; i < 4; ++i)
         if (pl.S[i] > 40 || ((it[i].dy.cols * it[i].x.cols / 256) & 1)) cpw = 1;
-    if (const char* e = getenv("SWV2_SLAB_RED_CPW")) cpw = atoi(e) == 2 ? 2 : 1;
-    for (int i = 0; i < 4 && cpw == 2; ++i)
-        if ((it[i].dy.cols * it[i].x.cols / 256) & 1) cpw = 1;
     r.cpw = cpw;
     for (int i = 0; i < 4; ++i) {
         SlProd& p = a.p[i];

@@ -219,9 +219,7 @@ __global__ __launch_bounds__(256, 2) void mlp_fwd_kernel(const MlpFwd a) {
             }
         }
         STAMP(5);
-#ifndef SWV2_MLP_ABL_NO_BARRIER      // (timing ablation, wrong results: tools/build_variant.sh)
         __syncthreads();
-#endif
         STAMP(6);
     };
     // residual rows and drop-path scales of ALL row passes, unconditionally: loaded inside the pass loop each one was a
@@ -765,8 +763,7 @@ extern "C" int swv2_mlp_fwd(const swv2_mlp_args* a, void* stream) {
     hipStream_t st = (hipStream_t)stream;
     // rows per workgroup (64 * MT): two tiles per wave halve the LDS fragment reads per MFMA (measured at C = 128,
     // M = 129600: 113 us vs 138 us), one tile keeps small problems spread over the CUs
-    static const int force_mt = getenv("SWV2_MLP_MT") ? atoi(getenv("SWV2_MLP_MT")) : 0;
-    const bool mt2 = force_mt ? force_mt == 2 : a->M >= 128 * 256;
+    const bool mt2 = a->M >= 128 * 256;
     switch (a->C) {
         case 32: mt2 ? launch_mlp_fwd<32, 2>(k, st) : launch_mlp_fwd<32, 1>(k, st); break;
         case 64: mt2 ? launch_mlp_fwd<64, 2>(k, st) : launch_mlp_fwd<64, 1>(k, st); break;
@@ -774,11 +771,10 @@ extern "C" int swv2_mlp_fwd(const swv2_mlp_args* a, void* stream) {
         case 128: mt2 ? launch_mlp_fwd<128, 2>(k, st) : launch_mlp_fwd<128, 1>(k, st); break;
         case 192: {
             // <192, 2>: 94 KB of LDS and 359 registers, ONE 4-wave workgroup per CU (cfg 4: 47.8 -> 45.7 ms/step against <192, 1> at one
-            // workgroup per CU); <192, 1> with its fc1-bias table trimmed fits twice (SWV2_MLP_FWD192=2 restores two row tiles)
-            static const int v192 = getenv("SWV2_MLP_FWD192") ? atoi(getenv("SWV2_MLP_FWD192")) : 1;
+            // workgroup per CU); <192, 1> with its fc1-bias table trimmed fits twice
             // <192, 1> holds an fc1-bias table of 1 024 entries (mlp_fwd_kernel::B1N): wider hidden layers run <192, 2> whatever the row
             // count (selected on `mt2 &&` the small-M case wrote past the table)
-            (a->hidden > 1024 || (mt2 && v192 == 2)) ? launch_mlp_fwd<192, 2>(k, st) : launch_mlp_fwd<192, 1>(k, st);
+            a->hidden > 1024 ? launch_mlp_fwd<192, 2>(k, st) : launch_mlp_fwd<192, 1>(k, st);
             break;
         }
         case 256: launch_mlp_fwd<256, 1>(k, st); break;
@@ -807,9 +803,7 @@ int swv2_mlp_bwd_impl(const swv2_mlp_bwd_args* a, void* stream, int* deferred, f
                 (const uint16_t*)a->w2t, (const uint16_t*)a->w1t, (uint16_t*)a->da2, (uint16_t*)a->dh, a->dx, a->ws, a->M,
                 a->hidden, a->rows_per_sample, zero, zero_n, a->x, (const uint16_t*)a->w1, a->b1};
     hipStream_t st = (hipStream_t)stream;
-    static const int force_mt = getenv("SWV2_MLP_MT") ? atoi(getenv("SWV2_MLP_MT")) : 0;
-    const bool mt2 = force_mt ? force_mt == 2 : a->M >= 128 * 256;      // measured at C = 128, M = 129600: 170 us vs 185 us
-    bool two192 = false;
+    const bool mt2 = a->M >= 128 * 256;      // measured at C = 128, M = 129600: 170 us vs 185 us
     switch (a->C) {
         case 32: mt2 ? launch_mlp_bwd<32, 2>(k, st) : launch_mlp_bwd<32, 1>(k, st); break;
         case 64: mt2 ? launch_mlp_bwd<64, 2>(k, st) : launch_mlp_bwd<64, 1>(k, st); break;
@@ -818,16 +812,13 @@ int swv2_mlp_bwd_impl(const swv2_mlp_bwd_args* a, void* stream, int* deferred, f
         case 192: {
             // measured on BASELINE configs[4] (B = 2, ms per step): one row tile per wave, two workgroups per CU, GELU' by formula (the
             // full table does not fit beside two workgroups; since round 5 its positive half does, GHALF): 35.5; the same with the table and one workgroup per CU: 38.3; two row tiles
-            // per wave (302 registers, one workgroup per CU, table; SWV2_MLP_BWD192=2): 37.2
-            static const int v192 = getenv("SWV2_MLP_BWD192") ? atoi(getenv("SWV2_MLP_BWD192")) : 0;
-            two192 = k.hpre && mt2 && v192 == 2;
-            if (two192) hipLaunchKernelGGL((mlp_bwd_kernel<192, 2, false>), dim3(cdiv(k.M, 128)), dim3(256), 0, st, k);
-            else launch_mlp_bwd<192, 1>(k, st);
+            // per wave (302 registers, one workgroup per CU, table): 37.2
+            launch_mlp_bwd<192, 1>(k, st);
             break;
         }
         case 256: launch_mlp_bwd<256, 1>(k, st); break;
     }
-    const bool two = ((a->C <= 128) && mt2) || two192;
+    const bool two = (a->C <= 128) && mt2;
     if (deferred) *deferred = cdiv(a->M, two ? 128 : 64);
     else swv2_launch_ln_partials_reduce(a->ws, a->dgamma, a->dbeta, cdiv(a->M, two ? 128 : 64), a->C, st);
     SWV2_CHECK_LAUNCH("swv2_mlp_bwd");

@@ -363,8 +363,7 @@ extern "C" int swv2_proj_ln_fwd(const swv2_proj_ln_args* a, void* stream) {
     ProjLnFwd k = {(const uint16_t*)a->oh, (const uint16_t*)a->wp, a->bp, a->gamma, a->beta, a->scale, a->rowidx, a->x,
                    (uint16_t*)a->a1, a->mean, a->rstd, a->y, Mw, a->Lp, a->heads, a->rows_per_sample, a->eps};
     hipStream_t st = (hipStream_t)stream;
-    static const int force_mt = getenv("SWV2_PL_MT") ? atoi(getenv("SWV2_PL_MT")) : 0;
-    const bool mt2 = force_mt ? force_mt == 2 : Mw >= 128 * 256;
+    const bool mt2 = Mw >= 128 * 256;
 #define PL_CASE(CC)                                                                                                  \
     case CC:                                                                                                         \
         if (mt2) hipLaunchKernelGGL((proj_ln_fwd_kernel<CC, 2>), dim3(cdiv(Mw, 128)), dim3(256), 0, st, k);          \
@@ -393,8 +392,7 @@ int swv2_proj_ln_bwd_impl(const swv2_proj_ln_bwd_args* a, void* stream, int* def
     ProjLnBwd k = {a->dy, (const uint16_t*)a->a1, a->mean, a->rstd, a->gamma, a->scale, a->rowidx, (const uint16_t*)a->wpt,
                    (uint16_t*)a->da1, (uint16_t*)a->doh, a->ws, Mw, a->Lp, a->heads, a->rows_per_sample};
     hipStream_t st = (hipStream_t)stream;
-    static const int force_mtb = getenv("SWV2_PL_MT_BWD") ? atoi(getenv("SWV2_PL_MT_BWD")) : 0;
-    const bool mt2 = force_mtb ? force_mtb == 2 : Mw >= 128 * 256;
+    const bool mt2 = Mw >= 128 * 256;
 #define PL_CASE(CC)                                                                                                  \
     case CC:                                                                                                         \
         if (mt2) hipLaunchKernelGGL((proj_ln_bwd_kernel<CC, 2>), dim3(cdiv(Mw, 128)), dim3(256), 0, st, k);          \

@@ -1,7 +1,7 @@
 #!/bin/bash
 # Same-box A/B of a compile-time variant: builds a private copy of the library with the given -D macros, then alternates
 # bench.py runs with the shipped and the private library (box-to-box variance is +-1.5 %, a same-box pair is needed for
-# small effects).  Usage on the GPU box: tools/ab_macro.sh "-DSWV2_TN_GELU_ABL" [bench args...]
+# small effects).  Usage on the GPU box: tools/ab_macro.sh "-DSWV2_SLAB_PART_F32" [bench args...]
 set -e
 MACROS="$1"; shift
 SO=/tmp/libswv2_ab.so

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Build a variant of the library in the build container: recompile ONE source with extra -D macros, link with the shipped objects.
-# usage: tools/build_variant.sh attn.hip "-DSWV2_BWD_PIPE=2" tools/r05/_so/libswv2_p2.so   (select it with SWV2_LIB=...)
+# usage: tools/build_variant.sh gemm_tn_slab.hip "-DSWV2_SLAB_PART_F32" tools/_so/libswv2_f32.so   (select it with SWV2_LIB=...)
 set -e
 cd "$(dirname "$0")/.."
 SRC=$1; MACROS=$2; OUT=$3

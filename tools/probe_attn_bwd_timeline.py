@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """Timeline of ONE window of one workgroup of the streamed attention backward (GPU box; stamped library from tools/build_stamped.sh in PROBE_SO).
 Needs the event instrumentation (swv2_debug_attns_tl) of tools/experiments/attn_bwd_stream_nobar.hip: copy that file over csrc/attn_bwd_stream.hip in a
-scratch checkout (its macros select every form of LABNOTES round 6, second pass; -DSWV2_ATTNS_TAIL=0 -DSWV2_ATTNS_ISSUE_PRIO=0 -DSWV2_ATTNS_PREFETCH_ALL=0 is the
-shipped kernel), build with tools/build_stamped.sh:
+scratch checkout (its macros select every form of LABNOTES round 6, second pass; their defaults are the shipped kernel), build with
+tools/build_stamped.sh:
 every wave's events in cycles since the window's start.  Tags: 15 window start, 8 + p phase-1 signal of pair p, 1 phase 1 done, 4 dK / dV stored,
 0 prefetch issued, 2 pair counter reached, 3 dQ pass done, 5 commit done, 6 behind the barrier."""
 import ctypes, os, sys, torch

@@ -1,16 +1,7 @@
 #!/usr/bin/env python3
-"""Ablation probe of mlp_fwd: times the kernel as built (`normal`) or privately rebuilt with a macro given as the first
-argument (SWV2_MLP_GELU_ABL=1: no GELU, wrong results; SWV2_MLP_GELU_ABL=2: erf formula instead of the table) -- GPU box."""
-import os, subprocess, sys, torch
+"""Timing probe of mlp_fwd at the benchmark block shape (C 128, hidden 512, B = 2) -- GPU box."""
+import os, sys, torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__))); sys.path.insert(0, ROOT)
-from swin_v2_weather_amd import _lib as L
-variant = sys.argv[1] if len(sys.argv) > 1 else "normal"
-if variant != "normal":                       # e.g. SWV2_MLP_GELU_ABL=1 (no GELU), SWV2_MLP_GELU_ABL=2 (formula instead of the table)
-    so = "/tmp/libswv2_probe.so"
-    srcs = [os.path.join(L.CSRC, s) for s in L.SOURCES]
-    subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-D" + variant, "-o", so] + srcs,
-                          stderr=subprocess.DEVNULL)
-    L.LIB_PATH = so
 from swin_v2_weather_amd import ops
 dev = torch.device("cuda:0")
 T, Cc, hid = 64800, 128, 512
@@ -29,4 +20,4 @@ e0.record()
 for i in range(30):
     run(i)
 e1.record(); torch.cuda.synchronize()
-print(f"mlp_fwd {variant}: {e0.elapsed_time(e1) / 30 * 1e3:.1f} us per launch (incl. output allocation)")
+print(f"mlp_fwd: {e0.elapsed_time(e1) / 30 * 1e3:.1f} us per launch (incl. output allocation)")
