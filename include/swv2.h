@@ -230,9 +230,13 @@ int swv2_linear_wgrad_ws(const swv2_operand* dy, const swv2_operand* x, float* d
 
 /* The four weight gradients of one transformer block in ONE launch + one reduction (item 0: fc2 = (BF16, BF16_GELU),
  * 1: fc1 = (BF16, F32), 2: proj = (BF16, HEADS), 3: qkv = (HEADS, F32); any other operand kinds -> SWV2_ERR_INVALID).
- * Same results as four swv2_linear_wgrad_ws calls up to the summation order of the row slices.  slices = 0 picks the
- * count that fills the chip in one round (2 workgroups per CU); ws >= swv2_block_wgrad_ws_bytes(C, hidden, heads * DP,
- * slices) bytes.  Replaces: the autograd of the block's four nn.Linear weights (swinv2_global.py:146-201, 231-248). */
+ * slices > 0, and slices = 0 at block shapes the slab kernel does not cover, run the 128 x 128 tile kernel: the results of
+ * four swv2_linear_wgrad_ws calls up to the summation order of the row slices (count: slices; 0 = one round of 2 workgroups
+ * per CU).  slices = 0 at the slab kernel's shapes (gemm_tn_slab.hip: C 128 / hidden 512 / 8 x 16 head columns, C 192 / 768 /
+ * 8 x 32) runs one workgroup per CU, each rounding its partial dW tile to bf16 before the fp32 fold: per element
+ * |dW - exact| <= 2^-8 sum_m |dY[m][n] X[m][k]| instead of the fp32 paths' ~1e-7 of it (bias gradients stay fp32).
+ * ws >= swv2_block_wgrad_ws_bytes(C, hidden, heads * DP, slices) bytes.  Replaces: the autograd of the block's four
+ * nn.Linear weights (swinv2_global.py:146-201, 231-248). */
 typedef struct swv2_wgrad_item {
     swv2_operand dy, x;
     float* dW;
