@@ -30,8 +30,9 @@ extern "C" {
  * 100 rounds 1 - 4; 105 round 5: swv2_attn_args.dbias_partials, swv2_block_desc.bias_prepacked / dbias_part, the *_multi CPB
  * entry points, swv2_attn_pack_bias_multi / swv2_attn_bias_chunks, a (max, min) part in the packed bias buffer;
  * 106: SWV2_EPI_UNPATCH_LOSS writes slot 1 of loss_part only where swv2_loss_part_reduce reads it; 107: swv2_epilogue.q[3], the loss
- * epilogue with the rollout destinations. */
-#define SWV2_VERSION 107
+ * epilogue with the rollout destinations; 108: the kernel-selection queries swv2_linear_kernel, swv2_linear_wgrad_kernel,
+ * swv2_block_wgrad_kernel. */
+#define SWV2_VERSION 108
 
 enum {
     SWV2_OK = 0,
@@ -215,6 +216,19 @@ typedef struct swv2_epilogue {
 
 int swv2_linear(const swv2_operand* a, const void* w_bf16, const swv2_epilogue* e, int N, void* stream);
 
+/* Which kernel swv2_linear launches for these descriptors: one of SWV2_LINEAR_*, or a negative error for a kind pair it does not
+ * serve.  Pure host function: reads the descriptors' kinds, sizes and p[], tests rowidx / aux for presence only, dereferences no data
+ * pointer, launches nothing, needs no GPU.  The launcher switches on the same selection function, and the tests assert on this answer
+ * where they name a path.  SWV2_GEMM_WIDE (environment, default 1; 0 = the tile kernels in place of the wide ones) is read per call. */
+#define SWV2_LINEAR_RESIDENT_QKV128 0   /* resident-weight qkv product at C 128 (N 384, 16-wide head slots, gathered fp32 rows)          */
+#define SWV2_LINEAR_RESIDENT_QKV192X3 1 /* the same at C 192 (N 768, 8 heads in 32-wide slots): three launches, one per q / k / v part */
+#define SWV2_LINEAR_RESIDENT_DX128 2    /* resident-weight d(qkv) -> dx product at C 128 (N 128, K 384, residual add + scatter)        */
+#define SWV2_LINEAR_WIDE_DMA 3          /* 256 x 256 tiles, operand staged by LDS-DMA (raw bf16 rows, head-major layouts)              */
+#define SWV2_LINEAR_WIDE 4              /* 256 x 256 tiles, operand staged through registers (fp32 or gathered rows)                   */
+#define SWV2_LINEAR_TILE64 5            /* 64-row x 128-column tiles                                                                   */
+#define SWV2_LINEAR_TILE128 6           /* 128 x 128 tiles                                                                             */
+int swv2_linear_kernel(const swv2_operand* a, const swv2_epilogue* e, int N);
+
 /* Weight gradient: dW[nmap(n)][kmap(k)] += sum_m dY[m][n] X[m][k], db[nmap(n)] += sum_m dY[m][n]  (caller zeroes; db
  * may be NULL).  dW has row pitch ldw; nmap/kmap (NULL = identity, negative = drop) undo the head padding of the
  * SWV2_OP_HEADS layouts.  splits > 0 = number of row slices processed by different workgroups (x 2 for outputs of fewer
@@ -227,6 +241,11 @@ int swv2_linear_wgrad(const swv2_operand* dy, const swv2_operand* x, float* dW, 
 size_t swv2_linear_wgrad_ws_bytes(int M, int N, int K, int splits);
 int swv2_linear_wgrad_ws(const swv2_operand* dy, const swv2_operand* x, float* dW, float* db, const int32_t* nmap,
                          const int32_t* kmap, int ldw, int splits, void* ws, size_t ws_bytes, void* stream);
+/* Which kernel swv2_linear_wgrad_ws launches for operands the launcher accepts (ws_bytes = 0: no workspace, the atomic path of
+ * swv2_linear_wgrad): SWV2_WGRAD_*, or a negative error.  Pure host function like swv2_linear_kernel; reads SWV2_GEMM_WIDE per call. */
+#define SWV2_WGRAD_WIDE 0               /* 256 x 256 tiles by LDS-DMA, partial matrices in the workspace (N, K >= 512) */
+#define SWV2_WGRAD_TILE 1               /* 128 x 128 tiles: atomics, or per-slice partial tiles in the workspace       */
+int swv2_linear_wgrad_kernel(const swv2_operand* dy, const swv2_operand* x, int splits, size_t ws_bytes);
 
 /* The four weight gradients of one transformer block in ONE launch + one reduction (item 0: fc2 = (BF16, BF16_GELU),
  * 1: fc1 = (BF16, F32), 2: proj = (BF16, HEADS), 3: qkv = (HEADS, F32); any other operand kinds -> SWV2_ERR_INVALID).
@@ -247,6 +266,12 @@ typedef struct swv2_wgrad_item {
 } swv2_wgrad_item;
 size_t swv2_block_wgrad_ws_bytes(int C, int hidden, int heads_dp, int slices);
 int swv2_block_wgrad(const swv2_wgrad_item* items4, int slices, void* ws, size_t ws_bytes, void* stream);
+/* Which kernel swv2_block_wgrad launches: SWV2_BLOCK_WGRAD_*, or a negative error.  Pure host function like swv2_linear_kernel.  The
+ * slab kernel's plan depends on the CU count of the calling thread's current device; in a process without a GPU the answer is the one
+ * for 256 CUs (the library's fallback count). */
+#define SWV2_BLOCK_WGRAD_SLAB 0         /* gemm_tn_slab.hip: slices = 0 at its two block shapes with a workspace that holds its plan */
+#define SWV2_BLOCK_WGRAD_GROUPED 1      /* the grouped 128 x 128 tile kernel                                                          */
+int swv2_block_wgrad_kernel(const swv2_wgrad_item* items4, int slices, size_t ws_bytes);
 
 /* Head dims 65 .. 128 (DP = 96 up to 96 channels, else 128): SWV2_EPI_QKV_HEADS then leaves the squared norms of q, k in rnorm (which the
  * caller zeroes first) and un-normalised values in qkvh; this pass finishes F.normalize (swinv2_global.py:300-304):

@@ -15,7 +15,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIB_PATH = os.environ.get("SWV2_LIB") or os.path.join(HERE, "libswv2.so")     # SWV2_LIB: a privately built variant (tools/ab_macro.sh)
 SOURCES = ["capi.hip", "attn.hip", "attn2.hip", "attn_bwd_stream.hip", "attn_wide.hip", "attn_d256.hip", "gemm.hip", "gemm_tn.hip", "gemm_tn_slab.hip", "rowops.hip", "block.hip", "cpb.hip", "mlp.hip", "proj_ln.hip", "dataio.hip"]
 
-ABI_VERSION = 107          # SWV2_VERSION of the include/swv2.h these ctypes mirrors were written against (checked in load())
+ABI_VERSION = 108          # SWV2_VERSION of the include/swv2.h these ctypes mirrors were written against (checked in load())
 
 _lib = None
 _lock = threading.Lock()
@@ -158,6 +158,11 @@ class BlockDesc(C.Structure):
 
 OP_F32, OP_BF16, OP_BF16_GELU, OP_HEADS, OP_PATCH, OP_MERGE_LN, OP_BF16_CSCALE = range(7)
 EPI_BF16, EPI_F32, EPI_QKV_HEADS, EPI_GELU_GRAD, EPI_UNPATCH, EPI_HEADS, EPI_F32_ACC, EPI_BF16_GELU, EPI_UNPATCH_LOSS = range(9)
+# answers of the kernel-selection queries swv2_linear_kernel / swv2_linear_wgrad_kernel / swv2_block_wgrad_kernel (SWV2_LINEAR_* ...)
+LINEAR_RESIDENT_QKV128, LINEAR_RESIDENT_QKV192X3, LINEAR_RESIDENT_DX128, LINEAR_WIDE_DMA, LINEAR_WIDE, LINEAR_TILE64, LINEAR_TILE128 = range(7)
+LINEAR_WIDE_KERNELS, LINEAR_TILE_KERNELS = (LINEAR_WIDE_DMA, LINEAR_WIDE), (LINEAR_TILE64, LINEAR_TILE128)
+WGRAD_WIDE, WGRAD_TILE = range(2)
+BLOCK_WGRAD_SLAB, BLOCK_WGRAD_GROUPED = range(2)
 
 # every symbol include/swv2.h declares: (name, restype, argtypes)
 _P, _I, _L, _F = C.c_void_p, C.c_int, C.c_long, C.c_float
@@ -174,6 +179,9 @@ SYMBOLS = {
     "swv2_attn_fwd": (_I, [C.POINTER(AttnArgs), _P]),
     "swv2_attn_bwd": (_I, [C.POINTER(AttnArgs), _P]),
     "swv2_linear": (_I, [C.POINTER(Operand), _P, C.POINTER(Epilogue), _I, _P]),
+    "swv2_linear_kernel": (_I, [C.POINTER(Operand), C.POINTER(Epilogue), _I]),
+    "swv2_linear_wgrad_kernel": (_I, [C.POINTER(Operand), C.POINTER(Operand), _I, C.c_size_t]),
+    "swv2_block_wgrad_kernel": (_I, [C.POINTER(WgradItem), _I, C.c_size_t]),
     "swv2_linear_wgrad": (_I, [C.POINTER(Operand), C.POINTER(Operand), _P, _P, _P, _P, _I, _I, _P]),
     "swv2_linear_wgrad_ws_bytes": (C.c_size_t, [_I, _I, _I, _I]),
     "swv2_qk_normalize": (_I, [_P, _P, _I, _I, _I, _I, _I, _P]),

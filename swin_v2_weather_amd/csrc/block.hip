@@ -28,6 +28,25 @@ swv2_attn_args attn(const swv2_block_desc* d) {
     a.mask_thr = d->mask_thr; a.max_chunks = 64;
     return a;
 }
+// the block's four weight-gradient products (0 fc2, 1 fc1, 2 proj, 3 qkv; the item order of swv2_block_wgrad), described ONCE: the single
+// launches and the grouped launch of swv2_block_bwd read the same items.  fused: the fused MLP path stores no hact, fc2's X operand is
+// GELU(hpre) on load
+void wgrad_items(const swv2_block_desc* d, bool fused, swv2_wgrad_item it[4]) {
+    const int BT = d->B * d->T, Bw = d->B * d->nwh * d->nww, Mw = Bw * d->Lp, C = d->C, h = d->heads, hid = d->hidden;
+    it[0].dy = op(SWV2_OP_BF16, d->da2, BT, C, C);
+    it[0].x = fused ? op(SWV2_OP_BF16_GELU, d->hpre, BT, hid, hid) : op(SWV2_OP_BF16, d->hact, BT, hid, hid);
+    it[0].dW = d->d_fc2_w; it[0].db = d->d_fc2_b; it[0].ldw = hid;
+    it[1].dy = op(SWV2_OP_BF16, d->dh, BT, hid, hid); it[1].x = op(SWV2_OP_F32, d->x1, BT, C, C);
+    it[1].dW = d->d_fc1_w; it[1].db = d->d_fc1_b; it[1].ldw = C;
+    it[2].dy = op(SWV2_OP_BF16, d->da1, Mw, C, C); it[2].x = op_heads(d->oh, Bw, h, 1, d->Lp, d->DP);
+    it[2].dW = d->d_proj_w; it[2].db = d->d_proj_b; it[2].kmap = d->proj_map; it[2].ldw = C;
+    it[3].dy = op_heads(d->dqkvh, Bw, h, 3, d->Lp, d->DP); it[3].x = op(SWV2_OP_F32, d->x, Mw, C, C, d->rowidx);
+    it[3].dW = d->d_qkv_w; it[3].db = d->d_qkv_b; it[3].nmap = d->qkv_map; it[3].ldw = C;
+}
+// one of them as a launch of its own (sp row slices, the block's workspace)
+int wgrad_single(const swv2_block_desc* d, const swv2_wgrad_item& w, int sp, void* stream) {
+    return swv2_linear_wgrad_ws(&w.dy, &w.x, w.dW, w.db, w.nmap, w.kmap, w.ldw, sp, d->wgrad_ws, d->wgrad_ws_bytes, stream);
+}
 #define TRY(x) do { int rc_ = (x); if (rc_) return rc_; } while (0)
 
 // ---- side stream for the weight-gradient products ------------------------------------------------------------
@@ -167,6 +186,8 @@ extern "C" int swv2_block_bwd(const swv2_block_desc* d, void* st) {
     // (needs the fused MLP path's operand set: GELU(hpre) on load; the proj + LN1 pair may be fused or not)
     const bool group = d->wgrad_group && fused && d->wgrad_ws && !ss &&
                        d->wgrad_ws_bytes >= swv2_block_wgrad_ws_bytes(C, hid, h * d->DP, 0);
+    swv2_wgrad_item it[4] = {};
+    wgrad_items(d, fused, it);
     if (fused) {
         // 7', 6', 5' data path fused: LN2 backward, dh = (da2 W2) * GELU'(hpre), dx1 = dx2 + dh W1 in one kernel
         swv2_mlp_bwd_args m = {};
@@ -176,12 +197,10 @@ extern "C" int swv2_block_bwd(const swv2_block_desc* d, void* st) {
         m.ws = d->ln_ws;
         LAUNCH(13, swv2_mlp_bwd_impl(&m, st, defer ? &n_ln2 : nullptr, (float*)d->grad_zero, (long)(d->grad_zero_bytes / 4)));
         // weight gradients (hact was not stored: GELU(hpre) on load)
-        swv2_operand dy2 = op(SWV2_OP_BF16, d->da2, BT, C, C), x2 = op(SWV2_OP_BF16_GELU, d->hpre, BT, hid, hid);
-        swv2_operand dy1 = op(SWV2_OP_BF16, d->dh, BT, hid, hid), x1 = op(SWV2_OP_F32, d->x1, BT, C, C);
         if (ss) fork_to(ss, (hipStream_t)st);
         if (!group) {
-        LAUNCH(12, swv2_linear_wgrad_ws(&dy2, &x2, d->d_fc2_w, d->d_fc2_b, nullptr, nullptr, hid, sp, d->wgrad_ws, d->wgrad_ws_bytes, ws));
-        LAUNCH(14, swv2_linear_wgrad_ws(&dy1, &x1, d->d_fc1_w, d->d_fc1_b, nullptr, nullptr, C, sp, d->wgrad_ws, d->wgrad_ws_bytes, ws));
+        LAUNCH(12, wgrad_single(d, it[0], sp, ws));
+        LAUNCH(14, wgrad_single(d, it[1], sp, ws));
         }
     } else {
     // 7'. LN2 backward
@@ -193,20 +212,17 @@ extern "C" int swv2_block_bwd(const swv2_block_desc* d, void* st) {
     }
     // 6'. fc2: dW = da2^T GELU(h) ; dh = (da2 W2) * GELU'(h)
     {
-        swv2_operand dy = op(SWV2_OP_BF16, d->da2, BT, C, C),
-                     x = op(SWV2_OP_BF16, d->hact, BT, hid, hid);
         if (ss) fork_to(ss, (hipStream_t)st);
-        LAUNCH(12, swv2_linear_wgrad_ws(&dy, &x, d->d_fc2_w, d->d_fc2_b, nullptr, nullptr, hid, sp, d->wgrad_ws, d->wgrad_ws_bytes, ws));
+        LAUNCH(12, wgrad_single(d, it[0], sp, ws));
         swv2_epilogue e = epi(SWV2_EPI_GELU_GRAD, d->dh, hid, nullptr, d->hpre);
-        LAUNCH(13, swv2_linear(&dy, d->w_fc2t, &e, hid, st));
+        LAUNCH(13, swv2_linear(&it[0].dy, d->w_fc2t, &e, hid, st));
     }
     // 5'. fc1: dW = dh^T x1 ; dx1 = dx2 + dh W1
     {
-        swv2_operand dy = op(SWV2_OP_BF16, d->dh, BT, hid, hid), x = op(SWV2_OP_F32, d->x1, BT, C, C);
         if (ss) fork_to(ss, (hipStream_t)st);
-        LAUNCH(14, swv2_linear_wgrad_ws(&dy, &x, d->d_fc1_w, d->d_fc1_b, nullptr, nullptr, C, sp, d->wgrad_ws, d->wgrad_ws_bytes, ws));
+        LAUNCH(14, wgrad_single(d, it[1], sp, ws));
         swv2_epilogue e = epi(SWV2_EPI_F32, d->dx1, C, nullptr, d->dx2);
-        LAUNCH(15, swv2_linear(&dy, d->w_fc1t, &e, C, st));
+        LAUNCH(15, swv2_linear(&it[1].dy, d->w_fc1t, &e, C, st));
     }
     }
     if (fused_pl) {
@@ -217,28 +233,23 @@ extern "C" int swv2_block_bwd(const swv2_block_desc* d, void* st) {
         m.Bw = Bw; m.Lp = d->Lp; m.heads = h; m.C = C; m.rows_per_sample = d->T;
         if (defer) m.ws = d->ln_ws + swv2_mlp_bwd_ws_floats(BT, C);      // second region: LN2's partial rows are still unfolded
         LAUNCH(16, swv2_proj_ln_bwd_impl(&m, st, defer ? &n_ln1 : nullptr));
-        swv2_operand dy = op(SWV2_OP_BF16, d->da1, Mw, C, C), x = op_heads(d->oh, Bw, h, 1, d->Lp, d->DP);
-        if (ss) fork_to(ss, (hipStream_t)st);
-        if (!group)
-        LAUNCH(17, swv2_linear_wgrad_ws(&dy, &x, d->d_proj_w, d->d_proj_b, nullptr, d->proj_map, C, sp, d->wgrad_ws, d->wgrad_ws_bytes, ws));
     } else {
-    // 4'. LN1 backward (gathers dx1 rows through the window table; padded rows -> 0)
-    {
+        // 4'. LN1 backward (gathers dx1 rows through the window table; padded rows -> 0)
         swv2_ln_args l = {};
         l.a = d->a1; l.dy = d->dx1; l.gamma = d->n1_w; l.scale = d->dp1; l.rowidx = d->rowidx; l.mean = d->mean1; l.rstd = d->rstd1;
         l.da = d->da1; l.dgamma = d->d_n1_w; l.dbeta = d->d_n1_b; l.ws = d->ln_ws; l.M = Mw; l.C = C; l.rows_per_sample = d->T;
         LAUNCH(16, swv2_ln_residual_bwd(&l, st));
     }
-    // 3'. proj: dW = da1^T merge(oh) ; d(oh) = split(da1 Wp)
+    // 3'. proj: dW = da1^T merge(oh) ; d(oh) = split(da1 Wp) (unless the fused kernel above wrote it)
     {
-        swv2_operand dy = op(SWV2_OP_BF16, d->da1, Mw, C, C), x = op_heads(d->oh, Bw, h, 1, d->Lp, d->DP);
         if (ss) fork_to(ss, (hipStream_t)st);
         if (!group)
-        LAUNCH(17, swv2_linear_wgrad_ws(&dy, &x, d->d_proj_w, d->d_proj_b, nullptr, d->proj_map, C, sp, d->wgrad_ws, d->wgrad_ws_bytes, ws));
-        swv2_epilogue e = epi(SWV2_EPI_HEADS, d->doh, 0);
-        e.p[0] = h; e.p[2] = d->Lp; e.p[3] = d->DP; e.p[4] = d->L;
-        LAUNCH(18, swv2_linear(&dy, d->w_projt, &e, h * d->DP, st));
-    }
+        LAUNCH(17, wgrad_single(d, it[2], sp, ws));
+        if (!fused_pl) {
+            swv2_epilogue e = epi(SWV2_EPI_HEADS, d->doh, 0);
+            e.p[0] = h; e.p[2] = d->Lp; e.p[3] = d->DP; e.p[4] = d->L;
+            LAUNCH(18, swv2_linear(&it[2].dy, d->w_projt, &e, h * d->DP, st));
+        }
     }
     // 2'. attention backward (incl. the backward of the q / k normalisation)
     {
@@ -261,12 +272,11 @@ extern "C" int swv2_block_bwd(const swv2_block_desc* d, void* st) {
     }
     // 1'. qkv: dW = dqkv^T gather(x) ; dx = dx1 + scatter(dqkv Wqkv)
     {
-        swv2_operand dy = op_heads(d->dqkvh, Bw, h, 3, d->Lp, d->DP), x = op(SWV2_OP_F32, d->x, Mw, C, C, d->rowidx);
         if (ss) fork_to(ss, (hipStream_t)st);
         if (!group)
-        LAUNCH(20, swv2_linear_wgrad_ws(&dy, &x, d->d_qkv_w, d->d_qkv_b, d->qkv_map, nullptr, C, sp, d->wgrad_ws, d->wgrad_ws_bytes, ws));
+        LAUNCH(20, wgrad_single(d, it[3], sp, ws));
         swv2_epilogue e = epi(SWV2_EPI_F32, d->dx, C, nullptr, d->dx1, nullptr, d->rowidx);
-        LAUNCH(21, swv2_linear(&dy, d->w_qkvt, &e, C, st));
+        LAUNCH(21, swv2_linear(&it[3].dy, d->w_qkvt, &e, C, st));
     }
     // d gamma / d beta of both LayerNorms: one reduction for both -- riding on the weight-gradient reduction launch when the grouped
     // products run (swv2_block_wgrad_ln), a launch of its own otherwise
@@ -279,18 +289,7 @@ extern "C" int swv2_block_bwd(const swv2_block_desc* d, void* st) {
             swv2_launch_ln_partials_reduce2(lnp.ws[0], lnp.dgamma[0], lnp.dbeta[0], n_ln2, lnp.ws[1], lnp.dgamma[1], lnp.dbeta[1], n_ln1, C,
                                             (hipStream_t)st);
     }
-    if (group) {
-        swv2_wgrad_item it[4] = {};
-        it[0].dy = op(SWV2_OP_BF16, d->da2, BT, C, C); it[0].x = op(SWV2_OP_BF16_GELU, d->hpre, BT, hid, hid);
-        it[0].dW = d->d_fc2_w; it[0].db = d->d_fc2_b; it[0].ldw = hid;
-        it[1].dy = op(SWV2_OP_BF16, d->dh, BT, hid, hid); it[1].x = op(SWV2_OP_F32, d->x1, BT, C, C);
-        it[1].dW = d->d_fc1_w; it[1].db = d->d_fc1_b; it[1].ldw = C;
-        it[2].dy = op(SWV2_OP_BF16, d->da1, Mw, C, C); it[2].x = op_heads(d->oh, Bw, h, 1, d->Lp, d->DP);
-        it[2].dW = d->d_proj_w; it[2].db = d->d_proj_b; it[2].kmap = d->proj_map; it[2].ldw = C;
-        it[3].dy = op_heads(d->dqkvh, Bw, h, 3, d->Lp, d->DP); it[3].x = op(SWV2_OP_F32, d->x, Mw, C, C, d->rowidx);
-        it[3].dW = d->d_qkv_w; it[3].db = d->d_qkv_b; it[3].nmap = d->qkv_map; it[3].ldw = C;
-        LAUNCH(22, swv2_block_wgrad_ln(it, 0, d->wgrad_ws, d->wgrad_ws_bytes, defer ? &lnp : nullptr, st));
-    }
+    if (group) LAUNCH(22, swv2_block_wgrad_ln(it, 0, d->wgrad_ws, d->wgrad_ws_bytes, defer ? &lnp : nullptr, st));
     if (ss) join_from(ss, (hipStream_t)st);
     return SWV2_OK;
 }

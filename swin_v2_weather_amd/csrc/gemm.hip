@@ -1417,8 +1417,79 @@ __global__ __launch_bounds__(512) void gemm_rw_kernel(ALoad<AK> al, const uint16
 #endif
 }
 
-template <int AK, int EK>
-int launch_nt2(const swv2_operand* a, const void* w, const swv2_epilogue* e, int M, int N, int K, hipStream_t st) {
+// ------------------------------------------------------------------------------------------------
+// Which kernel serves a product: linear_kernel_for is the ONE place that knows.  launch_nt2 switches on it, swv2_linear_kernel reports it.
+// ------------------------------------------------------------------------------------------------
+enum class LinearKernel {
+    RESIDENT_QKV128 = SWV2_LINEAR_RESIDENT_QKV128, RESIDENT_QKV192X3 = SWV2_LINEAR_RESIDENT_QKV192X3, RESIDENT_DX128 = SWV2_LINEAR_RESIDENT_DX128,
+    WIDE_DMA = SWV2_LINEAR_WIDE_DMA, WIDE = SWV2_LINEAR_WIDE, TILE64 = SWV2_LINEAR_TILE64, TILE128 = SWV2_LINEAR_TILE128
+};
+
+// the (loader, epilogue) pairs the special kernels are instantiated for: the selector tests them at run time, launch_nt2 at compile time
+constexpr bool qkv_pair(int ak, int ek) { return ak == A_F32 && ek == E_QKV_HEADS; }      // a block's qkv product
+constexpr bool dx_pair(int ak, int ek) { return ak == A_HEADS && ek == E_F32; }           // a block's d(qkv) -> dx product
+constexpr bool loss_epi(int ek) { return ek == E_UNPATCH_LOSS || ek == E_UNPATCH_LOSS_SKIP; }
+constexpr bool wide_pair(int ak, int ek) {
+    return (ak == A_F32 || ak == A_BF16 || ak == A_HEADS) &&
+           (ek == E_BF16 || ek == E_F32 || ek == E_F32_ACC || ek == E_QKV_HEADS || ek == E_HEADS || ek == E_GELU_GRAD || ek == E_BF16_GELU);
+}
+constexpr bool dma_loader(int ak) { return ak == A_BF16 || ak == A_HEADS; }               // raw bf16 in memory: LDS-DMA can fetch it
+
+// Pure function of the descriptors' shape fields (no data pointer is dereferenced; rowidx / aux only as "present or not"), the internal
+// kinds ak (A_*) / ek (E_*) and the value of SWV2_GEMM_WIDE.
+LinearKernel linear_kernel_for(int ak, int ek, const swv2_operand* a, const swv2_epilogue* e, int N, int wide) {
+    const int M = a->rows, K = a->cols;
+    // the two per-block products at the benchmark width: resident-weight persistent kernel
+    if (qkv_pair(ak, ek) && M >= 256 * 128 && a->rowidx) {
+        if (N == 384 && K == 128 && e->p[3] == 16) return LinearKernel::RESIDENT_QKV128;
+        // BASELINE configs[4] (192 channels, 8 heads in 32-wide slots): the 768 x 192 weight does not fit LDS beside an A tile, one
+        // of its q / k / v parts (256 x 192 = 96 KB) does: three launches, each over all rows (the gathered fp32 rows are read three
+        // times, 3 x 108 MB, against the generic kernel's re-read of the weight per 64-row tile: 207 -> 3 x ~45 us)
+        if (N == 768 && K == 192 && e->p[3] == 32 && e->p[0] == 8) return LinearKernel::RESIDENT_QKV192X3;
+    }
+    if (dx_pair(ak, ek) && N == 128 && K == 384 && M >= 256 * 64 && e->rowidx && e->aux && !a->rowidx) return LinearKernel::RESIDENT_DX128;
+    // wide products (K, N >= 512, N a multiple of 256): 256 x 256 tiles
+    if (wide_pair(ak, ek)) {
+        // BASELINE configs[4]'s d(qkv) -> dx product (N = 192, K = 768, head-major operand): one partial column tile of the DMA kernel --
+        // the operand is read exactly once, the weight's 192 rows stream from L2; a quarter of the MFMAs multiply clamped rows
+        // (the 64-row tile kernel re-reads the weight per tile behind a barrier per 64 k: 165 us)
+        const bool part192 = dx_pair(ak, ek) && N == 192 && K == 768 && !a->rowidx && M >= 64 * WBM &&
+                             (double)a->rows * a->cols * 2 < 4.29e9;                  // (only the DMA kernel clamps the weight rows)
+        if (wide && (N % WBN == 0 || part192) && K % BK == 0 && (N >= 512 || part192) && K >= 512 && M >= 16 * WBM) {
+            // 32-bit byte offsets in the DMA addressing: the operand below 4 GB (the weight: checked by the launcher)
+            const bool small = (double)a->rows * (ak == A_HEADS ? a->cols : a->ld) * 2 < 4.29e9;
+            return dma_loader(ak) && small && K % 128 == 0 && (ak == A_HEADS || !a->rowidx) ? LinearKernel::WIDE_DMA : LinearKernel::WIDE;
+        }
+    }
+    // 64-row workgroups (one 32-row partial-sum group per wave) for the loss epilogues.  128-row workgroups (two groups per wave)
+    // measured equal -- 422.8 vs 420.9 us -- with 23 registers spilled: not instantiated
+    if (loss_epi(ek)) return LinearKernel::TILE64;
+    // 64-row workgroups where they fill the 768 slots (3 per CU) better; only for the two per-block products
+    if (qkv_pair(ak, ek) || dx_pair(ak, ek)) {
+        const double w1 = cdiv(M, BM), w2 = cdiv(M, BM / 2), slots = 768.0;
+        const double e1 = w1 / (std::ceil(w1 / slots) * slots), e2 = w2 / (std::ceil(w2 / slots) * slots);
+        if (e2 > e1 + 0.08) return LinearKernel::TILE64;
+    }
+    return LinearKernel::TILE128;
+}
+
+// the internal epilogue kind (E_*) of a public one for loader kind ak, or a negative error: the pairs launch_nt1 instantiates
+int linear_epi_kind(int ak, const swv2_epilogue* e) {
+    static_assert(E_BF16 == SWV2_EPI_BF16 && E_BF16_GELU == SWV2_EPI_BF16_GELU && A_F32 == SWV2_OP_F32 && A_BF16_CS == SWV2_OP_BF16_CSCALE,
+                  "A_* / E_* mirror the public kinds");
+    if (ak == A_BF16_CS) {                         // the loss-gradient operand feeds exactly one product: d(e) = G W_head, fp32 out
+        if (e->kind == SWV2_EPI_F32) return E_F32;
+        swv2_set_error("swv2_linear: SWV2_OP_BF16_CSCALE supports SWV2_EPI_F32 only (got %d)", e->kind);
+        return SWV2_ERR_INVALID;
+    }
+    if (ak == A_F32 && e->kind == SWV2_EPI_UNPATCH_LOSS) return e->p[3] ? E_UNPATCH_LOSS_SKIP : E_UNPATCH_LOSS;
+    if (e->kind >= SWV2_EPI_BF16 && e->kind <= SWV2_EPI_BF16_GELU) return e->kind;        // (E_* = SWV2_EPI_* up to the loss epilogue)
+    swv2_set_error("swv2_linear: unknown epilogue kind %d (or not available for operand kind %d)", e->kind, ak);
+    return SWV2_ERR_INVALID;
+}
+
+template <int EK>
+Epi<EK> make_epi(const swv2_epilogue* e, int M, int N) {
     Epi<EK> ep;
     ep.d.out = e->out; ep.d.bias = e->bias; ep.d.aux = e->aux; ep.d.aux_out = e->aux_out; ep.d.rowidx = e->rowidx;
     ep.d.ld = e->ld; ep.d.M = M; ep.d.N = N;
@@ -1426,8 +1497,8 @@ int launch_nt2(const swv2_operand* a, const void* w, const swv2_epilogue* e, int
     ep.d.mg0 = ep.d.mg1 = ep.d.mg2 = 0;
     ep.d.loss_tar = nullptr; ep.d.loss_qw = nullptr; ep.d.loss_part = nullptr; ep.d.loss_resid = nullptr; ep.d.q0 = ep.d.q1 = ep.d.q2 = ep.d.q3 = 0;
     if (EK == E_QKV_HEADS || EK == E_HEADS) { ep.d.mg0 = fdiv_magic(e->p[2]); ep.d.mg1 = fdiv_magic(e->p[0]); ep.d.mg2 = fdiv_magic(e->p[3]); }
-    if (EK == E_UNPATCH || EK == E_UNPATCH_LOSS || EK == E_UNPATCH_LOSS_SKIP) { ep.d.mg0 = fdiv_magic((e->p[1] / 4) * (e->p[2] / 4)); ep.d.mg1 = fdiv_magic(e->p[2] / 4); }
-    if (EK == E_UNPATCH_LOSS || EK == E_UNPATCH_LOSS_SKIP) {
+    if (EK == E_UNPATCH || loss_epi(EK)) { ep.d.mg0 = fdiv_magic((e->p[1] / 4) * (e->p[2] / 4)); ep.d.mg1 = fdiv_magic(e->p[2] / 4); }
+    if (loss_epi(EK)) {
         ep.d.loss_tar = e->loss_tar; ep.d.loss_qw = e->loss_qw; ep.d.loss_part = e->loss_part; ep.d.loss_resid = (uint16_t*)e->loss_resid;
         ep.d.q0 = e->q[0]; ep.d.q1 = e->q[1];
         const long nb = M / ((e->p[1] / 4) * (e->p[2] / 4)), plane = (long)e->p[1] * e->p[2];
@@ -1436,115 +1507,91 @@ int launch_nt2(const swv2_operand* a, const void* w, const swv2_epilogue* e, int
         ep.d.q2 = e->q[2] ? e->q[2] : (int)(nb * e->p[0] * plane);
         ep.d.q3 = (int)(nb * e->ld * plane);
     }
-    // the two per-block products at the benchmark width: resident-weight persistent kernel
-    if constexpr (AK == A_F32 && EK == E_QKV_HEADS) {
-        if (N == 384 && K == 128 && M >= 256 * 128 && e->p[3] == 16 && a->rowidx) {
-            Epi<EK> ep1 = ep;
-            ep1.d.p1 = 0;                                 // (first part of the launch's columns; p[1] is not a parameter of this epilogue)
-            hipLaunchKernelGGL((gemm_rw_kernel<AK, EK, 384, 128, 128>), dim3(256), dim3(512), 0, st, make_loader<AK>(a),
-                               (const uint16_t*)w, ep1, M);
-            SWV2_CHECK_LAUNCH("swv2_linear");
-            return SWV2_OK;
-        }
-        // BASELINE configs[4] (192 channels, 8 heads in 32-wide slots): the 768 x 192 weight does not fit LDS beside an A tile, one
-        // of its q / k / v parts (256 x 192 = 96 KB) does: three launches, each over all rows (the gathered fp32 rows are read three
-        // times, 3 x 108 MB, against the generic kernel's re-read of the weight per 64-row tile: 207 -> 3 x ~45 us)
-        if (N == 768 && K == 192 && M >= 256 * 128 && e->p[3] == 32 && e->p[0] == 8 && a->rowidx) {
-            for (int part = 0; part < 3; ++part) {
-                Epi<EK> ep2 = ep;
-                ep2.d.N = 256;
-                ep2.d.p1 = part;
-                ep2.d.bias = e->bias ? e->bias + 256 * part : nullptr;
-                hipLaunchKernelGGL((gemm_rw_kernel<AK, EK, 256, 192, 128, 32>), dim3(256), dim3(512), 0, st, make_loader<AK>(a),
-                                   (const uint16_t*)w + (size_t)part * 256 * 192, ep2, M);
+    return ep;
+}
+
+// one launch shape per LinearKernel; `if constexpr` keeps each kernel to the pairs it is instantiated for (the selector returns it for no other)
+template <int AK, int EK>
+int launch_nt2(const swv2_operand* a, const void* w, const swv2_epilogue* e, int M, int N, int K, hipStream_t st) {
+    const Epi<EK> ep = make_epi<EK>(e, M, N);
+    const uint16_t* wb = (const uint16_t*)w;
+    const LinearKernel kern = linear_kernel_for(AK, EK, a, e, N, swv2_gemm_wide());
+    switch (kern) {
+        case LinearKernel::RESIDENT_QKV128:
+            if constexpr (qkv_pair(AK, EK)) {
+                Epi<EK> ep1 = ep;
+                ep1.d.p1 = 0;                                 // (first part of the launch's columns; p[1] is not a parameter of this epilogue)
+                hipLaunchKernelGGL((gemm_rw_kernel<AK, EK, 384, 128, 128>), dim3(256), dim3(512), 0, st, make_loader<AK>(a), wb, ep1, M);
             }
-            SWV2_CHECK_LAUNCH("swv2_linear");
-            return SWV2_OK;
-        }
-    }
-    if constexpr (AK == A_HEADS && EK == E_F32) {
-        if (N == 128 && K == 384 && M >= 256 * 64 && e->rowidx && e->aux && !a->rowidx) {
-            hipLaunchKernelGGL((gemm_rw_kernel<AK, EK, 128, 384, 64>), dim3(256), dim3(512), 0, st, make_loader<AK>(a),
-                               (const uint16_t*)w, ep, M);
-            SWV2_CHECK_LAUNCH("swv2_linear");
-            return SWV2_OK;
-        }
-    }
-    // wide products (K, N >= 512, N a multiple of 256): 256 x 256 tiles
-    if constexpr ((AK == A_F32 || AK == A_BF16 || AK == A_HEADS) &&
-                  (EK == E_BF16 || EK == E_F32 || EK == E_F32_ACC || EK == E_QKV_HEADS || EK == E_HEADS || EK == E_GELU_GRAD || EK == E_BF16_GELU)) {
-        const int wide = getenv("SWV2_GEMM_WIDE") ? atoi(getenv("SWV2_GEMM_WIDE")) : 1;      // (read per call: the tests toggle it)
-        // BASELINE configs[4]'s d(qkv) -> dx product (N = 192, K = 768, head-major operand): one partial column tile of the DMA kernel --
-        // the operand is read exactly once, the weight's 192 rows stream from L2; a quarter of the MFMAs multiply clamped rows
-        // (the 64-row tile kernel re-reads the weight per tile behind a barrier per 64 k: 165 us)
-        const bool part192 = AK == A_HEADS && EK == E_F32 && N == 192 && K == 768 && !a->rowidx && M >= 64 * WBM &&
-                             (double)a->rows * a->cols * 2 < 4.29e9;                  // (only the DMA kernel clamps the weight rows)
-        if (wide && (N % WBN == 0 || part192) && K % BK == 0 && (N >= 512 || part192) && K >= 512 && M >= 16 * WBM) {
-            const int mtiles = cdiv(M, WBM), ntn = cdiv(N, WBN), groups = cdiv(mtiles, 8);
-            const int grid = 8 * cdiv(groups, 8) * 8 * ntn;
-            // 32-bit byte offsets in the DMA addressing: weights and operand below 4 GB (the operand: checked for its kind below)
-            SWV2_CHECK_ARG((double)N * K * 2 < 4.29e9, "swv2_linear: weight too large for the wide kernel's 32-bit offsets");
-            const bool small = (double)a->rows * (AK == A_HEADS ? a->cols : a->ld) * 2 < 4.29e9;
-            constexpr bool CAN_DMA = AK == A_BF16 || AK == A_HEADS;
-            const int vmax = cdiv(groups, 8) * 8 * ntn;            // tile sequence length per XCD
-            const int persist = getenv("SWV2_WIDE_PERSIST") ? atoi(getenv("SWV2_WIDE_PERSIST")) : 1;
-            if (CAN_DMA && small && K % 128 == 0 && (AK == A_HEADS || !a->rowidx)) {
-                if constexpr (CAN_DMA)
-                    hipLaunchKernelGGL((gemm_nt_wide_dma_kernel<AK, EK>), dim3(8 * (vmax < 32 || !persist ? vmax : 32)), dim3(WTH), 0, st, make_loader<AK>(a),
-                                       (const uint16_t*)w, ep, M, N, K, mtiles, ntn, vmax);
-            } else {
-                hipLaunchKernelGGL((gemm_nt_wide_kernel<AK, EK>), dim3(grid), dim3(WTH), 0, st, make_loader<AK>(a), (const uint16_t*)w,
-                                   ep, M, N, K, mtiles, ntn);
+            break;
+        case LinearKernel::RESIDENT_QKV192X3:
+            if constexpr (qkv_pair(AK, EK)) {
+                for (int part = 0; part < 3; ++part) {
+                    Epi<EK> ep2 = ep;
+                    ep2.d.N = 256;
+                    ep2.d.p1 = part;
+                    ep2.d.bias = e->bias ? e->bias + 256 * part : nullptr;
+                    hipLaunchKernelGGL((gemm_rw_kernel<AK, EK, 256, 192, 128, 32>), dim3(256), dim3(512), 0, st, make_loader<AK>(a),
+                                       wb + (size_t)part * 256 * 192, ep2, M);
+                }
             }
-            SWV2_CHECK_LAUNCH("swv2_linear");
-            return SWV2_OK;
-        }
+            break;
+        case LinearKernel::RESIDENT_DX128:
+            if constexpr (dx_pair(AK, EK))
+                hipLaunchKernelGGL((gemm_rw_kernel<AK, EK, 128, 384, 64>), dim3(256), dim3(512), 0, st, make_loader<AK>(a), wb, ep, M);
+            break;
+        case LinearKernel::WIDE_DMA:
+        case LinearKernel::WIDE:
+            if constexpr (wide_pair(AK, EK)) {
+                // 32-bit byte offsets in the DMA addressing: weights below 4 GB (the operand: part of the selection)
+                SWV2_CHECK_ARG((double)N * K * 2 < 4.29e9, "swv2_linear: weight too large for the wide kernel's 32-bit offsets");
+                const int mtiles = cdiv(M, WBM), ntn = cdiv(N, WBN), groups = cdiv(mtiles, 8);
+                const int vmax = cdiv(groups, 8) * 8 * ntn;            // tile sequence length per XCD
+                if (kern == LinearKernel::WIDE_DMA) {
+                    // persistent: at most 32 workgroups per XCD walk the tile sequence (a grid choice, not another kernel)
+                    if constexpr (dma_loader(AK))
+                        hipLaunchKernelGGL((gemm_nt_wide_dma_kernel<AK, EK>), dim3(8 * (vmax < 32 || !swv2_wide_persist() ? vmax : 32)), dim3(WTH), 0, st,
+                                           make_loader<AK>(a), wb, ep, M, N, K, mtiles, ntn, vmax);
+                } else {
+                    hipLaunchKernelGGL((gemm_nt_wide_kernel<AK, EK>), dim3(8 * vmax), dim3(WTH), 0, st, make_loader<AK>(a), wb, ep, M, N, K, mtiles, ntn);
+                }
+            }
+            break;
+        case LinearKernel::TILE64:
+            if constexpr (qkv_pair(AK, EK) || dx_pair(AK, EK) || loss_epi(EK))
+                hipLaunchKernelGGL((gemm_nt_kernel<AK, EK, BM / 2>), dim3(cdiv(M, BM / 2)), dim3(NTHREADS), 0, st, make_loader<AK>(a), wb, ep, M, N, K);
+            break;
+        case LinearKernel::TILE128:
+            if constexpr (!loss_epi(EK))
+                hipLaunchKernelGGL((gemm_nt_kernel<AK, EK>), dim3(cdiv(M, BM)), dim3(NTHREADS), 0, st, make_loader<AK>(a), wb, ep, M, N, K);
+            break;
     }
-    // 64-row workgroups where they fill the 768 slots (3 per CU) better; only for the two per-block products
-    bool half = false;
-    if constexpr ((AK == A_F32 && EK == E_QKV_HEADS) || (AK == A_HEADS && EK == E_F32)) {
-        const double w1 = cdiv(M, BM), w2 = cdiv(M, BM / 2), slots = 768.0;
-        const double e1 = w1 / (std::ceil(w1 / slots) * slots), e2 = w2 / (std::ceil(w2 / slots) * slots);
-        half = e2 > e1 + 0.08;
-        if (half)
-            hipLaunchKernelGGL((gemm_nt_kernel<AK, EK, BM / 2>), dim3(cdiv(M, BM / 2)), dim3(NTHREADS), 0, st, make_loader<AK>(a),
-                               (const uint16_t*)w, ep, M, N, K);
-    }
-    if constexpr (EK == E_UNPATCH_LOSS || EK == E_UNPATCH_LOSS_SKIP) {
-        // 64-row workgroups (one 32-row partial-sum group per wave).  128-row workgroups (two groups per wave) measured equal -- 422.8 vs
-        // 420.9 us -- with 23 registers spilled: not instantiated
-        half = true;
-        hipLaunchKernelGGL((gemm_nt_kernel<AK, EK, BM / 2>), dim3(cdiv(M, BM / 2)), dim3(NTHREADS), 0, st, make_loader<AK>(a),
-                           (const uint16_t*)w, ep, M, N, K);
-    }
-    if constexpr (EK != E_UNPATCH_LOSS && EK != E_UNPATCH_LOSS_SKIP)
-    if (!half)
-        hipLaunchKernelGGL((gemm_nt_kernel<AK, EK>), dim3(cdiv(M, BM)), dim3(NTHREADS), 0, st, make_loader<AK>(a),
-                           (const uint16_t*)w, ep, M, N, K);
     SWV2_CHECK_LAUNCH("swv2_linear");
     return SWV2_OK;
 }
 
 template <int AK>
 int launch_nt1(const swv2_operand* a, const void* w, const swv2_epilogue* e, int M, int N, int K, hipStream_t st) {
-    if constexpr (AK == A_BF16_CS) {               // the loss-gradient operand feeds exactly one product: d(e) = G W_head, fp32 out
-        if (e->kind == SWV2_EPI_F32) return launch_nt2<AK, E_F32>(a, w, e, M, N, K, st);
-        swv2_set_error("swv2_linear: SWV2_OP_BF16_CSCALE supports SWV2_EPI_F32 only (got %d)", e->kind);
-        return SWV2_ERR_INVALID;
+    const int ek = linear_epi_kind(AK, e);
+    if (ek < 0) return ek;
+    // only the pairs linear_epi_kind lets through are instantiated (compile time)
+    if constexpr (AK == A_BF16_CS) {
+        return launch_nt2<AK, E_F32>(a, w, e, M, N, K, st);
     } else {
-    if constexpr (AK == A_F32) if (e->kind == SWV2_EPI_UNPATCH_LOSS)
-        return e->p[3] ? launch_nt2<AK, E_UNPATCH_LOSS_SKIP>(a, w, e, M, N, K, st) : launch_nt2<AK, E_UNPATCH_LOSS>(a, w, e, M, N, K, st);
-    switch (e->kind) {
-        case SWV2_EPI_BF16: return launch_nt2<AK, E_BF16>(a, w, e, M, N, K, st);
-        case SWV2_EPI_F32: return launch_nt2<AK, E_F32>(a, w, e, M, N, K, st);
-        case SWV2_EPI_F32_ACC: return launch_nt2<AK, E_F32_ACC>(a, w, e, M, N, K, st);
-        case SWV2_EPI_QKV_HEADS: return launch_nt2<AK, E_QKV_HEADS>(a, w, e, M, N, K, st);
-        case SWV2_EPI_HEADS: return launch_nt2<AK, E_HEADS>(a, w, e, M, N, K, st);
-        case SWV2_EPI_GELU_GRAD: return launch_nt2<AK, E_GELU_GRAD>(a, w, e, M, N, K, st);
-        case SWV2_EPI_UNPATCH: return launch_nt2<AK, E_UNPATCH>(a, w, e, M, N, K, st);
-        case SWV2_EPI_BF16_GELU: return launch_nt2<AK, E_BF16_GELU>(a, w, e, M, N, K, st);
+    if constexpr (AK == A_F32) {
+        if (ek == E_UNPATCH_LOSS_SKIP) return launch_nt2<AK, E_UNPATCH_LOSS_SKIP>(a, w, e, M, N, K, st);
+        if (ek == E_UNPATCH_LOSS) return launch_nt2<AK, E_UNPATCH_LOSS>(a, w, e, M, N, K, st);
     }
-    swv2_set_error("swv2_linear: unknown epilogue kind %d (or not available for operand kind %d)", e->kind, a->kind);
+    switch (ek) {
+        case E_BF16: return launch_nt2<AK, E_BF16>(a, w, e, M, N, K, st);
+        case E_F32: return launch_nt2<AK, E_F32>(a, w, e, M, N, K, st);
+        case E_F32_ACC: return launch_nt2<AK, E_F32_ACC>(a, w, e, M, N, K, st);
+        case E_QKV_HEADS: return launch_nt2<AK, E_QKV_HEADS>(a, w, e, M, N, K, st);
+        case E_HEADS: return launch_nt2<AK, E_HEADS>(a, w, e, M, N, K, st);
+        case E_GELU_GRAD: return launch_nt2<AK, E_GELU_GRAD>(a, w, e, M, N, K, st);
+        case E_UNPATCH: return launch_nt2<AK, E_UNPATCH>(a, w, e, M, N, K, st);
+        case E_BF16_GELU: return launch_nt2<AK, E_BF16_GELU>(a, w, e, M, N, K, st);
+    }
     return SWV2_ERR_INVALID;
     }
 }
@@ -1572,6 +1619,13 @@ extern "C" int swv2_debug_rw_stamps(void* out) {
     return hipMemcpyFromSymbol(out, HIP_SYMBOL(rw_stamps), sizeof(unsigned long long) * 256 * 8) == hipSuccess ? 0 : -3;
 }
 #endif
+
+extern "C" int swv2_linear_kernel(const swv2_operand* a, const swv2_epilogue* e, int N) {
+    SWV2_CHECK_ARG(a && e && N > 0 && a->rows > 0 && a->cols > 0, "swv2_linear_kernel: null operand / epilogue or empty product");
+    SWV2_CHECK_ARG(a->kind >= SWV2_OP_F32 && a->kind <= SWV2_OP_BF16_CSCALE, "swv2_linear_kernel: unknown operand kind %d", a->kind);
+    const int ek = linear_epi_kind(a->kind, e);
+    return ek < 0 ? ek : (int)linear_kernel_for(a->kind, ek, a, e, N, swv2_gemm_wide());
+}
 
 extern "C" int swv2_linear(const swv2_operand* a, const void* w_bf16, const swv2_epilogue* e, int N, void* stream) {
     int rc = check_operand(a, "swv2_linear");

@@ -1,15 +1,25 @@
 // Shared pieces of the GEMM engine: tile constants, LDS swizzle, GELU, bf16 packing, operand loaders, host checks.
 // Included by gemm.hip (NT products + epilogues) and gemm_tn.hip (weight-gradient products).
 #pragma once
+#include <cstdlib>
 #include "common.h"
 
 // gemm.hip: the wide weight-gradient kernel (partial matrices), launched by gemm_tn.hip
 int swv2_tn_wide_launch(const swv2_operand* y, const swv2_operand* x, float* part, float* dbpart, int M, int N, int K, int S, hipStream_t st);
 
-// gemm_tn_slab.hip: the block's four weight gradients with every operand byte fetched once (LDS-DMA slabs); launch returns 1 when
-// the shape / workspace is not covered (the caller then takes gemm_tn_group_kernel)
+// gemm_tn_slab.hip: the block's four weight gradients with every operand byte fetched once (LDS-DMA slabs).  swv2_tn_slab_covers: the
+// kernel runs these items with a workspace of ws_bytes on the current device (256 CUs assumed in a process without one); a covered
+// shape with too small a workspace is reported on stderr once per process.  swv2_block_wgrad asks it, then launches (0 or a negative error)
 size_t swv2_tn_slab_ws_bytes(int C, int hidden, int heads_dp);
+bool swv2_tn_slab_covers(const swv2_wgrad_item* it, size_t ws_bytes);
 int swv2_tn_slab_launch(const swv2_wgrad_item* it, void* ws, size_t ws_bytes, const swv2_ln_partials* ln, hipStream_t st);
+
+// The two run-time switches of the GEMM engine, each parsed here and nowhere else; read per call (the tests toggle them in-process).
+// SWV2_GEMM_WIDE (default 1): 0 = the 128-row tile kernels where swv2_linear / swv2_linear_wgrad_ws would run a 256 x 256 kernel.
+// SWV2_WIDE_PERSIST (default 1): 0 = one workgroup per tile in the wide LDS-DMA kernel instead of persistent workgroups.
+inline int swv2_env_switch(const char* name) { const char* v = getenv(name); return v ? atoi(v) : 1; }
+inline int swv2_gemm_wide() { return swv2_env_switch("SWV2_GEMM_WIDE"); }
+inline int swv2_wide_persist() { return swv2_env_switch("SWV2_WIDE_PERSIST"); }
 
 namespace {
 

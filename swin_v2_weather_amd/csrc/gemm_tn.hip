@@ -431,34 +431,50 @@ TnOut tn_out(float* dW, float* db, const int32_t* nmap, const int32_t* kmap, int
     return o;
 }
 
-template <int YK, int XK>
-int launch_tn2(const swv2_operand* y, const swv2_operand* x, float* dW, float* db, const int32_t* nmap,
-               const int32_t* kmap, int ldw, int M, int N, int K, int splits, float* ws, size_t ws_bytes, hipStream_t st) {
-    // wide widths: 256 x 256 tiles by LDS-DMA (gemm.hip), workspace path only
-    if constexpr ((YK == A_BF16 || YK == A_HEADS) && (XK == A_BF16 || XK == A_HEADS || XK == A_F32)) {
-        const TnWidePlan wp = tn_wide_plan(M, N, K);
-        const int wide = getenv("SWV2_GEMM_WIDE") ? atoi(getenv("SWV2_GEMM_WIDE")) : 1;
-        const bool kinds = !(YK == A_HEADS && XK == A_HEADS) && !y->rowidx && (XK == A_F32 || !x->rowidx);
-        if (wide && wp.ok && kinds && ws && ws_bytes >= wp.total) {
-            float* part = ws;
-            float* dbpart = db ? (float*)((char*)ws + wp.part_bytes) : nullptr;
-            swv2_operand xb = *x;
-            if constexpr (XK == A_F32) {           // bf16 (gathered) copy of the fp32 rows
-                uint16_t* cb = (uint16_t*)((char*)ws + wp.part_bytes + wp.db_bytes);
-                const long chunks = (long)M * (K / 8);
-                hipLaunchKernelGGL(cast_rows_kernel, dim3((unsigned)((chunks + 255) / 256)), dim3(256), 0, st, (const float*)x->ptr, x->rowidx, cb,
-                                   M, K, x->ld);
-                xb.kind = SWV2_OP_BF16; xb.ptr = cb; xb.rowidx = nullptr; xb.ld = K;
-            }
-            int rc = swv2_tn_wide_launch(y, &xb, part, dbpart, M, N, K, wp.S, st);
-            if (rc) return rc;
-            const long quads = (long)N * K / 4;
-            hipLaunchKernelGGL(tn_wide_reduce_kernel, dim3((unsigned)((quads + 255) / 256)), dim3(256), 0, st, (const float*)part,
-                               (const float*)dbpart, dW, db, nmap, kmap, ldw, N, K, wp.S);
-            SWV2_CHECK_LAUNCH("swv2_linear_wgrad");
-            return SWV2_OK;
-        }
+// ------------------------------------------------------------------------------------------------
+// Which kernel serves a weight gradient: wgrad_kernel_for is the ONE place that knows.  launch_tn2 switches on it,
+// swv2_linear_wgrad_kernel reports it.
+// ------------------------------------------------------------------------------------------------
+enum class WgradKernel { WIDE = SWV2_WGRAD_WIDE, TILE = SWV2_WGRAD_TILE };
+
+// Pure function of the operands' shape fields (rowidx only as "present or not"), the workspace size (0 = none: the atomic path) and the
+// value of SWV2_GEMM_WIDE.  Wide widths: 256 x 256 tiles by LDS-DMA (gemm.hip), workspace path only; the operands raw bf16 (dY never
+// gathered, not both head-major) or fp32 X rows, which are cast -- and gathered -- into the workspace first.
+WgradKernel wgrad_kernel_for(const swv2_operand* y, const swv2_operand* x, size_t ws_bytes, int wide) {
+    const int yk = y->kind, xk = x->kind;
+    const bool kinds = (yk == A_BF16 || yk == A_HEADS) && (xk == A_BF16 || xk == A_HEADS || xk == A_F32) && !(yk == A_HEADS && xk == A_HEADS) &&
+                       !y->rowidx && (xk == A_F32 || !x->rowidx);
+    const TnWidePlan wp = tn_wide_plan(y->rows, y->cols, x->cols);
+    return wide && wp.ok && kinds && ws_bytes >= wp.total ? WgradKernel::WIDE : WgradKernel::TILE;
+}
+
+// the wide kernel + its reduction (the operand kinds are run-time arguments of swv2_tn_wide_launch)
+int launch_tn_wide(const swv2_operand* y, const swv2_operand* x, float* dW, float* db, const int32_t* nmap, const int32_t* kmap, int ldw,
+                   int M, int N, int K, float* ws, hipStream_t st) {
+    const TnWidePlan wp = tn_wide_plan(M, N, K);
+    float* part = ws;
+    float* dbpart = db ? (float*)((char*)ws + wp.part_bytes) : nullptr;
+    swv2_operand xb = *x;
+    if (x->kind == SWV2_OP_F32) {           // bf16 (gathered) copy of the fp32 rows
+        uint16_t* cb = (uint16_t*)((char*)ws + wp.part_bytes + wp.db_bytes);
+        const long chunks = (long)M * (K / 8);
+        hipLaunchKernelGGL(cast_rows_kernel, dim3((unsigned)((chunks + 255) / 256)), dim3(256), 0, st, (const float*)x->ptr, x->rowidx, cb,
+                           M, K, x->ld);
+        xb.kind = SWV2_OP_BF16; xb.ptr = cb; xb.rowidx = nullptr; xb.ld = K;
     }
+    int rc = swv2_tn_wide_launch(y, &xb, part, dbpart, M, N, K, wp.S, st);
+    if (rc) return rc;
+    const long quads = (long)N * K / 4;
+    hipLaunchKernelGGL(tn_wide_reduce_kernel, dim3((unsigned)((quads + 255) / 256)), dim3(256), 0, st, (const float*)part,
+                       (const float*)dbpart, dW, db, nmap, kmap, ldw, N, K, wp.S);
+    SWV2_CHECK_LAUNCH("swv2_linear_wgrad");
+    return SWV2_OK;
+}
+
+// the 128 x 128 tile kernel: fp32 atomics on dW (ws == NULL) or per-slice partial tiles + tn_reduce_kernel
+template <int YK, int XK>
+int launch_tn_tile(const swv2_operand* y, const swv2_operand* x, float* dW, float* db, const int32_t* nmap,
+                   const int32_t* kmap, int ldw, int M, int N, int K, int splits, float* ws, size_t ws_bytes, hipStream_t st) {
     const TnPlan p = tn_plan(M, N, K, splits);
     if (ws && ws_bytes < p.ws_bytes) {
         swv2_set_error("swv2_linear_wgrad_ws: workspace of %zu bytes, %zu needed (swv2_linear_wgrad_ws_bytes)", ws_bytes, p.ws_bytes);
@@ -488,6 +504,16 @@ int launch_tn2(const swv2_operand* y, const swv2_operand* x, float* dW, float* d
     }
     SWV2_CHECK_LAUNCH("swv2_linear_wgrad");
     return SWV2_OK;
+}
+
+template <int YK, int XK>
+int launch_tn2(const swv2_operand* y, const swv2_operand* x, float* dW, float* db, const int32_t* nmap,
+               const int32_t* kmap, int ldw, int M, int N, int K, int splits, float* ws, size_t ws_bytes, hipStream_t st) {
+    switch (wgrad_kernel_for(y, x, ws ? ws_bytes : 0, swv2_gemm_wide())) {
+        case WgradKernel::WIDE: return launch_tn_wide(y, x, dW, db, nmap, kmap, ldw, M, N, K, ws, st);
+        case WgradKernel::TILE: break;
+    }
+    return launch_tn_tile<YK, XK>(y, x, dW, db, nmap, kmap, ldw, M, N, K, splits, ws, ws_bytes, st);
 }
 
 template <int YK>
@@ -546,6 +572,11 @@ extern "C" int swv2_linear_wgrad(const swv2_operand* dy, const swv2_operand* x, 
     return swv2_linear_wgrad_ws(dy, x, dW, db, nmap, kmap, ldw, splits, nullptr, 0, stream);
 }
 
+extern "C" int swv2_linear_wgrad_kernel(const swv2_operand* dy, const swv2_operand* x, int splits, size_t ws_bytes) {
+    SWV2_CHECK_ARG(dy && x && splits > 0 && dy->rows > 0 && dy->rows == x->rows, "swv2_linear_wgrad_kernel: null operand, non-positive splits or row mismatch");
+    return (int)wgrad_kernel_for(dy, x, ws_bytes, swv2_gemm_wide());       // (splits shapes the tile kernel's plan, not the choice)
+}
+
 // ------------------------------------------------------------------------------------------------
 // grouped launch: the four weight gradients of one block (see gemm_tn_group_kernel)
 // ------------------------------------------------------------------------------------------------
@@ -566,12 +597,59 @@ extern "C" int swv2_block_wgrad(const swv2_wgrad_item* it, int slices, void* ws,
     return swv2_block_wgrad_ln(it, slices, ws, ws_bytes, nullptr, stream);
 }
 
+namespace {
+enum class BlockWgradKernel { SLAB = SWV2_BLOCK_WGRAD_SLAB, GROUPED = SWV2_BLOCK_WGRAD_GROUPED };
+
+// second-generation kernel (gemm_tn_slab.hip: operands fetched once, by LDS-DMA) for the shapes, workspace and device it covers; an
+// explicit slice count selects the 128 x 128 tile kernel
+BlockWgradKernel block_wgrad_kernel_for(const swv2_wgrad_item* it, int slices, size_t ws_bytes) {
+    return slices <= 0 && swv2_tn_slab_covers(it, ws_bytes) ? BlockWgradKernel::SLAB : BlockWgradKernel::GROUPED;
+}
+
+// gemm_tn_group_kernel + tn_reduce_kernel over the four items (already checked)
+int launch_tn_group(const swv2_wgrad_item* it, int slices, void* ws, size_t ws_bytes, const swv2_ln_partials* ln, hipStream_t st) {
+    TnGroup g = {};
+    int tt = 0;
+    for (int i = 0; i < 4; ++i) {
+        g.first[i] = tt;
+        tt += cdiv(it[i].dy.cols, BN) * cdiv(it[i].x.cols, BN);
+    }
+    g.first[4] = tt;
+    const int S = group_slices(tt, slices);
+    SWV2_CHECK_ARG(ws_bytes >= (size_t)S * tt * BN * BN * sizeof(float), "swv2_block_wgrad: workspace of %zu bytes, %zu needed",
+                   ws_bytes, (size_t)S * tt * BN * BN * sizeof(float));
+    // (the tile kernel's reduction carries no rider.  Launched only after every argument check: an error return must not leave the
+    // LayerNorm gradients accumulated and the weight gradients not -- ADVICE r4)
+    if (ln && ln->C > 0)
+        swv2_launch_ln_partials_reduce2(ln->ws[0], ln->dgamma[0], ln->dbeta[0], ln->n[0], ln->ws[1], ln->dgamma[1], ln->dbeta[1], ln->n[1], ln->C, st);
+    TnReduce r = {};
+    for (int i = 0; i < 4; ++i) {
+        g.o[i] = tn_out(it[i].dW, it[i].db, it[i].nmap, it[i].kmap, it[i].ldw, it[i].dy.rows, it[i].dy.cols, it[i].x.cols,
+                        (float*)ws + (size_t)g.first[i] * S * BN * BN);
+        r.o[i] = g.o[i];
+    }
+    for (int i = 0; i < 5; ++i) r.first[i] = g.first[i];
+    g.y0 = make_loader<A_BF16>(&it[0].dy); g.x0 = make_loader<A_BF16_GELU>(&it[0].x);
+    g.y1 = make_loader<A_BF16>(&it[1].dy); g.x1 = make_loader<A_F32>(&it[1].x);
+    g.y2 = make_loader<A_BF16>(&it[2].dy); g.x2 = make_loader<A_HEADS>(&it[2].x);
+    g.y3 = make_loader<A_HEADS>(&it[3].dy); g.x3 = make_loader<A_F32>(&it[3].x);
+    g.slices = r.slices = S;
+    hipLaunchKernelGGL(gemm_tn_group_kernel, dim3(tt * S), dim3(NTHREADS), 0, st, g);
+    hipLaunchKernelGGL(tn_reduce_kernel, dim3(BN * BN / 64, tt), dim3(256), 0, st, r);
+    SWV2_CHECK_LAUNCH("swv2_block_wgrad");
+    return SWV2_OK;
+}
+}  // namespace
+
+extern "C" int swv2_block_wgrad_kernel(const swv2_wgrad_item* it, int slices, size_t ws_bytes) {
+    SWV2_CHECK_ARG(it, "swv2_block_wgrad_kernel: null items");
+    return (int)block_wgrad_kernel_for(it, slices, ws_bytes);
+}
+
 int swv2_block_wgrad_ln(const swv2_wgrad_item* it, int slices, void* ws, size_t ws_bytes, const swv2_ln_partials* ln, void* stream) {
     SWV2_CHECK_ARG(it && ws, "swv2_block_wgrad: null items or workspace");
     static const int want[4][2] = {{SWV2_OP_BF16, SWV2_OP_BF16_GELU}, {SWV2_OP_BF16, SWV2_OP_F32}, {SWV2_OP_BF16, SWV2_OP_HEADS},
                                    {SWV2_OP_HEADS, SWV2_OP_F32}};
-    TnGroup g = {};
-    int tt = 0;
     for (int i = 0; i < 4; ++i) {
         int rc = check_operand(&it[i].dy, "swv2_block_wgrad(dy)");
         if (rc) return rc;
@@ -582,41 +660,10 @@ int swv2_block_wgrad_ln(const swv2_wgrad_item* it, int slices, void* ws, size_t 
         SWV2_CHECK_ARG(it[i].dW && it[i].ldw > 0 && it[i].dy.rows == it[i].x.rows, "swv2_block_wgrad: item %d: null dW or row mismatch", i);
         SWV2_CHECK_ARG(!it[i].dy.rowidx && (i == 3 ? it[i].x.rowidx != nullptr : it[i].x.rowidx == nullptr),
                        "swv2_block_wgrad: item %d: only the qkv product's X rows are gathered (and they must be)", i);
-        g.first[i] = tt;
-        tt += cdiv(it[i].dy.cols, BN) * cdiv(it[i].x.cols, BN);
     }
-    g.first[4] = tt;
-    // second-generation kernel (gemm_tn_slab.hip: operands fetched once, by LDS-DMA) for the shapes it covers; an explicit slice
-    // count selects the 128 x 128 tile kernel below
-    if (slices <= 0) {
-        const int rc = swv2_tn_slab_launch(it, ws, ws_bytes, ln, (hipStream_t)stream);
-        if (rc <= 0) return rc;
+    switch (block_wgrad_kernel_for(it, slices, ws_bytes)) {
+        case BlockWgradKernel::SLAB: return swv2_tn_slab_launch(it, ws, ws_bytes, ln, (hipStream_t)stream);
+        case BlockWgradKernel::GROUPED: break;
     }
-    const int S = group_slices(tt, slices);
-    SWV2_CHECK_ARG(ws_bytes >= (size_t)S * tt * BN * BN * sizeof(float), "swv2_block_wgrad: workspace of %zu bytes, %zu needed",
-                   ws_bytes, (size_t)S * tt * BN * BN * sizeof(float));
-    // (the tile kernel's reduction carries no rider.  Launched only after every argument check: an error return must not leave the
-    // LayerNorm gradients accumulated and the weight gradients not -- ADVICE r4)
-    if (ln && ln->C > 0)
-        swv2_launch_ln_partials_reduce2(ln->ws[0], ln->dgamma[0], ln->dbeta[0], ln->n[0], ln->ws[1], ln->dgamma[1], ln->dbeta[1], ln->n[1], ln->C,
-                                        (hipStream_t)stream);
-    TnReduce r = {};
-    for (int i = 0; i < 4; ++i) {
-        const int tiles = cdiv(it[i].dy.cols, BN) * cdiv(it[i].x.cols, BN);
-        g.o[i] = tn_out(it[i].dW, it[i].db, it[i].nmap, it[i].kmap, it[i].ldw, it[i].dy.rows, it[i].dy.cols, it[i].x.cols,
-                        (float*)ws + (size_t)g.first[i] * S * BN * BN);
-        (void)tiles;
-        r.o[i] = g.o[i];
-    }
-    for (int i = 0; i < 5; ++i) r.first[i] = g.first[i];
-    g.y0 = make_loader<A_BF16>(&it[0].dy); g.x0 = make_loader<A_BF16_GELU>(&it[0].x);
-    g.y1 = make_loader<A_BF16>(&it[1].dy); g.x1 = make_loader<A_F32>(&it[1].x);
-    g.y2 = make_loader<A_BF16>(&it[2].dy); g.x2 = make_loader<A_HEADS>(&it[2].x);
-    g.y3 = make_loader<A_HEADS>(&it[3].dy); g.x3 = make_loader<A_F32>(&it[3].x);
-    g.slices = r.slices = S;
-    hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(gemm_tn_group_kernel, dim3(tt * S), dim3(NTHREADS), 0, st, g);
-    hipLaunchKernelGGL(tn_reduce_kernel, dim3(BN * BN / 64, tt), dim3(256), 0, st, r);
-    SWV2_CHECK_LAUNCH("swv2_block_wgrad");
-    return SWV2_OK;
+    return launch_tn_group(it, slices, ws, ws_bytes, ln, (hipStream_t)stream);
 }

@@ -705,16 +705,21 @@ size_t swv2_tn_slab_ws_bytes(int C, int hidden, int heads_dp) {
     return (size_t)cus * tile + (size_t)cus * std::max(hidden, 3 * heads_dp) * 4 + 4 * 256;
 }
 
-// 0: launched; 1: shape / workspace not covered (the caller takes the 128 x 128 tile kernel); < 0: error code
-int swv2_tn_slab_launch(const swv2_wgrad_item* it, void* ws, size_t ws_bytes, const swv2_ln_partials* ln, hipStream_t st) {
-    const int cus = sl_cus();
-    const SlPlan pl = sl_plan(it, cus);
+// the slab kernel runs these items with this workspace on the current device (see gemm_common.h)
+bool swv2_tn_slab_covers(const swv2_wgrad_item* it, size_t ws_bytes) {
+    const SlPlan pl = sl_plan(it, sl_cus());
     if (pl.ok && ws_bytes < pl.total) {
         static int once = 0;
         if (!once++) fprintf(stderr, "swv2: grouped weight gradient declined (workspace %zu bytes, %zu needed): size it with swv2_block_wgrad_ws_bytes; "
                                      "running the 128 x 128 tile kernels\n", ws_bytes, pl.total);
     }
-    if (!pl.ok || ws_bytes < pl.total) return 1;
+    return pl.ok && ws_bytes >= pl.total;
+}
+
+// for items swv2_tn_slab_covers accepts; 0 or a negative error code
+int swv2_tn_slab_launch(const swv2_wgrad_item* it, void* ws, size_t ws_bytes, const swv2_ln_partials* ln, hipStream_t st) {
+    const SlPlan pl = sl_plan(it, sl_cus());
+    SWV2_CHECK_ARG(pl.ok && ws_bytes >= pl.total, "swv2_block_wgrad(slab): items or workspace not covered (swv2_tn_slab_covers)");
     const SlShape& sh = SL_SETS[pl.set];
     SlArgs a = {};
     SlRedArgs r = {};

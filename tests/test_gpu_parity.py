@@ -145,9 +145,21 @@ def test_wide_gemm_kernels_equal_the_128_tile_kernel_bit_for_bit(dev, K, persist
     """The 256 x 256 kernels of the wide widths (reference swin.yaml: embed_dim 768) -- LDS-DMA pipeline for raw bf16 operands,
     register-staged fp32 / gathered rows, full-line epilogue -- against gemm_nt_kernel on the same inputs: same k order per output
     element and the same epilogue arithmetic, so the results must be IDENTICAL; plus a torch reference per product.  Every
-    loader x epilogue pair the width-768 block uses; ragged M (last row tile partly outside), gather tables with zero rows, scatter."""
+    loader x epilogue pair the width-768 block uses; ragged M (last row tile partly outside), gather tables with zero rows, scatter.
+    Every product asserts the path it names: swv2_linear_kernel reports a wide kernel under SWV2_GEMM_WIDE=1 and a tile kernel under
+    =0, the same one whatever SWV2_WIDE_PERSIST says (persistence is a grid choice, not a kernel)."""
     ops, L = K["ops"], K["L"]
     monkeypatch.setenv("SWV2_WIDE_PERSIST", persist)
+    lib = L.load()
+
+    def linear(a, w, e, N):
+        kern = lib.swv2_linear_kernel(ctypes.byref(a), ctypes.byref(e), N)
+        wide = os.environ["SWV2_GEMM_WIDE"] == "1"
+        assert kern in (L.LINEAR_WIDE_KERNELS if wide else L.LINEAR_TILE_KERNELS), (kern, wide, a.kind, e.kind, a.rows, a.cols, N)
+        with pytest.MonkeyPatch.context() as mp:
+            mp.setenv("SWV2_WIDE_PERSIST", "0" if persist == "1" else "1")
+            assert lib.swv2_linear_kernel(ctypes.byref(a), ctypes.byref(e), N) == kern
+        ops.linear(a, w, e, N)
     torch.manual_seed(11)
     M, Kd = 4500, 512
 
@@ -174,13 +186,13 @@ def test_wide_gemm_kernels_equal_the_128_tile_kernel_bit_for_bit(dev, K, persist
         ri[::5] = -1                                          # rows that are dropped by the scatter
         aux = torch.randn(M, Nn, device=dev)
         o32 = torch.empty(M, Nn, device=dev)
-        (g,) = both(lambda: ops.linear(ops.op_bf16(xb), wb, ops.epilogue(L.EPI_F32, o32, ld=Nn, bias=b.to(dev)), Nn), [o32])
+        (g,) = both(lambda: linear(ops.op_bf16(xb), wb, ops.epilogue(L.EPI_F32, o32, ld=Nn, bias=b.to(dev)), Nn), [o32])
         assert rel(g, ref) < 1e-5
         o32.zero_()
         sc = torch.zeros(M, Nn, device=dev)
         def run_scatter():
             sc.zero_()
-            ops.linear(ops.op_bf16(xb), wb, ops.epilogue(L.EPI_F32, sc, ld=Nn, aux=aux, rowidx=ri), Nn)
+            linear(ops.op_bf16(xb), wb, ops.epilogue(L.EPI_F32, sc, ld=Nn, aux=aux, rowidx=ri), Nn)
         got = []
         for flag in ("0", "1"):
             _with_wide(flag, run_scatter)
@@ -191,22 +203,22 @@ def test_wide_gemm_kernels_equal_the_128_tile_kernel_bit_for_bit(dev, K, persist
         exp[idx[keep]] = (rb(x) @ rb(w).T)[keep] + aux.cpu()[idx[keep]]
         assert rel(got[1], exp) < 1e-5
         ob = torch.empty(M, Nn, dtype=BF, device=dev)
-        (g,) = both(lambda: ops.linear(ops.op_bf16(xb), wb, ops.epilogue(L.EPI_BF16, ob, ld=Nn, bias=b.to(dev)), Nn), [ob])
+        (g,) = both(lambda: linear(ops.op_bf16(xb), wb, ops.epilogue(L.EPI_BF16, ob, ld=Nn, bias=b.to(dev)), Nn), [ob])
         assert rel(g.float(), ref) < 4e-3
         # fp32 rows (register-staged): gathered with zero rows -> bf16 ; fc1 epilogue (pre-activation + GELU)
         ri2 = torch.randperm(M).to(torch.int32)
         ri2[::7] = -1
-        (g,) = both(lambda: ops.linear(ops.op_f32(x.to(dev), rowidx=ri2.to(dev)), wb, ops.epilogue(L.EPI_BF16, ob, ld=Nn), Nn), [ob])
+        (g,) = both(lambda: linear(ops.op_f32(x.to(dev), rowidx=ri2.to(dev)), wb, ops.epilogue(L.EPI_BF16, ob, ld=Nn), Nn), [ob])
         exp = (rb(x) @ rb(w).T)[ri2.clamp(min=0).long()]
         exp[ri2 < 0] = 0
         assert rel(g.float(), exp) < 4e-3
         act = torch.empty(M, Nn, dtype=BF, device=dev)
-        g_pre, g_act = both(lambda: ops.linear(ops.op_f32(x.to(dev)), wb, ops.epilogue(L.EPI_BF16_GELU, ob, ld=Nn, bias=b.to(dev), aux_out=act), Nn),
+        g_pre, g_act = both(lambda: linear(ops.op_f32(x.to(dev)), wb, ops.epilogue(L.EPI_BF16_GELU, ob, ld=Nn, bias=b.to(dev), aux_out=act), Nn),
                             [ob, act])
         assert rel(g_pre.float(), ref) < 4e-3 and rel(g_act.float(), O.gelu_erf(g_pre.float().cpu())) < 4e-3
         # dh = (dy W) * GELU'(pre-activation)
         hpre = torch.randn(M, Nn).to(BF).to(dev)
-        (g,) = both(lambda: ops.linear(ops.op_bf16(xb), wb, ops.epilogue(L.EPI_GELU_GRAD, ob, ld=Nn, aux=hpre), Nn), [ob])
+        (g,) = both(lambda: linear(ops.op_bf16(xb), wb, ops.epilogue(L.EPI_GELU_GRAD, ob, ld=Nn, aux=hpre), Nn), [ob])
         hp = hpre.float().cpu().double().requires_grad_(True)
         O.gelu_erf(hp).backward((rb(x) @ rb(w).T).double())
         assert rel(g.float(), hp.grad) < 4e-3
@@ -217,10 +229,10 @@ def test_wide_gemm_kernels_equal_the_128_tile_kernel_bit_for_bit(dev, K, persist
     wl = torch.randn(768, Kd) * 0.05
     wlb = ops.prep_weight(wl.to(dev))
     o32 = torch.empty(Mb, 768, device=dev)
-    (g,) = both(lambda: ops.linear(ops.op_bf16(xl), wlb, ops.epilogue(L.EPI_F32, o32, ld=768), 768), [o32])
+    (g,) = both(lambda: linear(ops.op_bf16(xl), wlb, ops.epilogue(L.EPI_F32, o32, ld=768), 768), [o32])
     assert rel(g, xl.float().cpu() @ rb(wl).T) < 1e-5
     ob = torch.empty(Mb, 768, dtype=BF, device=dev)
-    (g,) = both(lambda: ops.linear(ops.op_bf16(xl), wlb, ops.epilogue(L.EPI_BF16, ob, ld=768), 768), [ob])
+    (g,) = both(lambda: linear(ops.op_bf16(xl), wlb, ops.epilogue(L.EPI_BF16, ob, ld=768), 768), [ob])
     assert rel(g.float(), xl.float().cpu() @ rb(wl).T) < 4e-3
 
     # head-major layouts of the wide heads (width 768 = 8 heads of 96: 96 columns, unpadded; 97 .. 128 channels: 128 columns):
@@ -237,7 +249,7 @@ def test_wide_gemm_kernels_equal_the_128_tile_kernel_bit_for_bit(dev, K, persist
         rn = torch.zeros(Bw, h, 2, Lp, device=dev)
         def run_qkv():
             rn.zero_()
-            ops.linear(ops.op_f32(xw.to(dev), rowidx=ri3.to(dev)), wqb,
+            linear(ops.op_f32(xw.to(dev), rowidx=ri3.to(dev)), wqb,
                        ops.epilogue(L.EPI_QKV_HEADS, qkvh, bias=bq.to(dev), aux_out=rn, p=(h, 0, Lp, DP, Lv)), 3 * h * DP)
         got = []
         for flag in ("0", "1"):
@@ -255,7 +267,7 @@ def test_wide_gemm_kernels_equal_the_128_tile_kernel_bit_for_bit(dev, K, persist
         da1 = torch.randn(Mw, Kd).to(BF).to(dev)
         wp = torch.randn(h * DP, Kd) * 0.05
         doh = torch.empty(Bw, h, 1, Lp, DP, dtype=BF, device=dev)
-        (g,) = both(lambda: ops.linear(ops.op_bf16(da1), ops.prep_weight(wp.to(dev)), ops.epilogue(L.EPI_HEADS, doh, p=(h, 0, Lp, DP, Lv)), h * DP), [doh])
+        (g,) = both(lambda: linear(ops.op_bf16(da1), ops.prep_weight(wp.to(dev)), ops.epilogue(L.EPI_HEADS, doh, p=(h, 0, Lp, DP, Lv)), h * DP), [doh])
         fullp = (da1.float().cpu() @ rb(wp).T).view(Bw, Lp, 1, h, DP).permute(0, 3, 2, 1, 4)
         assert rel(g.float(), torch.where(valid, fullp, torch.zeros(()))) < 4e-3
         for parts, Nn in ((1, 512), (3, 768)):
@@ -263,11 +275,11 @@ def test_wide_gemm_kernels_equal_the_128_tile_kernel_bit_for_bit(dev, K, persist
             wo = torch.randn(Nn, parts * h * DP) * 0.05
             wob = ops.prep_weight(wo.to(dev))
             o32 = torch.empty(Mw, Nn, device=dev)
-            (g,) = both(lambda: ops.linear(ops.op_heads(src, Bw, h, parts, Lp, DP), wob, ops.epilogue(L.EPI_F32, o32, ld=Nn), Nn), [o32])
+            (g,) = both(lambda: linear(ops.op_heads(src, Bw, h, parts, Lp, DP), wob, ops.epilogue(L.EPI_F32, o32, ld=Nn), Nn), [o32])
             rows = src.float().cpu().permute(0, 3, 2, 1, 4).reshape(Mw, parts * h * DP)
             assert rel(g, rows @ rb(wo).T) < 1e-5
             ob = torch.empty(Mw, Nn, dtype=BF, device=dev)
-            (g,) = both(lambda: ops.linear(ops.op_heads(src, Bw, h, parts, Lp, DP), wob, ops.epilogue(L.EPI_BF16, ob, ld=Nn), Nn), [ob])
+            (g,) = both(lambda: linear(ops.op_heads(src, Bw, h, parts, Lp, DP), wob, ops.epilogue(L.EPI_BF16, ob, ld=Nn), Nn), [ob])
             assert rel(g.float(), rows @ rb(wo).T) < 4e-3
 
 

@@ -1,5 +1,6 @@
 """GPU (-m gpu): 256-channel attention heads (embed 2048 / 8 heads; csrc/attn_d256.hip) and the rest of the block at that width,
 against exact fp64 autograd and against the oracle in the kernels' rounding mode.  Bars as in tests/test_gpu_parity.py."""
+import ctypes
 import os
 
 import numpy as np
@@ -7,6 +8,7 @@ import pytest
 import torch
 
 from oracle import swin_oracle as O
+from swin_v2_weather_amd import _lib
 from tests.test_gpu_parity import (BLOCK_LOGIT_TOL, ORACLE_LOGIT_TOL, _with_wide, block_cfg, emulate_kernels, from_heads, rb, rel,
                                    to_heads, worst_grad)
 
@@ -144,23 +146,44 @@ def chunk_rel(a, b, dim=-1, width=64):
     return max(rel(x, y) for x, y in zip(a.split(width, dim), b.split(width, dim)))
 
 
-def _both(run):
-    """run() under the 128-tile kernels (SWV2_GEMM_WIDE=0) and the wide ones (=1); returns the two result lists"""
+def _both(run, kernel, families=(_lib.LINEAR_TILE_KERNELS, _lib.LINEAR_WIDE_KERNELS)):
+    """run() under the 128-tile kernels (SWV2_GEMM_WIDE=0) and the wide ones (=1); returns the two result lists.  kernel(): the
+    library's answer for the product run() launches (swv2_linear_kernel / swv2_linear_wgrad_kernel), which must be a tile kernel
+    under =0 and a wide one under =1"""
     out = []
     for flag in ("0", "1"):
         res = []
-        _with_wide(flag, lambda: res.extend(t.clone() for t in run()))
+
+        def go():
+            assert kernel() in families[int(flag)], (flag, kernel())
+            res.extend(t.clone() for t in run())
+        _with_wide(flag, go)
         out.append(res)
     return out
+
+
+def _linear_kernel(a, e, N):
+    return lambda: _lib.load().swv2_linear_kernel(ctypes.byref(a), ctypes.byref(e), N)
+
+
+def _wgrad_kernel(dy, x):
+    """for ops.linear_wgrad(dy, x, ...) with its workspace (sized by swv2_linear_wgrad_ws_bytes: covers the wide plan for any slice count)"""
+    lib = _lib.load()
+    return lambda: lib.swv2_linear_wgrad_kernel(ctypes.byref(dy), ctypes.byref(x), 64, lib.swv2_linear_wgrad_ws_bytes(dy.rows, dy.cols, x.cols, 64))
+
+
+_WGRAD = ((_lib.WGRAD_TILE,), (_lib.WGRAD_WIDE,))
 
 
 def test_qkv_epilogue_normalisation_and_head_major_loaders_at_dp_256(dev, K):
     """The GEMM side of the 256-column head layout at C = 2048, 8 heads, against torch fp32: the qkv epilogue with head split
     (un-normalised bf16 values + squared norms in rnorm, four addends per row), swv2_qk_normalize, the head split of d(oh), the
-    head-major operand in the proj forward and the d(qkv) -> dx product, and the two weight gradients that read it."""
+    head-major operand in the proj forward and the d(qkv) -> dx product, and the two weight gradients that read it.  48 windows: 8 448
+    rows, from which the wide kernels take the NT products (M >= 4 096) and the weight gradients (M >= 8 192, a multiple of 32) --
+    every product asserts that the library's kernel query says so under SWV2_GEMM_WIDE=1, and the tile kernels under =0."""
     ops, L = K["ops"], K["L"]
     torch.manual_seed(31)
-    h, DP, Lp, Lv, Bw, Cc = 8, 256, 176, 162, 6, 2048
+    h, DP, Lp, Lv, Bw, Cc = 8, 256, 176, 162, 48, 2048
     Mw = Bw * Lp
     valid = (torch.arange(Lp) < Lv).view(1, 1, 1, Lp, 1)
     xw = torch.randn(Mw, Cc)
@@ -171,13 +194,15 @@ def test_qkv_epilogue_normalisation_and_head_major_loaders_at_dp_256(dev, K):
     qkvh = torch.empty(Bw, h, 3, Lp, DP, dtype=BF, device=dev)
     rn = torch.zeros(Bw, h, 2, Lp, device=dev)
 
+    a_qkv = ops.op_f32(xw.to(dev), rowidx=ri.to(dev))
+    e_qkv = ops.epilogue(L.EPI_QKV_HEADS, qkvh, bias=bq.to(dev), aux_out=rn, p=(h, 0, Lp, DP, Lv))
+
     def run_qkv():
         qkvh.fill_(float("nan"))
         rn.zero_()
-        ops.linear(ops.op_f32(xw.to(dev), rowidx=ri.to(dev)), wqb,
-                   ops.epilogue(L.EPI_QKV_HEADS, qkvh, bias=bq.to(dev), aux_out=rn, p=(h, 0, Lp, DP, Lv)), 3 * h * DP)
+        ops.linear(a_qkv, wqb, e_qkv, 3 * h * DP)
         return [qkvh, rn]
-    (q0, r0), (q1, r1) = _both(run_qkv)
+    (q0, r0), (q1, r1) = _both(run_qkv, _linear_kernel(a_qkv, e_qkv, 3 * h * DP))
     assert torch.equal(q0, q1) and rel(r0, r1) < 1e-6          # four float addends per norm: equal up to their order
     full = torch.where(valid, (rb(xw) @ rb(wq).T + bq).view(Bw, Lp, 3, h, DP).permute(0, 3, 2, 1, 4), torch.zeros(()))
     got = q1.float().cpu()
@@ -202,11 +227,13 @@ def test_qkv_epilogue_normalisation_and_head_major_loaders_at_dp_256(dev, K):
     wp = torch.randn(h * DP, Cc) * 0.03
     doh = torch.empty(Bw, h, 1, Lp, DP, dtype=BF, device=dev)
 
+    a_sp, e_sp = ops.op_bf16(da1), ops.epilogue(L.EPI_HEADS, doh, p=(h, 0, Lp, DP, Lv))
+
     def run_split():
         doh.fill_(float("nan"))
-        ops.linear(ops.op_bf16(da1), ops.prep_weight(wp.to(dev)), ops.epilogue(L.EPI_HEADS, doh, p=(h, 0, Lp, DP, Lv)), h * DP)
+        ops.linear(a_sp, ops.prep_weight(wp.to(dev)), e_sp, h * DP)
         return [doh]
-    (g0,), (g1,) = _both(run_split)
+    (g0,), (g1,) = _both(run_split, _linear_kernel(a_sp, e_sp, h * DP))
     fullp = torch.where(valid, (da1.float().cpu() @ rb(wp).T).view(Bw, Lp, 1, h, DP).permute(0, 3, 2, 1, 4), torch.zeros(()))
     for g_ in (g0, g1):
         assert not torch.isnan(g_.float()).any() and chunk_rel(g_.float(), fullp) < 4e-3
@@ -219,9 +246,10 @@ def test_qkv_epilogue_normalisation_and_head_major_loaders_at_dp_256(dev, K):
         ref = rows @ rb(wo).T
         o32 = torch.empty(Mw, Cc, device=dev)
         ob = torch.empty(Mw, Cc, dtype=BF, device=dev)
-        for g_ in _both(lambda: (ops.linear(ops.op_heads(src, Bw, h, parts, Lp, DP), wob, ops.epilogue(L.EPI_F32, o32, ld=Cc), Cc), [o32])[1]):
+        a_h, e32, eb = ops.op_heads(src, Bw, h, parts, Lp, DP), ops.epilogue(L.EPI_F32, o32, ld=Cc), ops.epilogue(L.EPI_BF16, ob, ld=Cc)
+        for g_ in _both(lambda: (ops.linear(a_h, wob, e32, Cc), [o32])[1], _linear_kernel(a_h, e32, Cc)):
             assert chunk_rel(g_[0], ref) < 1e-5
-        for g_ in _both(lambda: (ops.linear(ops.op_heads(src, Bw, h, parts, Lp, DP), wob, ops.epilogue(L.EPI_BF16, ob, ld=Cc), Cc), [ob])[1]):
+        for g_ in _both(lambda: (ops.linear(a_h, wob, eb, Cc), [ob])[1], _linear_kernel(a_h, eb, Cc)):
             assert chunk_rel(g_[0].float(), ref) < 4e-3
     # weight gradients: qkv (head-major dY x gathered fp32 rows) and proj (bf16 dY x head-major X)
     dq = torch.zeros(Bw, h, 3, Lp, DP)
@@ -232,13 +260,15 @@ def test_qkv_epilogue_normalisation_and_head_major_loaders_at_dp_256(dev, K):
     tok = torch.randperm(Bw * Lv).to(torch.int32)
     rg.view(Bw, Lp)[:, :Lv] = tok.view(Bw, Lv)
 
+    dy_q, x_q = ops.op_heads(dqb, Bw, h, 3, Lp, DP), ops.op_f32(xs.to(dev), rows=Mw, rowidx=rg.to(dev))
+
     def run_wq():
         dW, db = torch.zeros(3 * h * DP, Cc, device=dev), torch.zeros(3 * h * DP, device=dev)
-        ops.linear_wgrad(ops.op_heads(dqb, Bw, h, 3, Lp, DP), ops.op_f32(xs.to(dev), rows=Mw, rowidx=rg.to(dev)), dW, db)
+        ops.linear_wgrad(dy_q, x_q, dW, db)
         return [dW, db]
     rows = dqb.float().cpu().permute(0, 3, 2, 1, 4)[:, :Lv].reshape(Bw * Lv, 3 * h * DP)
     xg = rb(xs)[tok.long()]
-    for dW, db in _both(run_wq):
+    for dW, db in _both(run_wq, _wgrad_kernel(dy_q, x_q), _WGRAD):
         assert chunk_rel(dW, rows.T @ xg, dim=0) < 1e-5 and chunk_rel(db, rows.sum(0), dim=0) < 1e-5
     oh = torch.zeros(Bw, h, 1, Lp, DP)
     oh[:, :, :, :Lv] = torch.randn(Bw, h, 1, Lv, DP)
@@ -247,12 +277,14 @@ def test_qkv_epilogue_normalisation_and_head_major_loaders_at_dp_256(dev, K):
     da[:, :Lv] = torch.randn(Bw, Lv, Cc) * 0.5
     dab = da.reshape(Mw, Cc).to(BF).to(dev)
 
+    dy_p, x_p = ops.op_bf16(dab), ops.op_heads(ohb, Bw, h, 1, Lp, DP)
+
     def run_wp():
         dW, db = torch.zeros(Cc, h * DP, device=dev), torch.zeros(Cc, device=dev)
-        ops.linear_wgrad(ops.op_bf16(dab), ops.op_heads(ohb, Bw, h, 1, Lp, DP), dW, db)
+        ops.linear_wgrad(dy_p, x_p, dW, db)
         return [dW, db]
     xo = ohb.float().cpu()[:, :, 0].permute(0, 2, 1, 3).reshape(Mw, h * DP)
-    for dW, db in _both(run_wp):
+    for dW, db in _both(run_wp, _wgrad_kernel(dy_p, x_p), _WGRAD):
         assert chunk_rel(dW, dab.float().cpu().T @ xo) < 1e-5 and rel(db, dab.float().cpu().sum(0)) < 1e-5
 
 

@@ -112,6 +112,115 @@ def test_weight_gradient_workspace_budget_covers_the_wide_path():
     assert lib.swv2_linear_wgrad_ws_bytes(0, 768, 768, 8) == 0
 
 
+# ---- kernel selection (swv2_linear_kernel / swv2_linear_wgrad_kernel / swv2_block_wgrad_kernel) ---------------------------
+_FAKE = 0x10000          # stands for "a pointer is present": the queries dereference no data pointer
+
+
+def _op(kind, rows, cols, ld, gather=False, p=(0, 0, 0, 0)):
+    o = L.Operand()
+    o.kind, o.ptr, o.rowidx, o.ld, o.rows, o.cols = kind, _FAKE, _FAKE if gather else None, ld, rows, cols
+    o.p = (ctypes.c_int * 4)(*p)
+    return o
+
+
+def _op_heads(Bw, h, parts, Lp, DP):
+    return _op(L.OP_HEADS, Bw * Lp, parts * h * DP, parts, p=(h, 0, Lp, DP))
+
+
+def _epi(kind, ld=0, aux=False, scatter=False, p=(0, 0, 0, 0, 0)):
+    e = L.Epilogue()
+    e.kind, e.out, e.aux, e.rowidx, e.ld = kind, _FAKE, _FAKE if aux else None, _FAKE if scatter else None, ld
+    e.p = (ctypes.c_int * 5)(*p)
+    return e
+
+
+def _block_products(B, C, hid, h, DP, fused):
+    """the descriptors swv2_block_fwd / swv2_block_bwd build (csrc/block.hip) for one block on the 180 x 360 patch grid of the
+    721 x 1440 fields in 9 x 18 windows (WindowPlan: 400 windows per sample, 162 tokens padded to 176 rows), local batch B"""
+    Lw, Lp, BT, Bw = 162, 176, B * 180 * 360, B * 400
+    Mw = Bw * Lp
+    hp = (h, 0, Lp, DP, Lw)
+    linear = {
+        "qkv": (_op(L.OP_F32, Mw, C, C, gather=True), _epi(L.EPI_QKV_HEADS, p=hp), 3 * h * DP),
+        "proj": (_op_heads(Bw, h, 1, Lp, DP), _epi(L.EPI_BF16, C), C),
+        "fc1": (_op(L.OP_F32, BT, C, C), _epi(L.EPI_BF16_GELU, hid), hid),
+        "fc2": (_op(L.OP_BF16, BT, hid, hid), _epi(L.EPI_BF16, C), C),
+        "d_fc2": (_op(L.OP_BF16, BT, C, C), _epi(L.EPI_GELU_GRAD, hid, aux=True), hid),
+        "dx1": (_op(L.OP_BF16, BT, hid, hid), _epi(L.EPI_F32, C, aux=True), C),
+        "d_oh": (_op(L.OP_BF16, Mw, C, C), _epi(L.EPI_HEADS, p=hp), h * DP),
+        "dx": (_op_heads(Bw, h, 3, Lp, DP), _epi(L.EPI_F32, C, aux=True, scatter=True), C),
+        "head": (_op(L.OP_F32, BT, C, C), _epi(L.EPI_UNPATCH, p=(73, 720, 1440, 0, 0)), 73 * 16),
+        "head_loss": (_op(L.OP_F32, BT, C, C), _epi(L.EPI_UNPATCH_LOSS, p=(73, 720, 1440, 0, 0)), 73 * 16),
+    }
+    # items 0 .. 3 of swv2_block_wgrad; the fused MLP path keeps no GELU output: fc2's X operand is GELU(hpre) on load
+    wgrad = [(_op(L.OP_BF16, BT, C, C), _op(L.OP_BF16_GELU if fused else L.OP_BF16, BT, hid, hid)),
+             (_op(L.OP_BF16, BT, hid, hid), _op(L.OP_F32, BT, C, C)),
+             (_op(L.OP_BF16, Mw, C, C), _op_heads(Bw, h, 1, Lp, DP)),
+             (_op_heads(Bw, h, 3, Lp, DP), _op(L.OP_F32, Mw, C, C, gather=True))]
+    return linear, wgrad
+
+
+def test_kernel_selection_for_the_products_the_model_launches(monkeypatch):
+    """The selection the launchers switch on, pinned for the products of the four block shapes the repository runs.  The expected
+    kernels were read off the launch ladders as they stood before the selection functions existed (swv2_linear: resident-weight
+    shapes, then the wide condition N % 256 == 0, N, K >= 512, M >= 4096 with LDS-DMA staging for raw bf16 / head-major operands,
+    then 64-row tiles for the loss epilogue and where the qkv / dx products fill 768 workgroup slots better; weight gradients: wide
+    from N, K >= 512 in multiples of 256 with a raw-bf16 or fp32 X, the slab at its two block shapes).  No GPU: the slab query
+    sees the library's 256-CU fallback."""
+    lib = L.load()
+    monkeypatch.delenv("SWV2_GEMM_WIDE", raising=False)
+    Q128, Q192, DX128, DMA, WIDE, T64, T128 = (L.LINEAR_RESIDENT_QKV128, L.LINEAR_RESIDENT_QKV192X3, L.LINEAR_RESIDENT_DX128,
+                                               L.LINEAR_WIDE_DMA, L.LINEAR_WIDE, L.LINEAR_TILE64, L.LINEAR_TILE128)
+    order = ("qkv", "proj", "fc1", "fc2", "d_fc2", "dx1", "d_oh", "dx", "head", "head_loss")
+    shapes = {
+        # (local batch, C, hidden, heads, head columns, fused MLP): linear kernels in `order`, single weight gradients, block
+        "bench C 128": ((2, 128, 512, 8, 16, True), (Q128, T128, T128, T128, T128, T128, T128, DX128, T128, T64),
+                        [L.WGRAD_TILE] * 4, L.BLOCK_WGRAD_SLAB),
+        "geo C 192": ((2, 192, 768, 8, 32, True), (Q192, T128, T128, T128, T128, T128, T128, DMA, T128, T64),
+                      [L.WGRAD_TILE] * 4, L.BLOCK_WGRAD_SLAB),
+        "yaml default C 768": ((1, 768, 3072, 8, 96, False), (WIDE, DMA, WIDE, DMA, DMA, DMA, DMA, DMA, T128, T64),
+                               [L.WGRAD_WIDE] * 4, L.BLOCK_WGRAD_GROUPED),
+        "embed 2048": ((1, 2048, 4096, 8, 256, False), (WIDE, DMA, WIDE, DMA, DMA, DMA, DMA, DMA, T128, T64),
+                       [L.WGRAD_WIDE] * 4, L.BLOCK_WGRAD_GROUPED),
+    }
+
+    def wgrad_ws(dy, x):
+        return lib.swv2_linear_wgrad_ws_bytes(dy.rows, dy.cols, x.cols, 128)
+
+    for name, (cfg, want_linear, want_wgrad, want_block) in shapes.items():
+        linear, wgrad = _block_products(*cfg)
+        got = tuple(lib.swv2_linear_kernel(ctypes.byref(a), ctypes.byref(e), n) for a, e, n in (linear[k] for k in order))
+        assert got == want_linear, (name, dict(zip(order, got)))
+        got = [lib.swv2_linear_wgrad_kernel(ctypes.byref(dy), ctypes.byref(x), 128, wgrad_ws(dy, x)) for dy, x in wgrad]
+        assert got == want_wgrad, (name, got)
+        # without a workspace (swv2_linear_wgrad: atomics) only the tile kernel runs
+        assert all(lib.swv2_linear_wgrad_kernel(ctypes.byref(dy), ctypes.byref(x), 64, 0) == L.WGRAD_TILE for dy, x in wgrad), name
+        items = (L.WgradItem * 4)()
+        for i, (dy, x) in enumerate(wgrad):
+            items[i].dy, items[i].x, items[i].dW, items[i].ldw = dy, x, _FAKE, x.cols
+        _, C_, hid, h, DP, _ = cfg
+        ws = lib.swv2_block_wgrad_ws_bytes(C_, hid, h * DP, 0)
+        assert lib.swv2_block_wgrad_kernel(items, 0, ws) == want_block, name
+        assert lib.swv2_block_wgrad_kernel(items, 8, ws) == L.BLOCK_WGRAD_GROUPED, name      # an explicit slice count: the tile kernel
+
+    # the embed-768 fc2 gradient with the fused path's GELU-on-load operand is not a wide-kernel kind
+    _, wg = _block_products(1, 768, 3072, 8, 96, True)
+    assert lib.swv2_linear_wgrad_kernel(ctypes.byref(wg[0][0]), ctypes.byref(wg[0][1]), 128, wgrad_ws(*wg[0])) == L.WGRAD_TILE
+    # SWV2_GEMM_WIDE=0: the wide rows fall to the tile kernels (64-row tiles where 2 200 workgroups fill 3 x 768 slots, 128-row ones
+    # where 550 / 1 100 workgroups fill 768 / 1 536 equally)
+    monkeypatch.setenv("SWV2_GEMM_WIDE", "0")
+    lin192, _ = _block_products(2, 192, 768, 8, 32, True)
+    lin768, wg768 = _block_products(1, 768, 3072, 8, 96, False)
+    assert lib.swv2_linear_kernel(ctypes.byref(lin192["dx"][0]), ctypes.byref(lin192["dx"][1]), 192) == T64
+    assert lib.swv2_linear_kernel(ctypes.byref(lin768["qkv"][0]), ctypes.byref(lin768["qkv"][1]), 2304) == T128
+    assert lib.swv2_linear_kernel(ctypes.byref(lin768["fc2"][0]), ctypes.byref(lin768["fc2"][1]), 768) == T128
+    assert all(lib.swv2_linear_wgrad_kernel(ctypes.byref(dy), ctypes.byref(x), 128, wgrad_ws(dy, x)) == L.WGRAD_TILE for dy, x in wg768)
+    monkeypatch.delenv("SWV2_GEMM_WIDE")
+    # argument errors come back as negative codes
+    assert lib.swv2_linear_kernel(None, None, 4) == -1 and lib.swv2_block_wgrad_kernel(None, 0, 0) == -1
+    assert lib.swv2_linear_kernel(ctypes.byref(_op(L.OP_BF16_CSCALE, 64, 64, 64)), ctypes.byref(_epi(L.EPI_BF16, 64)), 64) == -1
+
+
 def test_model_refuses_cpu_tensors():
     m = N.SwinTransformerV2Cr(img_size=(24, 36), patch_size=4, depths=(1,), num_heads=(2,), in_chans=3, out_chans=3,
                               embed_dim=16, img_window_ratio=4, full_pos_embed=True, rel_pos=False)

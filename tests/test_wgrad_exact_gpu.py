@@ -24,6 +24,10 @@ library's own bf16(GELU(pre)), read from the library by the gelu_lut fixture).  
   * slab (bf16 partials):                        |dW - ref| <= 2^-8 * A  (each partial rounded once: <= 2^-9 of itself)
   * bias gradients: the same with A = sum_m |dY[m, n]| (every path keeps its bias partials in fp32: C32)
 
+Every result is filed under a path name, and the error bar follows from the name (_family); before each launch the library is asked
+which kernel it will run for exactly these arguments (swv2_block_wgrad_kernel / swv2_linear_wgrad_kernel), and the answer must be
+the one the name claims: a slab that declines (workspace, shape, CU count) fails the test instead of borrowing the looser bar.
+
 Conventions of the product the operands follow (swv2_block_bwd): the padded rows t >= L of a window are zero in the
 head-major operands and in the proj product's dY (their bias gradient counts every row); the padded head columns
 (j >= head dim) hold anything -- here large finite values -- and are dropped through nmap / kmap.
@@ -338,7 +342,9 @@ def make_block(K, sd, M, Bw, mode, seed, lut, dev, signs=(None, None, None, None
 # ---------------------------------------------------------------------------------------------------------------
 # The paths
 # ---------------------------------------------------------------------------------------------------------------
-def run_block(K, sd, prods, slices, bases, dev):
+def run_block(K, sd, prods, slices, bases, dev, path):
+    """swv2_block_wgrad; `path` is the name the caller files the result under, and the library must say that this launch runs the
+    kernel the name claims: "slab" -> the slab kernel, "grouped..." -> the grouped tile kernel"""
     L = K["L"]
     lib = L.load()
     items = (L.WgradItem * 4)()
@@ -353,12 +359,20 @@ def run_block(K, sd, prods, slices, bases, dev):
         items[i].ldw = p.kout
     nb = lib.swv2_block_wgrad_ws_bytes(sd["C"], sd["hid"], sd["h"] * sd["DP"], slices)
     ws = torch.empty(nb, dtype=torch.uint8, device=dev)
+    assert lib.swv2_block_wgrad_kernel(items, slices, nb) == (L.BLOCK_WGRAD_SLAB if path == "slab" else L.BLOCK_WGRAD_GROUPED), (path, slices)
     L.check(lib.swv2_block_wgrad(items, slices, ctypes.c_void_p(ws.data_ptr()), nb, None), "swv2_block_wgrad")
     torch.cuda.synchronize()
     return bufs
 
 
-def run_single(K, p, splits, workspace, base, dev):
+def run_single(K, p, splits, workspace, base, dev, family):
+    """swv2_linear_wgrad(_ws) through ops.linear_wgrad; `family` ("wide" / anything else: the tile kernel) is what the caller's
+    path name claims for this product, checked against the library's answer for the launch's own arguments"""
+    L = K["L"]
+    lib = L.load()
+    nb = lib.swv2_linear_wgrad_ws_bytes(p.dy_op.rows, p.dy_op.cols, p.x_op.cols, splits) if workspace else 0      # (as ops.linear_wgrad sizes it)
+    assert lib.swv2_linear_wgrad_kernel(ctypes.byref(p.dy_op), ctypes.byref(p.x_op), splits, nb) == \
+        (L.WGRAD_WIDE if family == "wide" else L.WGRAD_TILE), (family, splits, workspace)
     bw, bb, w, b = p.buffers(dev, *base)
     K["ops"].linear_wgrad(p.dy_op, p.x_op, w, b, nmap=p.nmap, kmap=p.kmap, splits=splits, workspace=workspace)
     torch.cuda.synchronize()
@@ -369,14 +383,15 @@ def all_results(K, sd, prods, bases, dev, monkeypatch, wide):
     """{path name: [(bw, bb, w, b) per product]}"""
     res = {}
     for blk in (0, 8, 16):
-        res[("slab" if sd["slab"] else "grouped0") if blk == 0 else f"grouped{blk}"] = run_block(K, sd, prods, blk, bases, dev)
+        name = ("slab" if sd["slab"] else "grouped0") if blk == 0 else f"grouped{blk}"
+        res[name] = run_block(K, sd, prods, blk, bases, dev, name)
     flags = ("0", "1") if wide else (None,)
     for fl in flags:
         if fl is not None:
             monkeypatch.setenv("SWV2_GEMM_WIDE", fl)
         for s, wsp in SINGLE:
             name = f"{'ws' if wsp else 'atomic'}{s}" + ("" if fl is None else ("/wide" if fl == "1" and wsp else f"/gemm_wide={fl}"))
-            res[name] = [run_single(K, p, s, wsp, bases[i], dev) for i, p in enumerate(prods)]
+            res[name] = [run_single(K, p, s, wsp, bases[i], dev, _family(name, i)) for i, p in enumerate(prods)]
         if fl is not None:
             monkeypatch.delenv("SWV2_GEMM_WIDE")
     return res
@@ -442,6 +457,7 @@ def test_exact_integer_operands_wide_kernel(dev, K, monkeypatch, gelu_lut, M, Bw
 # Part 2: random data, per element, small elements included
 # ---------------------------------------------------------------------------------------------------------------
 def _family(path, item):
+    """the kernel family a path name claims for item (run_block / run_single check the claim against the library)"""
     if "/wide" in path and item > 0:          # (fc2's GELU operand is not a wide-kernel kind: the tile kernel runs it)
         return "wide"
     return path.split("/")[0].rstrip("0123456789")
@@ -549,7 +565,7 @@ def test_slab_on_cancelling_data(dev, K, monkeypatch, gelu_lut, tag, how):
     prods = make_block(K, sd, M, Bw, "random", 77, gelu_lut, dev, signs=signs)
     bases = _bases(prods, "random", 77, dev)
     refs = [p.reference(*bases[i]) for i, p in enumerate(prods)]
-    res = {"slab": run_block(K, sd, prods, 0, bases, dev), "grouped8": run_block(K, sd, prods, 8, bases, dev)}
+    res = {"slab": run_block(K, sd, prods, 0, bases, dev, "slab"), "grouped8": run_block(K, sd, prods, 8, bases, dev, "grouped8")}
     _check_per_element(res, prods, refs, tag, M, Bw)
     line = []
     for path, outs in res.items():
