@@ -31,8 +31,9 @@ extern "C" {
  * entry points, swv2_attn_pack_bias_multi / swv2_attn_bias_chunks, a (max, min) part in the packed bias buffer;
  * 106: SWV2_EPI_UNPATCH_LOSS writes slot 1 of loss_part only where swv2_loss_part_reduce reads it; 107: swv2_epilogue.q[3], the loss
  * epilogue with the rollout destinations; 108: the kernel-selection queries swv2_linear_kernel, swv2_linear_wgrad_kernel,
- * swv2_block_wgrad_kernel. */
-#define SWV2_VERSION 108
+ * swv2_block_wgrad_kernel; 109: swv2_block_plan (+ swv2_block_plan_t, enum swv2_block_step, swv2_block_step_id / _name),
+ * swv2_block_desc loses fuse_attn and wgrad_side_stream. */
+#define SWV2_VERSION 109
 
 enum {
     SWV2_OK = 0,
@@ -535,9 +536,10 @@ int swv2_cpb_bwd_multi(const float* dbias_tables, int nchunk, const float* const
                        float* grads, int wh, int ww, int heads, int hidden, float drop_p, void* ws, size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
- * Whole-block orchestration: one host call enqueues the 7 forward / 13 backward launches of a Swin block
- * (reference SwinTransformerV2CrBlock.forward, swinv2_global.py:480-497, and its autograd) from C++, so the per-launch
- * host cost is a few microseconds instead of a Python round trip.  All memory is caller-owned.
+ * Whole-block orchestration: one host call enqueues every launch of a Swin block (reference
+ * SwinTransformerV2CrBlock.forward, swinv2_global.py:480-497, and its autograd) from C++, so the per-launch host cost is a few
+ * microseconds instead of a Python round trip.  Which launches those are is decided by swv2_block_plan (below the descriptor) and
+ * by nothing else: 4 forward / 5 backward steps with every fusion, 7 / 11 with none.  All memory is caller-owned.
  * ------------------------------------------------------------------------------------------------------------ */
 typedef struct swv2_block_desc {
     /* geometry */
@@ -557,42 +559,39 @@ typedef struct swv2_block_desc {
     const float* dp2;
     /* saved activations: written by forward, read by backward */
     void* qkvh;  float* rnorm; void* oh; float* lse; void* a1; float* mean1; float* rstd1; float* x1;
-    void* hpre;  void* hact;   void* a2; float* mean2; float* rstd2;
+    void* hpre;  void* hact;   void* a2; float* mean2; float* rstd2;      /* hact: need_hact_bytes of the plan (may be NULL at 0) */
     float* x2;               /* forward output [B*T][C] */
     /* backward only */
     const float* dx2;        /* grad of x2 */
     void *da2, *dh, *da1, *doh, *dqkvh;   /* bf16 scratch: [BT][C], [BT][hid], [Bw*Lp][C], [Bw][h][Lp][DP], [Bw][h][3][Lp][DP] */
     float* dx1;              /* fp32 scratch [BT][C] */
-    float* ln_ws;            /* max(SWV2_LN_BWD_MAX_BLOCKS*2*C, swv2_mlp_bwd_ws_floats(B*T, C), swv2_proj_ln_bwd_ws_floats(Bw*Lp, C)) floats */
+    float* ln_ws;            /* ln_ws_floats floats, at least max(SWV2_LN_BWD_MAX_BLOCKS*2*C, swv2_mlp_bwd_ws_floats(B*T, C),
+                                swv2_proj_ln_bwd_ws_floats(Bw*Lp, C)); need_ln_ws_floats of the plan for one fold of both LayerNorms */
     float* dx;               /* out: grad of x */
     /* parameter gradients, ACCUMULATED (caller zeroes) */
     float *d_logit_scale, *d_bias, *d_qkv_w, *d_qkv_b, *d_proj_w, *d_proj_b, *d_n1_w, *d_n1_b, *d_fc1_w, *d_fc1_b,
           *d_fc2_w, *d_fc2_b, *d_n2_w, *d_n2_b;
-    int wgrad_splits;        /* row slices of the weight-gradient products (128 with a workspace, 64 without) */
-    /* optional timing of ONE launch with HIP events on the launch stream (bench.py's roofline): if ev_kernel matches a
-       launch id (forward 1 qkv, 2 attn_fwd, 3 proj, 4 ln1, 5 fc1, 6 fc2, 7 ln2; backward 11 ln2, 12 wgrad fc2, 13 dh,
-       14 wgrad fc1, 15 dx1, 16 ln1, 17 wgrad proj, 18 d(oh), 19 attn_bwd, 20 wgrad qkv, 21 dx), ev_start / ev_stop
-       (hipEvent_t) are recorded around it; 0 = off */
+    int wgrad_splits;        /* row slices of the single weight-gradient products (0 = 64) */
+    /* optional timing of ONE launch with HIP events on the launch stream (bench.py's roofline): if ev_kernel matches the
+       launch id of a step of the plan (swv2_block_step_id: forward 1 qkv, 2 attn_fwd, 3 proj, 4 ln1, 5 fc1, 6 fc2, 7 ln2; backward
+       11 ln2, 12 wgrad fc2, 13 dh, 14 wgrad fc1, 15 dx1, 16 ln1, 17 wgrad proj, 18 d(oh), 19 attn_bwd, 20 wgrad qkv, 21 dx, 22 grouped
+       weight gradients; a fused kernel answers to the id of the first launch it replaces), ev_start / ev_stop (hipEvent_t) are
+       recorded around it; 0 = off */
     int ev_kernel;
     void* ev_start;
     void* ev_stop;
-    int fuse_proj_ln;        /* 1: proj + LN1 run as swv2_proj_ln_fwd / _bwd when the shape is supported (forward steps 3-4,
-                                backward steps 16, 18) */
-    int fuse_attn;           /* reserved, must be 0 (the one-kernel attention branch of round 2 did not beat the four kernels and
-                                lives in tools/experiments/attn_fused.hip, outside the library) */
-    int fuse_mlp;            /* 1: forward steps 5-7 run as swv2_mlp_fwd when the shape is supported (hact is then neither
-                                written nor read: the backward applies GELU to hpre on load); 0: three launches.  The backward
-                                likewise runs steps 11, 13, 15 as swv2_mlp_bwd */
+    /* requests; what runs is swv2_block_plan's answer */
+    int fuse_proj_ln;        /* 1: proj + LN1 run as swv2_proj_ln_fwd / _bwd when the shape is supported */
+    int fuse_mlp;            /* 1: fc1, fc2 and LN2 run as swv2_mlp_fwd / _bwd when the shape is supported (hact is then neither
+                                written nor read: the backward applies GELU to hpre on load) */
     void* wgrad_ws;          /* optional workspace of the weight-gradient products (swv2_linear_wgrad_ws), shared by the four
                                 products of the block (they are ordered on one stream); NULL = atomic accumulation */
     size_t wgrad_ws_bytes;
-    int wgrad_side_stream;   /* 1: backward launches the 4 weight-gradient products on the library's per-device side stream
-                                (fork after each producer, join before returning) so they overlap with the dX chain */
-    int wgrad_group;         /* 1 (with fuse_mlp + fuse_proj_ln paths and a workspace): the four products run as ONE
+    int wgrad_group;         /* 1 (with the fused MLP path and a workspace of swv2_block_wgrad_ws_bytes): the four products run as ONE
                                 swv2_block_wgrad launch at the end of the backward (launch id 22) */
     void* grad_zero;         /* optional: one buffer holding all 13 parameter gradients of the block (16-byte aligned, a multiple
-                                of 16 bytes); with the fused MLP path the backward's first kernel zeroes it, so the caller need
-                                not (NULL: the caller zeroes every d_* buffer itself) */
+                                of 16 bytes); where the plan says grad_zero_in_kernel the backward's first kernel zeroes it, so the
+                                caller need not (otherwise, and with NULL, the caller zeroes every d_* buffer itself) */
     size_t grad_zero_bytes;
     size_t ln_ws_floats;     /* floats available at ln_ws; >= swv2_mlp_bwd_ws_floats + swv2_proj_ln_bwd_ws_floats lets the backward
                                 keep both LayerNorms' d gamma / d beta partial rows and fold them with ONE launch (0: one each) */
@@ -603,6 +602,64 @@ typedef struct swv2_block_desc {
                                 touch d_bias (may be NULL): the caller sums them with swv2_cpb_bwd_multi */
     size_t dbias_part_bytes;
 } swv2_block_desc;
+
+/* The launch plan of a block: THE place where its launches are decided.  swv2_block_fwd / swv2_block_bwd compute it per call and run
+ * its step lists, one launch per step, so what they enqueue is what it says.  Host arithmetic with no launch; the one HIP call is
+ * in wgrad_kernel of a grouped plan, where swv2_block_wgrad_kernel asks for the current device's CU count (256 in a process without
+ * a GPU) -- swv2_block_fwd / _bwd skip that field, which no launch depends on.  It reads from the descriptor: the geometry; the requests fuse_mlp, fuse_proj_ln,
+ * wgrad_group, wgrad_splits; bias, bias_pack, dbias_part, grad_zero and wgrad_ws for PRESENCE (no pointer is dereferenced; a NULL
+ * wgrad_ws counts as 0 bytes); bias_prepacked; the capacities ln_ws_floats and wgrad_ws_bytes.  A caller sizes its buffers by
+ * filling geometry and requests, reading the three need_* fields (they do not depend on the capacities), and calling again with the
+ * capacities it provides: a capacity below the need is legal and only loses the decision that needs it. */
+enum swv2_block_step {       /* forward */
+    SWV2_STEP_RNORM_ZERO = 1,    /* DP > 64: memset of rnorm (the qkv epilogue accumulates squared norms there)       */
+    SWV2_STEP_QKV,               /* roll + partition gather | qkv GEMM | + bias, split heads, (DP <= 64) L2-normalise */
+    SWV2_STEP_QK_NORMALIZE,      /* DP > 64: swv2_qk_normalize                                                        */
+    SWV2_STEP_PACK_BIAS,         /* a table that is not prepacked: swv2_attn_pack_bias into bias_pack                 */
+    SWV2_STEP_ATTN_FWD,
+    SWV2_STEP_PROJ, SWV2_STEP_LN1_FWD,
+    SWV2_STEP_PROJ_LN_FWD,       /* the two above as swv2_proj_ln_fwd                                                 */
+    SWV2_STEP_FC1, SWV2_STEP_FC2, SWV2_STEP_LN2_FWD,
+    SWV2_STEP_MLP_FWD,           /* the three above as swv2_mlp_fwd                                                   */
+    /* backward */
+    SWV2_STEP_LN2_BWD, SWV2_STEP_WGRAD_FC2, SWV2_STEP_DH, SWV2_STEP_WGRAD_FC1, SWV2_STEP_DX1,
+    SWV2_STEP_MLP_BWD,           /* LN2_BWD + DH + DX1 as swv2_mlp_bwd                                                */
+    SWV2_STEP_LN1_BWD,
+    SWV2_STEP_PROJ_LN_BWD,       /* LN1_BWD + DOH as swv2_proj_ln_bwd                                                 */
+    SWV2_STEP_WGRAD_PROJ, SWV2_STEP_DOH, SWV2_STEP_ATTN_BWD, SWV2_STEP_WGRAD_QKV, SWV2_STEP_DX,
+    SWV2_STEP_LN_FOLD,           /* deferred, not grouped: both LayerNorms' partial rows -> d gamma / d beta, one launch */
+    SWV2_STEP_WGRAD_GROUP,       /* the four WGRAD_* as swv2_block_wgrad (+ the deferred fold riding on its reduction)  */
+    SWV2_STEP_COUNT
+};
+#define SWV2_BLOCK_MAX_STEPS 12
+enum { SWV2_DBIAS_NONE = 0,      /* no CPB table                                                                              */
+       SWV2_DBIAS_ATOMICS = 1,   /* no workspace at all: float atomics on d_bias                                              */
+       SWV2_DBIAS_WGRAD_WS = 2,  /* wgrad_ws (idle at that point) is lent to swv2_attn_bwd as dbias_ws, one more launch sums
+                                    into d_bias; a workspace too small for the tables: atomics (swv2_attn_args.dbias_ws)      */
+       SWV2_DBIAS_PART = 3 };    /* left in dbias_part for the caller to sum (swv2_cpb_bwd_multi); d_bias untouched           */
+typedef struct swv2_block_plan_t {
+    /* decisions */
+    int mlp_fused;               /* fuse_mlp && swv2_mlp_supported                                                            */
+    int proj_ln_fused;           /* fuse_proj_ln && swv2_proj_ln_supported                                                    */
+    int ln_deferred;             /* both fused and ln_ws_floats >= swv2_mlp_bwd_ws_floats + swv2_proj_ln_bwd_ws_floats: both
+                                    LayerNorms' partial rows are kept and folded once (otherwise each kernel folds its own)   */
+    int wgrad_grouped;           /* wgrad_group, MLP fused and wgrad_ws_bytes >= swv2_block_wgrad_ws_bytes(C, hidden, heads*DP, 0) */
+    int wgrad_kernel;            /* grouped: swv2_block_wgrad_kernel's answer (SWV2_BLOCK_WGRAD_*) for it; else -1            */
+    int grad_zero_in_kernel;     /* grad_zero offered and MLP fused: the backward's first kernel zeroes it                    */
+    int attn_fwd_chunks, attn_bwd_chunks;   /* swv2_attn_args.max_chunks of the two attention launches                        */
+    int dbias_dest;              /* SWV2_DBIAS_*                                                                              */
+    /* what the caller provides for the full plan */
+    size_t need_hact_bytes;      /* 0 when the MLP branch is fused                                                            */
+    size_t need_ln_ws_floats;
+    size_t need_wgrad_ws_bytes;  /* the largest of the four swv2_linear_wgrad_ws_bytes and, with wgrad_group, swv2_block_wgrad_ws_bytes */
+    /* the steps each direction enqueues, in order */
+    int n_fwd, n_bwd;
+    int fwd[SWV2_BLOCK_MAX_STEPS], bwd[SWV2_BLOCK_MAX_STEPS];
+} swv2_block_plan_t;
+int swv2_block_plan(const swv2_block_desc* d, swv2_block_plan_t* out);
+/* launch id of a step (the value swv2_block_desc.ev_kernel names it by; 0: never bracketed; -1: no such step) and its name */
+int swv2_block_step_id(int step);
+const char* swv2_block_step_name(int step);
 
 int swv2_block_fwd(const swv2_block_desc* d, void* stream);
 int swv2_block_bwd(const swv2_block_desc* d, void* stream);

@@ -15,7 +15,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIB_PATH = os.environ.get("SWV2_LIB") or os.path.join(HERE, "libswv2.so")     # SWV2_LIB: a privately built variant (tools/ab_macro.sh)
 SOURCES = ["capi.hip", "attn.hip", "attn2.hip", "attn_bwd_stream.hip", "attn_wide.hip", "attn_d256.hip", "gemm.hip", "gemm_tn.hip", "gemm_tn_slab.hip", "rowops.hip", "block.hip", "cpb.hip", "mlp.hip", "proj_ln.hip", "dataio.hip"]
 
-ABI_VERSION = 108          # SWV2_VERSION of the include/swv2.h these ctypes mirrors were written against (checked in load())
+ABI_VERSION = 109          # SWV2_VERSION of the include/swv2.h these ctypes mirrors were written against (checked in load())
 
 _lib = None
 _lock = threading.Lock()
@@ -151,9 +151,32 @@ class BlockDesc(C.Structure):
                     "d_logit_scale", "d_bias", "d_qkv_w", "d_qkv_b", "d_proj_w", "d_proj_b", "d_n1_w", "d_n1_b", "d_fc1_w",
                     "d_fc1_b", "d_fc2_w", "d_fc2_b", "d_n2_w", "d_n2_b")] +
                 [("wgrad_splits", C.c_int), ("ev_kernel", C.c_int), ("ev_start", C.c_void_p), ("ev_stop", C.c_void_p),
-                 ("fuse_proj_ln", C.c_int), ("fuse_attn", C.c_int), ("fuse_mlp", C.c_int), ("wgrad_ws", C.c_void_p), ("wgrad_ws_bytes", C.c_size_t), ("wgrad_side_stream", C.c_int), ("wgrad_group", C.c_int), ("grad_zero", C.c_void_p),
+                 ("fuse_proj_ln", C.c_int), ("fuse_mlp", C.c_int), ("wgrad_ws", C.c_void_p), ("wgrad_ws_bytes", C.c_size_t), ("wgrad_group", C.c_int), ("grad_zero", C.c_void_p),
                  ("grad_zero_bytes", C.c_size_t), ("ln_ws_floats", C.c_size_t),
                  ("bias_prepacked", C.c_int), ("dbias_part", C.c_void_p), ("dbias_part_bytes", C.c_size_t)])
+
+
+BLOCK_MAX_STEPS = 12          # SWV2_BLOCK_MAX_STEPS
+DBIAS_NONE, DBIAS_ATOMICS, DBIAS_WGRAD_WS, DBIAS_PART = range(4)      # swv2_block_plan_t.dbias_dest
+
+
+class BlockPlan(C.Structure):
+    """swv2_block_plan's answer: what swv2_block_fwd / swv2_block_bwd run for a descriptor (include/swv2.h)"""
+    _fields_ = ([(n, C.c_int) for n in ("mlp_fused", "proj_ln_fused", "ln_deferred", "wgrad_grouped", "wgrad_kernel", "grad_zero_in_kernel",
+                                        "attn_fwd_chunks", "attn_bwd_chunks", "dbias_dest")] +
+                [(n, C.c_size_t) for n in ("need_hact_bytes", "need_ln_ws_floats", "need_wgrad_ws_bytes")] +
+                [("n_fwd", C.c_int), ("n_bwd", C.c_int), ("fwd", C.c_int * BLOCK_MAX_STEPS), ("bwd", C.c_int * BLOCK_MAX_STEPS)])
+
+    def steps(self, phase):
+        """names of the steps of "fwd" / "bwd", in launch order"""
+        lib = load()
+        return [lib.swv2_block_step_name(s).decode() for s in getattr(self, phase)[:getattr(self, "n_" + phase)]]
+
+
+def block_plan(desc: BlockDesc) -> BlockPlan:
+    plan = BlockPlan()
+    check(load().swv2_block_plan(C.byref(desc), C.byref(plan)), "swv2_block_plan")
+    return plan
 
 
 OP_F32, OP_BF16, OP_BF16_GELU, OP_HEADS, OP_PATCH, OP_MERGE_LN, OP_BF16_CSCALE = range(7)
@@ -224,6 +247,9 @@ SYMBOLS = {
     "swv2_cpb_fwd_multi": (_I, [_P, _I, _P, _P, _I, _I, _I, _I, _F, _P]),
     "swv2_cpb_bwd_multi_ws_bytes": (C.c_size_t, [_I, _I, _I, _I, _I]),
     "swv2_cpb_bwd_multi": (_I, [_P, _I, _P, _I, _P, _P, _I, _I, _I, _I, _F, _P, C.c_size_t, _P]),
+    "swv2_block_plan": (_I, [C.POINTER(BlockDesc), C.POINTER(BlockPlan)]),
+    "swv2_block_step_id": (_I, [_I]),
+    "swv2_block_step_name": (C.c_char_p, [_I]),
     "swv2_block_fwd": (_I, [C.POINTER(BlockDesc), _P]),
     "swv2_block_bwd": (_I, [C.POINTER(BlockDesc), _P]),
 }

@@ -6,10 +6,11 @@ WindowMultiHeadAttention{,NoPos} :122-321, PatchEmbed :526-546, PatchMerging :50
 `get_model(params)` are drop-in.  The modules here are only parameter containers + autograd glue: every
 forward / backward arithmetic op is a HIP kernel from libswv2.so (see ops.py, include/swv2.h):
 
-  block forward  = 7 launches   x --[gather roll+partition | qkv GEMM | split heads + L2-norm]--> qkvh
+  block forward                 x --[gather roll+partition | qkv GEMM | split heads + L2-norm]--> qkvh
                                   --[cosine window attention (MFMA), CPB bias, closed-form shift mask]--> oh
                                   --[merge heads | proj GEMM]--> a1 --[LN + drop-path + residual, reverse+un-roll scatter]--> x1
                                   --[fc1 GEMM | + bias, GELU]--> h, g --[fc2 GEMM]--> a2 --[LN + drop-path + residual]--> x2
+  (7 launches as separate kernels; 4 where swv2_block_plan fuses proj + LN and the MLP branch: `_BlockRunner.launch_plan`)
 
 The module constructors draw their initial parameters in the same order as the reference's, so the same
 `torch.manual_seed` gives the same initial weights.  There is no CPU / eager fallback: forward raises if the input is
@@ -134,8 +135,8 @@ def window_reverse(windows, window_size: Tuple[int, int], img_size: Tuple[int, i
 
 
 # ================================================================================================
-# block: one autograd node; forward (7 launches) and backward (13 launches) are each ONE host call into
-# libswv2.so (swv2_block_fwd / swv2_block_bwd), all buffers carved out of three torch allocations
+# block: one autograd node; forward and backward are each ONE host call into libswv2.so (swv2_block_fwd / swv2_block_bwd run the
+# steps of swv2_block_plan: 4 + 5 launches with every fusion, 7 + 11 with none), all buffers carved out of three torch allocations
 # ================================================================================================
 def _carve(sizes, align=256):
     """byte offsets of consecutive `sizes`-byte regions, each aligned"""
@@ -161,31 +162,30 @@ class _BlockRunner:
         d.L, d.Lp, d.DP, d.nwh, d.nww, d.mask_thr = Lw, Lp, DP, plan.nwh, plan.nww, plan.mask_thr
         d.rowidx, d.qkv_map, d.proj_map = plan.rowidx.data_ptr(), plan.qkv_map.data_ptr(), plan.proj_map.data_ptr()
         d.wgrad_splits = int(os.environ.get("SWV2_WGRAD_SPLITS", "128"))
-        lib = L.load()
-        ws_bytes = max(lib.swv2_linear_wgrad_ws_bytes(m, n_, k, d.wgrad_splits)
-                       for m, n_, k in ((BT, Cc, hid), (BT, hid, Cc), (Mw, Cc, h * DP), (Mw, 3 * h * DP, Cc)))
         # the four products as one grouped launch (swv2_block_wgrad): 242 -> ~125 us per block at local batch 2
         d.wgrad_group = int(os.environ.get("SWV2_WGRAD_GROUP", "1"))
-        if d.wgrad_group:
-            ws_bytes = max(ws_bytes, lib.swv2_block_wgrad_ws_bytes(Cc, hid, h * DP, 0))
-        d.wgrad_ws_bytes = ws_bytes
-        # weight-gradient GEMMs on the library's side stream: +8 % when they took 4 x 130 us per block with atomics; since
-        # the partial-tile kernels (4 x 30-70 us) the overlap only slows the co-running dX chain down (143.3 vs 144.2
-        # samples/s, attention backward 0.216 vs 0.134 ms) -- opt-in
-        d.wgrad_side_stream = int(os.environ.get("SWV2_WGRAD_SIDE_STREAM", "0"))
         d.fuse_mlp = int(os.environ.get("SWV2_FUSE_MLP", "1"))
         d.fuse_proj_ln = int(os.environ.get("SWV2_FUSE_PROJ_LN", "1"))
-        d.fuse_attn = 0         # (reserved: the one-kernel attention branch lives in tools/experiments/, LABNOTES.md)
-        fused = bool(d.fuse_mlp) and bool(L.load().swv2_mlp_supported(Cc, hid))
+        # What the block runs is swv2_block_plan's answer (csrc/block.hip), asked twice: without bounds for the full plan and its needs,
+        # then with the capacities this runner provides.  launch_plan holds what is the same for every call (fused or separate kernels,
+        # deferred fold, grouped weight gradients and their kernel, the needs).  It is asked without a CPB table and with workspace and
+        # gradient carve on offer (pointers are tested for presence only): pack_bias, the attention chunk counts and dbias_dest follow
+        # the table per call, and grad_zero_in_kernel holds where _BlockFn.backward offers the carve.
+        d.wgrad_ws = d.grad_zero = 1
+        d.ln_ws_floats = d.wgrad_ws_bytes = 1 << 62
+        full = L.block_plan(d)
+        d.ln_ws_floats, d.wgrad_ws_bytes = full.need_ln_ws_floats, full.need_wgrad_ws_bytes
+        self.launch_plan = lp = L.block_plan(d)
+        if any(getattr(lp, n) != getattr(full, n) for n in ("mlp_fused", "proj_ln_fused", "ln_deferred", "wgrad_grouped", "wgrad_kernel")):
+            raise L.Swv2Error("swv2_block_plan: the reported workspace needs do not cover the full plan")
+        d.wgrad_ws = d.grad_zero = None
         self.desc = d
         act_sizes = [Bw * h * 3 * Lp * DP * 2, Bw * h * 2 * Lp * 4, Bw * h * Lp * DP * 2, Bw * h * Lp * 4, Mw * Cc * 2, Mw * 4,
-                     Mw * 4, BT * Cc * 4, BT * hid * 2, 0 if fused else BT * hid * 2, BT * Cc * 2, BT * 4, BT * 4,
-                     lib.swv2_attn_pack_bias_bytes(h, Lw)]
+                     Mw * 4, BT * Cc * 4, BT * hid * 2, lp.need_hact_bytes, BT * Cc * 2, BT * 4, BT * 4,
+                     L.load().swv2_attn_pack_bias_bytes(h, Lw)]
         self.act_off, self.act_bytes = _carve(act_sizes)
-        # LayerNorm partial rows: both LayerNorms' sets side by side, so the backward folds them with one launch
-        d.ln_ws_floats = max(L.LN_BWD_MAX_BLOCKS * 2 * Cc, lib.swv2_mlp_bwd_ws_floats(BT, Cc) + lib.swv2_proj_ln_bwd_ws_floats(Mw, Cc))
         scr_sizes = [BT * Cc * 2, BT * hid * 2, Mw * Cc * 2, Bw * h * Lp * DP * 2, Bw * h * 3 * Lp * DP * 2, BT * Cc * 4,
-                     d.ln_ws_floats * 4, ws_bytes]
+                     d.ln_ws_floats * 4, d.wgrad_ws_bytes]
         self.scr_off, self.scr_bytes = _carve(scr_sizes)
         self.grad_shapes = [(h,), (3 * Cc, Cc), (3 * Cc,), (Cc, Cc), (Cc,), (Cc,), (Cc,), (hid, Cc), (hid,), (Cc, hid), (Cc,),
                             (Cc,), (Cc,)]
@@ -337,10 +337,9 @@ class _BlockFn(torch.autograd.Function):
                 setattr(d, name, v.data_ptr())
             d.grad_zero, d.grad_zero_bytes = None, 0
         else:
-            # all 13 parameter gradients in one buffer; zeroed by the backward's first kernel when that is the fused MLP
-            # kernel (d.grad_zero), by one memset otherwise
-            in_kernel = bool(d.fuse_mlp) and bool(L.load().swv2_mlp_supported(run.C, run.hid)) and \
-                os.environ.get("SWV2_GRAD_ZERO_IN_KERNEL", "1") != "0"
+            # all 13 parameter gradients in one buffer; zeroed by the backward's first kernel where the plan says so (d.grad_zero
+            # offered), by one memset otherwise
+            in_kernel = bool(run.launch_plan.grad_zero_in_kernel)
             nfl = (run.grad_bytes // 4 + 3) // 4 * 4
             # (+ the CPB bias gradient table, zeroed by the same kernel instead of a fill of its own)
             nb = (bias_c.numel() + 3) // 4 * 4 if own_bias else 0

@@ -82,7 +82,7 @@ _RR = {"fwd": 0, "bwd": 0}
 
 
 def block_event_pair(phase, desc):
-    """If kernels of this phase ("fwd": launch ids 1-7, "bwd": 11-21) are being timed (start_kernel_timing), attach a
+    """If kernels of this phase ("fwd": launch ids 1-7, "bwd": 11-22; swv2_block_step_id holds the same table) are being timed (start_kernel_timing), attach a
     fresh HIP event pair to the block descriptor so that swv2_block_fwd/bwd brackets exactly ONE launch on the launch
     stream; with several requested kernels of a phase the calls take turns (round robin over the blocks of the step)."""
     desc.ev_kernel = 0

@@ -879,7 +879,11 @@ def test_block_at_baseline_head_geometry(dev, K, monkeypatch, tag):
     y = blk(x)
     y.backward(torch.from_numpy(fx["gy"]).to(dev))
     if tag == "cfg4_nopos":
-        assert K["L"].load().swv2_proj_ln_supported(Cc, h, 32) == 1 and blk._runner(B, x.device).desc.fuse_proj_ln == (0 if variant else 1)
+        # (the shape has a fused instantiation, so the variant is the switch's doing) what ran is the launch plan's answer
+        lp = blk._runner(B, x.device).launch_plan
+        assert K["L"].load().swv2_proj_ln_supported(Cc, h, 32) == 1 and lp.proj_ln_fused == (0 if variant else 1)
+        assert ("proj_ln_fwd" in lp.steps("fwd"), "proj_ln_bwd" in lp.steps("bwd")) == ((False, False) if variant else (True, True))
+        assert (lp.mlp_fused, lp.wgrad_grouped, lp.wgrad_kernel, lp.ln_deferred) == (1, 1, K["L"].BLOCK_WGRAD_SLAB, 0 if variant else 1)
     big, step = int(fx["gbig"]), int(fx["gstep"])
     # bf16 tolerance against the fp32 reference (logit scales near their ln 10 init: no arg-max head in these fixtures)
     assert rel(y, torch.from_numpy(fx["y"]).float()) < 1.5e-2 and rel(x.grad, torch.from_numpy(fx["gx"]).float()) < 4e-2
@@ -2082,8 +2086,19 @@ def test_block_fused_and_unfused_paths(dev, K, monkeypatch, knob, value):
     x = torch.from_numpy(fx["x"]).to(dev).requires_grad_(True)
     y = blk(x)
     y.backward(torch.from_numpy(fx["gy"]).to(dev))
-    desc = blk._runner(B, x.device).desc
-    assert {"SWV2_FUSE_MLP": desc.fuse_mlp, "SWV2_FUSE_PROJ_LN": desc.fuse_proj_ln, "SWV2_WGRAD_GROUP": desc.wgrad_group}[knob] == int(value)
+    # what ran: the launch plan the runner executes (swv2_block_plan), not the request.  Grouping needs the fused MLP path's operands,
+    # the single LayerNorm fold both fused kernels; C = 32 is a tile-kernel shape of the grouped launch
+    run = blk._runner(B, x.device)
+    lp = run.launch_plan
+    mlp = int(not (knob == "SWV2_FUSE_MLP" and value == "0"))
+    pl = int(not (knob == "SWV2_FUSE_PROJ_LN" and value == "0"))
+    grp = int(mlp and not (knob == "SWV2_WGRAD_GROUP" and value == "0"))
+    assert (lp.mlp_fused, lp.proj_ln_fused, lp.wgrad_grouped, lp.ln_deferred, lp.grad_zero_in_kernel) == (mlp, pl, grp, mlp & pl, mlp)
+    assert lp.wgrad_kernel == (L.BLOCK_WGRAD_GROUPED if grp else -1)
+    assert ("mlp_fwd" in lp.steps("fwd"), "mlp_bwd" in lp.steps("bwd"), "wgrad_group" in lp.steps("bwd")) == (bool(mlp), bool(mlp), bool(grp))
+    i = run.ACTS.index("hact")
+    assert lp.need_hact_bytes == (0 if mlp else B * gh * gw * 4 * Cc * 2)
+    assert (run.act_off[i + 1] - run.act_off[i] >= lp.need_hact_bytes) and (run.act_off[i + 1] > run.act_off[i]) == (not mlp)
     p = {"b." + k[2:]: torch.from_numpy(fx[k]).clone().requires_grad_(True) for k in fx.files if k.startswith("p:")}
     xo = torch.from_numpy(fx["x"]).clone().requires_grad_(True)
     emulate_kernels(K, wh * ww, Cc // h, False, OF)
@@ -2160,7 +2175,9 @@ def test_grouped_weight_gradients_match_separate_launches(dev, K, monkeypatch, g
         blk = blk.to(dev).train()
         x = x0.to(dev).requires_grad_(True)
         blk(x).backward(gy0.to(dev))
-        assert blk._runner(B, x.device).desc.wgrad_group == int(grp)
+        lp = blk._runner(B, x.device).launch_plan              # what ran, not what was asked for
+        assert lp.wgrad_grouped == int(grp) and ("wgrad_group" in lp.steps("bwd")) == (grp == "1") and lp.mlp_fused == 1
+        assert lp.wgrad_kernel == (-1 if grp == "0" else K["L"].BLOCK_WGRAD_SLAB if Cc in (128, 192) and h == 8 else K["L"].BLOCK_WGRAD_GROUPED)
         grads[grp] = {n_: p_.grad.detach().cpu() for n_, p_ in blk.named_parameters()} | {"x": x.grad.cpu()}
     # round 6: the slab kernel hands its per-workgroup partial tiles to the fold in bf16 (half the 56 MB a block wrote and re-read whatever the
     # batch): a partial is rounded once to 8 bits, the fold over the slices stays fp32 in a fixed order.  On this test's random data the

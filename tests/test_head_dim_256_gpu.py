@@ -328,7 +328,8 @@ def _block_2048(K, sh, sw, drop_path):
                          ids=["unshifted_eval", "shifted_eval", "unshifted_train", "shifted_train"])
 def test_block_at_embed_2048_against_oracle(dev, K, sh, sw, train):
     """One block at C = 2048, 8 heads of 256, hidden 4096 on an 18 x 36 grid with 9 x 18 windows: the unfused launch sequence (qkv
-    epilogue + normalisation, attn_d256.hip, proj, LayerNorm at C = 2048, MLP, grouped weight gradients).  Train mode draws the
+    epilogue + normalisation, attn_d256.hip, proj, LayerNorm at C = 2048, MLP as three launches, four single weight gradients: asserted
+    on the runner's launch plan).  Train mode draws the
     DropPath scales (drop_path 0.3) and replays them through the oracle.  Forward and backward against the oracle in the kernels'
     rounding mode, bars of test_block_wide_heads_against_oracle."""
     gh, gw, wh, ww, Cc, h, B = 18, 36, 9, 18, 2048, 8, 2
@@ -342,7 +343,14 @@ def test_block_at_embed_2048_against_oracle(dev, K, sh, sw, train):
     torch.manual_seed(1234)
     y = blk(x)
     y.backward(gy0.to(dev))
-    assert blk._runner(B, x.device).plan.DP == 256
+    run = blk._runner(B, x.device)
+    assert run.plan.DP == 256
+    lp = run.launch_plan
+    assert (lp.mlp_fused, lp.proj_ln_fused, lp.ln_deferred, lp.wgrad_grouped, lp.wgrad_kernel, lp.grad_zero_in_kernel) == (0, 0, 0, 0, -1, 0)
+    assert lp.steps("fwd") == ["rnorm_zero", "qkv", "qk_normalize", "attn_fwd", "proj", "ln1_fwd", "fc1", "fc2", "ln2_fwd"]
+    assert lp.steps("bwd") == ["ln2_bwd", "wgrad_fc2", "dh", "wgrad_fc1", "dx1", "ln1_bwd", "wgrad_proj", "doh", "attn_bwd", "wgrad_qkv", "dx"]
+    i = run.ACTS.index("hact")
+    assert run.act_off[i + 1] - run.act_off[i] >= lp.need_hact_bytes == B * gh * gw * 4096 * 2
     dpo = None
     if train:
         torch.manual_seed(1234)                                  # replay the draws in the block's order

@@ -62,7 +62,7 @@ def test_ctypes_structs_follow_the_header_field_order():
     pairs = {"swv2_attn_args": L.AttnArgs, "swv2_operand": L.Operand, "swv2_epilogue": L.Epilogue, "swv2_block_desc": L.BlockDesc,
              "swv2_mlp_args": L.MlpArgs, "swv2_mlp_bwd_args": L.MlpBwdArgs, "swv2_proj_ln_args": L.ProjLnArgs,
              "swv2_proj_ln_bwd_args": L.ProjLnBwdArgs, "swv2_ln_args": L.LnArgs,
-             "swv2_wgrad_item": L.WgradItem}
+             "swv2_wgrad_item": L.WgradItem, "swv2_block_plan_t": L.BlockPlan}
     from swin_v2_weather_amd.utils.optim import _Item
     pairs["swv2_adam_item"] = _Item
     for cname, cls in pairs.items():
@@ -219,6 +219,169 @@ def test_kernel_selection_for_the_products_the_model_launches(monkeypatch):
     # argument errors come back as negative codes
     assert lib.swv2_linear_kernel(None, None, 4) == -1 and lib.swv2_block_wgrad_kernel(None, 0, 0) == -1
     assert lib.swv2_linear_kernel(ctypes.byref(_op(L.OP_BF16_CSCALE, 64, 64, 64)), ctypes.byref(_epi(L.EPI_BF16, 64)), 64) == -1
+
+
+# ---- the block's launch plan (swv2_block_plan) ---------------------------------------------------------------------------------
+def _block_desc(B, C, hid, h, bias=False, grid=(180, 360), **over):
+    """a descriptor as _BlockRunner fills it (geometry + requests, 9 x 18 windows on `grid` patches) with everything the full plan
+    needs on offer: workspace and gradient carve present (the plan tests pointers for presence only), capacities = the reported
+    needs.  `over` overrides fields afterwards."""
+    lib = L.load()
+    d = L.BlockDesc()
+    lp, dp = ctypes.c_int(), ctypes.c_int()
+    assert lib.swv2_attn_geometry(162, C // h, ctypes.byref(lp), ctypes.byref(dp)) == 0
+    d.B, d.T, d.C, d.heads, d.head_dim, d.hidden = B, grid[0] * grid[1], C, h, C // h, hid
+    d.L, d.Lp, d.DP, d.nwh, d.nww = 162, lp.value, dp.value, grid[0] // 9, grid[1] // 18
+    d.fuse_mlp = d.fuse_proj_ln = d.wgrad_group = 1
+    d.wgrad_splits = 128
+    d.wgrad_ws = d.grad_zero = _FAKE
+    if bias:
+        d.bias = d.bias_pack = _FAKE
+    for k in ("fuse_mlp", "fuse_proj_ln", "wgrad_group"):
+        if k in over:
+            setattr(d, k, over.pop(k))
+    need = L.block_plan(d)
+    d.ln_ws_floats, d.wgrad_ws_bytes = need.need_ln_ws_floats, need.need_wgrad_ws_bytes
+    for k, v in over.items():
+        setattr(d, k, v)
+    return d
+
+
+# the step sequences below were read off swv2_block_fwd / swv2_block_bwd as they stood before swv2_block_plan existed (nested ifs over
+# fuse_mlp && swv2_mlp_supported, fuse_proj_ln && swv2_proj_ln_supported, defer, group), not off the plan function
+_FWD_FUSED = ["qkv", "attn_fwd", "proj_ln_fwd", "mlp_fwd"]
+_BWD_FUSED = ["mlp_bwd", "proj_ln_bwd", "attn_bwd", "dx", "wgrad_group"]
+_FWD_SEPARATE_WIDE = ["rnorm_zero", "qkv", "qk_normalize", "attn_fwd", "proj", "ln1_fwd", "fc1", "fc2", "ln2_fwd"]
+_BWD_SEPARATE = ["ln2_bwd", "wgrad_fc2", "dh", "wgrad_fc1", "dx1", "ln1_bwd", "wgrad_proj", "doh", "attn_bwd", "wgrad_qkv", "dx"]
+_BWD_FUSED_SINGLE = ["mlp_bwd", "wgrad_fc2", "wgrad_fc1", "proj_ln_bwd", "wgrad_proj", "attn_bwd", "wgrad_qkv", "dx", "ln_fold"]
+_FWD_STEPS = {"rnorm_zero", "qkv", "qk_normalize", "pack_bias", "attn_fwd", "proj", "ln1_fwd", "proj_ln_fwd", "fc1", "fc2", "ln2_fwd", "mlp_fwd"}
+_BLOCK_SHAPES = {       # (local batch, C, hidden, heads) of test_kernel_selection_for_the_products_the_model_launches
+    "bench C 128": (2, 128, 512, 8), "geo C 192": (2, 192, 768, 8), "yaml default C 768": (1, 768, 3072, 8), "embed 2048": (1, 2048, 4096, 8)}
+
+
+def _with_pack(steps):
+    i = steps.index("attn_fwd")
+    return steps[:i] + ["pack_bias"] + steps[i:]
+
+
+@pytest.mark.parametrize("name", list(_BLOCK_SHAPES))
+@pytest.mark.parametrize("bias", [False, True])
+def test_block_plan_of_the_shapes_the_model_runs(name, bias):
+    """The default plan of the four block shapes the repository runs, with and without a CPB table (every one of them accepts one:
+    swv2_attn_fwd_regime >= 0).  C 128 / 192: forward 4 launches, backward 4 + the grouped weight gradients (the slab kernel), one
+    deferred LayerNorm fold riding on their reduction, gradients zeroed in kernel, no hact.  C 768 / 2048 (no fused instantiation,
+    wide head slots): 9 forward steps with the rnorm memset and swv2_qk_normalize, 11 backward launches."""
+    lib = L.load()
+    B, C, hid, h = _BLOCK_SHAPES[name]
+    assert lib.swv2_attn_fwd_regime(162, C // h, int(bias), 0) >= 0
+    p = L.block_plan(_block_desc(B, C, hid, h, bias))
+    small = C <= 192
+    fwd = _FWD_FUSED if small else _FWD_SEPARATE_WIDE
+    assert p.steps("fwd") == (_with_pack(fwd) if bias else fwd)
+    assert p.steps("bwd") == (_BWD_FUSED if small else _BWD_SEPARATE)
+    assert (p.mlp_fused, p.proj_ln_fused, p.ln_deferred, p.wgrad_grouped, p.grad_zero_in_kernel) == ((1,) * 5 if small else (0,) * 5)
+    assert p.wgrad_kernel == (L.BLOCK_WGRAD_SLAB if small else -1)
+    assert p.need_hact_bytes == (0 if small else B * 180 * 360 * hid * 2)
+    # attention workgroups per head: 64; 32 with a table (forward: per-workgroup table load; backward: swv2_attn_bias_chunks of >= 32
+    # windows); without one at the 176-row window the backward runs 256 / heads
+    assert (p.attn_fwd_chunks, p.attn_bwd_chunks) == ((32, 32) if bias else (64, 256 // h))
+    assert p.dbias_dest == (L.DBIAS_WGRAD_WS if bias else L.DBIAS_NONE)
+    if bias:
+        # the stage's one-launch CPB pipeline: table prepacked, the workgroups' d bias tables stay in the stage's buffer
+        q = L.block_plan(_block_desc(B, C, hid, h, True, bias_prepacked=1, dbias_part=_FAKE))
+        assert q.steps("fwd") == fwd and q.steps("bwd") == p.steps("bwd") and q.dbias_dest == L.DBIAS_PART
+        assert L.block_plan(_block_desc(B, C, hid, h, True, wgrad_ws=None)).dbias_dest == L.DBIAS_ATOMICS
+
+
+def test_block_plan_follows_each_switch_and_capacity():
+    """one request off at a time at the benchmark shape, then every capacity fallback: each loses exactly the decision that needs it"""
+    lib = L.load()
+    cfg = _BLOCK_SHAPES["bench C 128"]
+    B, C, hid, h = cfg
+    p = L.block_plan(_block_desc(*cfg, fuse_mlp=0))         # (wgrad_group stays 1: the grouped launch needs the fused path's operands)
+    assert p.steps("fwd") == ["qkv", "attn_fwd", "proj_ln_fwd", "fc1", "fc2", "ln2_fwd"]
+    assert p.steps("bwd") == ["ln2_bwd", "wgrad_fc2", "dh", "wgrad_fc1", "dx1", "proj_ln_bwd", "wgrad_proj", "attn_bwd", "wgrad_qkv", "dx"]
+    assert (p.mlp_fused, p.proj_ln_fused, p.ln_deferred, p.wgrad_grouped, p.wgrad_kernel, p.grad_zero_in_kernel) == (0, 1, 0, 0, -1, 0)
+    assert p.need_hact_bytes == B * 180 * 360 * hid * 2
+    p = L.block_plan(_block_desc(*cfg, fuse_proj_ln=0))
+    assert p.steps("fwd") == ["qkv", "attn_fwd", "proj", "ln1_fwd", "mlp_fwd"]
+    assert p.steps("bwd") == ["mlp_bwd", "ln1_bwd", "doh", "attn_bwd", "dx", "wgrad_group"]
+    assert (p.mlp_fused, p.proj_ln_fused, p.ln_deferred, p.wgrad_grouped, p.wgrad_kernel, p.grad_zero_in_kernel) == (1, 0, 0, 1, L.BLOCK_WGRAD_SLAB, 1)
+    p = L.block_plan(_block_desc(*cfg, wgrad_group=0))      # the deferred fold is then a launch of its own
+    assert p.steps("fwd") == _FWD_FUSED and p.steps("bwd") == _BWD_FUSED_SINGLE
+    assert (p.mlp_fused, p.proj_ln_fused, p.ln_deferred, p.wgrad_grouped, p.wgrad_kernel) == (1, 1, 1, 0, -1)
+
+    # capacities.  The needs do not move with them
+    full = L.block_plan(_block_desc(*cfg))
+    needs = lambda q: (q.need_hact_bytes, q.need_ln_ws_floats, q.need_wgrad_ws_bytes)
+    BT, Mw = B * 180 * 360, B * 400 * 176
+    assert full.need_ln_ws_floats == max(L.LN_BWD_MAX_BLOCKS * 2 * C, lib.swv2_mlp_bwd_ws_floats(BT, C) + lib.swv2_proj_ln_bwd_ws_floats(Mw, C))
+    group_ws = lib.swv2_block_wgrad_ws_bytes(C, hid, h * 16, 0)
+    assert full.need_wgrad_ws_bytes == max([group_ws] + [lib.swv2_linear_wgrad_ws_bytes(m, n, k, 128) for m, n, k in
+                                                         ((BT, C, hid), (BT, hid, C), (Mw, C, h * 16), (Mw, 3 * h * 16, C))])
+    # one float short of both LayerNorms' rows side by side: not deferred -- each fused kernel folds its own rows inside its launcher
+    # (as the separate LayerNorm kernels always do), so no fold step appears; everything else stays
+    p = L.block_plan(_block_desc(*cfg, ln_ws_floats=lib.swv2_mlp_bwd_ws_floats(BT, C) + lib.swv2_proj_ln_bwd_ws_floats(Mw, C) - 1))
+    assert (p.ln_deferred, p.wgrad_grouped) == (0, 1) and p.steps("bwd") == _BWD_FUSED and needs(p) == needs(full)
+    # one byte short of the grouped launch's workspace, none, or a NULL pointer: four single products + the fold as its own step
+    for over in (dict(wgrad_ws_bytes=group_ws - 1), dict(wgrad_ws_bytes=0), dict(wgrad_ws=None)):
+        p = L.block_plan(_block_desc(*cfg, **over))
+        assert (p.ln_deferred, p.wgrad_grouped, p.wgrad_kernel) == (1, 0, -1) and p.steps("bwd") == _BWD_FUSED_SINGLE, over
+        assert needs(p) == needs(full)
+    assert L.block_plan(_block_desc(*cfg, wgrad_ws_bytes=group_ws)).wgrad_grouped == 1
+    # no gradient carve on offer: the caller zeroes
+    p = L.block_plan(_block_desc(*cfg, grad_zero=None))
+    assert p.grad_zero_in_kernel == 0 and p.steps("bwd") == _BWD_FUSED
+
+
+def test_block_plan_invariants_and_step_table():
+    lib = L.load()
+    from swin_v2_weather_amd import ops
+    # the step table: every (name, launch id) bench.py's kernel names resolve through is a step with that id; the rest is unbracketed
+    table, s = {}, 1
+    while lib.swv2_block_step_name(s):
+        table[lib.swv2_block_step_name(s).decode()] = lib.swv2_block_step_id(s)
+        s += 1
+    assert {n: i for n, i in table.items() if i} == ops.BLOCK_KERNEL_IDS
+    assert sorted(n for n, i in table.items() if not i) == ["ln_fold", "pack_bias", "qk_normalize", "rnorm_zero"]
+    assert sorted(set(ops.BLOCK_KERNEL_IDS.values())) == list(range(1, 8)) + list(range(11, 23))
+    assert lib.swv2_block_step_id(0) == lib.swv2_block_step_id(s) == -1 and lib.swv2_block_step_name(0) is None
+    # NULL arguments
+    assert lib.swv2_block_plan(None, None) == -1 and lib.swv2_block_plan(None, ctypes.byref(L.BlockPlan())) == -1
+    assert lib.swv2_block_plan(ctypes.byref(_block_desc(1, 32, 128, 2, grid=(18, 36))), None) == -1
+    assert lib.swv2_block_plan(ctypes.byref(L.BlockDesc()), ctypes.byref(L.BlockPlan())) == -1        # no geometry
+    lp, dp = ctypes.c_int(), ctypes.c_int()
+    seen = 0
+    for C in (32, 64, 96, 128, 192, 768, 2048):
+        for h in (1, 2, 4, 6, 8, 16):
+            if C % h or lib.swv2_attn_geometry(162, C // h, ctypes.byref(lp), ctypes.byref(dp)):
+                continue
+            for bits in range(8):
+                req = dict(fuse_mlp=bits & 1, fuse_proj_ln=bits >> 1 & 1, wgrad_group=bits >> 2 & 1)
+                d = _block_desc(1, C, 4 * C, h, bias=bool(h & 2), grid=(18, 36), **req)
+                p = L.block_plan(d)
+                seen += 1
+                fwd, bwd = p.steps("fwd"), p.steps("bwd")
+                # written out, not asked of swv2_mlp_supported / swv2_proj_ln_supported: the MLP branch has a fused instantiation at
+                # every C of this sweep up to 192 (hidden 4 C) and none at 768 / 2048; proj + LN1 has none there either, and has one
+                # at the shapes the GPU fixtures and the benchmark run (C 32 with 2 heads, C 128 and 192 with 8)
+                assert p.mlp_fused == int(req["fuse_mlp"] and C <= 192), (C, h, req)
+                assert not p.proj_ln_fused or (req["fuse_proj_ln"] and C <= 192), (C, h, req)
+                if (C, h) in ((32, 2), (128, 8), (192, 8)):
+                    assert p.proj_ln_fused == req["fuse_proj_ln"], (C, h, req)
+                # the decisions are the step lists: a fused kernel stands in both directions exactly where its separate ones do not
+                assert bool(p.mlp_fused) == ("mlp_fwd" in fwd) == ("mlp_bwd" in bwd) == ("fc1" not in fwd) == ("dh" not in bwd), (C, h, req)
+                assert bool(p.proj_ln_fused) == ("proj_ln_fwd" in fwd) == ("proj_ln_bwd" in bwd) == ("proj" not in fwd) == ("doh" not in bwd)
+                assert bool(p.wgrad_grouped) == ("wgrad_group" in bwd) == ("wgrad_qkv" not in bwd), (C, h, req)
+                assert (p.need_hact_bytes == 0) == bool(p.mlp_fused), (C, h, req)
+                assert not p.ln_deferred or (p.mlp_fused and p.proj_ln_fused), (C, h, req)
+                assert not p.wgrad_grouped or (p.mlp_fused and req["wgrad_group"]), (C, h, req)
+                assert (p.wgrad_kernel >= 0) == bool(p.wgrad_grouped)
+                for phase, steps in (("fwd", fwd), ("bwd", bwd)):
+                    n = getattr(p, "n_" + phase)
+                    assert 0 < n <= L.BLOCK_MAX_STEPS and all(lib.swv2_block_step_id(s) >= 0 for s in getattr(p, phase)[:n])
+                assert set(fwd) <= _FWD_STEPS and not set(bwd) & _FWD_STEPS, (C, h, req)
+    assert seen >= 8 * 20
 
 
 def test_model_refuses_cpu_tensors():
