@@ -308,6 +308,12 @@ int swv2_prep_multi(const swv2_prep_item* items_dev, const int* chunks_dev, int 
  * Fused LayerNorm + drop-path + residual add, with the window_reverse + reverse cyclic roll folded into the row
  * scatter:  y[dst] = res[res_mod ? dst % res_mod : dst] + scale[dst / rows_per_sample] * (LN(a[m])*gamma + beta),
  * dst = rowidx ? rowidx[m] : m (negative = padded row, skipped).
+ * The drop-path factor is scale[dst / rows_per_sample] of the DESTINATION row and nothing more: rows_per_sample need not divide M,
+ * the rows of a window or any tile height.  mean / rstd are written for every row m, padded ones included (the statistics of
+ * a[m] like any other row); only the y row is skipped, and y rows that no table entry names are not written.  The backward
+ * reads a, mean, rstd of every row (they must be finite on padded rows too), writes da = +0 on padded rows and counts them in
+ * neither dgamma nor dbeta.  Forward: 4096 workgroups at most, backward SWV2_LN_BWD_MAX_BLOCKS, then grid stride.
+ * Per-element accuracy against fp64 of the saved tensors: tests/test_proj_ln_exact_gpu.py (bounds: tests/proj_ln_reference.py).
  * Replaces  x + drop_path(norm(branch))  (swinv2_global.py:490,496), window_reverse + roll (:468-476) and
  * PatchEmbed's norm + pos_embed add (:545,780 with res = pos_embed as [T][C], res_mod = T).
  * ------------------------------------------------------------------------------------------------------------ */
@@ -415,7 +421,16 @@ int swv2_era5_static(const float* stat, float* out, int B, int Cs, int H, int W,
  *   backward: da1 = LN backward of scale * dy[dst] (zeros for padded rows), d(oh) = split_heads(da1 Wp), head-major;
  *             dgamma / dbeta ACCUMULATED; ws >= swv2_proj_ln_bwd_ws_floats(Bw*Lp, C) floats   (replaces swv2_ln_residual_bwd + swv2_linear)
  * C in {32,64,96,128}, head dim padded to 16, an even number of heads with heads * 16 <= 128; or C = 192 with up to 8 heads in
- * 32-wide slots (oh / doh [Bw][heads][Lp][32], wp [192][heads*32], wpt [heads*32][192]: BASELINE configs[4])  (swv2_proj_ln_supported). */
+ * 32-wide slots (oh / doh [Bw][heads][Lp][32], wp [192][heads*32], wpt [heads*32][192]: BASELINE configs[4])  (swv2_proj_ln_supported).
+ * Lp % 16 == 0.  Anything else is refused with a non-zero return before any launch; nothing is written.
+ * Padded rows (rowidx[m] < 0): a1, mean and rstd are computed and stored like those of any other row (from whatever oh holds
+ * there: the attention kernels leave zeros, so a1 = bf16(bp)); only their y row is skipped.  The backward reads them (they must
+ * be finite), writes da1 = +0 and d(oh) = 0 on these rows -- the proj weight gradient relies on it -- and counts them in neither
+ * dgamma nor dbeta.  The padded head columns of d(oh) are 0 (zero rows of wpt).  Rows past Bw*Lp in a ragged last row tile are
+ * clamped to the last row: nothing outside the tensors is written and the last row counts once.
+ * scale[b]: b = dst / rows_per_sample of the DESTINATION row and nothing more; rows_per_sample need not divide the row count,
+ * Lp, the valid rows of a window or a tile height.  y rows that no table entry names are not written.
+ * Both directions are bit-reproducible.  Per-element accuracy: tests/test_proj_ln_exact_gpu.py (bounds: tests/proj_ln_reference.py). */
 typedef struct {
     const void* oh;        /* bf16 [Bw][heads][Lp][16] */
     const void* wp;        /* bf16 [C][heads*16] (swv2_prep_weight with the head-padding column map) */
@@ -423,7 +438,7 @@ typedef struct {
     const float* gamma; const float* beta; const float* scale;
     const int32_t* rowidx; /* [Bw*Lp] or NULL (identity) */
     const float* x;        /* fp32 [rows][C] residual, destination order */
-    void* a1; float* mean; float* rstd;     /* out, window order */
+    void* a1; float* mean; float* rstd;     /* out, window order: bf16 [Bw*Lp][C], [Bw*Lp], [Bw*Lp]; every row, padded ones included */
     float* y;              /* out fp32 [rows][C], destination order */
     int Bw, Lp, heads, C, rows_per_sample;
     float eps;
@@ -433,7 +448,7 @@ typedef struct {
     const void* a1; const float* mean; const float* rstd; const float* gamma; const float* scale;
     const int32_t* rowidx;
     const void* wpt;       /* bf16 [heads*16][C] = proj.weight^T (swv2_prep_weight, transpose, head-padding row map) */
-    void* da1;             /* out bf16 [Bw*Lp][C] */
+    void* da1;             /* out bf16 [Bw*Lp][C]; +0 on padded rows */
     void* doh;             /* out bf16 [Bw][heads][Lp][16] */
     float* dgamma; float* dbeta; float* ws;
     int Bw, Lp, heads, C, rows_per_sample;

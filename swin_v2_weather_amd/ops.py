@@ -484,6 +484,45 @@ def mlp_bwd(dy, a2, mean, rstd, gamma, scale, hpre, w2t, w1t, dgamma, dbeta, row
     return dx, da2, dh
 
 
+def proj_ln_fwd(oh, wp, bp, gamma, beta, scale, rowidx, x, Bw, Lp, heads, rows_per_sample, eps=1e-5, out=None):
+    """Fused merge heads -> proj -> LayerNorm -> drop-path -> +x, scattered through the row table.  oh bf16 [Bw][heads][Lp][slot],
+    wp bf16 [C][heads * slot] (prep_weight with the head-padding column map), x fp32 [rows][C] in destination order; scale / rowidx
+    may be None.  Returns (y, a1, mean, rstd); out = (y, a1, mean, rstd) hands in the caller's own tensors (y rows that no table
+    entry names are left as they were: a fresh y is uninitialised there)."""
+    Cc, Mw = wp.shape[0], Bw * Lp
+    _chk(oh, BF16, "proj_ln oh"); _chk(wp, BF16, "proj_ln wp"); _chk(x, torch.float32, "proj_ln x")
+    dev = x.device
+    if out is None:
+        out = (torch.empty_like(x), torch.empty(Mw, Cc, dtype=BF16, device=dev), torch.empty(Mw, device=dev), torch.empty(Mw, device=dev))
+    y, a1, mean, rstd = out
+    a = L.ProjLnArgs()
+    a.oh, a.wp, a.bp, a.gamma, a.beta, a.scale, a.rowidx, a.x = (_p(t) for t in (oh, wp, bp, gamma, beta, scale, rowidx, x))
+    a.a1, a.mean, a.rstd, a.y = (_p(t) for t in (a1, mean, rstd, y))
+    a.Bw, a.Lp, a.heads, a.C, a.rows_per_sample, a.eps = Bw, Lp, heads, Cc, rows_per_sample, eps
+    L.check(_timed("proj_ln_fwd", L.load().swv2_proj_ln_fwd, C.byref(a), _stream()), "swv2_proj_ln_fwd")
+    return y, a1, mean, rstd
+
+
+def proj_ln_bwd(dy, a1, mean, rstd, gamma, scale, rowidx, wpt, dgamma, dbeta, Bw, Lp, heads, rows_per_sample, out=None, ws=None):
+    """Fused LN backward (dy rows gathered through the row table) -> d(oh) = split_heads(da1 Wp).  wpt bf16 [heads * slot][C]
+    (prep_weight, transpose, head-padding row map).  Returns (da1, doh); dgamma / dbeta accumulated.  out = (da1, doh) and ws
+    (fp32, swv2_proj_ln_bwd_ws_floats(Bw * Lp, C) floats) hand in the caller's own tensors."""
+    Cc, Mw = wpt.shape[1], Bw * Lp
+    _chk(dy, torch.float32, "proj_ln dy"); _chk(a1, BF16, "proj_ln a1"); _chk(wpt, BF16, "proj_ln wpt")
+    dev = dy.device
+    if out is None:
+        out = (torch.empty(Mw, Cc, dtype=BF16, device=dev), torch.empty(Bw, heads, Lp, wpt.shape[0] // max(heads, 1), dtype=BF16, device=dev))
+    if ws is None:
+        ws = torch.empty(L.load().swv2_proj_ln_bwd_ws_floats(Mw, Cc), dtype=torch.float32, device=dev)
+    da1, doh = out
+    a = L.ProjLnBwdArgs()
+    a.dy, a.a1, a.mean, a.rstd, a.gamma, a.scale, a.rowidx, a.wpt = (_p(t) for t in (dy, a1, mean, rstd, gamma, scale, rowidx, wpt))
+    a.da1, a.doh, a.dgamma, a.dbeta, a.ws = (_p(t) for t in (da1, doh, dgamma, dbeta, ws))
+    a.Bw, a.Lp, a.heads, a.C, a.rows_per_sample = Bw, Lp, heads, Cc, rows_per_sample
+    L.check(_timed("proj_ln_bwd", L.load().swv2_proj_ln_bwd, C.byref(a), _stream()), "swv2_proj_ln_bwd")
+    return da1, doh
+
+
 def cpb_fwd(w1, b1, w2, b2, keep, bias, wh, ww, heads, hidden, drop_p):
     L.check(L.load().swv2_cpb_fwd(_p(w1), _p(b1), _p(w2), _p(b2), _p(keep), _p(bias), wh, ww, heads, hidden, drop_p, _stream()),
             "swv2_cpb_fwd")
