@@ -32,8 +32,9 @@ extern "C" {
  * 106: SWV2_EPI_UNPATCH_LOSS writes slot 1 of loss_part only where swv2_loss_part_reduce reads it; 107: swv2_epilogue.q[3], the loss
  * epilogue with the rollout destinations; 108: the kernel-selection queries swv2_linear_kernel, swv2_linear_wgrad_kernel,
  * swv2_block_wgrad_kernel; 109: swv2_block_plan (+ swv2_block_plan_t, enum swv2_block_step, swv2_block_step_id / _name),
- * swv2_block_desc loses fuse_attn and wgrad_side_stream. */
-#define SWV2_VERSION 109
+ * swv2_block_desc loses fuse_attn and wgrad_side_stream; 110: the attention kernel-selection queries swv2_attn_fwd_kernel /
+ * swv2_attn_bwd_kernel (+ swv2_attn_kernel_t, SWV2_ATTN_K_*). */
+#define SWV2_VERSION 110
 
 enum {
     SWV2_OK = 0,
@@ -53,6 +54,15 @@ const char* swv2_last_error(void);
  *   lse   [Bw][heads][Lp]        fp32   log2-domain log-sum-exp of the scaled, biased, masked scores
  * Bw = B * windows per sample, window index = b*nW + wi*nww + wj, token index t = r*ww + c
  * (reference: window_partition, swinv2_global.py:89-101).  Lp, DP: swv2_attn_geometry().
+ * Padding contract, the same for every kernel family (checked element by element in tests/test_attn_exact_gpu.py):
+ *   inputs : rows >= L and columns >= head_dim of qkvh and doh are zero, rows >= L of rnorm are zero (the qkv epilogue and
+ *            swv2_proj_ln_bwd / the d(oh) product leave them so); the kernels read them.
+ *   oh     : rows >= L and columns >= head_dim are written as exactly 0 by the forward.
+ *   lse    : rows >= L are written as exactly 0.
+ *   dqkvh  : rows >= L of all three parts (dq, dk, dv) are written as exactly 0 -- the weight-gradient kernels sum over all Lp rows and
+ *            rely on it; columns >= head_dim of rows < L are UNSPECIFIED (a caller must not read them; the qkv weight gradient drops them
+ *            through its column map).
+ *   dlogit_scale, dbias: only the [heads] / [heads][L][L] elements are touched; a head with tau > ln 100 adds exactly 0.
  * ------------------------------------------------------------------------------------------------------------ */
 int swv2_attn_geometry(int L, int head_dim, int* Lp, int* DP);
 
@@ -60,7 +70,8 @@ int swv2_attn_geometry(int L, int head_dim, int* Lp, int* DP);
  * operand-folded softmax of csrc/attn2.hip (160 .. 176-token windows; 16- and 32-wide head slots without a table, 16-wide ones with
  * a packed table; exponent reference sigma' (+ the table's maximum) where 2 sigma' + (table max - min) <= 80 in unmasked windows,
  * normaliser = sum of the bf16-rounded exponentials), 0 = row maximum + exact sum (csrc/attn.hip, attn_wide.hip); negative: unsupported geometry.
- * Pure host function.  The parity tests declare the regime their oracle emulates and check it against this (reference: the softmax of
+ * Pure host function; the `regime` field of swv2_attn_fwd_kernel's answer for the same geometry.  It speaks of a head WIDTH, not of one launch: at
+ * head_dim 256, which has no table form, it answers 0 whatever has_bias says, while swv2_attn_fwd_kernel refuses a table there.  The parity tests declare the regime their oracle emulates and check it against this (reference: the softmax of
  * swinv2_global.py:309-314, one function in both regimes up to rounding). */
 int swv2_attn_fwd_regime(int L, int head_dim, int has_bias, int dbg);
 
@@ -104,6 +115,33 @@ typedef struct swv2_attn_args {
     int dbias_partials;       /* bwd, 1 (needs dbias_ws): LEAVE the workgroups' tables in dbias_ws -- [swv2_attn_bias_chunks(Bw)][heads][L][L],
                                  every entry written -- and do not touch dbias (may be NULL): the caller sums them, e.g. swv2_cpb_bwd_multi */
 } swv2_attn_args;
+
+/* Which kernel swv2_attn_fwd / swv2_attn_bwd launch for these arguments: the family (SWV2_ATTN_K_*, also the return value) and the
+ * template arguments of the instantiation, or a negative error for a geometry no kernel serves (head_dim 129 .. 255, head_dim 256 with
+ * a table or in the 64-row layout, L > 176).  Pure host functions: they read L, head_dim, dbg and the PRESENCE of bias / bias_pack,
+ * dereference no pointer, launch nothing and need no GPU (`out` may be NULL).  The launchers switch on the same selection function,
+ * and the tests assert on this answer where they name a path. */
+#define SWV2_ATTN_K_D256 0       /* csrc/attn_d256.hip: 256-channel heads, 176-row layout, no table                                  */
+#define SWV2_ATTN_K_FWD3 1       /* csrc/attn2.hip: operand-folded forward, 16-wide slots, 160 .. 176 tokens, no table              */
+#define SWV2_ATTN_K_FWD3W 2      /* the same at 32-wide slots                                                                       */
+#define SWV2_ATTN_K_FWD3B 3      /* the same at 16-wide slots with a PACKED table                                                   */
+#define SWV2_ATTN_K_WIDE 4       /* csrc/attn_wide.hip: 65 .. 96 channels, 176-row layout, no table                                 */
+#define SWV2_ATTN_K_STREAM 5     /* csrc/attn_bwd_stream.hip: streamed-dQ backward, 176-row layout, 16-wide slots, no table         */
+#define SWV2_ATTN_K_FIRST_GEN 6  /* csrc/attn.hip: attn_fwd_kernel / attn_bwd_kernel<LT, DK, bias, LFIX>                            */
+typedef struct swv2_attn_kernel_t {
+    int family;              /* SWV2_ATTN_K_* */
+    int Lp, DP;              /* swv2_attn_geometry */
+    int LT, DK;              /* Lp / 16, DP / 16: the layout's row and column tiles */
+    int LFIX;                /* the window area the instantiation is specialised for, 0 = the run-time-L one */
+    int regime;              /* forward: swv2_attn_fwd_regime (1 = operand-folded softmax, normaliser = sum of the rounded exponentials) */
+    /* backward, first generation (and `aug` of the streamed kernel): the compile-time variants that change arithmetic */
+    int aug;                 /* softmax statistics, padded-key flag and shift mask ride in the MFMA operands (bf16 parts: lse and delta in
+                                three, |error| <= 2^-24 |v|; the mask term -100 / sigma in two, <= 2^-17 of it) instead of fp32 from LDS */
+    int bias_lds;            /* the table's image sits in LDS (else: rows in registers) */
+    int qg;                  /* q / dO fragments are read from global memory */
+} swv2_attn_kernel_t;
+int swv2_attn_fwd_kernel(const swv2_attn_args* a, swv2_attn_kernel_t* out);
+int swv2_attn_bwd_kernel(const swv2_attn_args* a, swv2_attn_kernel_t* out);
 
 /* bytes of swv2_attn_args.dbias_ws for swv2_attn_bwd with a bias */
 size_t swv2_attn_dbias_ws_bytes(int heads, int L, int max_chunks);

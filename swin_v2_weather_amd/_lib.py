@@ -15,7 +15,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIB_PATH = os.environ.get("SWV2_LIB") or os.path.join(HERE, "libswv2.so")     # SWV2_LIB: a privately built variant (tools/ab_macro.sh)
 SOURCES = ["capi.hip", "attn.hip", "attn2.hip", "attn_bwd_stream.hip", "attn_wide.hip", "attn_d256.hip", "gemm.hip", "gemm_tn.hip", "gemm_tn_slab.hip", "rowops.hip", "block.hip", "cpb.hip", "mlp.hip", "proj_ln.hip", "dataio.hip"]
 
-ABI_VERSION = 109          # SWV2_VERSION of the include/swv2.h these ctypes mirrors were written against (checked in load())
+ABI_VERSION = 110          # SWV2_VERSION of the include/swv2.h these ctypes mirrors were written against (checked in load())
 
 _lib = None
 _lock = threading.Lock()
@@ -74,6 +74,15 @@ class AttnArgs(C.Structure):
                 ("Bw", C.c_int), ("heads", C.c_int), ("L", C.c_int), ("head_dim", C.c_int),
                 ("nwh", C.c_int), ("nww", C.c_int), ("mask_thr", C.c_int), ("max_chunks", C.c_int), ("dbg", C.c_int),
                 ("dbias_ws", C.c_void_p), ("dbias_ws_bytes", C.c_size_t), ("dbias_partials", C.c_int)]
+
+
+class AttnKernelInfo(C.Structure):        # swv2_attn_kernel_t: the answer of swv2_attn_fwd_kernel / swv2_attn_bwd_kernel
+    _fields_ = [(n, C.c_int) for n in ("family", "Lp", "DP", "LT", "DK", "LFIX", "regime", "aug", "bias_lds", "qg")]
+
+
+# SWV2_ATTN_K_*: the attention kernel families
+ATTN_K_D256, ATTN_K_FWD3, ATTN_K_FWD3W, ATTN_K_FWD3B, ATTN_K_WIDE, ATTN_K_STREAM, ATTN_K_FIRST_GEN = range(7)
+ATTN_K_NAMES = ("D256", "FWD3", "FWD3W", "FWD3B", "WIDE", "STREAM", "FIRST_GEN")
 
 
 class Operand(C.Structure):
@@ -194,6 +203,8 @@ SYMBOLS = {
     "swv2_last_error": (C.c_char_p, []),
     "swv2_attn_geometry": (_I, [_I, _I, C.POINTER(_I), C.POINTER(_I)]),
     "swv2_attn_fwd_regime": (_I, [_I, _I, _I, _I]),
+    "swv2_attn_fwd_kernel": (_I, [C.POINTER(AttnArgs), C.POINTER(AttnKernelInfo)]),
+    "swv2_attn_bwd_kernel": (_I, [C.POINTER(AttnArgs), C.POINTER(AttnKernelInfo)]),
     "swv2_attn_pack_bias_bytes": (C.c_size_t, [_I, _I]),
     "swv2_attn_dbias_ws_bytes": (C.c_size_t, [_I, _I, _I]),
     "swv2_attn_pack_bias": (_I, [_P, _I, _I, _P, _P]),

@@ -309,13 +309,27 @@ __device__ unsigned long long attn1_win[64 * 128];        // wave 8 of the first
 // the K = 32 operand, the same 16 issue cycles as K = 16):
 //   A operand (query side, one 32-slot row per query in the Q / dO slabs, written by the staging threads):
 //       Q slab : k 0..15 q^ | k 16..18 lse / (sigma log2 e) as three bf16 parts hi + lo + lolo (|error| <= 2^-24 |v|) | k 19: 1 |
-//                k 20, 21: the query's mask-region flags (region 1, region 0) | zeros
+//                k 20, 21: the query's mask-region flags (region 1, region 0) | k 22, 23: the same flags again | zeros
 //       dO slab: k 0..15 dO | k 16..18 delta = rowsum(dO O) in three parts | zeros
 //   B operand (key side, built once per wave): k 0..15 k^ resp. v | k 16..18: -1, -1, -1 | k 19: -1e30 on padded keys (K only) |
-//                k 20, 21: the key's mask terms (c if the key is in region 0 resp. 1, with c = -100 log2 e / (sigma log2 e)) | zeros
+//                k 20, 21: the key's mask terms (bf16(c) if the key is in region 0 resp. 1, with c = -100 log2 e / (sigma log2 e)) |
+//                k 22, 23: their low parts bf16(c - bf16(c)), so the mask enters as c (1 + e), |e| <= 2^-17 | zeros
 //   so  S' = Q_aug K_aug^T = cos - lse / (sigma log2 e) + [pad] + [mask]  and  dP' = dO_aug V_aug^T = dP - delta  come out of the
 //   matrix pipe, and the softmax backward is  p = exp2(S' sigma log2 e),  dS = p dP'.  The reference's mask (-100 where the query's
 //   and the key's regions differ, swinv2_global.py:403-424) is bilinear in the two region flags, hence two slots.
+// The compile-time variants of attn_bwd_kernel that change its arithmetic, as functions of the template arguments: used by the kernel
+// itself and by swv2_attn_bwd_kernel, which reports them.
+//   qg      : q / dO fragments read from global memory (the slabs do not fit the LDS beside K, V and the dcos image)
+//   bias_lds: the bias image sits in LDS (else: bias rows in registers)
+//   aug     : softmax statistics, padded-key flag and shift mask inside the MFMA operands
+constexpr bool bwd_var_qg(int LT, int DK) { return 4 * (16 * LT * 16 * DK) * 2 + 16 * LT * (16 * LT + 4) * 2 + 16 * LT * 8 + 256 > 160 * 1024; }
+constexpr bool bwd_var_bias_lds(int LT, int DK, bool bias) { return bias && LT * DK <= 11; }
+constexpr bool bwd_var_aug(int LT, int DK, bool bias, int LFIX, bool augp) {
+    return augp && DK <= 2 && !bwd_var_qg(LT, DK) && (!bias || (DK == 1 && bwd_var_bias_lds(LT, DK, bias) && LFIX > 0));
+}
+// AUGP as the launcher passes it: 16-wide slots with a table, 16- and 32-wide ones without, unless SWV2_ATTN_PLAIN_STATS
+constexpr bool bwd_augp(int DK, bool bias, int dbg) { return (bias ? DK == 1 : DK <= 2) && !(dbg & SWV2_ATTN_PLAIN_STATS); }
+
 template <int LT, int DK, bool HAS_BIAS, int LFIX, bool AUGP = false>
 __global__ __launch_bounds__(64 * LT) void attn_bwd_kernel(
     const uint16_t* __restrict__ qkvh, const float* __restrict__ logit_scale, const float* __restrict__ bias,
@@ -331,7 +345,7 @@ __global__ __launch_bounds__(64 * LT) void attn_bwd_kernel(
     constexpr int Lp = C::Lp, DP = C::DP, SLAB = C::SLAB;
     constexpr int TPW = 1, WAVES = LT, NT = 64 * WAVES;
     constexpr int DSP = Lp + 4;                              // row pitch (elements) of the [key][q] bf16 images
-    constexpr bool BIAS_LDS = HAS_BIAS && (LT * DK <= 11);   // 145 KB at LT=11, DK=1
+    constexpr bool BIAS_LDS = bwd_var_bias_lds(LT, DK, HAS_BIAS);   // LT * DK <= 11: 145 KB at LT=11, DK=1
     constexpr int CH = SLAB / 8;                             // 16-byte chunks per slab
     constexpr int CPT = (CH + NT - 1) / NT;                  // chunks per thread
     constexpr int CPR = 2 * DK;                              // chunks per row
@@ -341,8 +355,8 @@ __global__ __launch_bounds__(64 * LT) void attn_bwd_kernel(
     // QG: the q / dO slabs do not fit beside K, V and the dcos image (head dim padded to 128 at the 176-token window:
     // 4 x 45 KB + 63 KB) -- their fragments are then read from global memory / L2 (the slab layout in memory is the LDS
     // image), the transposed ones as four 2-byte loads.  A coverage path for wide heads, not a tuned one.
-    constexpr bool QG = (4 * SLAB * 2 + Lp * DSP * 2 + Lp * 8 + 256 > 160 * 1024);
-    constexpr bool AUG = AUGP && DK <= 2 && !QG && (!HAS_BIAS || (DK == 1 && BIAS_LDS && LFIX > 0));
+    constexpr bool QG = bwd_var_qg(LT, DK);     // 4 * SLAB * 2 + Lp * DSP * 2 + Lp * 8 + 256 > 160 KB
+    constexpr bool AUG = bwd_var_aug(LT, DK, HAS_BIAS, LFIX, AUGP);
     // bias image rows (keys): with AUG the padded keys are switched off inside the operand, so the image ends at the last real key
     // (rounded up to 4) and the last wave reads a clamped row -- 5 KB that the 80-byte Q / dO rows need
     constexpr int BROWS = (HAS_BIAS && AUG) ? (LFIX + 3) / 4 * 4 : Lp;
@@ -507,7 +521,7 @@ __global__ __launch_bounds__(64 * LT) void attn_bwd_kernel(
                         const float e1 = dl - bf2f(d0);
                         const uint16_t d1 = f2bf(e1), d2 = f2bf(e1 - bf2f(d1));
                         const uint32_t one = 0x3f80u, rqf = (row >= mask_thr) ? 0x3f80u : 0u;
-                        aq = make_uint4(l0 | ((uint32_t)l1 << 16), l2 | (one << 16), rqf | ((one - rqf) << 16), 0);
+                        aq = make_uint4(l0 | ((uint32_t)l1 << 16), l2 | (one << 16), rqf | ((one - rqf) << 16), rqf | ((one - rqf) << 16));
                         ad = make_uint4(d0 | ((uint32_t)d1 << 16), d2, 0, 0);
                     }
                     if (DK == 1 || (c % CPR) == 0) {          // (DK = 1: the odd chunk's thread writes the zero slots 24 .. 31)
@@ -639,8 +653,11 @@ __global__ __launch_bounds__(64 * LT) void attn_bwd_kernel(
                 const uint32_t m1 = 0xbf80u;                                       // -1
                 const uint32_t padk = (key < Lc) ? 0u : (uint32_t)f2bf(-1.0e30f);
                 const bool kreg = key >= mask_thr;
-                const uint32_t mk0 = f2bf(kreg ? 0.f : cmask), mk1 = f2bf(kreg ? cmask : 0.f);
-                const uint4 augk = make_uint4(m1 | (m1 << 16), m1 | (padk << 16), mk0 | (mk1 << 16), 0);
+                // the mask term as hi + lo bf16 parts (k 20, 21 and k 22, 23; |error| <= 2^-17 |c|): one part alone is off by up to 2^-9 |c|,
+                // 0.28 in the log2 domain, which shows as soon as a masked key carries weight
+                const uint32_t chi = f2bf(cmask), clo = f2bf(cmask - bf2f((uint16_t)chi));
+                const uint32_t mk0 = kreg ? 0u : chi, mk1 = kreg ? chi : 0u, ml0 = kreg ? 0u : clo, ml1 = kreg ? clo : 0u;
+                const uint4 augk = make_uint4(m1 | (m1 << 16), m1 | (padk << 16), mk0 | (mk1 << 16), ml0 | (ml1 << 16));
                 const uint4 augv = make_uint4(m1 | (m1 << 16), m1, 0, 0);
                 const uint4 z = make_uint4(0, 0, 0, 0);
                 const uint4 rk = *(const uint4*)(Ks + key * DP + (g & 1) * 8), rv = *(const uint4*)(Vs + key * DP + (g & 1) * 8);
@@ -732,8 +749,11 @@ __global__ __launch_bounds__(64 * LT) void attn_bwd_kernel(
                 const uint32_t m1 = 0xbf80u;                                       // -1
                 const uint32_t padk = (key < Lc) ? 0u : (uint32_t)f2bf(-1.0e30f);
                 const bool kreg = key >= mask_thr;
-                const uint32_t mk0 = f2bf(kreg ? 0.f : cmask), mk1 = f2bf(kreg ? cmask : 0.f);
-                const uint4 augk = make_uint4(m1 | (m1 << 16), m1 | (padk << 16), mk0 | (mk1 << 16), 0);
+                // the mask term as hi + lo bf16 parts (k 20, 21 and k 22, 23; |error| <= 2^-17 |c|): one part alone is off by up to 2^-9 |c|,
+                // 0.28 in the log2 domain, which shows as soon as a masked key carries weight
+                const uint32_t chi = f2bf(cmask), clo = f2bf(cmask - bf2f((uint16_t)chi));
+                const uint32_t mk0 = kreg ? 0u : chi, mk1 = kreg ? chi : 0u, ml0 = kreg ? 0u : clo, ml1 = kreg ? clo : 0u;
+                const uint4 augk = make_uint4(m1 | (m1 << 16), m1 | (padk << 16), mk0 | (mk1 << 16), ml0 | (ml1 << 16));
                 const uint4 augv = make_uint4(m1 | (m1 << 16), m1, 0, 0);
                 const uint4 z = make_uint4(0, 0, 0, 0);
                 if constexpr (DK == 1) {
@@ -1114,7 +1134,7 @@ int launch_bwd(const swv2_attn_args* a, hipStream_t st) {
         // (in FRONT of the launch: with dbias == NULL and a too small workspace the kernel would add into address 0 -- ADVICE r5)
         if (a->dbias_partials) SWV2_CHECK_ARG(dbws != nullptr, "attn_bwd: dbias_partials needs a workspace of %zu bytes", need);
         // 16-wide heads with the bias image in LDS: statistics / mask inside the MFMA operands here too
-        if (DK == 1 && !(a->dbg & SWV2_ATTN_PLAIN_STATS))
+        if (bwd_augp(DK, true, a->dbg))
             hipLaunchKernelGGL((attn_bwd_kernel<LT, DK, true, LFIX, true>), grid, block, 0, st, (const uint16_t*)a->qkvh, a->logit_scale,
                                a->bias, bimg, (const uint16_t*)a->oh, (const uint16_t*)a->doh, a->lse, a->rnorm,
                                (uint16_t*)a->dqkvh, a->dlogit_scale, a->dbias, a->Bw, a->heads, a->L, nW, a->nww, a->nwh,
@@ -1131,7 +1151,7 @@ int launch_bwd(const swv2_attn_args* a, hipStream_t st) {
     } else {
         dim3 grid(nchunk, a->heads), block(64 * LT);
         // 16-wide heads: statistics / mask inside the MFMA operands (SWV2_ATTN_PLAIN_STATS keeps the kernel that reads them from LDS)
-        if (DK <= 2 && !(a->dbg & SWV2_ATTN_PLAIN_STATS))
+        if (bwd_augp(DK, false, a->dbg))
             hipLaunchKernelGGL((attn_bwd_kernel<LT, DK, false, LFIX, true>), grid, block, 0, st, (const uint16_t*)a->qkvh,
                                a->logit_scale, a->bias, (const uint16_t*)nullptr, (const uint16_t*)a->oh, (const uint16_t*)a->doh, a->lse,
                                a->rnorm, (uint16_t*)a->dqkvh, a->dlogit_scale, a->dbias, a->Bw, a->heads, a->L, nW, a->nww, a->nwh,
@@ -1181,24 +1201,18 @@ extern "C" int swv2_attn_geometry(int L, int head_dim, int* Lp, int* DP) {
 }
 
 // kernels are specialised for the window areas of the reference configurations (9x18 = 162 at 720x1440 / ratio 80,
-// 6x9 = 54 at 192x288 / ratio 32); any other area <= 176 runs the generic (runtime-L) instantiation
-#define SWV2_ATTN_DISPATCH(FN)                                                         \
-    hipStream_t st = (hipStream_t)stream;                                              \
-    if (Lp == 176 && DP == 16 && a->L == 162) return FN<11, 1, 162>(a, st);            \
-    if (Lp == 64 && DP == 16 && a->L == 54) return FN<4, 1, 54>(a, st);                \
-    if (Lp == 64 && DP == 16) return FN<4, 1, 0>(a, st);                               \
-    if (Lp == 64 && DP == 32) return FN<4, 2, 0>(a, st);                               \
-    if (Lp == 176 && DP == 16) return FN<11, 1, 0>(a, st);                             \
-    if (Lp == 176 && DP == 32 && a->L == 162) return FN<11, 2, 162>(a, st);            \
-    if (Lp == 176 && DP == 32) return FN<11, 2, 0>(a, st);                             \
-    if (Lp == 64 && DP == 64) return FN<4, 4, 0>(a, st);                               \
-    if (Lp == 64 && DP == 96) return FN<4, 6, 0>(a, st);                               \
-    if (Lp == 176 && DP == 96) return FN<11, 6, 0>(a, st);                             \
-    if (Lp == 64 && DP == 128) return FN<4, 8, 0>(a, st);                              \
-    if (Lp == 176 && DP == 64) return FN<11, 4, 0>(a, st);                             \
-    if (Lp == 176 && DP == 128) return FN<11, 8, 0>(a, st);                            \
-    swv2_set_error("attention: no kernel for Lp=%d DP=%d", Lp, DP);                    \
+// 6x9 = 54 at 192x288 / ratio 32); any other area <= 176 runs the generic (runtime-L) instantiation.  The 13 instantiations of the
+// first-generation pair; which one serves a geometry is first_gen_lfix()'s answer over the layout's tiles (LT, DK, LFIX), nothing else.
+#define SWV2_ATTN_ROWS(X) \
+    X(11, 1, 162) X(4, 1, 54) X(4, 1, 0) X(4, 2, 0) X(11, 1, 0) X(11, 2, 162) X(11, 2, 0) X(4, 4, 0) X(4, 6, 0) X(11, 6, 0) X(4, 8, 0) \
+    X(11, 4, 0) X(11, 8, 0)
+#define SWV2_ATTN_DISPATCH(FN)                                                                                       \
+    hipStream_t st = (hipStream_t)stream;                                                                            \
+    SWV2_ATTN_ROWS(SWV2_ATTN_ROW_##FN)                                                                               \
+    swv2_set_error("attention: no kernel for LT=%d DK=%d LFIX=%d", sel.LT, sel.DK, sel.LFIX);                        \
     return SWV2_ERR_UNSUPPORTED;
+#define SWV2_ATTN_ROW_launch_fwd(LT_, DK_, LF_) if (sel.LT == LT_ && sel.DK == DK_ && sel.LFIX == LF_) return launch_fwd<LT_, DK_, LF_>(a, st);
+#define SWV2_ATTN_ROW_launch_bwd(LT_, DK_, LF_) if (sel.LT == LT_ && sel.DK == DK_ && sel.LFIX == LF_) return launch_bwd<LT_, DK_, LF_>(a, st);
 
 #ifdef SWV2_ATTN1_STAMPS
 extern "C" int swv2_debug_attn1_win(void* out) {
@@ -1253,7 +1267,9 @@ int swv2_attn_bwd_stream(const swv2_attn_args* a, void* stream);                
 
 namespace {
 
-enum class AttnKernel { D256, FWD3, FWD3W, FWD3B, WIDE, STREAM, FIRST_GEN };
+// families in the order of SWV2_ATTN_K_* (swv2.h)
+enum class AttnKernel { D256 = SWV2_ATTN_K_D256, FWD3 = SWV2_ATTN_K_FWD3, FWD3W = SWV2_ATTN_K_FWD3W, FWD3B = SWV2_ATTN_K_FWD3B,
+                        WIDE = SWV2_ATTN_K_WIDE, STREAM = SWV2_ATTN_K_STREAM, FIRST_GEN = SWV2_ATTN_K_FIRST_GEN };
 
 // 65 .. 96-channel heads in the 176-row layout without a table: attn_wide.hip
 bool wide_shape(int head_dim, int Lp, int DP, bool bias) {
@@ -1287,45 +1303,105 @@ AttnKernel attn_bwd_kernel_for(int head_dim, int Lp, int DP, bool bias, int dbg)
     return AttnKernel::FIRST_GEN;
 }
 
+// window area a first-generation instantiation is specialised for (0 = the run-time-L one)
+int first_gen_lfix(int Lp, int DP, int L) {
+    if (Lp == 176 && (DP == 16 || DP == 32) && L == 162) return 162;
+    if (Lp == 64 && DP == 16 && L == 54) return 54;
+    return 0;
+}
+
+// THE selection: geometry, family and template arguments of the launch swv2_attn_fwd / swv2_attn_bwd make for these arguments, or a
+// negative error.  Reads sizes, dbg and the PRESENCE of bias / bias_pack; dereferences nothing, launches nothing.
+int attn_select(const swv2_attn_args* a, bool bwd, swv2_attn_kernel_t* out) {
+    SWV2_CHECK_ARG(a != nullptr && out != nullptr, "attn: null args");
+    SWV2_CHECK_ARG(a->L > 0 && a->head_dim > 0, "attn: non-positive size");
+    SWV2_CHECK_ARG(a->head_dim % 4 == 0, "attn: head_dim %d must be a multiple of 4", a->head_dim);
+    int Lp, DP;
+    const int rc = swv2_attn_geometry(a->L, a->head_dim, &Lp, &DP);
+    if (rc) return rc;
+    const bool bias = a->bias != nullptr;
+    const AttnKernel k = bwd ? attn_bwd_kernel_for(a->head_dim, Lp, DP, bias, a->dbg)
+                             : attn_fwd_kernel_for(a->L, a->head_dim, Lp, DP, bias, a->bias_pack != nullptr, a->dbg);
+    if (k == AttnKernel::D256 && bias) {
+        swv2_set_error("attention: no CPB bias at head_dim=%d (the 256-column kernels have no table)", a->head_dim);
+        return SWV2_ERR_UNSUPPORTED;
+    }
+    *out = swv2_attn_kernel_t{};
+    out->family = (int)k;
+    out->Lp = Lp;
+    out->DP = DP;
+    out->LT = Lp / 16;
+    out->DK = DP / 16;
+    // every other family has one instantiation for the 162-token window and a run-time-L one
+    out->LFIX = k == AttnKernel::FIRST_GEN ? first_gen_lfix(Lp, DP, a->L) : attn_lfix_other(a->L);
+    // regime 1: the operand-folded softmax of attn2.hip (normaliser = sum of the rounded exponentials)
+    out->regime = !bwd && (k == AttnKernel::FWD3 || k == AttnKernel::FWD3W || k == AttnKernel::FWD3B);
+    if (bwd && k == AttnKernel::FIRST_GEN) {
+        const bool augp = bwd_augp(out->DK, bias, a->dbg);
+        out->aug = bwd_var_aug(out->LT, out->DK, bias, out->LFIX, augp);
+        out->bias_lds = bwd_var_bias_lds(out->LT, out->DK, bias);
+        out->qg = bwd_var_qg(out->LT, out->DK);
+    }
+    // attn_bwd_stream.hip has no other form: its only kernel carries statistics and mask in the operands (same construction, same slots)
+    if (bwd && k == AttnKernel::STREAM) out->aug = 1;
+    return (int)k;
+}
+
 }  // namespace
 
-// which forward kernel family serves a geometry (pure host function, no launch): 1 = the operand-folded softmax of attn2.hip, 0 = row
+extern "C" int swv2_attn_fwd_kernel(const swv2_attn_args* a, swv2_attn_kernel_t* out) {
+    swv2_attn_kernel_t tmp;
+    return attn_select(a, false, out ? out : &tmp);
+}
+
+extern "C" int swv2_attn_bwd_kernel(const swv2_attn_args* a, swv2_attn_kernel_t* out) {
+    swv2_attn_kernel_t tmp;
+    return attn_select(a, true, out ? out : &tmp);
+}
+
+// which forward softmax regime serves a geometry (pure host function, no launch): 1 = the operand-folded softmax of attn2.hip, 0 = row
 // maximum + exact sum (attn.hip, attn_wide.hip, attn_d256.hip); negative: geometry not covered.  The parity tests declare the regime
-// their oracle emulates and check it against this.  (has_bias: a table in its PACKED form, as the model always passes it.)
+// their oracle emulates and check it against this.  (has_bias: a table in its PACKED form, as the model always passes it.)  The
+// `regime` field of swv2_attn_fwd_kernel's answer for the same geometry.
 extern "C" int swv2_attn_fwd_regime(int L, int head_dim, int has_bias, int dbg) {
-    int Lp, DP;
-    const int rc = swv2_attn_geometry(L, head_dim, &Lp, &DP);
-    if (rc) return rc;
-    switch (attn_fwd_kernel_for(L, head_dim, Lp, DP, has_bias, has_bias, dbg)) {
-        case AttnKernel::FWD3: case AttnKernel::FWD3W: case AttnKernel::FWD3B: return 1;
-        default: return 0;
-    }
+    swv2_attn_args a{};
+    swv2_attn_kernel_t sel;
+    a.L = L;
+    a.head_dim = head_dim;
+    a.dbg = dbg;
+    a.bias = has_bias ? (const float*)&a : nullptr;           // presence only
+    a.bias_pack = has_bias ? (const void*)&a : nullptr;
+    // 256-channel heads have no table form: the regime asked for is that of the WIDTH (row maximum), as before ABI 110 -- see swv2.h;
+    // swv2_attn_fwd_kernel, which speaks of one launch, refuses a table there
+    if (head_dim == 256) a.bias = nullptr, a.bias_pack = nullptr;
+    const int rc = attn_select(&a, false, &sel);
+    return rc < 0 ? rc : sel.regime;
 }
 
 extern "C" int swv2_attn_fwd(const swv2_attn_args* a, void* stream) {
-    int Lp, DP;
+    swv2_attn_kernel_t sel;
     int rc = check_args(a, false);
-    if (!rc) rc = swv2_attn_geometry(a->L, a->head_dim, &Lp, &DP);
-    if (rc) return rc;
-    switch (attn_fwd_kernel_for(a->L, a->head_dim, Lp, DP, a->bias, a->bias_pack, a->dbg)) {
-        case AttnKernel::D256: return swv2_attn_fwd_d256(a, Lp, stream);
+    if (!rc) rc = attn_select(a, false, &sel);
+    if (rc < 0) return rc;
+    switch ((AttnKernel)sel.family) {
+        case AttnKernel::D256: return swv2_attn_fwd_d256(a, sel.Lp, stream);
         case AttnKernel::FWD3: return swv2_attn_fwd3(a, stream);
         case AttnKernel::FWD3W: return swv2_attn_fwd3w(a, stream);
         case AttnKernel::FWD3B: return swv2_attn_fwd3b(a, stream);
-        case AttnKernel::WIDE: return swv2_attn_fwd_wide(a, DP, stream);
+        case AttnKernel::WIDE: return swv2_attn_fwd_wide(a, sel.DP, stream);
         default: break;
     }
     SWV2_ATTN_DISPATCH(launch_fwd)
 }
 
 extern "C" int swv2_attn_bwd(const swv2_attn_args* a, void* stream) {
-    int Lp, DP;
+    swv2_attn_kernel_t sel;
     int rc = check_args(a, true);
-    if (!rc) rc = swv2_attn_geometry(a->L, a->head_dim, &Lp, &DP);
-    if (rc) return rc;
-    switch (attn_bwd_kernel_for(a->head_dim, Lp, DP, a->bias, a->dbg)) {
-        case AttnKernel::D256: return swv2_attn_bwd_d256(a, Lp, stream);
-        case AttnKernel::WIDE: return swv2_attn_bwd_wide(a, DP, stream);
+    if (!rc) rc = attn_select(a, true, &sel);
+    if (rc < 0) return rc;
+    switch ((AttnKernel)sel.family) {
+        case AttnKernel::D256: return swv2_attn_bwd_d256(a, sel.Lp, stream);
+        case AttnKernel::WIDE: return swv2_attn_bwd_wide(a, sel.DP, stream);
         case AttnKernel::STREAM: return swv2_attn_bwd_stream(a, stream);
         default: break;
     }

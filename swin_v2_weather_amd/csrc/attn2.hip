@@ -717,7 +717,7 @@ extern "C" int swv2_debug_fwd3_span(void* out) {
 // layout, 16- or 32-wide head slots, L >= 160.
 int swv2_attn_fwd3(const swv2_attn_args* a, void* stream) {
     hipStream_t st = (hipStream_t)stream;
-    if (a->L == 162) return launch_fwd3<11, 162, 4, 3>(a, st);          // measured best: 49 us at B = 2 (first generation: 72)
+    if (attn_lfix_other(a->L) == 162) return launch_fwd3<11, 162, 4, 3>(a, st);          // measured best: 49 us at B = 2 (first generation: 72)
     return launch_fwd3<11, 0, 4, 3>(a, st);
 }
 
@@ -726,7 +726,7 @@ int swv2_attn_fwd3(const swv2_attn_args* a, void* stream) {
 // workgroups (SIMDs loaded 4 / 4 / 2 / 2): 112; first generation: 203
 int swv2_attn_fwd3w(const swv2_attn_args* a, void* stream) {
     hipStream_t st = (hipStream_t)stream;
-    return a->L == 162 ? launch_fwd3w<11, 162, 4, 2, 2>(a, st) : launch_fwd3w<11, 0, 4, 2, 2>(a, st);
+    return attn_lfix_other(a->L) == 162 ? launch_fwd3w<11, 162, 4, 2, 2>(a, st) : launch_fwd3w<11, 0, 4, 2, 2>(a, st);
 }
 
 // with a CPB table in its packed form (swv2_attn_pack_bias): its forward part is the register image, its (max, min) part bounds the
@@ -735,5 +735,5 @@ int swv2_attn_fwd3b(const swv2_attn_args* a, void* stream) {
     hipStream_t st = (hipStream_t)stream;
     const uint32_t* bpack = (const uint32_t*)a->bias_pack;
     const float* brange = (const float*)((const char*)a->bias_pack + swv2_attn_bias_range_offset(a->heads, a->L));
-    return a->L == 162 ? launch_fwd3b<11, 162, 4, 3>(a, bpack, brange, st) : launch_fwd3b<11, 0, 4, 2>(a, bpack, brange, st);
+    return attn_lfix_other(a->L) == 162 ? launch_fwd3b<11, 162, 4, 3>(a, bpack, brange, st) : launch_fwd3b<11, 0, 4, 2>(a, bpack, brange, st);
 }

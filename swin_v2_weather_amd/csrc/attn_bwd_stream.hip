@@ -177,7 +177,7 @@ __global__ __launch_bounds__(1024) void attn_bwd_stream_kernel(
                 const float e1 = dl - bf2f(d0);
                 const uint16_t d1 = f2bf(e1), d2 = f2bf(e1 - bf2f(d1));
                 const uint32_t one_ = 0x3f80u, rqf = (row >= mask_thr) ? 0x3f80u : 0u;
-                aq = make_uint4(l0 | ((uint32_t)l1 << 16), l2 | (one_ << 16), rqf | ((one_ - rqf) << 16), 0);
+                aq = make_uint4(l0 | ((uint32_t)l1 << 16), l2 | (one_ << 16), rqf | ((one_ - rqf) << 16), rqf | ((one_ - rqf) << 16));
                 ad = make_uint4(d0 | ((uint32_t)d1 << 16), d2, 0, 0);
             }
             if (craw < CH) {
@@ -292,8 +292,11 @@ __global__ __launch_bounds__(1024) void attn_bwd_stream_kernel(
                 const uint32_t m1 = 0xbf80u;                                       // -1
                 const uint32_t padk = (key < Lc) ? 0u : (uint32_t)f2bf(-1.0e30f);
                 const bool kreg = key >= mask_thr;
-                const uint32_t mk0 = f2bf(kreg ? 0.f : cmask), mk1 = f2bf(kreg ? cmask : 0.f);
-                const uint4 augk = make_uint4(m1 | (m1 << 16), m1 | (padk << 16), mk0 | (mk1 << 16), 0);
+                // the mask term as hi + lo bf16 parts (k 20, 21 and k 22, 23; |error| <= 2^-17 |c|): one part alone is off by up to 2^-9 |c|,
+                // 0.28 in the log2 domain, which shows as soon as a masked key carries weight
+                const uint32_t chi = f2bf(cmask), clo = f2bf(cmask - bf2f((uint16_t)chi));
+                const uint32_t mk0 = kreg ? 0u : chi, mk1 = kreg ? chi : 0u, ml0 = kreg ? 0u : clo, ml1 = kreg ? clo : 0u;
+                const uint4 augk = make_uint4(m1 | (m1 << 16), m1 | (padk << 16), mk0 | (mk1 << 16), ml0 | (ml1 << 16));
                 const uint4 augv = make_uint4(m1 | (m1 << 16), m1, 0, 0);
                 const uint4 z = make_uint4(0, 0, 0, 0);
                 const uint4 rk = *(const uint4*)(Ks + key * DP + (g & 1) * 8), rv = *(const uint4*)(Vs + key * DP + (g & 1) * 8);
@@ -490,7 +493,7 @@ int swv2_attn_bwd_stream(const swv2_attn_args* a, void* stream) {
     const int nchunk = a->Bw < a->max_chunks ? a->Bw : a->max_chunks;
     dim3 grid(nchunk, a->heads), block(1024);
     const int nW = a->nwh * a->nww;
-    if (a->L == 162)
+    if (attn_lfix_other(a->L) == 162)
         hipLaunchKernelGGL((attn_bwd_stream_kernel<162>), grid, block, 0, st, (const uint16_t*)a->qkvh, a->logit_scale, (const uint16_t*)a->oh,
                            (const uint16_t*)a->doh, a->lse, a->rnorm, (uint16_t*)a->dqkvh, a->dlogit_scale, a->Bw, a->heads, a->L, nW, a->nww,
                            a->nwh, a->mask_thr);

@@ -46,4 +46,9 @@ __device__ __forceinline__ float score_pass(f32x4 (&acc)[LT], const uint32_t (&b
     return mx;
 }
 
+// Window area the families outside attn.hip (attn2.hip, attn_wide.hip, attn_d256.hip, attn_bwd_stream.hip) are specialised for: each has
+// one instantiation for the 162-token window of the reference configuration and a run-time-L one.  THE rule: their launchers and the
+// selection query (attn_select, attn.hip) both call it.
+inline int attn_lfix_other(int L) { return L == 162 ? 162 : 0; }
+
 }  // namespace

@@ -439,7 +439,7 @@ int swv2_attn_fwd_d256(const swv2_attn_args* a, int Lp, void* stream) {
 #define SWV2_LAUNCH_D256(LFIX)                                                                                                        \
     hipLaunchKernelGGL((attn_fwd_d256_kernel<LFIX>), d256_grid(a), dim3(D256_NT), 0, st, (const uint16_t*)a->qkvh, a->logit_scale, \
                        (uint16_t*)a->oh, a->lse, a->Bw, a->heads, a->L, nW, a->nww, a->nwh, a->mask_thr)
-    if (a->L == 162) SWV2_LAUNCH_D256(162); else SWV2_LAUNCH_D256(0);
+    if (attn_lfix_other(a->L) == 162) SWV2_LAUNCH_D256(162); else SWV2_LAUNCH_D256(0);
 #undef SWV2_LAUNCH_D256
     SWV2_CHECK_LAUNCH("swv2_attn_fwd");
     return SWV2_OK;
@@ -454,7 +454,7 @@ int swv2_attn_bwd_d256(const swv2_attn_args* a, int Lp, void* stream) {
     hipLaunchKernelGGL((attn_bwd_d256_kernel<LFIX>), d256_grid(a), dim3(D256_NT), 0, st, (const uint16_t*)a->qkvh, a->logit_scale,  \
                        (const uint16_t*)a->oh, (const uint16_t*)a->doh, a->lse, a->rnorm, (uint16_t*)a->dqkvh, a->dlogit_scale, a->Bw, \
                        a->heads, a->L, nW, a->nww, a->nwh, a->mask_thr)
-    if (a->L == 162) SWV2_LAUNCH_D256(162); else SWV2_LAUNCH_D256(0);
+    if (attn_lfix_other(a->L) == 162) SWV2_LAUNCH_D256(162); else SWV2_LAUNCH_D256(0);
 #undef SWV2_LAUNCH_D256
     SWV2_CHECK_LAUNCH("swv2_attn_bwd");
     return SWV2_OK;

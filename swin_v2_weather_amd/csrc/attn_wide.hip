@@ -427,8 +427,8 @@ int swv2_attn_bwd_wide(const swv2_attn_args* a, int DP, void* stream) {
     hipLaunchKernelGGL((attn_bwd_wide_kernel<11, 6, LFIX, DPL>), grid, block, 0, st, (const uint16_t*)a->qkvh, a->logit_scale,         \
                        (const uint16_t*)a->oh, (const uint16_t*)a->doh, a->lse, a->rnorm, (uint16_t*)a->dqkvh, a->dlogit_scale, a->Bw, \
                        a->heads, a->L, nW, a->nww, a->nwh, a->mask_thr)
-    if (DP == 96) { if (a->L == 162) SWV2_LAUNCH_WIDE(162, 96); else SWV2_LAUNCH_WIDE(0, 96); }
-    else { if (a->L == 162) SWV2_LAUNCH_WIDE(162, 128); else SWV2_LAUNCH_WIDE(0, 128); }
+    if (DP == 96) { if (attn_lfix_other(a->L) == 162) SWV2_LAUNCH_WIDE(162, 96); else SWV2_LAUNCH_WIDE(0, 96); }
+    else { if (attn_lfix_other(a->L) == 162) SWV2_LAUNCH_WIDE(162, 128); else SWV2_LAUNCH_WIDE(0, 128); }
 #undef SWV2_LAUNCH_WIDE
     SWV2_CHECK_LAUNCH("swv2_attn_bwd");
     return SWV2_OK;
@@ -444,8 +444,8 @@ int swv2_attn_fwd_wide(const swv2_attn_args* a, int DP, void* stream) {
 #define SWV2_LAUNCH_WIDE(LFIX, DPL)                                                                                                    \
     hipLaunchKernelGGL((attn_fwd_wide_kernel<11, 6, LFIX, DPL>), grid, block, 0, st, (const uint16_t*)a->qkvh, a->logit_scale,         \
                        (uint16_t*)a->oh, a->lse, a->Bw, a->heads, a->L, nW, a->nww, a->nwh, a->mask_thr)
-    if (DP == 96) { if (a->L == 162) SWV2_LAUNCH_WIDE(162, 96); else SWV2_LAUNCH_WIDE(0, 96); }
-    else { if (a->L == 162) SWV2_LAUNCH_WIDE(162, 128); else SWV2_LAUNCH_WIDE(0, 128); }
+    if (DP == 96) { if (attn_lfix_other(a->L) == 162) SWV2_LAUNCH_WIDE(162, 96); else SWV2_LAUNCH_WIDE(0, 96); }
+    else { if (attn_lfix_other(a->L) == 162) SWV2_LAUNCH_WIDE(162, 128); else SWV2_LAUNCH_WIDE(0, 128); }
 #undef SWV2_LAUNCH_WIDE
     SWV2_CHECK_LAUNCH("swv2_attn_fwd");
     return SWV2_OK;

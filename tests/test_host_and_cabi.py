@@ -62,7 +62,7 @@ def test_ctypes_structs_follow_the_header_field_order():
     pairs = {"swv2_attn_args": L.AttnArgs, "swv2_operand": L.Operand, "swv2_epilogue": L.Epilogue, "swv2_block_desc": L.BlockDesc,
              "swv2_mlp_args": L.MlpArgs, "swv2_mlp_bwd_args": L.MlpBwdArgs, "swv2_proj_ln_args": L.ProjLnArgs,
              "swv2_proj_ln_bwd_args": L.ProjLnBwdArgs, "swv2_ln_args": L.LnArgs,
-             "swv2_wgrad_item": L.WgradItem, "swv2_block_plan_t": L.BlockPlan}
+             "swv2_wgrad_item": L.WgradItem, "swv2_block_plan_t": L.BlockPlan, "swv2_attn_kernel_t": L.AttnKernelInfo}
     from swin_v2_weather_amd.utils.optim import _Item
     pairs["swv2_adam_item"] = _Item
     for cname, cls in pairs.items():
@@ -766,3 +766,95 @@ def test_host_halves_under_address_and_ub_sanitizers():
     r = subprocess.run([os.path.join(ROOT, "tools", "sanitize_host.sh")], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=1800)
     out = r.stdout.decode()
     assert r.returncode == 0 and " passed" in out and "ERROR: AddressSanitizer" not in out and "runtime error" not in out, out[-3000:]
+
+
+# ---- attention kernel selection (swv2_attn_fwd_kernel / swv2_attn_bwd_kernel) ---------------------------------------------------
+def _attn_query(Lw, d, bias=None, dbg=0, bwd=False):
+    """-> (return code, "FAMILY<LT,DK,LFIX>+variants") for a geometry; bias: None / "raw" / "packed" (presence only: nothing is read)"""
+    from tests import attn_reference as R
+    a = L.AttnArgs()
+    a.L, a.head_dim, a.dbg = Lw, d, dbg
+    a.bias = _FAKE if bias else None
+    a.bias_pack = _FAKE if bias == "packed" else None
+    info = L.AttnKernelInfo()
+    lib = L.load()
+    rc = (lib.swv2_attn_bwd_kernel if bwd else lib.swv2_attn_fwd_kernel)(ctypes.byref(a), ctypes.byref(info))
+    return rc, (R.kernel_name(info, L.ATTN_K_NAMES, bwd) if rc >= 0 else None), info
+
+
+def test_attention_kernel_selection_is_pinned_for_every_case_of_the_exact_tests():
+    """The answer of swv2_attn_fwd_kernel / swv2_attn_bwd_kernel -- the function swv2_attn_fwd / swv2_attn_bwd dispatch on -- for every
+    row of the case table of tests/test_attn_exact_gpu.py (tests/attn_reference.py::CASES), without a GPU; every first-generation
+    instantiation and every other family is reached by a row."""
+    from tests import attn_reference as R
+    lib = L.load()
+    seen_f, seen_b = set(), set()
+    for c in R.CASES:
+        rc, name, info = _attn_query(c.L, c.d, c.bias, c.fdbg)
+        assert rc == info.family and name == c.fwd, (R.case_id(c), name)
+        lp, dp = ctypes.c_int(), ctypes.c_int()
+        assert lib.swv2_attn_geometry(c.L, c.d, ctypes.byref(lp), ctypes.byref(dp)) == 0 and (info.Lp, info.DP) == (lp.value, dp.value)
+        assert (info.LT, info.DK) == (info.Lp // 16, info.DP // 16)
+        if c.fdbg == 0 and c.bias != "raw":         # swv2_attn_fwd_regime is the same answer (it speaks of a packed table)
+            assert lib.swv2_attn_fwd_regime(c.L, c.d, int(bool(c.bias)), 0) == info.regime
+        assert info.regime == int(name.startswith("FWD3"))
+        seen_f.add(name)
+        rc, name, info = _attn_query(c.L, c.d, c.bias, c.bdbg, bwd=True)
+        assert rc == info.family and name == c.bwd, (R.case_id(c), name)
+        seen_b.add(name)
+    rows = ["<11,1,162>", "<4,1,54>", "<4,1,0>", "<4,2,0>", "<11,1,0>", "<11,2,162>", "<11,2,0>", "<4,4,0>", "<4,6,0>", "<11,6,0>", "<4,8,0>",
+            "<11,4,0>", "<11,8,0>"]                  # SWV2_ATTN_ROWS of csrc/attn.hip
+    for r in rows:
+        assert "FIRST_GEN" + r in seen_f, r
+        assert any(n.startswith("FIRST_GEN" + r) for n in seen_b), r
+    # every first-generation instantiation, forward and backward, without a table, with a raw and with a packed one, at the smallest and the
+    # largest window area of its layout (the rows specialised for one area: that area)
+    for (LT, DK, LFIX) in R.FIRST_GEN_ROWS:
+        name = f"FIRST_GEN<{LT},{DK},{LFIX}>"
+        areas = {LFIX} if LFIX else ({9, 64} if LT == 4 else {65, 176})
+        for form in (None, "raw", "packed"):
+            for attr in ("fwd", "bwd"):
+                got = {c.L for c in R.CASES if c.bias == form and getattr(c, attr).split("+")[0] == name}
+                assert areas <= got, (name, form, attr, got)
+    assert sorted(f"<{a},{b},{c}>" for a, b, c in R.FIRST_GEN_ROWS) == sorted(rows)
+    for fam in ("FWD3<", "FWD3W<", "FWD3B<", "WIDE<", "D256<"):
+        assert any(n.startswith(fam) for n in seen_f), fam
+    for fam in ("STREAM<", "WIDE<", "D256<"):
+        assert any(n.startswith(fam) for n in seen_b), fam
+    for var in ("+aug", "+aug+biaslds", "+biaslds", "+qg"):
+        assert any(n.startswith("FIRST_GEN") and n.endswith(">" + var) for n in seen_b), var
+
+
+def test_attention_kernel_selection_switches_and_refusals():
+    q = lambda *a, **k: _attn_query(*a, **k)[1]          # noqa: E731
+    # each dbg switch, where it selects another kernel -- and where it does not apply
+    assert q(162, 16) == "FWD3<11,1,162>" and q(162, 16, dbg=L.ATTN_FIRST_GEN) == "FIRST_GEN<11,1,162>"
+    assert q(170, 24) == "FWD3W<11,2,0>" and q(170, 24, dbg=L.ATTN_FIRST_GEN) == "FIRST_GEN<11,2,0>"
+    assert q(162, 16, "packed") == "FWD3B<11,1,162>" and q(162, 16, "packed", dbg=L.ATTN_FIRST_GEN) == q(162, 16, "raw") == "FIRST_GEN<11,1,162>"
+    assert q(159, 16) == "FIRST_GEN<11,1,0>" and q(160, 16) == "FWD3<11,1,0>"          # attn2.hip's L >= 160 rule
+    assert q(162, 96) == "WIDE<11,6,162>" and q(162, 96, dbg=L.ATTN_FIRST_GEN) == "FIRST_GEN<11,6,0>" and q(162, 96, "raw") == "FIRST_GEN<11,6,0>"
+    assert q(162, 100) == "FIRST_GEN<11,8,0>" and q(64, 96) == "FIRST_GEN<4,6,0>" and q(65, 96) == "WIDE<11,6,0>"
+    assert q(162, 256) == q(162, 256, dbg=L.ATTN_FIRST_GEN) == "D256<11,16,162>"
+    assert q(162, 16, bwd=True) == "STREAM<11,1,162>+aug"
+    assert q(162, 16, dbg=L.ATTN_BWD_TWO_PHASE, bwd=True) == "FIRST_GEN<11,1,162>+aug"
+    assert q(162, 16, dbg=L.ATTN_PLAIN_STATS, bwd=True) == "FIRST_GEN<11,1,162>"
+    assert q(162, 16, dbg=L.ATTN_FIRST_GEN, bwd=True) == "STREAM<11,1,162>+aug"            # (a forward switch)
+    assert q(54, 16, dbg=L.ATTN_BWD_TWO_PHASE, bwd=True) == q(54, 16, bwd=True) == "FIRST_GEN<4,1,54>+aug"
+    assert q(54, 24, bwd=True) == "FIRST_GEN<4,2,0>+aug" and q(54, 24, dbg=L.ATTN_PLAIN_STATS, bwd=True) == "FIRST_GEN<4,2,0>"
+    assert q(162, 16, "packed", bwd=True) == "FIRST_GEN<11,1,162>+aug+biaslds"
+    assert q(162, 16, "packed", dbg=L.ATTN_PLAIN_STATS, bwd=True) == "FIRST_GEN<11,1,162>+biaslds"
+    assert q(170, 16, "packed", bwd=True) == "FIRST_GEN<11,1,0>+biaslds"                   # operand statistics with a table need a fixed L
+    assert q(162, 96, bwd=True) == "WIDE<11,6,162>" and q(162, 96, dbg=L.ATTN_FIRST_GEN, bwd=True) == "FIRST_GEN<11,6,0>+qg"
+    assert q(162, 64, bwd=True) == "FIRST_GEN<11,4,0>" and q(162, 128, bwd=True) == "FIRST_GEN<11,8,0>+qg"
+    assert q(162, 256, dbg=L.ATTN_PLAIN_STATS | L.ATTN_BWD_TWO_PHASE, bwd=True) == "D256<11,16,162>"
+    # refused geometries: negative return, a message, nothing launched (there is no GPU here)
+    lib = L.load()
+    for bwd in (False, True):
+        for (Lw, d, bias) in ((162, 132, None), (162, 192, None), (162, 252, None), (162, 256, "raw"), (162, 256, "packed"), (64, 256, None),
+                              (9, 256, None), (177, 16, None), (400, 16, None), (162, 18, None)):
+            rc, name, _ = _attn_query(Lw, d, bias, bwd=bwd)
+            assert rc < 0 and name is None and lib.swv2_last_error(), (Lw, d, bias, bwd)
+    assert lib.swv2_attn_fwd_kernel(None, None) == -1
+    a = L.AttnArgs()
+    a.L, a.head_dim = 162, 16
+    assert lib.swv2_attn_fwd_kernel(ctypes.byref(a), None) == L.ATTN_K_FWD3           # `out` is optional
