@@ -500,7 +500,20 @@ int swv2_proj_ln_bwd(const swv2_proj_ln_bwd_args* a, void* stream);
  * :381-386) in one kernel; the [M][hidden] activation stays in registers.  Saves for the backward: hpre = bf16(fc1(x)),
  * a2 = bf16(fc2 output), mean / rstd of the LayerNorm.  Same results as swv2_linear(EPI_BF16_GELU) + swv2_linear +
  * swv2_ln_residual_fwd (identical rounding points).  C in {32,64,96,128,192,256}, hidden % 32 == 0,
- * hidden <= 2048 (swv2_mlp_supported); other shapes return SWV2_ERR_UNSUPPORTED -- use the unfused sequence. */
+ * hidden <= 2048 (swv2_mlp_supported); other shapes return SWV2_ERR_UNSUPPORTED -- use the unfused sequence.
+ * Contracts (pinned element by element by tests/test_mlp_exact_gpu.py; they hold for swv2_mlp_bwd as well):
+ *   - nothing outside rows 0 .. M-1 of an output is written, whatever M is (1 included): a row tile's rows past M are computed as
+ *     copies of row M-1 and stored to row M-1 again (same values), and count once in dgamma / dbeta;
+ *   - rows_per_sample is any positive number: it need not divide M, a row tile or a workgroup's rows;
+ *   - a refused call (non-zero return: unsupported C / hidden, M <= 0, rows_per_sample <= 0, a missing pointer) writes nothing;
+ *   - GELU and GELU' are taken of the STORED bf16 pre-activation.  For 2^-14 <= |x| < 16 they come from a table each workgroup
+ *     fills with the fp32 formulas (the backward at C = 192 holds the positive half and uses GELU'(-x) = 1 - GELU'(x); at C = 256
+ *     it evaluates the formula); +-0, |x| < 2^-14, |x| >= 16 and non-finite arguments take the formula, together with the other
+ *     values of their 16-row x 16-hidden-unit tile.  Either way the activation fed to fc2 is bit for bit the bf16(GELU) that
+ *     SWV2_OP_BF16_GELU / SWV2_EPI_BF16_GELU produce for the same stored value;
+ *   - results are deterministic: a second call gives the same bits in every output, dgamma / dbeta and ws included;
+ *   - the mode that keeps no pre-activation (hpre == NULL here, recompute mode in swv2_mlp_bwd) gives bit for bit the outputs of
+ *     the mode that keeps it. */
 typedef struct {
     const float* x;        /* [M][C] fp32 rows: GEMM input and residual */
     const void* w1;        /* bf16 [hidden][C]  (swv2_prep_weight) */
@@ -510,7 +523,7 @@ typedef struct {
     const float* gamma;    /* LayerNorm weight / bias [C] */
     const float* beta;
     const float* scale;    /* per-sample drop-path factor [M / rows_per_sample] or NULL */
-    void* hpre;            /* out bf16 [M][hidden] */
+    void* hpre;            /* out bf16 [M][hidden], or NULL: not kept (the backward then runs in recompute mode) */
     void* a2;              /* out bf16 [M][C] */
     float* mean;           /* out [M] */
     float* rstd;

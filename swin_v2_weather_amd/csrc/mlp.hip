@@ -331,8 +331,9 @@ void launch_mlp_fwd(const MlpFwd& k, hipStream_t st) {
 // The same chained-MFMA skeleton as the forward: da2 fragments and the dx^T accumulators stay in registers, the
 // weights stream through LDS in chunks of 32 hidden units, dH is written once (bf16, for the fc1 weight gradient) and
 // never re-read here.  Replaces LN backward + two GEMM launches (693 MB -> 462 MB at the benchmark shape).
-// d gamma / d beta: per-lane column sums -> DPP reduction over the 16 rows of a tile -> LDS over the 4 waves -> one
-// partial row per workgroup in `ws`, folded by swv2_launch_ln_partials_reduce.
+// d gamma / d beta: a thread keeps 4 columns and sums its rows of every row pass by fma -> the row groups' sums through LDS, added
+// in order -> one partial row per workgroup in `ws`, folded by swv2_launch_ln_partials_reduce (the rounding count of this order
+// is C_FOLD_MLP in tests/mlp_reference.py).
 // ------------------------------------------------------------------------------------------------------------------
 struct MlpBwd {
     const float* dy; const uint16_t* a2; const float* mean; const float* rstd; const float* gamma; const float* scale;

@@ -446,17 +446,18 @@ def adam_step(p, g, m, v, lr, beta1, beta2, eps, step, grad_inv_scale=1.0):
                                     _stream()), "swv2_adam_step")
 
 
-def mlp_fwd(x, w1, b1, w2, b2, gamma, beta, scale, rows_per_sample, eps=1e-5, keep_hpre=True):
+def mlp_fwd(x, w1, b1, w2, b2, gamma, beta, scale, rows_per_sample, eps=1e-5, keep_hpre=True, out=None):
     """Fused fc1 -> GELU -> fc2 -> LayerNorm -> drop-path -> +x.  Returns (y, hpre, a2, mean, rstd); keep_hpre=False: the
-    pre-activation is not written (hpre = None; the backward's recompute mode rebuilds it from x)."""
+    pre-activation is not written (hpre = None; the backward's recompute mode rebuilds it from x).  out = (y, hpre, a2, mean, rstd)
+    hands in the caller's own tensors (hpre = None there selects the mode that keeps none, whatever keep_hpre says)."""
     M, Cc = x.shape
     hid = w1.shape[0]
     _chk(x, torch.float32, "mlp x"); _chk(w1, BF16, "mlp w1"); _chk(w2, BF16, "mlp w2")
     dev = x.device
-    y = torch.empty(M, Cc, dtype=torch.float32, device=dev)
-    hpre = torch.empty(M, hid, dtype=BF16, device=dev) if keep_hpre else None
-    a2 = torch.empty(M, Cc, dtype=BF16, device=dev)
-    mean, rstd = torch.empty(M, device=dev), torch.empty(M, device=dev)
+    if out is None:
+        out = (torch.empty(M, Cc, dtype=torch.float32, device=dev), torch.empty(M, hid, dtype=BF16, device=dev) if keep_hpre else None,
+               torch.empty(M, Cc, dtype=BF16, device=dev), torch.empty(M, device=dev), torch.empty(M, device=dev))
+    y, hpre, a2, mean, rstd = out
     a = L.MlpArgs()
     a.x, a.w1, a.b1, a.w2, a.b2, a.gamma, a.beta, a.scale = (_p(t) for t in (x, w1, b1, w2, b2, gamma, beta, scale))
     a.hpre, a.a2, a.mean, a.rstd, a.y = (_p(t) for t in (hpre, a2, mean, rstd, y))
@@ -465,16 +466,19 @@ def mlp_fwd(x, w1, b1, w2, b2, gamma, beta, scale, rows_per_sample, eps=1e-5, ke
     return y, hpre, a2, mean, rstd
 
 
-def mlp_bwd(dy, a2, mean, rstd, gamma, scale, hpre, w2t, w1t, dgamma, dbeta, rows_per_sample, x=None, w1=None, b1=None):
+def mlp_bwd(dy, a2, mean, rstd, gamma, scale, hpre, w2t, w1t, dgamma, dbeta, rows_per_sample, x=None, w1=None, b1=None, out=None, ws=None):
     """Fused LN backward -> dh = (da2 W2) * GELU'(hpre) -> dx = dy + dh W1.  Returns (dx, da2, dh); dgamma/dbeta accumulated.
-    hpre=None: recompute mode -- the pre-activation is rebuilt from the forward's input x, fc1.weight w1 (bf16 [hid, C]), b1."""
+    hpre=None: recompute mode -- the pre-activation is rebuilt from the forward's input x, fc1.weight w1 (bf16 [hid, C]), b1.
+    out = (dx, da2, dh) and ws (fp32, swv2_mlp_bwd_ws_floats(M, C) floats) hand in the caller's own tensors."""
     M, Cc = dy.shape
     hid = w2t.shape[0]
     dev = dy.device
-    da2 = torch.empty(M, Cc, dtype=BF16, device=dev)
-    dh = torch.empty(M, hid, dtype=BF16, device=dev)
-    dx = torch.empty(M, Cc, dtype=torch.float32, device=dev)
-    ws = torch.empty(L.load().swv2_mlp_bwd_ws_floats(M, Cc), dtype=torch.float32, device=dev)
+    if out is None:
+        out = (torch.empty(M, Cc, dtype=torch.float32, device=dev), torch.empty(M, Cc, dtype=BF16, device=dev),
+               torch.empty(M, hid, dtype=BF16, device=dev))
+    if ws is None:
+        ws = torch.empty(L.load().swv2_mlp_bwd_ws_floats(M, Cc), dtype=torch.float32, device=dev)
+    dx, da2, dh = out
     a = L.MlpBwdArgs()
     a.dy, a.a2, a.mean, a.rstd, a.gamma, a.scale, a.hpre, a.w2t, a.w1t = (_p(t) for t in (dy, a2, mean, rstd, gamma, scale, hpre, w2t, w1t))
     a.da2, a.dh, a.dx, a.dgamma, a.dbeta, a.ws = (_p(t) for t in (da2, dh, dx, dgamma, dbeta, ws))

@@ -266,14 +266,16 @@ def within(got, ref, bound):
     return int(bad.sum()), float(ratio.reshape(-1)[flat]), idx
 
 
-def assert_within(name, got, ref, bound, what="", rnd=None):
+def assert_within(name, got, ref, bound, what="", rnd=None, worst=None):
     """asserts |got - ref| <= bound on every element; -> worst |err| / bound.  rnd: the share of `bound` that is the bf16 rounding of
-    the result itself; the worst of (|err| - rnd) / (bound - rnd) is then filed in WORST under name + ' beyond rounding'"""
+    the result itself; the worst of (|err| - rnd) / (bound - rnd) is then filed in WORST (or the table `worst`) under name + ' beyond
+    rounding'"""
+    worst = WORST if worst is None else worst
     nbad, ratio, idx = within(got, ref, bound)
-    WORST[name] = max(WORST.get(name, 0.0), ratio if math.isfinite(ratio) and nbad == 0 else WORST.get(name, 0.0))
+    worst[name] = max(worst.get(name, 0.0), ratio if math.isfinite(ratio) and nbad == 0 else worst.get(name, 0.0))
     if rnd is not None and nbad == 0:
         ex = (((got.double() - ref).abs() - rnd).clamp_min(0) / (bound - rnd).clamp_min(1e-300)).max()
-        WORST[name + " beyond rounding"] = max(WORST.get(name + " beyond rounding", 0.0), float(ex))
+        worst[name + " beyond rounding"] = max(worst.get(name + " beyond rounding", 0.0), float(ex))
     assert nbad == 0, (f"{name} {what}: {nbad} elements out of bound, worst |err| / bound {ratio:.3g} at {idx}: got {float(got[idx]):.9g}, "
                        f"ref {float(ref[idx]):.9g}, bound {float(bound[idx]):.3g}")
     return ratio

@@ -38,6 +38,8 @@ import math
 import pytest
 import torch
 
+from tests.mlp_reference import bf16_bits_all, gelu64, library_gelu_lut, lut_of
+
 pytestmark = pytest.mark.gpu
 
 BF = torch.bfloat16
@@ -99,43 +101,11 @@ def K():
     return dict(L=L, ops=ops)
 
 
-def gelu64(x):
-    """erf-GELU in fp64, through erfc so that the negative tail keeps its digits"""
-    x = x.double()
-    return 0.5 * x * torch.special.erfc(-x / math.sqrt(2.0))
-
-
-def bf16_bits_all(device):
-    return torch.arange(65536, dtype=torch.int32, device=device).to(torch.int16).view(BF)
-
-
 @pytest.fixture(scope="module")
 def gelu_lut(dev, K):
-    """the library's own bf16(GELU(x)) for all 65 536 bf16 patterns x, as fp32 [65536] indexed by the pattern: the identity
-    product  linear(op_bf16(x, gelu=True), I, EPI_F32)  returns the GELU operand exactly (one non-zero term per output).
-    Non-finite inputs get a row of their own with zeros elsewhere (0 * inf is NaN in the other columns)."""
-    L, ops = K["L"], K["ops"]
-    pats = bf16_bits_all(dev)
-    bits = torch.arange(65536, device=dev)
-    finite = torch.isfinite(pats.float())
-    fin_bits, inf_bits = bits[finite], bits[~finite]
-    assert fin_bits.numel() == 65280 and inf_bits.numel() == 256
-    W = 256
-    x = torch.zeros(255 + 256, W, dtype=BF, device=dev)
-    x[:255] = pats[fin_bits].view(255, W)
-    rows = torch.arange(256, device=dev)
-    x[255 + rows, rows] = pats[inf_bits]                        # one non-finite input per row, in column (its index)
-    out = torch.empty(x.shape[0], W, dtype=torch.float32, device=dev)
-    ops.linear(ops.op_bf16(x, gelu=True), torch.eye(W, dtype=BF, device=dev), ops.epilogue(L.EPI_F32, out, ld=W), W)
-    torch.cuda.synchronize()
-    lut = torch.empty(65536, dtype=torch.float32, device=dev)
-    lut[fin_bits] = out[:255].reshape(-1)
-    lut[inf_bits] = out[255 + rows, rows]
-    return lut
-
-
-def lut_of(lut, pre_bf16):
-    return lut[pre_bf16.contiguous().view(torch.int16).long() & 0xFFFF]
+    """the library's own bf16(GELU(x)) for all 65 536 bf16 patterns x, as fp32 [65536] indexed by the pattern (shared with the fused
+    MLP's tests: tests/mlp_reference.py)"""
+    return library_gelu_lut(K["ops"], K["L"], dev)
 
 
 # ---------------------------------------------------------------------------------------------------------------
