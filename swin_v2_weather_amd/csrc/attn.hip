@@ -112,7 +112,7 @@ __global__ __launch_bounds__(64 * LT) void attn_fwd_kernel(
     const int hd = blockIdx.y;
     const int q = 16 * qt + fr;              // this lane's query (token index in the window)
 
-    const float sc2 = __expf(fminf(logit_scale[hd], SWV2_LN100)) * SWV2_LOG2E;
+    const float sc2 = clamped_logit_scale(logit_scale[hd]) * SWV2_LOG2E;
 
     // CPB bias rows of this (head, q-tile), log2 domain, -1e30 on padded keys; bf16 like the backward's LDS image
     // (identical P in both passes), held as packed pairs: 2 x LT registers
@@ -197,7 +197,7 @@ __global__ __launch_bounds__(64 * LT) void attn_fwd_kernel(
             }
         }
 
-        const bool do_mask = (mask_thr > 0) && (((bw % nW) / nww) == nwh - 1);
+        const bool do_mask = (mask_thr > 0) && last_window_row(bw, nW, nww, nwh);
         float mx, sum = 0.f;
         if (!HAS_BIAS && !do_mask) {
             // no bias, no mask: sigma > 0 commutes with the maximum, so the row maximum is taken over the raw cosines and
@@ -279,15 +279,9 @@ __global__ __launch_bounds__(64 * LT) void attn_fwd_kernel(
 #ifdef SWV2_ATTN1_STAMPS          // diagnostic build (tools/probe_attn1_stamps.py): per-phase s_memtime sums of every wave 0
 __device__ unsigned long long attn1_stamps[512 * 8];
 __device__ unsigned long long attn1_win[64 * 128];        // wave 8 of the first 64 workgroups of head 0: s_memtime at the end of every window
-#define GSTAMP_DECL unsigned long long st_prev = 0, st_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-#define GSTAMP_START() do { asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(st_prev) : : "memory"); } while (0)
-#define GSTAMP(k) do { unsigned long long t_; asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_) : : "memory"); \
-                       st_acc[k] += t_ - st_prev; st_prev = t_; } while (0)
-#else
-#define GSTAMP_DECL
-#define GSTAMP_START() do {} while (0)
-#define GSTAMP(k) do {} while (0)
+#define SWV2_STAMPS
 #endif
+#include "stamps.h"
 // ------------------------------------------------------------------------------------------------
 // backward
 // ------------------------------------------------------------------------------------------------
@@ -404,7 +398,7 @@ __global__ __launch_bounds__(64 * LT) void attn_bwd_kernel(
     };
 
     const float tau = logit_scale[hd];
-    const float sigma = __expf(fminf(tau, SWV2_LN100));
+    const float sigma = clamped_logit_scale(tau);
     const float sc2 = sigma * SWV2_LOG2E;
     const float inv_sc2 = 1.f / sc2;
     (void)inv_sc2;
@@ -489,40 +483,22 @@ __global__ __launch_bounds__(64 * LT) void attn_bwd_kernel(
                 *(uint4*)(Vs + c * 8) = sv[j];
             }
             // delta partial over this chunk's 8 channels, reduced over the CPR chunks of the row (adjacent lanes)
-            float dl = 0.f;
-            if (c < CH) {
-                const uint32_t a[4] = {sdo[j].x, sdo[j].y, sdo[j].z, sdo[j].w}, b[4] = {so[j].x, so[j].y, so[j].z, so[j].w};
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    dl = fmaf(__uint_as_float(a[e] << 16), __uint_as_float(b[e] << 16), dl);
-                    dl = fmaf(__uint_as_float(a[e] & 0xffff0000u), __uint_as_float(b[e] & 0xffff0000u), dl);
-                }
-            }
+            float dl = c < CH ? delta_partial(sdo[j], so[j]) : 0.f;
             if constexpr (CPR_P2) {
                 dl = group_allsum<CPR>(dl);             // (vector ALU only: common.h)
             } else {
                 if (c < CH) DLp[c] = dl;            // summed per row by finish_delta() behind the barrier (a row's chunks straddle lane groups)
             }
             if constexpr (AUG) {
-                // slots 16..23 of the row (the even chunk's thread): A-operand side of the statistics -- lse / (sigma log2 e) in three
-                // bf16 parts, a constant 1 (padded-key flag), the query's mask-region flags -- and delta in three parts for the dO
-                // slab; slots 24..31 (the odd chunk's thread): zeros.  The B-operand side (-1, -1, -1, flags) is built per wave.
+                // slots 16..23 of the row (the even chunk's thread): the A-operand side of the statistics; slots 24..31 (the odd chunk's
+                // thread): zeros.  The B-operand side (-1, -1, -1, flags) is built per wave.
                 if (c < CH) {
                     const int row = c / CPR;
                     uint4 aq = make_uint4(0, 0, 0, 0), ad = make_uint4(0, 0, 0, 0);
                     if ((c % CPR) == 0) {
-                        const bool q_ok = row < L;
-                        const float lq = q_ok ? slse_row * inv_sc2 : 1.0e30f;            // padded query rows: P = 0
-                        uint16_t l0 = f2bf(lq);
-                        const float r1 = lq - bf2f(l0);
-                        uint16_t l1 = f2bf(r1), l2 = f2bf(r1 - bf2f(l1));
-                        if (!q_ok) l1 = l2 = 0;
-                        const uint16_t d0 = f2bf(dl);
-                        const float e1 = dl - bf2f(d0);
-                        const uint16_t d1 = f2bf(e1), d2 = f2bf(e1 - bf2f(d1));
-                        const uint32_t one = 0x3f80u, rqf = (row >= mask_thr) ? 0x3f80u : 0u;
-                        aq = make_uint4(l0 | ((uint32_t)l1 << 16), l2 | (one << 16), rqf | ((one - rqf) << 16), rqf | ((one - rqf) << 16));
-                        ad = make_uint4(d0 | ((uint32_t)d1 << 16), d2, 0, 0);
+                        const u32x8 s = aug_query_row(row, L, mask_thr, slse_row * inv_sc2, dl);
+                        aq = make_uint4(s[0], s[1], s[2], s[3]);
+                        ad = make_uint4(s[4], s[5], s[6], s[7]);
                     }
                     if (DK == 1 || (c % CPR) == 0) {          // (DK = 1: the odd chunk's thread writes the zero slots 24 .. 31)
                         *(uint4*)((uint16_t*)(lds + OFF_Q) + row * QP + QSTAT + (DK == 1 ? (c & 1) * 8 : 0)) = aq;
@@ -555,8 +531,8 @@ __global__ __launch_bounds__(64 * LT) void attn_bwd_kernel(
     finish_delta();
 
     const int Lc = LFIX > 0 ? LFIX : L;
-    GSTAMP_DECL
-    GSTAMP_START();
+    STAMP_DECL(8)
+    STAMP_START();
 #ifdef SWV2_ATTN1_STAMPS
     const unsigned long long st_first = st_prev;
 #endif
@@ -566,7 +542,7 @@ __global__ __launch_bounds__(64 * LT) void attn_bwd_kernel(
         if (bw_next < Bw) issue(bw_next);
         if (QG) { Qs = qkvh + slab0; dOs = doh + ((size_t)bw * h + hd) * SLAB; }
 
-        GSTAMP(0);                      // prefetch issue of the next window
+        STAMP(0);                      // prefetch issue of the next window
         // ================= phase 1: wave = key tile(s) =================
         bf16x4 kf[TPW][DK], vf[TPW][DK];
         f32x4 dk[TPW][DK], dv[TPW][DK];
@@ -581,7 +557,7 @@ __global__ __launch_bounds__(64 * LT) void attn_bwd_kernel(
                 dv[i][kk] = (f32x4){0.f, 0.f, 0.f, 0.f};
             }
         }
-        const bool do_mask = (mask_thr > 0) && (((bw % nW) / nww) == nwh - 1);
+        const bool do_mask = (mask_thr > 0) && last_window_row(bw, nW, nww, nwh);
         // one q-tile step; `br` / `dbrow`: this lane's bias row / bias-gradient row of the tile
         // MASKED / PADT (shift-mask window / a key tile with padded keys) are wave-uniform and loop-invariant: separate
         // instantiations, so the common case carries no per-element selects
@@ -650,19 +626,11 @@ __global__ __launch_bounds__(64 * LT) void attn_bwd_kernel(
             const float cmask = do_mask ? fmaxf(-100.f * SWV2_LOG2E * inv_sc2, -1.0e30f) : 0.f;
             bf16x8 kf8, vf8;
             {
-                const uint32_t m1 = 0xbf80u;                                       // -1
-                const uint32_t padk = (key < Lc) ? 0u : (uint32_t)f2bf(-1.0e30f);
-                const bool kreg = key >= mask_thr;
-                // the mask term as hi + lo bf16 parts (k 20, 21 and k 22, 23; |error| <= 2^-17 |c|): one part alone is off by up to 2^-9 |c|,
-                // 0.28 in the log2 domain, which shows as soon as a masked key carries weight
-                const uint32_t chi = f2bf(cmask), clo = f2bf(cmask - bf2f((uint16_t)chi));
-                const uint32_t mk0 = kreg ? 0u : chi, mk1 = kreg ? chi : 0u, ml0 = kreg ? 0u : clo, ml1 = kreg ? clo : 0u;
-                const uint4 augk = make_uint4(m1 | (m1 << 16), m1 | (padk << 16), mk0 | (mk1 << 16), ml0 | (ml1 << 16));
-                const uint4 augv = make_uint4(m1 | (m1 << 16), m1, 0, 0);
+                const AugKey aug = aug_key_operands(key, Lc, mask_thr, cmask);
                 const uint4 z = make_uint4(0, 0, 0, 0);
                 const uint4 rk = *(const uint4*)(Ks + key * DP + (g & 1) * 8), rv = *(const uint4*)(Vs + key * DP + (g & 1) * 8);
-                kf8 = __builtin_bit_cast(bf16x8, g < 2 ? rk : (g == 2 ? augk : z));
-                vf8 = __builtin_bit_cast(bf16x8, g < 2 ? rv : (g == 2 ? augv : z));
+                kf8 = __builtin_bit_cast(bf16x8, g < 2 ? rk : (g == 2 ? aug.k : z));
+                vf8 = __builtin_bit_cast(bf16x8, g < 2 ? rv : (g == 2 ? aug.v : z));
             }
             const uint16_t* const Qa = (const uint16_t*)(lds + OFF_Q);
             const uint16_t* const Da = (const uint16_t*)(lds + OFF_DO);
@@ -746,25 +714,17 @@ __global__ __launch_bounds__(64 * LT) void attn_bwd_kernel(
             bf16x8 kf8, vf8;
             [[maybe_unused]] bf16x8 kx8, vx8;                                      // DK = 2: key side of the statistics product
             {
-                const uint32_t m1 = 0xbf80u;                                       // -1
-                const uint32_t padk = (key < Lc) ? 0u : (uint32_t)f2bf(-1.0e30f);
-                const bool kreg = key >= mask_thr;
-                // the mask term as hi + lo bf16 parts (k 20, 21 and k 22, 23; |error| <= 2^-17 |c|): one part alone is off by up to 2^-9 |c|,
-                // 0.28 in the log2 domain, which shows as soon as a masked key carries weight
-                const uint32_t chi = f2bf(cmask), clo = f2bf(cmask - bf2f((uint16_t)chi));
-                const uint32_t mk0 = kreg ? 0u : chi, mk1 = kreg ? chi : 0u, ml0 = kreg ? 0u : clo, ml1 = kreg ? clo : 0u;
-                const uint4 augk = make_uint4(m1 | (m1 << 16), m1 | (padk << 16), mk0 | (mk1 << 16), ml0 | (ml1 << 16));
-                const uint4 augv = make_uint4(m1 | (m1 << 16), m1, 0, 0);
+                const AugKey aug = aug_key_operands(key, Lc, mask_thr, cmask);
                 const uint4 z = make_uint4(0, 0, 0, 0);
                 if constexpr (DK == 1) {
                     const uint4 rk = *(const uint4*)(Ks + key * DP + (g & 1) * 8), rv = *(const uint4*)(Vs + key * DP + (g & 1) * 8);
-                    kf8 = __builtin_bit_cast(bf16x8, g < 2 ? rk : (g == 2 ? augk : z));
-                    vf8 = __builtin_bit_cast(bf16x8, g < 2 ? rv : (g == 2 ? augv : z));
+                    kf8 = __builtin_bit_cast(bf16x8, g < 2 ? rk : (g == 2 ? aug.k : z));
+                    vf8 = __builtin_bit_cast(bf16x8, g < 2 ? rv : (g == 2 ? aug.v : z));
                 } else {
                     kf8 = *(const bf16x8*)(Ks + key * DP + 8 * g);
                     vf8 = *(const bf16x8*)(Vs + key * DP + 8 * g);
-                    kx8 = __builtin_bit_cast(bf16x8, g == 0 ? augk : z);
-                    vx8 = __builtin_bit_cast(bf16x8, g == 0 ? augv : z);
+                    kx8 = __builtin_bit_cast(bf16x8, g == 0 ? aug.k : z);
+                    vx8 = __builtin_bit_cast(bf16x8, g == 0 ? aug.v : z);
                 }
             }
             const uint16_t* const Qa = (const uint16_t*)(lds + OFF_Q);
@@ -940,7 +900,7 @@ __global__ __launch_bounds__(64 * LT) void attn_bwd_kernel(
             else if (pad_wave) run(std::false_type{}, std::true_type{});
             else run(std::false_type{}, std::false_type{});
         }
-        GSTAMP(1);                      // phase 1 loop
+        STAMP(1);                      // phase 1 loop
         // ---- dK (through the L2-normalisation) and dV of this wave's key tile(s)
 #pragma unroll
         for (int i = 0; i < TPW; ++i) {
@@ -966,9 +926,9 @@ __global__ __launch_bounds__(64 * LT) void attn_bwd_kernel(
                 *(bf16x4*)(dqkvh + slab0 + 2 * SLAB + (size_t)key * DP + 16 * dt + 4 * g) = f2bf4(dv[i][dt]);
             }
         }
-        GSTAMP(2);                      // dK / dV normalisation backward + stores
+        STAMP(2);                      // dK / dV normalisation backward + stores
         __syncthreads();
-        GSTAMP(3);                      // barrier 1
+        STAMP(3);                      // barrier 1
 
         // ================= phase 2: wave = query tile(s) =================
         {
@@ -1037,14 +997,14 @@ __global__ __launch_bounds__(64 * LT) void attn_bwd_kernel(
                 }
             }
         }
-        GSTAMP(4);                      // phase 2: dQ + normalisation backward + stores
+        STAMP(4);                      // phase 2: dQ + normalisation backward + stores
         __syncthreads();
-        GSTAMP(5);                      // barrier 2
+        STAMP(5);                      // barrier 2
         if (bw_next < Bw) commit();
-        GSTAMP(6);                      // commit (wait for the prefetch + LDS writes + delta)
+        STAMP(6);                      // commit (wait for the prefetch + LDS writes + delta)
         __syncthreads();
         if (bw_next < Bw) finish_delta();
-        GSTAMP(7);                      // barrier 3
+        STAMP(7);                      // barrier 3
 #ifdef SWV2_ATTN1_STAMPS
         if (lane == 0 && tw == 8 && blockIdx.y == 0 && blockIdx.x < 64) {
             const int it_ = (bw - (int)blockIdx.x) / (int)gridDim.x;

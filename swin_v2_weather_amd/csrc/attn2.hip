@@ -27,15 +27,9 @@ typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 __device__ unsigned long long fwd3_span[2048 * 2];
 #endif
 #ifdef SWV2_ATTN_STAMPS
-#define STAMP_DECL unsigned long long st_prev = 0, st_acc[7] = {0, 0, 0, 0, 0, 0, 0};
-#define STAMP_START() do { asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(st_prev) : : "memory"); } while (0)
-#define STAMP(k, dep) do { unsigned long long t_; asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_) : "v"(dep) : "memory"); \
-                           st_acc[k] += t_ - st_prev; st_prev = t_; } while (0)
-#else
-#define STAMP_DECL
-#define STAMP_START() do {} while (0)
-#define STAMP(k, dep) do {} while (0)
+#define SWV2_STAMPS
 #endif
+#include "stamps.h"
 
 // ------------------------------------------------------------------------------------------------
 // forward, third form (head_dim <= 16, no CPB bias): the softmax's per-element vector work is cut from
@@ -75,7 +69,7 @@ __global__ __launch_bounds__(64 * WAVES, OCC) void attn_fwd3_kernel(
     const bool last_chunk_ok = (wave * 64 + (CPT - 1) * NT) < CH;          // wave-uniform
     const int Lc = LFIX > 0 ? LFIX : L;
 
-    const float sc2 = __expf(fminf(logit_scale[hd], SWV2_LN100)) * SWV2_LOG2E;
+    const float sc2 = clamped_logit_scale(logit_scale[hd]) * SWV2_LOG2E;
     const bool bounded = sc2 <= 40.f;
 
     u32x4 stage[CPT], stageq[QPT];
@@ -118,7 +112,7 @@ __global__ __launch_bounds__(64 * WAVES, OCC) void attn_fwd3_kernel(
     int bw = blockIdx.x;
     if (bw >= Bw) return;
     const int bw_first = bw;
-    STAMP_DECL
+    STAMP_DECL(7)
     issue_loads(bw);
     write_stage(0);
     __syncthreads();
@@ -146,7 +140,7 @@ __global__ __launch_bounds__(64 * WAVES, OCC) void attn_fwd3_kernel(
         // its first row, and it is the CU's other two workgroups that cover the latency.  Peeling the last row removes the flush and measured
         // slower, 9 843 against 9 310 cycles per item: LABNOTES round 6.)
         if (bw_next < Bw) issue_loads(bw_next);      // consumed by write_stage at the top of the wave's last row
-        const bool do_mask = (mask_thr > 0) && (((bw % nW) / nww) == nwh - 1);
+        const bool do_mask = (mask_thr > 0) && last_window_row(bw, nW, nww, nwh);
         const bool fixed = bounded && !do_mask;                       // wave-uniform
         const float c0 = fixed ? -sc2 : 0.f;
         // accumulator start of the last key tile: padded keys (rows of S^T = registers) get -1e30, so P = 0 there
@@ -154,7 +148,7 @@ __global__ __launch_bounds__(64 * WAVES, OCC) void attn_fwd3_kernel(
 #pragma unroll
         for (int r = 0; r < 4; ++r) cpad[r] = (16 * (LT - 1) + 4 * g + r < Lc) ? c0 : SWV2_NEG_BIG;
 
-        STAMP(5, cpad[0]);
+        STAMP_DEP(5, cpad[0]);
 #pragma unroll 1
         for (int qt = wave; qt < LT; qt += WAVES) {                   // wave-uniform trip count
             const int q = 16 * qt + fr;
@@ -183,7 +177,7 @@ __global__ __launch_bounds__(64 * WAVES, OCC) void attn_fwd3_kernel(
                 }
                 qB = __builtin_bit_cast(bf16x8, w);
             }
-            STAMP(0, qB[0]);
+            STAMP_DEP(0, qB[0]);
 
             // S'^T tiles: rows = keys 16t + 4g + r, column = query fr; already scaled, and (fixed) already minus sigma'
             f32x4 acc[LT];
@@ -211,7 +205,7 @@ __global__ __launch_bounds__(64 * WAVES, OCC) void attn_fwd3_kernel(
 #pragma unroll
                     for (int r = 0; r < 4; ++r) acc[t][r] -= mx;
             }
-            STAMP(1, acc[LT - 1][0]);
+            STAMP_DEP(1, acc[LT - 1][0]);
 #pragma unroll
             for (int t = 0; t < LT; ++t)
 #pragma unroll
@@ -220,7 +214,7 @@ __global__ __launch_bounds__(64 * WAVES, OCC) void attn_fwd3_kernel(
                     if (LFIX > 0 && 16 * t + 4 * 0 + r >= LFIX && t == LT - 1) acc[t][r] = 0.f;
                     else acc[t][r] = __builtin_amdgcn_exp2f(acc[t][r]);
                 }
-            STAMP(2, acc[LT - 1][1]);
+            STAMP_DEP(2, acc[LT - 1][1]);
 
             // O^T[d][q] = sum_keys V^T[d][key] P^T[key][q] and the row sums (all-ones A operand), pairs of key tiles per K = 32
             f32x4 o = {0.f, 0.f, 0.f, 0.f}, rs = {0.f, 0.f, 0.f, 0.f};
@@ -244,7 +238,7 @@ __global__ __launch_bounds__(64 * WAVES, OCC) void attn_fwd3_kernel(
                 rs += ts;
             }
             const float sum = rs[0];                                  // every row of the ones product holds the column sums
-            STAMP(3, sum);
+            STAMP_DEP(3, sum);
             const float inv = (q < L) ? __builtin_amdgcn_rcpf(sum) : 0.f;
             uint16_t* orow = oh + ((size_t)bw * h + hd) * SLAB + (size_t)q * DP;
             f32x4 v = o;
@@ -253,10 +247,10 @@ __global__ __launch_bounds__(64 * WAVES, OCC) void attn_fwd3_kernel(
                 *(bf16x4*)(orow + 4 * g) = f2bf4(v);
                 if (g == 0) lse[((size_t)bw * h + hd) * Lp + q] = (q < L) ? mx + __log2f(sum) : 0.f;
             }
-            STAMP(4, v[0]);
+            STAMP_DEP(4, v[0]);
         }
         __syncthreads();
-        STAMP(6, stage[0][0]);
+        STAMP_DEP(6, stage[0][0]);
     }
 #ifdef SWV2_ATTN_STAMPS
     if (tid == 0 && Lp - L >= 14) {
@@ -302,7 +296,7 @@ __global__ __launch_bounds__(64 * WAVES, OCC) void attn_fwd3w_kernel(
     const bool last_chunk_ok = (wave * 64 + (CPT - 1) * NT) < CH;          // wave-uniform (CH is a multiple of 64)
     const int Lc = LFIX > 0 ? LFIX : L;
 
-    const float sc2 = __expf(fminf(logit_scale[hd], SWV2_LN100)) * SWV2_LOG2E;
+    const float sc2 = clamped_logit_scale(logit_scale[hd]) * SWV2_LOG2E;
     const bool bounded = sc2 <= 40.f;
 
     u32x4 stage[CPT];
@@ -337,7 +331,7 @@ __global__ __launch_bounds__(64 * WAVES, OCC) void attn_fwd3w_kernel(
         const uint16_t* Ks = Qs + SLAB;
         const uint16_t* Vs = Ks + SLAB;
         if (bw_next < Bw) issue_loads(bw_next);
-        const bool do_mask = (mask_thr > 0) && (((bw % nW) / nww) == nwh - 1);
+        const bool do_mask = (mask_thr > 0) && last_window_row(bw, nW, nww, nwh);
         const bool fixed = bounded && !do_mask;                       // wave-uniform
         const float c0 = fixed ? -sc2 : 0.f;
         f32x4 cpad;                                                   // padded keys start at -1e30: P = 0 there
@@ -479,7 +473,7 @@ __global__ __launch_bounds__(64 * WAVES, OCC) void attn_fwd3b_kernel(
     const int hd = blockIdx.y;
     const bool last_chunk_ok = (wave * 64 + (CPT - 1) * NT) < CH;          // wave-uniform
 
-    const float sc2 = __expf(fminf(logit_scale[hd], SWV2_LN100)) * SWV2_LOG2E;
+    const float sc2 = clamped_logit_scale(logit_scale[hd]) * SWV2_LOG2E;
     const float bmax = brange[2 * hd], bmin = brange[2 * hd + 1];
     const bool bounded = 2.f * sc2 + (bmax - bmin) <= 80.f;
 
@@ -556,7 +550,7 @@ __global__ __launch_bounds__(64 * WAVES, OCC) void attn_fwd3b_kernel(
         const uint16_t* Vs = Ki + KIMG;
         const uint16_t* Qs = Vs + SLAB;
         if (bw_next < Bw) issue_loads(bw_next);
-        const bool do_mask = (mask_thr > 0) && (((bw % nW) / nww) == nwh - 1);
+        const bool do_mask = (mask_thr > 0) && last_window_row(bw, nW, nww, nwh);
         const bool fixed = bounded && !do_mask;                       // wave-uniform
         const float c0 = fixed ? -(sc2 + bmax) : 0.f;
         const f32x4 cinit = {c0, c0, c0, c0};

@@ -52,15 +52,9 @@ __device__ unsigned long long attns_arr[17 * 8];      // (8 windows; nothing els
 __device__ unsigned long long attns_stamps[512 * 8];
 __device__ unsigned long long attns_win[64 * 128];        // wave 8 of the first 64 workgroups of head 0: s_memtime at the end of every window
 __device__ unsigned long long attns_clock[512 * 2];       // per wave: s_memtime span, s_memrealtime span (100 MHz) of the window loop
-#define SSTAMP_DECL unsigned long long st_prev = 0, st_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-#define SSTAMP_START() do { asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(st_prev) : : "memory"); } while (0)
-#define SSTAMP(k) do { unsigned long long t_; asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_) : : "memory"); \
-                       st_acc[k] += t_ - st_prev; st_prev = t_; } while (0)
-#else
-#define SSTAMP_DECL
-#define SSTAMP_START() do {} while (0)
-#define SSTAMP(k) do {} while (0)
+#define SWV2_STAMPS
 #endif
+#include "stamps.h"
 
 #define SWV2_PRIO(n) __builtin_amdgcn_s_setprio(n)
 
@@ -98,7 +92,7 @@ __global__ __launch_bounds__(1024) void attn_bwd_stream_kernel(
     const int hw = tw - PW;
 
     const float tau = logit_scale[hd];
-    const float sigma = __expf(fminf(tau, SWV2_LN100));
+    const float sigma = clamped_logit_scale(tau);
     const float sc2 = sigma * SWV2_LOG2E;
     const float inv_sc2 = 1.f / sc2;
     const int Lc = LFIX > 0 ? LFIX : L;
@@ -134,8 +128,8 @@ __global__ __launch_bounds__(1024) void attn_bwd_stream_kernel(
             // k, v: LDS-DMA (M0 = the LDS address of the wave's first chunk, lane l lands 16 l bytes behind it), issued BEFORE the register
             // loads: the counter is in order, so the compiler's own wait for a younger register load covers them
             if (craw < CH) {
-                asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" : : "v"(o16), "s"(kb_), "s"(lds_k) : "memory");
-                asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" : : "v"(o16), "s"(vb_), "s"(lds_k + SLAB * 2) : "memory");
+                dma_x4(kb_, o16, lds_k);
+                dma_x4(vb_, o16, lds_k + SLAB * 2);
             }
             st.q = *(const uint4*)(qb + o16);
             st.dO = *(const uint4*)(dob + o16);
@@ -151,34 +145,17 @@ __global__ __launch_bounds__(1024) void attn_bwd_stream_kernel(
         unsigned char* const B = lds + buf * BUFB;
         auto one = [&](const Stg& st, const int craw) {
             const int c = min(craw, CH - 1);
-            const int row = c / CPR, half = c % CPR;
+            const int row = c / CPR;
             // delta partial over this chunk's 8 channels, reduced over the 2 chunks of the row (adjacent lanes; vector ALU only)
-            float dl = 0.f;
-            {
-                const uint32_t a[4] = {st.dO.x, st.dO.y, st.dO.z, st.dO.w}, b[4] = {st.o.x, st.o.y, st.o.z, st.o.w};
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    dl = fmaf(__uint_as_float(a[e] << 16), __uint_as_float(b[e] << 16), dl);
-                    dl = fmaf(__uint_as_float(a[e] & 0xffff0000u), __uint_as_float(b[e] & 0xffff0000u), dl);
-                }
-            }
-            dl = group_allsum<CPR>(dl);
-            // slots 16..23 of the row (the even chunk's thread): lse / (sigma log2 e) in three bf16 parts, a constant 1 (padded-key
-            // flag), the query's mask-region flags -- and delta in three parts for the dO row; slots 24..31 (odd chunk): zeros
+            const float dp = delta_partial(st.dO, st.o);
+            const int half = c % CPR;
+            const float dl = group_allsum<CPR>(dp);
+            // slots 16..23 of the row (the even chunk's thread): the statistics; slots 24..31 (odd chunk): zeros
             uint4 aq = make_uint4(0, 0, 0, 0), ad = make_uint4(0, 0, 0, 0);
             if (half == 0) {
-                const bool q_ok = row < L;
-                const float lq = q_ok ? st.lse * inv_sc2 : 1.0e30f;            // padded query rows: P = 0
-                uint16_t l0 = f2bf(lq);
-                const float r1 = lq - bf2f(l0);
-                uint16_t l1 = f2bf(r1), l2 = f2bf(r1 - bf2f(l1));
-                if (!q_ok) l1 = l2 = 0;
-                const uint16_t d0 = f2bf(dl);
-                const float e1 = dl - bf2f(d0);
-                const uint16_t d1 = f2bf(e1), d2 = f2bf(e1 - bf2f(d1));
-                const uint32_t one_ = 0x3f80u, rqf = (row >= mask_thr) ? 0x3f80u : 0u;
-                aq = make_uint4(l0 | ((uint32_t)l1 << 16), l2 | (one_ << 16), rqf | ((one_ - rqf) << 16), rqf | ((one_ - rqf) << 16));
-                ad = make_uint4(d0 | ((uint32_t)d1 << 16), d2, 0, 0);
+                const u32x8 s = aug_query_row(row, L, mask_thr, st.lse * inv_sc2, dl);
+                aq = make_uint4(s[0], s[1], s[2], s[3]);
+                ad = make_uint4(s[4], s[5], s[6], s[7]);
             }
             if (craw < CH) {
                 *(uint4*)((uint16_t*)(B + B_Q) + row * QP + half * 8) = st.q;
@@ -201,8 +178,8 @@ __global__ __launch_bounds__(1024) void attn_bwd_stream_kernel(
     __syncthreads();
 
     float dsig = 0.f;
-    SSTAMP_DECL
-    SSTAMP_START();
+    STAMP_DECL(8)
+    STAMP_START();
 #ifdef SWV2_ATTNS_STAMPS
     const unsigned long long ck0 = __builtin_amdgcn_s_memtime(), rt0 = __builtin_amdgcn_s_memrealtime();
 #endif
@@ -238,7 +215,7 @@ __global__ __launch_bounds__(1024) void attn_bwd_stream_kernel(
                     __builtin_amdgcn_s_sleep(decltype(sleep_c)::value);
                 }
             }
-            SSTAMP(2);
+            STAMP(2);
             f32x4 dq[NQ];
 #pragma unroll
             for (int i = 0; i < NQ; ++i) dq[i] = (f32x4){0.f, 0.f, 0.f, 0.f};
@@ -270,38 +247,24 @@ __global__ __launch_bounds__(1024) void attn_bwd_stream_kernel(
                 const int q = 16 * qt0 + 16 * i + fr;
                 const float rq = RN[q] * sigma;
                 const bf16x4 qn = *(const bf16x4*)(Qa + q * QP + 4 * g);
-                float dot = 0.f;
-#pragma unroll
-                for (int r = 0; r < 4; ++r) dot = fmaf(dq[i][r], bf2f(qn[r]), dot);
-                dot = xor32_allsum(xor16_allsum(dot));
-                f32x4 v;
-#pragma unroll
-                for (int r = 0; r < 4; ++r) v[r] = rq * (dq[i][r] - bf2f(qn[r]) * dot);
-                *(bf16x4*)(dqkvh + slab0 + (size_t)q * DP + 4 * g) = f2bf4(v);
+                const float dot = l2norm_bwd_dot(dq[i], qn);
+                *(bf16x4*)(dqkvh + slab0 + (size_t)q * DP + 4 * g) = l2norm_bwd_out(dq[i], qn, rq, dot);
             }
-            SSTAMP(3);
+            STAMP(3);
         };
         if (!helper) {
             // ================= phase 1: wave = key tile =================
             const int key = 16 * tw + fr;
-            const bool do_mask = (mask_thr > 0) && (((bw % nW) / nww) == nwh - 1);
+            const bool do_mask = (mask_thr > 0) && last_window_row(bw, nW, nww, nwh);
             const float cmask = do_mask ? fmaxf(-100.f * SWV2_LOG2E * inv_sc2, -1.0e30f) : 0.f;
             const bf16x4 kf = *(const bf16x4*)(Ks + key * DP + 4 * g);          // (the normalisation backward's copy of k^)
             bf16x8 kf8, vf8;
             {
-                const uint32_t m1 = 0xbf80u;                                       // -1
-                const uint32_t padk = (key < Lc) ? 0u : (uint32_t)f2bf(-1.0e30f);
-                const bool kreg = key >= mask_thr;
-                // the mask term as hi + lo bf16 parts (k 20, 21 and k 22, 23; |error| <= 2^-17 |c|): one part alone is off by up to 2^-9 |c|,
-                // 0.28 in the log2 domain, which shows as soon as a masked key carries weight
-                const uint32_t chi = f2bf(cmask), clo = f2bf(cmask - bf2f((uint16_t)chi));
-                const uint32_t mk0 = kreg ? 0u : chi, mk1 = kreg ? chi : 0u, ml0 = kreg ? 0u : clo, ml1 = kreg ? clo : 0u;
-                const uint4 augk = make_uint4(m1 | (m1 << 16), m1 | (padk << 16), mk0 | (mk1 << 16), ml0 | (ml1 << 16));
-                const uint4 augv = make_uint4(m1 | (m1 << 16), m1, 0, 0);
+                const AugKey aug = aug_key_operands(key, Lc, mask_thr, cmask);
                 const uint4 z = make_uint4(0, 0, 0, 0);
                 const uint4 rk = *(const uint4*)(Ks + key * DP + (g & 1) * 8), rv = *(const uint4*)(Vs + key * DP + (g & 1) * 8);
-                kf8 = __builtin_bit_cast(bf16x8, g < 2 ? rk : (g == 2 ? augk : z));
-                vf8 = __builtin_bit_cast(bf16x8, g < 2 ? rv : (g == 2 ? augv : z));
+                kf8 = __builtin_bit_cast(bf16x8, g < 2 ? rk : (g == 2 ? aug.k : z));
+                vf8 = __builtin_bit_cast(bf16x8, g < 2 ? rv : (g == 2 ? aug.v : z));
             }
             f32x4 dk = {0.f, 0.f, 0.f, 0.f}, dv = {0.f, 0.f, 0.f, 0.f};
 
@@ -391,24 +354,18 @@ __global__ __launch_bounds__(1024) void attn_bwd_stream_kernel(
                 dk += tk;
                 signal(NPAIR - 1);
             }
-            SSTAMP(1);                      // phase 1 loop
+            STAMP(1);                      // phase 1 loop
             // ---- dK (through the L2-normalisation) and dV of this wave's key tile
             {
                 const float rk = RN[Lp + key];
-                float dot = 0.f;
-#pragma unroll
-                for (int r = 0; r < 4; ++r) dot = fmaf(dk[r], bf2f(kf[r]), dot);
-                dot = xor32_allsum(xor16_allsum(dot));
+                const float dot = l2norm_bwd_dot(dk, kf);
                 // d logit_scale: sigma sum_{q,k} dS cos = sigma sum_k (sum_q dS[q][k] q^[q]) . k^[k] = sigma sum_k dot_k
                 if (g == 0) dsig += dot;
-                const float rks = rk * sigma;                     // the accumulators hold sum_q q^ dS: d(cos) = sigma dS
-                f32x4 v;
-#pragma unroll
-                for (int r = 0; r < 4; ++r) v[r] = rks * (dk[r] - bf2f(kf[r]) * dot);
-                *(bf16x4*)(dqkvh + slab0 + SLAB + (size_t)key * DP + 4 * g) = f2bf4(v);
+                // (rk sigma: the accumulators hold sum_q q^ dS, d(cos) = sigma dS)
+                *(bf16x4*)(dqkvh + slab0 + SLAB + (size_t)key * DP + 4 * g) = l2norm_bwd_out(dk, kf, rk * sigma, dot);
                 *(bf16x4*)(dqkvh + slab0 + 2 * SLAB + (size_t)key * DP + 4 * g) = f2bf4(dv);
             }
-            SSTAMP(4);                      // dK / dV normalisation backward + stores
+            STAMP(4);                      // dK / dV normalisation backward + stores
             // The dQ of the last six q-tiles, one single-tile pass each on the phase-1 waves that finish their key tile first (the four oldest + wave 7; wave 3,
             // alone with wave 7 and two helpers on its SIMD, takes two).  Which waves the window's barrier waits for, production build with one s_memtime per
             // wave and window (-DSWV2_ATTNS_ARRIVE, tools/probe_attn_bwd_arrive.py): with all dQ on the helpers the phase-1 waves arrived 900 - 2 600 cycles
@@ -426,11 +383,11 @@ __global__ __launch_bounds__(1024) void attn_bwd_stream_kernel(
             // ================= helper waves: the next window's prefetch, phase 2 (dQ), the commit =================
             const int hidx = hw * 64 + ln;
             if (bw_next < Bw) issue(bw_next, buf ^ 1, hidx);
-            SSTAMP(0);
+            STAMP(0);
             // every helper commits first (its loads were issued at the window's start), then helper 0: the first pair, helpers 1 .. 3: q-tiles 2 .. 4
             // (all complete by ~55 % of the window); helper 4 stages and commits two chunks per thread and takes no tile
             if (bw_next < Bw) commit(buf ^ 1, hidx);
-            SSTAMP(5);
+            STAMP(5);
             if (hw == 0) phase2(0, std::integral_constant<int, 2>{}, std::integral_constant<int, 4>{});
             else if (hw < HW - 1) phase2(hw + 1, std::integral_constant<int, 1>{}, std::integral_constant<int, 4>{});
         }
@@ -442,7 +399,7 @@ __global__ __launch_bounds__(1024) void attn_bwd_stream_kernel(
 #ifdef SWV2_ATTNS_ARRIVE
         if (arr_on && tid == 0) attns_arr[16 * 8 + it - 8] = __builtin_amdgcn_s_memtime();
 #endif
-        SSTAMP(6);                      // the window's barrier
+        STAMP(6);                      // the window's barrier
 #ifdef SWV2_ATTNS_STAMPS
         if (lane == 0 && tw == 8 && blockIdx.y == 0 && blockIdx.x < 64 && it < 128) attns_win[blockIdx.x * 128 + it] = st_prev - ck0;
 #endif

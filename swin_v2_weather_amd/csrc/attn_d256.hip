@@ -34,7 +34,7 @@ __global__ __launch_bounds__(D256_NT) void attn_fwd_d256_kernel(
     static_assert(Lp * QP * 2 <= 160 * 1024, "LDS");
     __shared__ __attribute__((aligned(16))) uint16_t KV[Lp * QP];       // K, then V
     const int hd = blockIdx.y;
-    const float sc2 = __expf(fminf(logit_scale[hd], SWV2_LN100)) * SWV2_LOG2E;
+    const float sc2 = clamped_logit_scale(logit_scale[hd]) * SWV2_LOG2E;
     // staging map: 32 threads per row (one 16-byte chunk each), 22 rows per pass, 8 passes
     constexpr int TPR = DP / 8, RPP = NT / TPR, PASSES = Lp / RPP;
     static_assert(Lp % RPP == 0, "staging map");
@@ -76,7 +76,7 @@ __global__ __launch_bounds__(D256_NT) void attn_fwd_d256_kernel(
         __syncthreads();                                      // every wave is done with K: V goes over it
         stage(slab0 + 2 * SLAB);
 
-        const bool do_mask = (mask_thr > 0) && (((bw % nW) / nww) == nwh - 1);
+        const bool do_mask = (mask_thr > 0) && last_window_row(bw, nW, nww, nwh);
         float mx, sum = 0.f;
         if (!do_mask) {          // sigma > 0 commutes with the maximum: the scale is folded into the exponent's fma (attn_fwd_kernel)
             const int Lc = LFIX > 0 ? LFIX : L;
@@ -175,7 +175,7 @@ __global__ __launch_bounds__(D256_NT) void attn_bwd_d256_kernel(
 
     const int hd = blockIdx.y;
     const float tau = logit_scale[hd];
-    const float sigma = __expf(fminf(tau, SWV2_LN100));
+    const float sigma = clamped_logit_scale(tau);
     const float sc2 = sigma * SWV2_LOG2E;
     const int Lc = LFIX > 0 ? LFIX : L;
     float dsig = 0.f;
@@ -201,7 +201,7 @@ __global__ __launch_bounds__(D256_NT) void attn_bwd_d256_kernel(
         };
         const size_t slab0 = ((size_t)bw * h + hd) * 3 * SLAB, oslab = ((size_t)bw * h + hd) * SLAB;
         const int key = 16 * tw + fr;
-        const bool do_mask = (mask_thr > 0) && (((bw % nW) / nww) == nwh - 1);
+        const bool do_mask = (mask_thr > 0) && last_window_row(bw, nW, nww, nwh);
         const bool kid = key >= mask_thr, key_ok = key < Lc;
 
         // ================= phase 1a / 1b, once per half of the query tiles (registers: 2 x 6 accumulators instead of 2 x 11) =================
@@ -319,10 +319,7 @@ __global__ __launch_bounds__(D256_NT) void attn_bwd_d256_kernel(
                 for (int dt = 0; dt < CT; ++dt) {
                     const size_t off = (size_t)key * DP + CW * c + 16 * dt + 4 * g;
                     const bf16x4 kn = *(const bf16x4*)(qkvh + slab0 + SLAB + off);
-                    f32x4 v;
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) v[r] = rks * (dk[dt][r] - bf2f(kn[r]) * dotk);
-                    *(bf16x4*)(dqkvh + slab0 + SLAB + off) = f2bf4(v);
+                    *(bf16x4*)(dqkvh + slab0 + SLAB + off) = l2norm_bwd_out(dk[dt], kn, rks, dotk);
                     *(bf16x4*)(dqkvh + slab0 + 2 * SLAB + off) = f2bf4(dv[dt]);
                 }
             }
@@ -388,10 +385,7 @@ __global__ __launch_bounds__(D256_NT) void attn_bwd_d256_kernel(
 #pragma unroll
             for (int dt = 0; dt < DT; ++dt) {
                 const bf16x4 qn = *(const bf16x4*)(qkvh + slab0 + (size_t)q * DP + 16 * dt + 4 * g);
-                f32x4 v;
-#pragma unroll
-                for (int r = 0; r < 4; ++r) v[r] = rq * (dq[dt][r] - bf2f(qn[r]) * dot);
-                *(bf16x4*)(dqkvh + slab0 + (size_t)q * DP + 16 * dt + 4 * g) = f2bf4(v);
+                *(bf16x4*)(dqkvh + slab0 + (size_t)q * DP + 16 * dt + 4 * g) = l2norm_bwd_out(dq[dt], qn, rq, dot);
             }
         }
         __syncthreads();                                      // the next window's staging overwrites the tiles and the dS image

@@ -46,7 +46,7 @@ __global__ __launch_bounds__(64 * LT) void attn_bwd_wide_kernel(
     const int fr = lane & 15, g = lane >> 4;
     const int hd = blockIdx.y;
     const float tau = logit_scale[hd];
-    const float sigma = __expf(fminf(tau, SWV2_LN100));
+    const float sigma = clamped_logit_scale(tau);
     const float sc2 = sigma * SWV2_LOG2E;
     const int Lc = LFIX > 0 ? LFIX : L;
     float dsig = 0.f;
@@ -105,7 +105,7 @@ __global__ __launch_bounds__(64 * LT) void attn_bwd_wide_kernel(
         f32x4 dk[DKR], dv[DKR];
 #pragma unroll
         for (int dt = 0; dt < DKR; ++dt) { dk[dt] = (f32x4){0.f, 0.f, 0.f, 0.f}; dv[dt] = (f32x4){0.f, 0.f, 0.f, 0.f}; }
-        const bool do_mask = (mask_thr > 0) && (((bw % nW) / nww) == nwh - 1);
+        const bool do_mask = (mask_thr > 0) && last_window_row(bw, nW, nww, nwh);
         const bool kid = key >= mask_thr, key_ok = key < Lc;
         auto step = [&](const int qt, auto masked_c, auto pad_c) {
             constexpr bool MASKED = decltype(masked_c)::value, PADT = decltype(pad_c)::value;
@@ -289,7 +289,7 @@ __global__ __launch_bounds__(64 * LT) void attn_fwd_wide_kernel(
     const int fr = lane & 15, g = lane >> 4;
     const int hd = blockIdx.y;
     const int q = 16 * qt + fr;
-    const float sc2 = __expf(fminf(logit_scale[hd], SWV2_LN100)) * SWV2_LOG2E;
+    const float sc2 = clamped_logit_scale(logit_scale[hd]) * SWV2_LOG2E;
     constexpr int RPP = NT / 16, PASSES = (Lp + RPP - 1) / RPP;
     const int srow = tid >> 4, scc = tid & 15;
     const bool sact = scc < 2 * DKR;
@@ -330,7 +330,7 @@ __global__ __launch_bounds__(64 * LT) void attn_fwd_wide_kernel(
                 acc[t] = mfma32(kf, qf[kk], acc[t]);
             }
         }
-        const bool do_mask = (mask_thr > 0) && (((bw % nW) / nww) == nwh - 1);
+        const bool do_mask = (mask_thr > 0) && last_window_row(bw, nW, nww, nwh);
         float mx, sum = 0.f;
         if (!do_mask) {          // sigma > 0 commutes with the maximum: the scale is folded into the exponent's fma (attn_fwd_kernel)
             const int Lc = LFIX > 0 ? LFIX : L;

@@ -50,6 +50,14 @@ __device__ __forceinline__ bf16x4 lds_tr_read(const uint16_t* p) {
     return __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_bf16x4*)p);
 }
 
+// LDS-DMA load: 16 bytes per lane from (scalar base + 32-bit byte offset) to LDS at m0 + 16 * lane, no register.  Inline assembly
+// on purpose: through the builtin the compiler orders every later LDS access behind the load with s_waitcnt vmcnt(0).  The
+// compiler does not count these in its own vmcnt bookkeeping; VMEM operations return in order, so an uncounted operation can
+// only make a compiler-placed wait longer, never too short; the waits for the DMA'd tiles are placed by hand.
+__device__ __forceinline__ void dma_x4(const void* base, uint32_t byte_off, uint32_t lds_addr) {
+    asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" : : "v"(byte_off), "s"(base), "s"(lds_addr) : "memory");
+}
+
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);

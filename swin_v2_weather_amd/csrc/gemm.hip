@@ -644,13 +644,6 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_nt_kernel(ALoad<AK> al, cons
 // once each (speed only: any mapping is correct).
 // ------------------------------------------------------------------------------------------------
 constexpr int WBM = 256, WBN = 256, WTH = 512;
-// LDS-DMA load: 16 bytes per lane from (scalar base + 32-bit byte offset) to LDS at m0 + 16 * lane, no register.  Inline assembly
-// on purpose: through the builtin the compiler orders every later LDS access behind the load with s_waitcnt vmcnt(0).  The
-// compiler does not count these in its own vmcnt bookkeeping; VMEM operations return in order, so an uncounted operation can
-// only make a compiler-placed wait longer, never too short; the waits for the DMA'd tiles are placed by hand.
-__device__ __forceinline__ void dma_x4(const void* base, uint32_t byte_off, uint32_t lds_addr) {
-    asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" : : "v"(byte_off), "s"(base), "s"(lds_addr) : "memory");
-}
 // Epilogue of a wave's 128 x 64 accumulator tile in the wide kernels.  Epi<>::tile loads its bias / residual / pre-activation
 // operands under conditions, which costs an s_waitcnt vmcnt(0) per 16-row sub-tile -- a wait for the acknowledgement of every
 // store of the previous sub-tile (measured: 20 us per tile for 256 KB, half the kernel at K = 768).  Here everything a lane needs
@@ -1187,17 +1180,9 @@ __global__ __launch_bounds__(WTH) void gemm_nt_wide_kernel(ALoad<AK> al, const u
 // ------------------------------------------------------------------------------------------------
 #ifdef SWV2_RW_STAMPS
 __device__ unsigned long long rw_stamps[256 * 8];
-#define RSTAMP_DECL unsigned long long st_prev = 0, st_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-#define RSTAMP_START() do { asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(st_prev) : : "memory"); } while (0)
-#define RSTAMP(k) do { unsigned long long t_; asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_) : : "memory"); \
-                       st_acc[k] += t_ - st_prev; st_prev = t_; } while (0)
-#define RSTAMP_WAITV() asm volatile("s_waitcnt vmcnt(0)" ::: "memory")
-#else
-#define RSTAMP_DECL
-#define RSTAMP_START() do {} while (0)
-#define RSTAMP(k) do {} while (0)
-#define RSTAMP_WAITV() do {} while (0)
+#define SWV2_STAMPS
 #endif
+#include "stamps.h"
 __device__ __forceinline__ int swzk(int r, int kc, int K) { return r * K + ((kc ^ ((r >> 1) & 7)) << 3); }
 
 template <int AK, int EK, int N, int K, int BMT, int HS = 16>
@@ -1296,22 +1281,22 @@ __global__ __launch_bounds__(512) void gemm_rw_kernel(ALoad<AK> al, const uint16
         }
     };
     const int G = gridDim.x;
-    RSTAMP_DECL
+    STAMP_DECL(8)
     auto tile_step = [&](int t) {
-        RSTAMP_WAITV();
-        RSTAMP(0);
+        STAMP_WAITV();
+        STAMP(0);
         commit();
         if constexpr (EK == E_F32) {
             erow_cur = erow_nxt;
 #pragma unroll
             for (int i = 0; i < 4; ++i) aux_cur[i] = aux_nxt[i];
         }
-        RSTAMP(1);
+        STAMP(1);
         __syncthreads();                                   // A tile (and, the first time, the weight) visible
-        RSTAMP(2);
+        STAMP(2);
         issue();                                           // next tile's rows: in flight during the MFMAs and the epilogue
         resolve(t + 2 * G);
-        RSTAMP(3);
+        STAMP(3);
         f32x4 acc[RT][CT];
 #pragma unroll
         for (int i = 0; i < RT; ++i)
@@ -1330,9 +1315,9 @@ __global__ __launch_bounds__(512) void gemm_rw_kernel(ALoad<AK> al, const uint16
             }
         }
         asm volatile("" :: "v"(acc[0][0][0]), "v"(acc[RT - 1][CT - 1][3]));
-        RSTAMP(4);
+        STAMP(4);
         __syncthreads();                                   // every wave is done with the A tile: it becomes the staging area
-        RSTAMP(5);
+        STAMP(5);
         float* st = stage_all + wave * 16 * EP;
 #pragma unroll
         for (int i = 0; i < RT; ++i)
@@ -1394,9 +1379,9 @@ __global__ __launch_bounds__(512) void gemm_rw_kernel(ALoad<AK> al, const uint16
                     ep.tile(st, m0, n0, lane);
                 }
             }
-        RSTAMP(6);
+        STAMP(6);
         __syncthreads();                                   // staging consumed before the next commit overwrites it
-        RSTAMP(7);
+        STAMP(7);
     };
     int t = blockIdx.x;
     resolve(t);
@@ -1409,7 +1394,7 @@ __global__ __launch_bounds__(512) void gemm_rw_kernel(ALoad<AK> al, const uint16
         *(uint4*)(Ws + swzk(n, kc, K)) = *(const uint4*)(Wb + (long)n * K + kc * 8);
     }
 
-    RSTAMP_START();
+    STAMP_START();
     for (; t < ntiles; t += G) tile_step(t);
 #ifdef SWV2_RW_STAMPS
     if (tid == 0)

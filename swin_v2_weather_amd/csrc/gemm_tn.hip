@@ -1,6 +1,12 @@
 // Weight-gradient products of the GEMM engine: dW[N][K] += sum_m dY[m][N]^T X[m][K] (+ bias gradient).  See gemm.hip for
 // the engine overview and gemm_common.h for the operand loaders shared with the NT kernel.
 #include "gemm_common.h"
+// In-kernel phase timing (diagnostic builds only, -DSWV2_TN_STAMPS, tools/probe_tn_stamps.py): wave 0 of every workgroup
+// accumulates s_memtime deltas per phase and overwrites the head of its partial tile with them (results are garbage then).
+#ifdef SWV2_TN_STAMPS
+#define SWV2_STAMPS
+#endif
+#include "stamps.h"
 
 namespace {
 
@@ -15,22 +21,7 @@ constexpr int TCH = TM * 16 / NTHREADS;     // 16-byte chunks per thread per ope
 struct TnOut {                 // one product's destination
     float* dW; float* db; const int32_t* nmap; const int32_t* kmap; int ldw, M, N, K, ntk, tiles; float* ws;
 };
-constexpr int TN_SMEM = 2 * TM * TP;
-
-// In-kernel phase timing (diagnostic builds only, -DSWV2_TN_STAMPS, tools/probe_tn_stamps.py): wave 0 of every workgroup
-// accumulates s_memtime deltas per phase and overwrites the head of its partial tile with them (results are garbage then).
-#ifdef SWV2_TN_STAMPS
-#define TSTAMP_DECL unsigned long long st_prev = 0, st_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-#define TSTAMP_START() do { asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(st_prev) : : "memory"); } while (0)
-#define TSTAMP(k) do { unsigned long long t_; asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_) : : "memory"); \
-                       st_acc[k] += t_ - st_prev; st_prev = t_; } while (0)
-#define TSTAMP_WAITV() asm volatile("s_waitcnt vmcnt(0)" ::: "memory")
-#else
-#define TSTAMP_DECL
-#define TSTAMP_START() do {} while (0)
-#define TSTAMP(k) do {} while (0)
-#define TSTAMP_WAITV() do {} while (0)
-#endif        // [Y | X][TM][TP] bf16, single buffer
+constexpr int TN_SMEM = 2 * TM * TP;        // [Y | X][TM][TP] bf16, single buffer
 
 // one 128 x 128 output tile over the row chunks of one slice (body shared by the single-product and the grouped kernel)
 // XG: the X rows are gathered through xl.d.rowidx (compile time, so the un-gathered products carry no index load at all)
@@ -166,21 +157,21 @@ __device__ __forceinline__ void tn_tile(const ALoad<YK>& yl, const ALoad<XK>& xl
 #pragma unroll
         for (int j = 0; j < 4; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
 
-    TSTAMP_DECL
-    TSTAMP_START();
+    STAMP_DECL(8)
+    STAMP_START();
     resolve(0);
     issue(0);
     resolve(1);
-    TSTAMP(7);
+    STAMP(7);
     for (int s = 0; s < steps; ++s) {
-        TSTAMP_WAITV();
-        TSTAMP(0);
+        STAMP_WAITV();
+        STAMP(0);
         commit();
-        TSTAMP(1);
+        STAMP(1);
         __syncthreads();
-        TSTAMP(2);
+        STAMP(2);
         if (s + 1 < steps) { issue(s + 1); resolve(s + 2); }
-        TSTAMP(3);
+        STAMP(3);
         const uint16_t* Ys = smem;
         const uint16_t* Xs = smem + TM * TP;
         // A operand = dY^T (rows n, k = m), B operand = X (k = m, cols k'): both are transposed reads of row-major tiles
@@ -203,9 +194,9 @@ __device__ __forceinline__ void tn_tile(const ALoad<YK>& yl, const ALoad<XK>& xl
                 for (int j = 0; j < 4; ++j) acc[i][j] = mfma32(af[i], bf[j], acc[i][j]);
         }
         asm volatile("" :: "v"(acc[0][0][0]), "v"(acc[3][3][3]));
-        TSTAMP(4);
+        STAMP(4);
         __syncthreads();                    // all waves done with the tile before the next commit overwrites it
-        TSTAMP(5);
+        STAMP(5);
     }
     // accumulate the tile: rows n = n_base + wr*64 + 16i + 4g + r, cols k = k_base + wc*64 + 16j + fr
     if (ws) {                               // workspace path: plain partial tile, summed by tn_reduce_kernel
@@ -218,8 +209,8 @@ __device__ __forceinline__ void tn_tile(const ALoad<YK>& yl, const ALoad<XK>& xl
                 for (int r = 0; r < 4; ++r)
                     pt[(wr * 64 + 16 * i + 4 * g + r) * BN + wc * 64 + 16 * j + fr] = acc[i][j][r];
 #ifdef SWV2_TN_STAMPS
-        TSTAMP_WAITV();
-        TSTAMP(6);
+        STAMP_WAITV();
+        STAMP(6);
         if (tid == 0) {
 #pragma unroll
             for (int k = 0; k < 8; ++k) ((unsigned long long*)pt)[k] = st_acc[k];

@@ -44,22 +44,12 @@ constexpr int SL_SMEM = 160 * 1024;           // the whole LDS of a CU: one work
 constexpr int SL_IDX_CAP = 4096;              // gather index table in LDS: a ring of two halves (2 x 2048 rows), refilled while the other half is in use
 enum { F_ROW = 0, F_ROWG = 1, F_F32 = 2, F_F32G = 3, F_HEAD = 4 };
 
-__device__ __forceinline__ void sl_dma(const void* base, uint32_t byte_off, uint32_t lds_addr) {
-    asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" : : "v"(byte_off), "s"(base), "s"(lds_addr) : "memory");
-}
-
 // In-kernel phase timing (diagnostic builds only, -DSWV2_SLAB_STAMPS, tools/probe_wgrad_slab.py stamps): wave 0 of every workgroup
 // sums s_memtime deltas per phase and overwrites the head of its partial tile with them (the results are garbage then).
 #ifdef SWV2_SLAB_STAMPS
-#define SSTAMP_DECL unsigned long long st_prev = 0, st_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-#define SSTAMP_START() do { asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(st_prev) : : "memory"); } while (0)
-#define SSTAMP(k) do { unsigned long long t_; asm volatile("s_waitcnt lgkmcnt(0)\n\ts_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_) : : "memory"); \
-                       st_acc[k] += t_ - st_prev; st_prev = t_; } while (0)
-#else
-#define SSTAMP_DECL
-#define SSTAMP_START() do {} while (0)
-#define SSTAMP(k) do {} while (0)
+#define SWV2_STAMPS
 #endif
+#include "stamps.h"
 
 // GELU of 8 packed bf16 (a B fragment) through the LDS table of gemm_common.h, which sits at LDS address 0 (the gathers then carry no
 // base add: the address is the 16-bit byte offset itself).  Per pair of values: magnitude - table origin (16-bit wrap-around for
@@ -217,7 +207,7 @@ __device__ __forceinline__ void slab_job(const SlProd& P, const int j, unsigned 
                 const int bw = fdiv(m, P.y.Lp, P.y.mgLp), tt = m - bw * P.y.Lp;
                 off = 2u * ((uint32_t)bw * ywst + (uint32_t)(tt * P.y.DP) + ocol[q]);
             }
-            sl_dma(P.y.ptr, off, lslot);
+            dma_x4(P.y.ptr, off, lslot);
         } else {
             uint32_t off;
             if constexpr (FX == F_F32G) {
@@ -232,7 +222,7 @@ __device__ __forceinline__ void slab_job(const SlProd& P, const int j, unsigned 
                     off = 2u * ((uint32_t)bw * xwst + (uint32_t)(tt * P.x.DP) + ocol[q]);
                 }
             }
-            sl_dma(P.x.ptr, off, lslot);
+            dma_x4(P.x.ptr, off, lslot);
         }
     };
     // instructions [lo, hi) of a stage: the issue of a stage is spread over the compute of the previous one (insertion points below),
@@ -275,21 +265,21 @@ __device__ __forceinline__ void slab_job(const SlProd& P, const int j, unsigned 
         return lds_tr_read(slab + (c >> 4) * (SR * 16) + row * 16 + (fr & 3) * 4);
     };
 
-    SSTAMP_DECL
-    SSTAMP_START();
+    STAMP_DECL(8)
+    STAMP_START();
     if (nst > 0) {
 #pragma unroll
         for (int d = 0; d < D; ++d) issue(min(d, nst - 1), d);
-        SSTAMP(7);
+        STAMP_DRAINED(7);
         for (int t = 0; t < nst; ++t) {
             // all but the (D - 1) youngest stages of this wave have landed
             if (NREM == 0 || wave < NREM) asm volatile("s_waitcnt vmcnt(%0)" : : "n"((D - 1) * NIW) : "memory");
             else asm volatile("s_waitcnt vmcnt(%0)" : : "n"((D - 1) * (NIW - 1)) : "memory");
-            SSTAMP(0);
+            STAMP_DRAINED(0);
             __builtin_amdgcn_sched_barrier(0);
             __builtin_amdgcn_s_barrier();             // stage t has landed (every wave's part); every wave is done with stage t - 1
             __builtin_amdgcn_sched_barrier(0);
-            SSTAMP(1);
+            STAMP_DRAINED(1);
             const int ti_n = min(t + D, nst - 1), slot_n = (t + D) % NS;
             if constexpr (FX == F_F32G) {
                 // every HS stages: the half of the gather table that held stages t - HS .. t - 1 (all consumed: issue and conversion of
@@ -331,7 +321,7 @@ __device__ __forceinline__ void slab_job(const SlProd& P, const int j, unsigned 
                 __syncthreads();
                 Xs = xdst;
             }
-            SSTAMP(3);
+            STAMP_DRAINED(3);
 #pragma unroll
             for (int kk = 0; kk < KS; ++kk) {
                 // Fragments in chunks of at most four along the longer side of the wave tile (the other side, <= 4 fragments, stays in
@@ -376,7 +366,7 @@ __device__ __forceinline__ void slab_job(const SlProd& P, const int j, unsigned 
                     bf16x8 bf[JB];
                     [&]<int... JJ>(std::integer_sequence<int, JJ...>) { ((bf[JJ] = read_b(std::integral_constant<int, JJ>{})), ...); }
                     (std::make_integer_sequence<int, JB>{});
-                    SSTAMP(4);
+                    STAMP_DRAINED(4);
 #pragma unroll
                     for (int i0 = 0; i0 < IA; i0 += 4) {
                         bf16x8 af[4];
@@ -410,12 +400,12 @@ __device__ __forceinline__ void slab_job(const SlProd& P, const int j, unsigned 
 #pragma unroll
                             for (int i = 0; i < IA; ++i) acc[i][jj] = mfma32(af[i], bf[jj - j0], acc[i][jj]);
                     }(), ...); }(std::make_integer_sequence<int, (JB + 3) / 4>{});
-                    SSTAMP(4);
+                    STAMP_DRAINED(4);
                 }
 #ifdef SWV2_SLAB_STAMPS
                 asm volatile("" :: "v"(acc[0][0][0]), "v"(acc[IA - 1][JB - 1][3]));
 #endif
-                SSTAMP(5);
+                STAMP_DRAINED(5);
             }
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // (the re-issued tail stages)
@@ -440,7 +430,7 @@ __device__ __forceinline__ void slab_job(const SlProd& P, const int j, unsigned 
     }
 #ifdef SWV2_SLAB_STAMPS
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    SSTAMP(6);
+    STAMP_DRAINED(6);
     if (tid == 0 && stamps) {
 #pragma unroll
         for (int k = 0; k < 8; ++k) stamps[(size_t)blockIdx.x * 8 + k] = st_acc[k];

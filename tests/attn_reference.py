@@ -5,9 +5,10 @@ checks the kernels).  Every element of every output is compared; there is no flo
 sums of absolute values of the terms a kernel adds, so cancellation needs no exemption.
 
 WHAT THE KERNELS READ (all tensors here are [Bw, h, L, d], un-padded, fp64 holding bf16 / fp32 values)
-  q^, k^ (L2-normalised) and v as bf16; tau = logit_scale fp32, sigma = exp(min(tau, ln 100)); the CPB table as bf16(b log2 e) --
+  q^, k^ (L2-normalised) and v as bf16; tau = logit_scale fp32, sigma = exp(min(tau, ln 100)) (clamped_logit_scale, csrc/attn_common.h); the CPB table as bf16(b log2 e) --
   the reference uses b' = bf16(fp32(b log2 e)) / log2 e; the shift mask of swv2.h in closed form: in the windows of the LAST window row
-  (wi == nwh - 1) a pair whose tokens lie on different sides of mask_thr gets -100 (finite, as in the reference).
+  (wi == nwh - 1: last_window_row, csrc/attn_common.h) a pair whose tokens lie on different sides of mask_thr gets -100 (finite, as in
+  the reference).
   S = sigma q^.k^ + b' + m,  P = softmax(S),  o = P v,  lse = log2 sum exp(S)  (log2 domain, as stored).
 
 BACKWARD, following the kernels' data flow from the STORED tensors it is handed (oh, lse, doh, rnorm):
@@ -24,7 +25,7 @@ BOUNDS.  u = 2^-9 is the relative error of one round-to-nearest bf16 conversion,
       -> 2^-17 |x| per channel, the (sigma' + table maximum) reference enters the same way, fp32 accumulation on top -> cS = 2^-15.
       mask_eps = 2^-22 where the mask is added in fp32 (-100 log2 e is one constant: 2^-24, then the additions around it).
       Backward kernels that carry the mask inside the MFMA operands (swv2_attn_kernel_t.aug) hold c = -100 / sigma as hi + lo bf16
-      parts: |error| <= 2^-9 |lo| <= 2^-17 |c| (hi exact to 2^-8 |c|, lo to 2^-9 of that) -> mask_eps = 2^-17 there.
+      parts (aug_key_operands, csrc/attn_common.h: the one place that builds them): |error| <= 2^-9 |lo| <= 2^-17 |c| (hi exact to 2^-8 |c|, lo to 2^-9 of that) -> mask_eps = 2^-17 there.
   e_q = max_k eS (a row's normaliser sees every key's error).
   o    : the exponentials feed the P.V product as bf16 (u each), regime 1 also sums the rounded ones (u), the row's exponent errors move
          numerator and normaliser by <= e_q each, o is stored as bf16 (u (|ref| + error)):
