@@ -33,8 +33,8 @@ extern "C" {
  * epilogue with the rollout destinations; 108: the kernel-selection queries swv2_linear_kernel, swv2_linear_wgrad_kernel,
  * swv2_block_wgrad_kernel; 109: swv2_block_plan (+ swv2_block_plan_t, enum swv2_block_step, swv2_block_step_id / _name),
  * swv2_block_desc loses fuse_attn and wgrad_side_stream; 110: the attention kernel-selection queries swv2_attn_fwd_kernel /
- * swv2_attn_bwd_kernel (+ swv2_attn_kernel_t, SWV2_ATTN_K_*). */
-#define SWV2_VERSION 110
+ * swv2_attn_bwd_kernel (+ swv2_attn_kernel_t, SWV2_ATTN_K_*); 111: the LAMB optimizer, swv2_lamb_* (+ swv2_lamb_item, SWV2_LAMB_*). */
+#define SWV2_VERSION 111
 
 enum {
     SWV2_OK = 0,
@@ -433,6 +433,52 @@ typedef struct swv2_adam_item {
 int swv2_adam_chunk(void);
 int swv2_adam_multi(const swv2_adam_item* items_dev, const int* chunks_dev, int n_chunks, float lr, float beta1, float beta2,
                     float eps, int step, float grad_inv_scale, void* stream);
+
+/* LAMB with apex FusedLAMB's semantics (replaces `optimizers.FusedLAMB(...)`, train.py:177-178, and its step at :330) for MANY fp32
+ * tensors, in the multi-tensor shape of swv2_adam_multi: ONE item table and ONE chunk table for the tensors of all parameter groups, one
+ * workgroup per chunk of swv2_lamb_chunk() elements.  chunks_dev holds int pairs (item index, chunk index within the item), item by item
+ * in ascending chunk order; an item's chunk0 is the position of its first pair.  A group is a range of items and the matching range of chunks.
+ *   step:  G = sqrt(sum over all items of (g grad_inv_scale)^2 + *extra_gnorm2);  c = G > max_grad_norm ? G / max_grad_norm : 1
+ *          g^ = g grad_inv_scale / c  (+ weight_decay p without SWV2_LAMB_ADAMW);  b3 = 1 - beta1 with SWV2_LAMB_GRAD_AVERAGING, else 1
+ *          m <- beta1 m + b3 g^;  v <- beta2 v + (1 - beta2) g^ g^;  a = (m / bc1) / (sqrt(v / bc2) + eps)
+ *          u = a (+ weight_decay p with SWV2_LAMB_ADAMW);  bc = 1 - beta^step with SWV2_LAMB_BIAS_CORRECTION, else 1
+ *          r = |p| / |u| per tensor if (SWV2_LAMB_NVLAMB or weight_decay != 0) and |p| != 0 and |u| != 0, else 1 (|p| before the update)
+ *          p <- p - lr r u
+ * g is read only; non-finite values propagate as the arithmetic dictates.  The square of an element passes through at most
+ * SWV2_LAMB_SUM_DEPTH fp32 additions on its way into a norm, in an order fixed by the tables (no float atomics: a second run from the
+ * same state gives the same bits).  All scalars reach the kernels as fp32; 1 - beta is formed in fp32.
+ * Workspace (the caller's, swv2_lamb_ws_bytes(n_items, n_chunks) bytes, 4-byte aligned), as floats, after the calls:
+ *   [SWV2_LAMB_WS_GNORM2] |g|^2 = G^2   [SWV2_LAMB_WS_CLIP] c   [SWV2_LAMB_WS_BC1], [SWV2_LAMB_WS_BC2] bc1, bc2 of the last group
+ *   [SWV2_LAMB_WS_ITEM(i) + 0, 1, 2]  |p|^2, |u|^2, r of item i;  the rest (chunk partial sums) is scratch.
+ * swv2_lamb_grad_norm: ONE launch, the chunk partial sums of |g|^2 over all items.  swv2_lamb_multi: one group, items [item_lo, item_hi)
+ * = chunks [chunk_lo, chunk_hi), four launches (|g|^2 and c; m, v and the partial sums of p^2, u^2; the norms and r; the update).
+ * extra_gnorm2: NULL or a device float added to |g|^2, the share of tensors the caller updates itself.  A refused call (null table,
+ * n_chunks <= 0, step < 1, a range outside the tables, a workspace that is too small) launches nothing and writes nothing. */
+typedef struct swv2_lamb_item {
+    float* p;
+    const float* g;
+    float* m;
+    float* v;
+    long n;
+    long chunk0;
+} swv2_lamb_item;
+#define SWV2_LAMB_SUM_DEPTH 64
+#define SWV2_LAMB_ADAMW 1
+#define SWV2_LAMB_BIAS_CORRECTION 2
+#define SWV2_LAMB_GRAD_AVERAGING 4
+#define SWV2_LAMB_NVLAMB 8
+#define SWV2_LAMB_WS_GNORM2 0
+#define SWV2_LAMB_WS_CLIP 1
+#define SWV2_LAMB_WS_BC1 2
+#define SWV2_LAMB_WS_BC2 3
+#define SWV2_LAMB_WS_ITEM(i) (4 + 4 * (i))
+int swv2_lamb_chunk(void);
+size_t swv2_lamb_ws_bytes(int n_items, int n_chunks);      /* 4 * (SWV2_LAMB_WS_ITEM(n_items) + 6 * n_chunks); 0 for a non-positive count */
+int swv2_lamb_grad_norm(const swv2_lamb_item* items_dev, const int* chunks_dev, int n_items, int n_chunks, float grad_inv_scale, void* ws,
+                        size_t ws_bytes, void* stream);
+int swv2_lamb_multi(const swv2_lamb_item* items_dev, const int* chunks_dev, int n_items, int n_chunks, int item_lo, int item_hi,
+                    int chunk_lo, int chunk_hi, float lr, float beta1, float beta2, float eps, float weight_decay, float grad_inv_scale,
+                    float max_grad_norm, int step, int flags, const float* extra_gnorm2, void* ws, size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * ERA5 input assembly (the step BEFORE the model): raw time slabs staged on the device by async H2D copies

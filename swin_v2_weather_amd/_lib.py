@@ -13,9 +13,9 @@ import threading
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB_PATH = os.environ.get("SWV2_LIB") or os.path.join(HERE, "libswv2.so")     # SWV2_LIB: a privately built variant (tools/ab_macro.sh)
-SOURCES = ["capi.hip", "attn.hip", "attn2.hip", "attn_bwd_stream.hip", "attn_wide.hip", "attn_d256.hip", "gemm.hip", "gemm_tn.hip", "gemm_tn_slab.hip", "rowops.hip", "block.hip", "cpb.hip", "mlp.hip", "proj_ln.hip", "dataio.hip"]
+SOURCES = ["capi.hip", "attn.hip", "attn2.hip", "attn_bwd_stream.hip", "attn_wide.hip", "attn_d256.hip", "gemm.hip", "gemm_tn.hip", "gemm_tn_slab.hip", "rowops.hip", "lamb.hip", "block.hip", "cpb.hip", "mlp.hip", "proj_ln.hip", "dataio.hip"]
 
-ABI_VERSION = 110          # SWV2_VERSION of the include/swv2.h these ctypes mirrors were written against (checked in load())
+ABI_VERSION = 111          # SWV2_VERSION of the include/swv2.h these ctypes mirrors were written against (checked in load())
 
 _lib = None
 _lock = threading.Lock()
@@ -166,6 +166,16 @@ class BlockDesc(C.Structure):
                  ("bias_prepacked", C.c_int), ("dbias_part", C.c_void_p), ("dbias_part_bytes", C.c_size_t)])
 
 
+LAMB_ADAMW, LAMB_BIAS_CORRECTION, LAMB_GRAD_AVERAGING, LAMB_NVLAMB = 1, 2, 4, 8      # SWV2_LAMB_*: flags of swv2_lamb_multi
+LAMB_SUM_DEPTH = 64           # SWV2_LAMB_SUM_DEPTH
+LAMB_WS_GNORM2, LAMB_WS_CLIP, LAMB_WS_BC1, LAMB_WS_BC2 = range(4)      # SWV2_LAMB_WS_*: floats at the head of the workspace
+
+
+def lamb_ws_item(i: int) -> int:
+    """SWV2_LAMB_WS_ITEM: float offset of item i's (|p|^2, |u|^2, r) in the workspace"""
+    return 4 + 4 * i
+
+
 BLOCK_MAX_STEPS = 12          # SWV2_BLOCK_MAX_STEPS
 DBIAS_NONE, DBIAS_ATOMICS, DBIAS_WGRAD_WS, DBIAS_PART = range(4)      # swv2_block_plan_t.dbias_dest
 
@@ -240,6 +250,10 @@ SYMBOLS = {
     "swv2_adam_chunk": (_I, []),
     "swv2_adam_multi": (_I, [_P, _P, _I, _F, _F, _F, _F, _I, _F, _P]),
     "swv2_adam_step": (_I, [_P, _P, _P, _P, _L, _F, _F, _F, _F, _I, _F, _P]),
+    "swv2_lamb_chunk": (_I, []),
+    "swv2_lamb_ws_bytes": (C.c_size_t, [_I, _I]),
+    "swv2_lamb_grad_norm": (_I, [_P, _P, _I, _I, _F, _P, C.c_size_t, _P]),
+    "swv2_lamb_multi": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _F, _F, _F, _F, _F, _F, _F, _I, _I, _P, _P, C.c_size_t, _P]),
     "swv2_era5_select_normalize": (_I, [_P, _P, _P, _P, _P] + [_I] * 10 + [_P]),
     "swv2_era5_zenith": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P]),
     "swv2_era5_static": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P]),

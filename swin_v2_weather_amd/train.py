@@ -6,8 +6,8 @@ same checkpoint dictionary and experiment-directory layout -- driving the HIP-ba
 
 Differences that are deliberate (reference quirks):
   * single-process runs work (the reference calls dist.get_world_size() without a group, train.py:294);
-  * wandb / apex / ruamel are optional: absent here, so logging goes to screen/file and `optimizer_type: FusedLAMB`
-    raises; hyperparams.yaml is written with PyYAML;
+  * wandb / apex / ruamel are optional: absent here, so logging goes to screen/file and hyperparams.yaml is written with PyYAML;
+    `optimizer_type: FusedLAMB` builds utils/optim.HipLamb, apex FusedLAMB's algorithm on this package's own HIP kernels;
   * --enable_amp is accepted for CLI compatibility.  The HIP path always computes its GEMMs and attention on bf16 MFMA
     with fp32 accumulation, fp32 LayerNorm / softmax / residual stream (what autocast does in the reference), and bf16
     needs no GradScaler, so the flag only sets params.enable_amp.  WITHOUT the flag the reference computes in fp32
@@ -154,7 +154,8 @@ class Trainer():
             else:
                 self.optimizer = torch.optim.Adam(self.model.parameters(), lr=params.lr, betas=(0.9, 0.95))
         elif params.optimizer_type == 'FusedLAMB':
-            raise Exception("optimizer type FusedLAMB needs apex, which is not available in this build")
+            from .utils.optim import HipLamb
+            self.optimizer = HipLamb(self.model.parameters(), lr=params.lr, max_grad_norm=5.)
         else:
             raise Exception(f"optimizer type {params.optimizer_type} not implemented")
 

@@ -1,4 +1,6 @@
-"""Adam on the HIP multi-tensor kernel (reference train.py:176: `optim.Adam(model.parameters(), lr, betas=(0.9, 0.95))`,
+"""Adam and LAMB on the HIP multi-tensor kernels.
+
+Adam (reference train.py:176: `optim.Adam(model.parameters(), lr, betas=(0.9, 0.95))`,
 stepped at train.py:330).
 
 `HipAdam` is a drop-in `torch.optim.Adam`: same constructor, same `state_dict()` layout (`step`, `exp_avg`, `exp_avg_sq`
@@ -6,6 +8,9 @@ per parameter, so the reference's checkpoints restore into it and its checkpoint
 updates every fp32 CUDA parameter of a group with ONE `swv2_adam_multi` launch (torch's fused path: 5 launches of ~45 us
 for the depth-12 model); options the kernel does not implement (amsgrad, weight decay, maximize, non-fp32 or CPU
 parameters) take torch's own path for that group, so nothing is silently dropped.
+
+`HipLamb` is apex's `FusedLAMB` (reference train.py:177-178: `optimizers.FusedLAMB(model.parameters(), lr, max_grad_norm=5.)`) on
+`swv2_lamb_grad_norm` / `swv2_lamb_multi`: see the class.
 """
 from __future__ import annotations
 
@@ -141,3 +146,229 @@ class HipAdam(torch.optim.Adam):
             finally:
                 self.param_groups = keep
         return loss
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# LAMB
+# ---------------------------------------------------------------------------------------------------------------
+class _LambItem(C.Structure):
+    _fields_ = [("p", C.c_void_p), ("g", C.c_void_p), ("m", C.c_void_p), ("v", C.c_void_p), ("n", C.c_long), ("chunk0", C.c_long)]
+
+
+def _f32(x) -> float:
+    """the fp32 value of a scalar, as a Python float: what the kernel receives (1 - beta2 formed from the DOUBLE 0.999 is off by 3e-5)"""
+    return float(np.float32(x))
+
+
+class HipLamb(torch.optim.Optimizer):
+    """apex `FusedLAMB`: the same constructor, defaults and state layout (`state[p] = {exp_avg, exp_avg_sq}`, one step counter per group
+    in `group['step']`, 1 on the first step), so its checkpoints restore here.  `amsgrad=True` raises, as in apex.
+
+    One `step()`:
+      1. G = sqrt(sum over the gradients of ALL groups of (g * grad_inv_scale)^2); c = G / max_grad_norm if G > max_grad_norm else 1
+         (max_grad_norm is the constructor's value, not a group's); g^ = g * grad_inv_scale / c.
+      2. per element, b3 = 1 - beta1 if grad_averaging else 1, bc_i = 1 - beta_i^step if bias_correction else 1:
+         adam_w_mode:  m <- beta1 m + b3 g^, v <- beta2 v + (1 - beta2) g^^2, a = (m / bc1) / (sqrt(v / bc2) + eps), u = a + weight_decay p
+         otherwise  :  g^ <- g^ + weight_decay p first, then m, v, a as above and u = a.
+      3. per tensor, r = |p| / |u| if (use_nvlamb or weight_decay != 0) and |p| != 0 and |u| != 0 else 1, |p| before the update.
+      4. p <- p - lr r u.
+    Non-finite gradients are NOT skipped: they propagate into m, v, the norms and p as the arithmetic dictates (an inf in one gradient
+    makes G inf and every g^ zero or NaN); guard the step from outside if the loss can overflow.
+
+    fp32, dense parameters on one GPU take the HIP kernels: one gradient-norm launch per step over all groups and four launches per group,
+    44 bytes moved per parameter, gradients only read (apex overwrites them with u; here u is recomputed from m, v and the old p), no
+    read-back and no synchronisation (pointer tables are uploaded from two pinned buffers, as in `HipAdam`).  A group the kernels cannot take
+    (CPU tensors, another dtype, non-dense layouts, sparse gradients) runs the same algorithm in torch ops, in float64 rounded once to the
+    tensors' dtype; the norm G always spans both kinds of group.  After a step `kernel_norms()` returns what the kernels stored: G^2 and
+    (|p|^2, |u|^2, r) per parameter, still on the device.
+    """
+
+    def __init__(self, params, lr=1e-3, bias_correction=True, betas=(0.9, 0.999), eps=1e-6, weight_decay=0.01, amsgrad=False,
+                 adam_w_mode=True, grad_averaging=True, set_grad_none=True, max_grad_norm=1.0, use_nvlamb=False):
+        if amsgrad:
+            raise RuntimeError("HipLamb does not support the AMSGrad variant.")
+        defaults = dict(lr=lr, bias_correction=bias_correction, betas=betas, eps=eps, weight_decay=weight_decay,
+                        grad_averaging=grad_averaging, max_grad_norm=max_grad_norm)
+        super().__init__(params, defaults)
+        self.adam_w_mode = 1 if adam_w_mode else 0
+        self.set_grad_none = set_grad_none
+        self.use_nvlamb = use_nvlamb
+        self._table = None          # launch tables of the groups the kernels take
+        self._torch_only = set()    # groups found unfit for the kernels (by index)
+
+    def __getstate__(self):
+        # (torch's Optimizer pickles defaults, state and param_groups only; the launch tables hold events and pinned buffers and stay behind)
+        return dict(super().__getstate__(), adam_w_mode=self.adam_w_mode, set_grad_none=self.set_grad_none, use_nvlamb=self.use_nvlamb)
+
+    def __setstate__(self, state):
+        super().__setstate__(state)
+        self._table, self._torch_only = None, set()
+
+    def zero_grad(self, set_to_none=None):
+        super().zero_grad(set_to_none=self.set_grad_none if set_to_none is None else set_to_none)
+
+    def load_state_dict(self, state_dict):
+        super().load_state_dict(state_dict)
+        self._table, self._torch_only = None, set()
+
+    # ---- launch tables -------------------------------------------------------------------------------------
+    @staticmethod
+    def _kernel_ok(p, s, dev):
+        g = p.grad
+        return (p.is_cuda and p.device == dev and p.dtype == torch.float32 and not g.is_sparse and g.dtype == torch.float32 and
+                g.device == dev and _dense(p) and g.stride() == p.stride() and
+                all(s[k].dtype == torch.float32 and s[k].device == dev and s[k].stride() == p.stride() for k in ("exp_avg", "exp_avg_sq")))
+
+    def _tables_for(self, work, dev):
+        """ONE item table and ONE chunk table for the tensors of every group the kernels take (group = a range of both), the workspace and
+        the pinned staging; sizes are static per parameter set, pointers are refreshed by `_upload`."""
+        sig = tuple((gi, tuple((p.data_ptr(), p.numel()) for p in pl)) for gi, _, pl in work)
+        t = self._table
+        if t is not None and t["sig"] == sig:
+            return t
+        lib = L.load()
+        chunk = lib.swv2_lamb_chunk()
+        pairs, chunk0, ranges, n_items = [], [], {}, 0
+        for gi, _, pl in work:
+            lo = (n_items, len(pairs))
+            for p in pl:
+                chunk0.append(len(pairs))
+                pairs += [(n_items, c) for c in range((p.numel() + chunk - 1) // chunk)]
+                n_items += 1
+            ranges[gi] = lo + (n_items, len(pairs))           # item_lo, chunk_lo, item_hi, chunk_hi
+        nbytes = C.sizeof(_LambItem) * n_items
+        ws_bytes = lib.swv2_lamb_ws_bytes(n_items, len(pairs))
+        t = {"sig": sig, "ranges": ranges, "chunk0": chunk0, "n_items": n_items, "n_chunks": len(pairs), "rows": None,
+             "host": [torch.empty(nbytes, dtype=torch.uint8).pin_memory() for _ in range(2)], "events": [None, None], "flip": 0,
+             "dev": torch.empty(nbytes, dtype=torch.uint8, device=dev), "chunks": torch.tensor(pairs, dtype=torch.int32).to(dev),
+             "ws": torch.zeros(ws_bytes // 4, dtype=torch.float32, device=dev), "ws_bytes": ws_bytes,
+             "params": [p for _, _, pl in work for p in pl]}
+        self._table = t
+        return t
+
+    @staticmethod
+    def _upload(t, rows):
+        """the pointer table through two pinned buffers used alternately, each guarded by an event behind its copy (`HipAdam._refresh`)"""
+        t["flip"] = 1 - t["flip"]
+        host, ev = t["host"][t["flip"]], t["events"]
+        if ev[t["flip"]] is not None:
+            ev[t["flip"]].synchronize()
+        np.frombuffer(host.numpy(), dtype=np.int64).reshape(t["n_items"], 6)[:] = np.asarray(rows, dtype=np.int64)
+        t["dev"].copy_(host, non_blocking=True)
+        e = torch.cuda.Event()
+        e.record(torch.cuda.current_stream(t["dev"].device))
+        ev[t["flip"]] = e
+        t["rows"] = rows
+
+    def kernel_norms(self):
+        """(G^2, {parameter: float tensor (|p|^2, |u|^2, r)}) as the kernels of the last step stored them (device tensors, views of the
+        workspace); None when no group took the kernels"""
+        t = self._table
+        if t is None:
+            return None
+        ws = t["ws"]
+        return ws[L.LAMB_WS_GNORM2], {p: ws[L.lamb_ws_item(i):L.lamb_ws_item(i) + 3] for i, p in enumerate(t["params"])}
+
+    # ---- step ----------------------------------------------------------------------------------------------
+    def _flags(self, group):
+        return ((L.LAMB_ADAMW if self.adam_w_mode else 0) | (L.LAMB_BIAS_CORRECTION if group["bias_correction"] else 0) |
+                (L.LAMB_GRAD_AVERAGING if group["grad_averaging"] else 0) | (L.LAMB_NVLAMB if self.use_nvlamb else 0))
+
+    @torch.no_grad()
+    def step(self, closure=None, grad_inv_scale: float = 1.0):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        inv = _f32(grad_inv_scale)
+        max_norm = _f32(self.defaults["max_grad_norm"])
+        groups = []
+        for gi, group in enumerate(self.param_groups):
+            group["step"] = group["step"] + 1 if "step" in group else 1
+            plist = [p for p in group["params"] if p.grad is not None and p.numel() > 0]
+            for p in plist:
+                s = self.state[p]
+                if len(s) == 0:
+                    s["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+                    s["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+            if plist:
+                groups.append((gi, group, plist))
+        # which groups the kernels take: the first CUDA parameter names the device; tensors are looked at again whenever a pointer moved
+        dev = next((p.device for _, _, pl in groups for p in pl if p.is_cuda), None)
+        while True:
+            work = [w for w in groups if dev is not None and w[0] not in self._torch_only]
+            if not work:
+                self._table, t = None, None
+                break
+            t = self._tables_for(work, dev)
+            rows = tuple((p.data_ptr(), p.grad.data_ptr(), self.state[p]["exp_avg"].data_ptr(), self.state[p]["exp_avg_sq"].data_ptr(),
+                          p.numel(), c0) for p, c0 in zip(t["params"], t["chunk0"]))
+            if rows == t["rows"]:
+                break
+            bad = {gi for gi, _, pl in work if not all(self._kernel_ok(p, self.state[p], dev) for p in pl)}
+            if not bad:
+                self._upload(t, rows)
+                break
+            self._torch_only |= bad
+        slow = [w for w in groups if t is None or w[0] not in t["ranges"]]
+        # the slow groups' share of G^2 (float64), handed to the kernels as a device float
+        extra = None
+        for _, _, pl in slow:
+            for p in pl:
+                g = p.grad.to_dense() if p.grad.is_sparse else p.grad
+                e = (g.double() * inv).pow(2).sum()
+                extra = e if extra is None else extra + e.to(extra.device)
+        if t is not None:
+            lib = L.load()
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            extra_dev = extra.to(dev, torch.float32).reshape(1) if extra is not None else None
+            ws = t["ws"]
+            L.check(lib.swv2_lamb_grad_norm(t["dev"].data_ptr(), t["chunks"].data_ptr(), t["n_items"], t["n_chunks"], inv, ws.data_ptr(),
+                                            t["ws_bytes"], stream), "swv2_lamb_grad_norm")
+            for gi, group, pl in work:
+                i0, c0, i1, c1 = t["ranges"][gi]
+                b1, b2 = group["betas"]
+                L.check(lib.swv2_lamb_multi(t["dev"].data_ptr(), t["chunks"].data_ptr(), t["n_items"], t["n_chunks"], i0, i1, c0, c1,
+                                            float(group["lr"]), float(b1), float(b2), float(group["eps"]), float(group["weight_decay"]), inv,
+                                            max_norm, int(group["step"]), self._flags(group),
+                                            extra_dev.data_ptr() if extra_dev is not None else None, ws.data_ptr(), t["ws_bytes"], stream),
+                        "swv2_lamb_multi")
+                # the kernel wrote the parameters behind autograd's back: bump their version counters like an in-place torch op would
+                torch.autograd.graph.increment_version(pl)
+            clip = ws[L.LAMB_WS_CLIP].double()             # the kernels' own c (spans both kinds of group)
+        elif extra is not None:
+            G = extra.sqrt()
+            clip = torch.where(G > max_norm, G / max_norm, torch.ones_like(G))
+        for _, group, pl in slow:
+            self._torch_group(group, pl, clip, inv)
+        return loss
+
+    def _torch_group(self, group, plist, clip, inv, ratios=None):
+        """the update of one group in torch ops: float64 arithmetic on the fp32 values of the scalars, rounded once into m, v and p.
+        ratios: {parameter: r} taken in place of the tensors' own trust ratios (a test steps both paths from the same c and r)"""
+        b1, b2 = (_f32(b) for b in group["betas"])
+        b3 = 1.0 - b1 if group["grad_averaging"] else 1.0
+        eps, lr, wd, step = _f32(group["eps"]), _f32(group["lr"]), _f32(group["weight_decay"]), int(group["step"])
+        bc1 = _f32(1.0 - b1 ** step) if group["bias_correction"] else 1.0
+        bc2 = _f32(1.0 - b2 ** step) if group["bias_correction"] else 1.0
+        for p in plist:
+            s = self.state[p]
+            m, v = s["exp_avg"], s["exp_avg_sq"]
+            g = p.grad.to_dense() if p.grad.is_sparse else p.grad
+            p64 = p.double()
+            gh = g.double() * inv / clip.to(p.device)
+            if not self.adam_w_mode:
+                gh = gh + wd * p64
+            m.copy_(b1 * m.double() + b3 * gh)
+            v.copy_(b2 * v.double() + (1.0 - b2) * gh * gh)
+            u = (m.double() / bc1) / ((v.double() / bc2).sqrt() + eps)         # from the moments as stored, like the kernels' stage 2
+            if self.adam_w_mode:
+                u = u + wd * p64
+            if ratios is not None:
+                r = ratios[p]
+            elif self.use_nvlamb or wd != 0:
+                pn, un = p64.norm(), u.norm()
+                r = torch.where((pn != 0) & (un != 0), pn / un, torch.ones_like(pn))
+            else:
+                r = 1.0
+            p.copy_(p64 - lr * r * u)

@@ -1,0 +1,441 @@
+"""GPU: the LAMB kernels (csrc/lamb.hip: swv2_lamb_grad_norm / swv2_lamb_multi) element by element against the fp64 statement in
+tests/lamb_reference.py, whose docstring derives every bound used here; then utils/optim.HipLamb on a model's real gradients against its
+own torch path, and the Trainer with `optimizer_type: FusedLAMB`.
+
+Every output is judged from the kernel's own upstream values (the stored |g|^2, bc1, bc2, the stored new m and v, the stored norms and r),
+steps are chained, and each step starts from the state the kernel itself left.  Each case prints its worst error / bound ratios."""
+import copy
+import ctypes
+import os
+from types import SimpleNamespace
+
+import numpy as np
+import pytest
+import torch
+
+from swin_v2_weather_amd import _lib as L
+from tests import lamb_reference as R
+
+pytestmark = pytest.mark.gpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CHUNK = 4096
+SIZES = [1, 5, 4095, 4096, 4097, 3 * 4096 + 5, 70 * 4096 + 123]
+SENT = -123456.75            # guard value around every p, g, m, v
+GUARD = 4                    # guard elements on each side: 16 bytes, so the interior keeps the buffer's alignment
+# extra elements in front: tensor 5 is a slice starting one element into its buffers (all four unaligned: the scalar path for four
+# chunks, one of them partial); tensor 2 has only its gradient off (one unaligned pointer of four is enough to leave the 16-byte path)
+SHIFT = {5: dict(p=1, g=1, m=1, v=1), 2: dict(g=1)}
+U, D = R.U, R.D
+
+
+@pytest.fixture(scope="module")
+def dev():
+    assert torch.cuda.is_available(), "GPU tests need an MI355X"
+    return torch.device("cuda:0")
+
+
+class Bed:
+    """p, g, m, v of a list of tensors between guards, the launch tables over `groups` (lists of tensor indices, items in that order)
+    and the workspace; `launch` is one optimizer step through the C ABI."""
+
+    def __init__(self, dev, sizes, groups, shift=None):
+        from swin_v2_weather_amd.utils.optim import _LambItem
+        self.dev, self.sizes, self.groups = dev, sizes, groups
+        self.order = [i for g in groups for i in g]
+        self.buf, self.view = {}, {}
+        for i in self.order:
+            for k in "pgmv":
+                s = (shift or {}).get(i, {}).get(k, 0)
+                b = torch.full((sizes[i] + 2 * GUARD + s,), SENT, dtype=torch.float32, device=dev)
+                self.buf[k, i], self.view[k, i] = b, b[GUARD + s:GUARD + s + sizes[i]]
+                assert self.view[k, i].data_ptr() % 16 == 4 * s
+        rows, pairs, self.ranges = [], [], []
+        for g in groups:
+            lo = (len(rows), len(pairs))
+            for i in g:
+                rows.append([self.view[k, i].data_ptr() for k in "pgmv"] + [sizes[i], len(pairs)])
+                pairs += [(len(rows) - 1, c) for c in range((sizes[i] + CHUNK - 1) // CHUNK)]
+            self.ranges.append(lo + (len(rows), len(pairs)))
+        assert ctypes.sizeof(_LambItem) == 48
+        self.n_items, self.n_chunks = len(rows), len(pairs)
+        self.items = torch.tensor(rows, dtype=torch.int64).to(dev)
+        self.chunks = torch.tensor(pairs, dtype=torch.int32).to(dev)
+        self.ws_bytes = L.load().swv2_lamb_ws_bytes(self.n_items, self.n_chunks)
+        self.ws = torch.zeros(self.ws_bytes // 4, dtype=torch.float32, device=dev)
+        self.item_of = {i: k for k, i in enumerate(self.order)}
+
+    def put(self, k, i, x):
+        self.view[k, i].copy_(torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32)))
+
+    def get(self, k, i):
+        return self.view[k, i].cpu().numpy().copy()
+
+    def guards_intact(self):
+        for (k, i), b in self.buf.items():
+            s = b.numel() - self.sizes[i] - 2 * GUARD
+            b = b.cpu()
+            if not (bool((b[:GUARD + s] == SENT).all()) and bool((b[GUARD + s + self.sizes[i]:] == SENT).all())):
+                return False
+        return True
+
+    def launch(self, hypers, inv, max_norm, extra=None):
+        """hypers: one lamb_reference.Hyper per group"""
+        lib = L.load()
+        st = torch.cuda.current_stream(self.dev).cuda_stream
+        tabs = (self.items.data_ptr(), self.chunks.data_ptr(), self.n_items, self.n_chunks)
+        L.check(lib.swv2_lamb_grad_norm(*tabs, inv, self.ws.data_ptr(), self.ws_bytes, st), "swv2_lamb_grad_norm")
+        for h, (i0, c0, i1, c1) in zip(hypers, self.ranges):
+            flags = ((L.LAMB_ADAMW if h.adam_w_mode else 0) | (L.LAMB_BIAS_CORRECTION if h.bias_correction else 0) |
+                     (L.LAMB_GRAD_AVERAGING if h.grad_averaging else 0) | (L.LAMB_NVLAMB if h.use_nvlamb else 0))
+            L.check(lib.swv2_lamb_multi(*tabs, i0, i1, c0, c1, h.lr, h.beta1, h.beta2, h.eps, h.weight_decay, inv, max_norm, h.step, flags,
+                                        extra.data_ptr() if extra is not None else None, self.ws.data_ptr(), self.ws_bytes, st),
+                    "swv2_lamb_multi")
+        torch.cuda.synchronize(self.dev)
+
+
+def carry_tail(x):
+    """the last element of a tensor whose last chunk is partial is 100 x the largest other magnitude: a dropped tail moves a norm by far
+    more than its bound"""
+    if x.size % CHUNK and x.size > 1:
+        x[-1] = 100.0 * np.abs(x[:-1]).max()
+    return x
+
+
+def draw_p(rng, n):
+    return carry_tail((0.02 * rng.standard_normal(n)).astype(np.float32))
+
+
+def draw_g(rng, n, scale):
+    """log-uniform magnitudes over e^-6 .. 1, times scale, random signs"""
+    return carry_tail((scale * np.exp(rng.uniform(-6, 0, n)) * rng.choice([-1.0, 1.0], n)).astype(np.float32))
+
+
+def ratio(err, bound):
+    """largest error / bound over the elements (an exact 0 <= 0 counts as 0)"""
+    err, bound = np.atleast_1d(np.abs(err)), np.atleast_1d(bound)
+    assert np.all(np.isfinite(err)) and np.all(np.isfinite(bound))
+    return float(np.max(np.where(err == 0, 0.0, err / np.where(bound == 0, np.finfo(np.float64).tiny, bound))))
+
+
+def judge_step(bed, old, grads, hypers, inv, max_norm, worst, extra2=0.0, expect_one=()):
+    """everything one launch left behind against the reference; `old` = {(k, i): array} of p, m, v before the step.  expect_one: tensors
+    whose trust ratio must be exactly 1 beyond the weight_decay = 0 rule.  Returns the kernel's clip divisor."""
+    def note(k, val):
+        worst[k] = max(worst.get(k, 0.0), val)
+    ws = bed.ws.cpu().numpy()
+    assert bed.guards_intact()
+    for i in bed.order:
+        assert np.array_equal(bed.get("g", i).view(np.uint32), grads[i].view(np.uint32)), "gradient %d was written" % i
+    # |g|^2 over ALL groups, the clip divisor from the stored value, the bias corrections
+    g2_ref = R.grad_norm2([grads[i] for i in bed.order], inv) + extra2
+    g2 = float(ws[L.LAMB_WS_GNORM2])
+    note("gnorm2", ratio(g2 - g2_ref, (D + 2) * U * g2_ref))
+    c_ref = R.clip_divisor(g2, max_norm)
+    c = float(ws[L.LAMB_WS_CLIP])
+    if c_ref == 1.0:
+        assert c == 1.0
+    else:
+        note("clip", ratio(c - c_ref, 2 * U * c_ref))
+    bc_ref = hypers[-1].bias_corrections()
+    bc = (float(ws[L.LAMB_WS_BC1]), float(ws[L.LAMB_WS_BC2]))
+    assert all(abs(a - b) <= 2 * U * b for a, b in zip(bc, bc_ref)) and (hypers[-1].bias_correction or bc == (1.0, 1.0))
+    for h, group in zip(hypers, bed.groups):
+        bcs = h.bias_corrections()
+        for i in group:
+            p0, m0, v0 = (old[k, i] for k in "pmv")
+            m1, v1, p1 = bed.get("m", i), bed.get("v", i), bed.get("p", i)
+            m_ref, v_ref, bm, bv, _ = R.moments(p0, grads[i], m0, v0, h, c_ref)
+            note("m", ratio(m1 - m_ref, bm))
+            note("v", ratio(v1 - v_ref, bv))
+            a, u = R.update(p0, m1, v1, h, bcs)
+            o = L.lamb_ws_item(bed.item_of[i])
+            p2, u2, r = (float(x) for x in ws[o:o + 3])
+            p2_ref, u2_ref = float(np.sum(R.d(p0) ** 2)), float(np.sum(u ** 2))
+            note("pnorm2", ratio(p2 - p2_ref, (D + 2) * U * p2_ref))
+            note("unorm2", ratio(u2 - u2_ref, (D + 2 + 2 * 16) * U * u2_ref))
+            assert (p2 == 0.0) == (p2_ref == 0.0) and (u2 == 0.0) == (u2_ref == 0.0)
+            r_ref = R.trust_ratio(p2, u2, h)
+            if r_ref == 1.0 and (not h.uses_ratio or p2 == 0 or u2 == 0):
+                assert r == 1.0
+            else:
+                note("r", ratio(r - r_ref, 4 * U * r_ref))
+            if i in expect_one or not h.uses_ratio:
+                assert r == 1.0, (i, r)
+            p_ref, bp = R.apply(p0, a, u, r, h)
+            note("p", ratio(p1 - p_ref, bp))
+    return c
+
+
+def run_case(dev, name, groups, wds, steps=5, gscale=10.0, inv=1.0, max_norm=1.0, zero_p=(), zero_g=(), clipped=True, **mode):
+    """`steps` chained steps of one configuration; asserts every bound, returns the worst error / bound ratios"""
+    rng = np.random.default_rng(sum(map(ord, name)))
+    bed = Bed(dev, SIZES, groups, SHIFT)
+    for i in bed.order:
+        bed.put("p", i, np.zeros(SIZES[i], np.float32) if i in zero_p else draw_p(rng, SIZES[i]))
+        bed.put("m", i, np.zeros(SIZES[i], np.float32))            # step 1 starts from all-zero moments
+        bed.put("v", i, np.zeros(SIZES[i], np.float32))
+    worst = {}
+    for step in range(1, steps + 1):
+        hypers = [R.Hyper(lr=2e-3, weight_decay=wd, grad_inv_scale=inv, max_grad_norm=max_norm, step=step, **mode) for wd in wds]
+        grads = {i: (np.zeros(SIZES[i], np.float32) if i in zero_g else draw_g(rng, SIZES[i], gscale / inv)) for i in bed.order}
+        for i in bed.order:
+            bed.put("g", i, grads[i])
+        old = {(k, i): bed.get(k, i) for i in bed.order for k in "pmv"}
+        bed.launch(hypers, inv, max_norm)
+        c = judge_step(bed, old, grads, hypers, inv, max_norm, worst,
+                       expect_one=tuple(zero_p if step == 1 else ()) + tuple(zero_g))
+        assert (c > 1.5) if clipped else (c == 1.0), c
+        if step == 2:                # the same step again from the same state: the same bits everywhere
+            after = {(k, i): bed.get(k, i) for i in bed.order for k in "pmv"}
+            ws1 = bed.ws.clone()
+            for (k, i), x in old.items():
+                bed.put(k, i, x)
+            bed.launch(hypers, inv, max_norm)
+            assert torch.equal(bed.ws.view(torch.int32), ws1.view(torch.int32))
+            for (k, i), x in after.items():
+                assert np.array_equal(bed.get(k, i).view(np.uint32), x.view(np.uint32)), (k, i)
+    print("lamb worst error/bound  %-22s " % name + "  ".join("%s %.3f" % kv for kv in sorted(worst.items())))
+    for k, val in worst.items():
+        assert val <= 1.0, (name, k, val)
+    return worst
+
+
+ALL = [list(range(len(SIZES)))]
+CASES = {
+    # G ~ 1e3 >> max_grad_norm = 1; tensor 3 starts as all zeros (|p| = 0 on step 1 -> r = 1)
+    "clipped": dict(groups=ALL, wds=[0.01], zero_p=(3,)),
+    # G ~ 0.1 << max_grad_norm = 5: c is exactly 1
+    "unclipped": dict(groups=ALL, wds=[0.01], gscale=1e-3, max_norm=5.0, clipped=False),
+    # two groups, weight_decay 0.01 and 0 (r = 1 there); the clip norm spans both; gradients arrive scaled by 128
+    "two_groups_scaled": dict(groups=[[0, 2, 4, 6], [1, 3, 5]], wds=[0.01, 0.0], inv=1.0 / 128),
+    "no_decay": dict(groups=ALL, wds=[0.0]),
+    # use_nvlamb takes the ratio at weight_decay = 0; tensor 1 never gets a gradient: u = 0 there, |p| != 0 -> r = 1
+    "nvlamb_no_decay": dict(groups=ALL, wds=[0.0], use_nvlamb=True, zero_g=(1,)),
+    "l2_mode": dict(groups=ALL, wds=[0.01], adam_w_mode=False),
+    "no_bias_correction": dict(groups=ALL, wds=[0.01], bias_correction=False),
+    "no_grad_averaging": dict(groups=ALL, wds=[0.01], grad_averaging=False),
+}
+
+
+@pytest.mark.parametrize("name", sorted(CASES))
+def test_lamb_kernels_against_fp64(dev, name):
+    w = run_case(dev, name, **CASES[name])
+    assert {"gnorm2", "m", "v", "p", "pnorm2", "unorm2"} <= set(w)
+    if name in ("clipped", "l2_mode", "nvlamb_no_decay"):
+        assert "r" in w and "clip" in w                  # (a ratio other than 1 and a clip other than 1 were judged)
+
+
+def test_results_do_not_depend_on_the_alignment_of_the_buffers(dev):
+    """The same tensors once 16-byte aligned and once shifted by one element (16-byte accesses against single-element ones): the same
+    thread sums the same elements in the same order, so p, m, v and every stored norm agree bit for bit -- a restored checkpoint continues
+    identically wherever the allocator puts its buffers (gradients written into slices of a shared buffer are not aligned)."""
+    rng = np.random.default_rng(11)
+    data = {(k, i): (draw_g(rng, n, 10.0) if k == "g" else draw_p(rng, n) if k == "p" else
+                     (1e-2 * rng.standard_normal(n)).astype(np.float32) if k == "m" else (1e-3 * rng.random(n)).astype(np.float32))
+            for i, n in enumerate(SIZES) for k in "pgmv"}
+    h = [R.Hyper(lr=2e-3, step=4)]
+    out = []
+    for shift in (None, {i: dict(p=1, g=1, m=1, v=1) for i in range(len(SIZES))}, SHIFT):
+        bed = Bed(dev, SIZES, ALL, shift)
+        for (k, i), x in data.items():
+            bed.put(k, i, x)
+        bed.launch(h, 1.0, 1.0)
+        assert bed.guards_intact()
+        out.append(({(k, i): bed.get(k, i) for i in bed.order for k in "pmv"}, bed.ws[:L.lamb_ws_item(bed.n_items)].cpu().numpy()))
+    for res, ws in out[1:]:
+        assert np.array_equal(ws.view(np.uint32), out[0][1].view(np.uint32))
+        for key, x in res.items():
+            assert np.array_equal(x.view(np.uint32), out[0][0][key].view(np.uint32)), key
+    assert not np.array_equal(out[0][0]["p", 6], data["p", 6])
+
+
+def test_partial_sums_beyond_one_tree_leaf_and_the_callers_share_of_the_norm(dev):
+    """4 101 chunks in one tensor: the norms' halving passes run twice (4 101 -> 2 051 -> 1 026, an odd count each time; below 2 049
+    chunks they do not run at all), for |g|^2 and for the tensor's |p|^2 and |u|^2.  extra_gnorm2 adds the caller's share to |g|^2.
+    The norms, c and r are judged in full; m, v and p on both ends and every 4 099th element between (their arithmetic does not
+    depend on the size, their addressing does), to keep the fp64 side of a 16.8 M-element tensor within a few seconds."""
+    n = 4100 * CHUNK + 3
+    rng = np.random.default_rng(5)
+    bed = Bed(dev, [n], [[0]])
+    assert bed.n_chunks == 4101
+    tile = lambda x: carry_tail(np.resize(x, n))               # (one 2^20 + 77 element draw repeated: the draw is the slow part)
+    p0, g = tile(draw_p(rng, 2 ** 20 + 77)), tile(draw_g(rng, 2 ** 20 + 77, 1e-3))
+    m0 = tile((1e-4 * rng.standard_normal(2 ** 20 + 77)).astype(np.float32))
+    v0 = tile((1e-8 * rng.random(2 ** 20 + 77)).astype(np.float32))
+    for k, x in zip("pgmv", (p0, g, m0, v0)):
+        bed.put(k, 0, x)
+    extra = torch.tensor([0.25], dtype=torch.float32, device=dev)
+    h = R.Hyper(lr=2e-3, max_grad_norm=0.125, step=3)
+    bed.launch([h], 1.0, 0.125, extra=extra)
+    ws = bed.ws[:L.lamb_ws_item(1)].cpu().numpy()
+    m1, v1, p1 = bed.get("m", 0), bed.get("v", 0), bed.get("p", 0)
+    assert bed.guards_intact() and np.array_equal(bed.get("g", 0).view(np.uint32), g.view(np.uint32))
+    g2, c = float(ws[L.LAMB_WS_GNORM2]), float(ws[L.LAMB_WS_CLIP])
+    p2, u2, r = (float(x) for x in ws[L.lamb_ws_item(0):L.lamb_ws_item(0) + 3])
+    g2_ref = R.grad_norm2([g], 1.0) + 0.25
+    c_ref = R.clip_divisor(g2, 0.125)
+    a, u = R.update(p0, m1, v1, h)
+    p2_ref, u2_ref = float(np.sum(R.d(p0) ** 2)), float(np.sum(u ** 2))
+    worst = {"gnorm2": ratio(g2 - g2_ref, (D + 2) * U * g2_ref), "clip": ratio(c - c_ref, 2 * U * c_ref),
+             "pnorm2": ratio(p2 - p2_ref, (D + 2) * U * p2_ref), "unorm2": ratio(u2 - u2_ref, (D + 34) * U * u2_ref),
+             "r": ratio(r - R.trust_ratio(p2, u2, h), 4 * U * r)}
+    assert c > 1.5 and r != 1.0
+    sub = np.r_[0:5000, 5000:n - 5000:4099, n - 5000:n]
+    m_ref, v_ref, bm, bv, _ = R.moments(p0[sub], g[sub], m0[sub], v0[sub], h, c_ref)
+    p_ref, bp = R.apply(p0[sub], a[sub], u[sub], r, h)
+    worst.update(m=ratio(m1[sub] - m_ref, bm), v=ratio(v1[sub] - v_ref, bv), p=ratio(p1[sub] - p_ref, bp))
+    print("lamb worst error/bound  %-22s " % "tree_4101_chunks" + "  ".join("%s %.3f" % kv for kv in sorted(worst.items())))
+    assert all(val <= 1.0 for val in worst.values()), worst
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# HipLamb on a model, the Trainer
+# ---------------------------------------------------------------------------------------------------------------
+def _tiny_params(tmp):
+    from swin_v2_weather_amd.utils.YParams import YParams
+    p = YParams(os.path.join(ROOT, "swin_v2_weather_amd", "config", "swin.yaml"), "bench_tiny")
+    p["img_size"] = [96, 144]
+    p["window_ratio"] = 16                      # patch grid 24 x 36, window 6 x 9
+    p["embed_dim"], p["num_heads"], p["depth"] = 32, 2, 2
+    p["in_channels"], p["out_channels"] = list(range(6)), list(range(6))
+    p["channel_names"] = p["channel_names"][:6]
+    p["track_channels"] = ["u10m", "t2m"]
+    p["batch_size"], p["max_epochs"] = 2, 1
+    p["synthetic_device_pool"], p["synthetic_steps_per_epoch"] = 2, 3
+    p["exp_dir"], p["save_checkpoint"], p["log_to_screen"] = str(tmp), True, False
+    p["loss"], p["drop_path_rate"], p["rel_pos"] = "squared geometric l2", 0.0, True
+    p["optimizer_type"] = "FusedLAMB"
+    return p
+
+
+def test_hiplamb_on_model_gradients_against_its_torch_path(dev):
+    """Three steps on the depth-2 bench_tiny model's real gradients.  The kernel path is judged like the raw kernels, from its own stored
+    norms.  Each step the torch path (a twin HipLamb's `_torch_group`) restarts from the state the kernel path started from and is fed the
+    kernel path's upstream values: c in fp64 from the stored |g|^2, and the stored r per tensor.  Its fp64 arithmetic is then the reference
+    rounded once, so the two paths are held to the same bounds plus that rounding: m to bound_m + u |m_t|, v to bound_v + u |v_t|.  For p the
+    twin's update comes from ITS m_t, v_t where the kernel's comes from its own m, v: a = (m / bc1) / den, den = sqrt(v / bc2) + eps, moves
+    by at most |dm| / (bc1 den) + |a| |d sqrt(v)| / sqrt(v) with |dm| <= bound_m + u |m_t| and |dv| / (2 v) <= (12 u + u) / 2 (8 u |a| with
+    the second-order terms), hence p to bound_p + u |p_t| + lr r ((bound_m + u |m_t|) / (bc1 den) + 8 u |a|).
+    Before step 3 state_dict() goes into a fresh HipLamb over clones of the parameters; both step, and every p, m, v and the stored
+    norms agree bit for bit.  Every parameter's version counter grows with the step."""
+    from swin_v2_weather_amd.networks.helpers import get_model
+    from swin_v2_weather_amd.utils.optim import HipLamb
+    params = _tiny_params("unused")
+    params["n_in_channels"], params["n_out_channels"] = 6, 6
+    torch.manual_seed(7)
+    model = get_model(params).to(dev).train()
+    plist = [p for p in model.parameters()]
+    kw = dict(lr=1e-3, max_grad_norm=5.0)
+    opt = HipLamb(plist, **kw)
+    g = torch.Generator().manual_seed(1)
+    x, y = torch.randn(2, 6, 96, 144, generator=g).to(dev), torch.randn(2, 6, 96, 144, generator=g).to(dev)
+    worst = {}
+    for step in range(1, 4):
+        model.zero_grad()
+        loss = ((model(x) - y) ** 2).sum()                     # (a sum: G of the order of max_grad_norm and above)
+        loss.backward()
+        live = [p for p in plist if p.grad is not None]
+        old = [(p.detach().clone(), (opt.state[p]["exp_avg"].clone() if p in opt.state else torch.zeros_like(p)),
+                (opt.state[p]["exp_avg_sq"].clone() if p in opt.state else torch.zeros_like(p)), p.grad.clone()) for p in live]
+        fresh = None
+        if step == 3:                                          # a checkpoint taken after step 2 goes on in a fresh optimizer over clones
+            pb = [torch.nn.Parameter(p.detach().clone()) for p in plist]
+            for q, p in zip(pb, plist):
+                q.grad = None if p.grad is None else p.grad.clone()
+            fresh = HipLamb(pb, **kw)
+            fresh.load_state_dict(copy.deepcopy(opt.state_dict()))      # (as a saved file would: load_state_dict itself keeps the tensors it is given)
+            assert fresh._table is None and fresh.param_groups[0]["step"] == 2
+        versions = [p._version for p in live]
+        opt.step()
+        assert all(p._version > v0 for p, v0 in zip(live, versions)) and opt.param_groups[0]["step"] == step
+        g2, norms = opt.kernel_norms()
+        assert set(norms) == set(live), "a parameter with a gradient was left to the torch path"
+        if fresh is not None:
+            fresh.step()
+            g2b, normsb = fresh.kernel_norms()
+            assert fresh.param_groups[0]["step"] == 3 and torch.equal(g2b, g2) and len(normsb) == len(norms)
+            names = [n for n, _ in model.named_parameters()]
+            off = []
+            for n, q, p in zip(names, pb, plist):
+                pairs = [("p", q, p)]
+                if p.grad is not None:
+                    pairs += [("grad", q.grad, p.grad), ("m", fresh.state[q]["exp_avg"], opt.state[p]["exp_avg"]),
+                              ("v", fresh.state[q]["exp_avg_sq"], opt.state[p]["exp_avg_sq"]), ("norms", normsb[q], norms[p])]
+                off += [(n, k, tuple(a.shape), a.stride(), b.stride(), float((a.detach() - b.detach()).abs().max())) for k, a, b in pairs if not torch.equal(a, b)]
+            assert not off, off[:6]
+        c = R.clip_divisor(float(g2), 5.0)
+        # the twin: same start, torch path only, the kernel path's c and r
+        tw = [torch.nn.Parameter(o[0].clone()) for o in old]
+        twin = HipLamb(tw, **kw)
+        for t, o in zip(tw, old):
+            t.grad = o[3].clone()
+            twin.state[t] = {"exp_avg": o[1].clone(), "exp_avg_sq": o[2].clone()}
+        twin.param_groups[0]["step"] = step
+        with torch.no_grad():
+            twin._torch_group(twin.param_groups[0], tw, torch.tensor(c, dtype=torch.float64, device=dev), 1.0,
+                              ratios={t: float(norms[p][2]) for t, p in zip(tw, live)})
+        h = R.Hyper(step=step, **kw)
+        grads = [o[3].cpu().numpy().ravel() for o in old]
+        g2_ref = R.grad_norm2(grads, 1.0)
+        worst["gnorm2"] = max(worst.get("gnorm2", 0), ratio(float(g2) - g2_ref, (D + 2) * U * g2_ref))
+        for p, t, o, gr in zip(live, tw, old, grads):
+            assert torch.equal(p.grad, o[3])                   # gradients are read only
+            p0, m0, v0 = (a.cpu().numpy().ravel() for a in o[:3])
+            # (parameters with another memory layout are compared in memory order on both sides: same strides for p, m, v, g)
+            flat = (lambda a: a.detach().cpu().numpy().ravel()) if p.is_contiguous() else \
+                (lambda a: a.detach().permute(0, 2, 3, 1).cpu().numpy().ravel())
+            if not p.is_contiguous():
+                p0, m0, v0, gr = (flat(a) for a in o)
+            m1, v1, p1 = flat(opt.state[p]["exp_avg"]), flat(opt.state[p]["exp_avg_sq"]), flat(p)
+            m_ref, v_ref, bm, bv, _ = R.moments(p0, gr, m0, v0, h, c)
+            a_, u_ = R.update(p0, m1, v1, h)
+            p2, u2, r = (float(x_) for x_ in norms[p].cpu())
+            p_ref, bp = R.apply(p0, a_, u_, r, h)
+            for k, val in (("m", ratio(m1 - m_ref, bm)), ("v", ratio(v1 - v_ref, bv)), ("p", ratio(p1 - p_ref, bp)),
+                           ("pnorm2", ratio(p2 - np.sum(R.d(p0) ** 2), (D + 2) * U * np.sum(R.d(p0) ** 2))),
+                           ("unorm2", ratio(u2 - np.sum(u_ ** 2), (D + 34) * U * np.sum(u_ ** 2))),
+                           ("r", ratio(r - R.trust_ratio(p2, u2, h), 4 * U * r))):
+                worst[k] = max(worst.get(k, 0), val)
+            # against the twin itself
+            mt, vt, pt = flat(twin.state[t]["exp_avg"]), flat(twin.state[t]["exp_avg_sq"]), flat(t)
+            bc1, bc2 = h.bias_corrections()
+            den = np.sqrt(R.d(v1) / bc2) + h.eps
+            dm = bm + U * np.abs(mt)
+            worst["m_twin"] = max(worst.get("m_twin", 0), ratio(m1 - mt, dm))
+            worst["v_twin"] = max(worst.get("v_twin", 0), ratio(v1 - vt, bv + U * np.abs(vt)))
+            worst["p_twin"] = max(worst.get("p_twin", 0), ratio(p1 - pt, bp + U * np.abs(pt) + h.lr * r * (dm / (bc1 * den) + 8 * U * np.abs(a_))))
+    print("lamb worst error/bound  %-22s " % "hiplamb_model" + "  ".join("%s %.3f" % kv for kv in sorted(worst.items())))
+    assert all(val <= 1.0 for val in worst.values()), worst
+    assert torch.isfinite(loss)
+
+
+def test_trainer_with_fusedlamb_trains_and_resumes(dev, tmp_path):
+    from swin_v2_weather_amd.train import Trainer
+    from swin_v2_weather_amd.utils.optim import HipLamb
+
+    def make():
+        return Trainer(_tiny_params(tmp_path), SimpleNamespace(sweep_id=None, config="bench_tiny", run_num="00", enable_amp=True))
+    t = make()
+    t.build()
+    assert isinstance(t.optimizer, HipLamb) and t.optimizer.defaults["max_grad_norm"] == 5.0
+    t.model.train()
+    before = [p.detach().clone() for p in t.model.parameters()]
+    losses = []
+    for i, data in enumerate(t.train_data_loader):
+        losses.append(float(t.train_step(data)))
+        if i == 2:
+            break
+    assert len(losses) == 3 and all(np.isfinite(losses)) and t.optimizer.param_groups[0]["step"] == 3
+    assert t.optimizer.kernel_norms() is not None and len(t.optimizer.kernel_norms()[1]) == sum(p.grad is not None for p in t.model.parameters())
+    assert any(not torch.equal(a, b) for a, b in zip(before, t.model.parameters()))
+    t.save_checkpoint(t.params.checkpoint_path)
+    t2 = make()
+    t2.build()                                   # finds the checkpoint and restores it
+    assert t2.params.resuming and isinstance(t2.optimizer, HipLamb) and t2.optimizer.param_groups[0]["step"] == 3
+    for (n1, p1), (n2, p2) in zip(t.model.state_dict().items(), t2.model.state_dict().items()):
+        assert n1 == n2 and torch.equal(p1, p2)
+    for p1, p2 in zip(t.model.parameters(), t2.model.parameters()):
+        if p1 in t.optimizer.state:
+            assert torch.equal(t.optimizer.state[p1]["exp_avg_sq"], t2.optimizer.state[p2]["exp_avg_sq"])
+    assert all(torch.isfinite(p).all() for p in t2.model.parameters())

@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""Per-kernel timing probe at the benchmark shape (GPU box): python tools/perf_probe.py [filter]"""
+"""Per-kernel timing probe at the benchmark shape (GPU box): python tools/perf_probe.py [filter]
+(filter `optim`: the optimizer steps, HipLamb beside HipAdam, on the depth-12 / C 128 model's parameter set)"""
 import os
 import sys
 import time
@@ -138,7 +139,49 @@ def probe_mlp(B=2, hid=512):
     say(f"mlp_bwd M={M} hidden={hid}: {t:.1f} us ({M * (Cc * 4 * 2 + hid * 2 * 2 + Cc * 2 * 2) / t / 1e3:.0f} GB/s)")
 
 
+def probe_optim():
+    """HipLamb.step and HipAdam.step on the parameter set of the depth-12 / C 128 model (73 x 720 x 1440), alternating, HIP event pairs
+    around 20 steps each; then the entry points on their own, alternating: swv2_adam_multi, the LAMB gradient-norm launch, the four launches of one LAMB group."""
+    from types import SimpleNamespace
+    from swin_v2_weather_amd.networks.helpers import get_model
+    from swin_v2_weather_amd.utils.optim import HipAdam, HipLamb
+    prm = SimpleNamespace(nettype="swin", img_size=[720, 1440], patch_size=4, depth=12, num_heads=8, n_in_channels=73, n_out_channels=73,
+                          embed_dim=128, window_ratio=80, drop_path_rate=0.0, full_pos_embed=True, rel_pos=False, mlp_ratio=4,
+                          activation_ckpt=False, residual=False, n_future=0, add_orography=False, add_landmask=False)
+    shapes = [q.shape for q in get_model(prm).parameters()]            # (the container only: nothing runs)
+    def make():
+        ps = [torch.nn.Parameter(0.02 * torch.randn(sh, device=dev)) for sh in shapes]
+        for q in ps:
+            q.grad = 1e-3 * torch.randn_like(q)
+        return ps
+    pa, pl = make(), make()
+    n = sum(q.numel() for q in pa)
+    adam, lamb = HipAdam(pa, lr=1e-3, betas=(0.9, 0.95)), HipLamb(pl, lr=1e-3, max_grad_norm=5.0)
+    say(f"optimizer probe: {len(pa)} tensors, {n / 1e6:.2f} M parameters, {sum((q.numel() + 4095) // 4096 for q in pa)} chunks")
+    for rnd in range(3):
+        ta, tl = timeit(adam.step, 20), timeit(lamb.step, 20)
+        say(f"  round {rnd}: HipAdam.step {ta:7.1f} us ({28 * n / ta / 1e6:5.2f} TB/s of 28 B/param)   HipLamb.step {tl:7.1f} us "
+            f"({44 * n / tl / 1e6:5.2f} TB/s of 44 B/param)")
+    t = lamb._table
+    lib, st = L.load(), torch.cuda.current_stream(dev).cuda_stream
+    tabs = (t["dev"].data_ptr(), t["chunks"].data_ptr(), t["n_items"], t["n_chunks"])
+    ws = (t["ws"].data_ptr(), t["ws_bytes"])
+    ta_ = adam._tables[0]
+    k_adam = lambda: L.check(lib.swv2_adam_multi(ta_["dev"].data_ptr(), ta_["chunks"].data_ptr(), ta_["n_chunks"], 1e-3, 0.9, 0.95, 1e-8, 7, 1.0, st))
+    k_norm = lambda: L.check(lib.swv2_lamb_grad_norm(*tabs, 1.0, *ws, st))
+    k_multi = lambda: L.check(lib.swv2_lamb_multi(*tabs, 0, t["n_items"], 0, t["n_chunks"], 1e-3, 0.9, 0.999, 1e-6, 0.01, 1.0, 5.0, 7, 7, None, *ws, st))
+    for rnd in range(3):                 # the entry points alone (no Python side), alternating
+        tk, tg, tm = timeit(k_adam, 50), timeit(k_norm, 50), timeit(k_multi, 50)
+        say(f"  round {rnd}: swv2_adam_multi {tk:6.1f} us ({28 * n / tk / 1e6:5.2f} TB/s of 28 B/param)   swv2_lamb_grad_norm {tg:6.1f} us "
+            f"({4 * n / tg / 1e6:5.2f} TB/s of 4 B/param)   swv2_lamb_multi (4 launches) {tm:6.1f} us ({40 * n / tm / 1e6:5.2f} TB/s of 40 B/param)")
+    x, y = torch.randn(1 << 28, device=dev), torch.empty(1 << 28, device=dev)
+    tc = timeit(lambda: y.copy_(x), 10)
+    say(f"  torch copy of 1 GiB fp32 (tools/hbm_ceiling.py's first row): {tc:.0f} us, {8 * (1 << 28) / tc / 1e6:5.2f} TB/s")
+
+
 if __name__ == "__main__":
+    if "optim" in (sys.argv[1] if len(sys.argv) > 1 else ""):
+        probe_optim()
     if "mlp" in (sys.argv[1] if len(sys.argv) > 1 else ""):
         for hid in ([128, 256, 512, 1024] if "sweep" in sys.argv[1] else [512]):      # (mlp_sweep: cost per 32-unit weight chunk vs fixed cost)
             probe_mlp(2, hid)
