@@ -33,8 +33,9 @@ extern "C" {
  * epilogue with the rollout destinations; 108: the kernel-selection queries swv2_linear_kernel, swv2_linear_wgrad_kernel,
  * swv2_block_wgrad_kernel; 109: swv2_block_plan (+ swv2_block_plan_t, enum swv2_block_step, swv2_block_step_id / _name),
  * swv2_block_desc loses fuse_attn and wgrad_side_stream; 110: the attention kernel-selection queries swv2_attn_fwd_kernel /
- * swv2_attn_bwd_kernel (+ swv2_attn_kernel_t, SWV2_ATTN_K_*); 111: the LAMB optimizer, swv2_lamb_* (+ swv2_lamb_item, SWV2_LAMB_*). */
-#define SWV2_VERSION 111
+ * swv2_attn_bwd_kernel (+ swv2_attn_kernel_t, SWV2_ATTN_K_*); 111: the LAMB optimizer, swv2_lamb_* (+ swv2_lamb_item, SWV2_LAMB_*);
+ * 112: forecast scores, swv2_score_*. */
+#define SWV2_VERSION 112
 
 enum {
     SWV2_OK = 0,
@@ -479,6 +480,28 @@ int swv2_lamb_grad_norm(const swv2_lamb_item* items_dev, const int* chunks_dev, 
 int swv2_lamb_multi(const swv2_lamb_item* items_dev, const int* chunks_dev, int n_items, int n_chunks, int item_lo, int item_hi,
                     int chunk_lo, int chunk_hi, float lr, float beta1, float beta2, float eps, float weight_decay, float grad_inv_scale,
                     float max_grad_norm, int step, int flags, const float* extra_gnorm2, void* ws, size_t ws_bytes, void* stream);
+
+/* Forecast scores (reference utils/weighted_acc_rmse.py:50-115): latitude-weighted RMSE and anomaly correlation of a prediction against
+ * the verifying analysis, per (sample, channel) plane, from ONE pass over prediction, truth and climatology.  All tensors fp32.
+ *   prd, tar  C planes of [H][W] per sample, sample b at ptr + b * bstride (elements): a channel block of a wider tensor is scored in
+ *             place (bstride = channels of the whole tensor * H * W); clim: [C][H][W] shared by all samples, or NULL; w: [H] row weights.
+ *   S_dd = sum w[h] (p - t)^2   S_pt = sum w[h] p' t'   S_pp = sum w[h] p'^2   S_tt = sum w[h] t'^2,   p' = p - clim, t' = t - clim
+ *   (p' = p, t' = t when clim is NULL; p - t is formed from p and t, so S_dd does not depend on clim).
+ * swv2_score_sums: one launch of B * C * swv2_score_slices(B * C, H, W) workgroups; workgroup (plane, slice) stores its four partial sums at
+ * ws[(plane * slices + slice) * 4 ..], plane = b * C + c, slice sl covering the elements [H W sl / slices / 4 * 4, H W (sl + 1) / slices / 4 * 4)
+ * of the plane (the last slice to the end; a slice without elements stores zeros).  No atomics, nothing to zero beforehand.
+ * swv2_score_finalize: one launch; folds the slices of each plane in a fixed order (two runs on the same inputs agree bit for bit) and writes
+ *   sums [B][C][4] = (S_dd, S_pt, S_pp, S_tt)    rmse [B][C] = sqrt(S_dd / (H W))    acc [B][C] = S_pt / sqrt(S_pp S_tt) (0 / 0 = NaN in that plane)
+ *   rmse_mean [C] = mean_b rmse[b][c] (* scale[c] when scale != NULL: the physical-unit stds)    acc_mean [C] = mean_b acc[b][c]
+ * Refused with SWV2_ERR_INVALID before any launch: a null pointer (clim and scale may be NULL), W % 4 != 0, prd / tar / clim / ws / sums not
+ * 16-byte aligned, a batch stride that is not a multiple of 4, a workspace smaller than swv2_score_ws_bytes, B * C >= 2^20, H * W >= 2^30.
+ * swv2_score_slices and swv2_score_ws_bytes are host-only (no HIP call); both return 0 for a non-positive argument. */
+int swv2_score_slices(int planes, int H, int W);
+size_t swv2_score_ws_bytes(int planes, int H, int W);     /* planes * swv2_score_slices(planes, H, W) * 16 */
+int swv2_score_sums(const float* prd, long prd_bstride, const float* tar, long tar_bstride, const float* clim, const float* w, int B, int C,
+                    int H, int W, void* ws, size_t ws_bytes, void* stream);
+int swv2_score_finalize(const void* ws, size_t ws_bytes, int B, int C, int H, int W, const float* scale, float* sums, float* rmse, float* acc,
+                        float* rmse_mean, float* acc_mean, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * ERA5 input assembly (the step BEFORE the model): raw time slabs staged on the device by async H2D copies

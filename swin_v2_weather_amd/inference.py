@@ -11,12 +11,18 @@ loads the weights with any of the prefixes the reference produces (`module.model
 `rollout` is the inference loop of MultiStepWrapper (helpers.py:26-41) for an arbitrary number of steps without autograd:
 prediction fed back, next cos-zenith channel and the invariant channels re-appended.
 
+`score_rollout` is the same loop with every step scored against the verifying analysis as soon as it is written
+(utils/weighted_acc_rmse.ForecastScorer: latitude-weighted RMSE and ACC per channel and lead time, one pass per step).
+
     python -m swin_v2_weather_amd.inference --registry DIR --steps 8 [--init x0.npy] [--out forecast.npy]
+                                            [--truth truth.npy [--climatology time_means.npy] [--scores-out scores.json]]
 """
 from __future__ import annotations
 
 import argparse
+import json
 import os
+from collections import namedtuple
 from types import SimpleNamespace
 
 import numpy as np
@@ -24,6 +30,7 @@ import torch
 
 from .networks.helpers import get_model
 from .utils.YParams import load_yaml
+from .utils.weighted_acc_rmse import ForecastScorer, load_climatology
 
 
 class _Params(dict):
@@ -82,6 +89,20 @@ def load_registry_model(model_dir: str, device="cuda:0", trust_checkpoint: bool 
     return model.to(device).eval(), p, stats
 
 
+def _rollout_steps(net, x0, n_steps, coszen, n_invar, out, coff_of):
+    """the autoregressive loop: step s writes its prediction into out[:, coff_of(s) : coff_of(s) + Cout]; yields s after each step"""
+    B, _, H, W = x0.shape
+    invars = x0[:, x0.shape[1] - n_invar:] if n_invar else None
+    x = x0
+    for s in range(n_steps):
+        extra = None
+        if s + 1 < n_steps:
+            parts = ([coszen[:, s:s + 1]] if coszen is not None else []) + ([invars] if n_invar else [])
+            extra = torch.cat(parts, 1).float() if parts else x0.new_empty(B, 0, H, W)
+        _, x = net.forward_rollout(x, out, coff_of(s), extra)
+        yield s
+
+
 @torch.no_grad()
 def rollout(model, x0: torch.Tensor, n_steps: int, coszen: torch.Tensor | None = None, n_invar: int = 0) -> torch.Tensor:
     """x0 [B, Cin, H, W] (fields | zenith(t0) | invariants) -> forecasts [B, n_steps, Cout, H, W].
@@ -90,27 +111,71 @@ def rollout(model, x0: torch.Tensor, n_steps: int, coszen: torch.Tensor | None =
     B, _, H, W = x0.shape
     Cout = net.out_chans
     out = torch.empty(B, n_steps * Cout, H, W, dtype=torch.float32, device=x0.device)
-    invars = x0[:, x0.shape[1] - n_invar:] if n_invar else None
-    x = x0
-    for s in range(n_steps):
-        extra = None
-        if s + 1 < n_steps:
-            parts = ([coszen[:, s:s + 1]] if coszen is not None else []) + ([invars] if n_invar else [])
-            extra = torch.cat(parts, 1).float() if parts else x0.new_empty(B, 0, H, W)
-        _, x = net.forward_rollout(x, out, s * Cout, extra)
+    for _ in _rollout_steps(net, x0, n_steps, coszen, n_invar, out, lambda s: s * Cout):
+        pass
     return out.view(B, n_steps, Cout, H, W)
 
 
-def main(argv=None):
+RolloutScores = namedtuple("RolloutScores", "rmse acc rmse_samples acc_samples forecast")
+
+
+@torch.no_grad()
+def score_rollout(model, x0: torch.Tensor, truth, n_steps: int, coszen: torch.Tensor | None = None, n_invar: int = 0,
+                  scorer: ForecastScorer | None = None, keep_forecast: bool = False) -> RolloutScores:
+    """`rollout` with every step's prediction scored against truth[:, s] as soon as it is written.  truth: [B, n_steps, Cout, H, W]
+    (normalised as the model's output) or a callable s -> [B, Cout, H, W].  scorer: a ForecastScorer (default: no climatology, so
+    no ACC; normalised units).  Unless keep_forecast, the predictions live in a two-slot ring [B, 2 Cout, H, W]: memory does not grow
+    with n_steps.  -> RolloutScores(rmse [n_steps, Cout] and acc [n_steps, Cout] | None: batch means (rmse x the scorer's stds);
+    rmse_samples, acc_samples [n_steps, B, Cout]; forecast [B, n_steps, Cout, H, W] | None).  The predictions are `rollout`'s, bit for bit."""
+    net = model.model if hasattr(model, "model") else model
+    B, _, H, W = x0.shape
+    Cout = net.out_chans
+    if scorer is None:
+        scorer = ForecastScorer(H, W, Cout, x0.device)
+    slots = n_steps if keep_forecast else 2
+    out = torch.empty(B, slots * Cout, H, W, dtype=torch.float32, device=x0.device)
+    coff_of = (lambda s: s * Cout) if keep_forecast else (lambda s: (s % 2) * Cout)
+    rmse = torch.empty(n_steps, Cout, dtype=torch.float32, device=x0.device)
+    rmse_s = torch.empty(n_steps, B, Cout, dtype=torch.float32, device=x0.device)
+    acc, acc_s = (torch.empty_like(rmse), torch.empty_like(rmse_s)) if scorer.clim is not None else (None, None)
+    for s in _rollout_steps(net, x0, n_steps, coszen, n_invar, out, coff_of):
+        tar = truth(s) if callable(truth) else truth[:, s]
+        r = scorer.score(out, tar.to(x0.device), coff_prd=coff_of(s))
+        rmse[s], rmse_s[s] = r.rmse_mean, r.rmse
+        if acc is not None:
+            acc[s], acc_s[s] = r.acc_mean, r.acc
+    return RolloutScores(rmse, acc, rmse_s, acc_s, out.view(B, n_steps, Cout, H, W) if keep_forecast else None)
+
+
+def lead_time_table(scores: RolloutScores, names, hours_per_step: float = 6.0) -> str:
+    """one line per lead time: RMSE (and ACC) of the named channels; names: [(column title, channel index)]"""
+    rm, ac = scores.rmse.cpu().numpy(), None if scores.acc is None else scores.acc.cpu().numpy()
+    cols = [f"rmse_{n}" for n, _ in names] + ([f"acc_{n}" for n, _ in names] if ac is not None else [])
+    lines = ["lead_h " + " ".join(f"{c:>12s}" for c in cols)]
+    for s in range(rm.shape[0]):
+        vals = [rm[s, i] for _, i in names] + ([ac[s, i] for _, i in names] if ac is not None else [])
+        lines.append(f"{hours_per_step * (s + 1):6.0f} " + " ".join(f"{v:12.5f}" for v in vals))
+    return "\n".join(lines)
+
+
+def build_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--registry", required=True, help="model folder with hyperparams.yaml + weights.tar")
     ap.add_argument("--steps", type=int, default=4)
     ap.add_argument("--init", default=None, help=".npy [B, Cin, H, W] normalised initial condition (default: seeded N(0,1))")
     ap.add_argument("--out", default=None)
     ap.add_argument("--trust-checkpoint", action="store_true", help="read weights.tar with the full unpickler (runs code from the file)")
-    a = ap.parse_args(argv)
+    ap.add_argument("--truth", default=None, help=".npy [B, steps, Cout, H, W] normalised verifying analysis: score every lead time against it")
+    ap.add_argument("--climatology", default=None, help=".npy time means [1, Call, Hfull, Wfull] for ACC (default: the registry's time_means.npy, "
+                                                        "else the hyper-parameters' time_means_path)")
+    ap.add_argument("--scores-out", default=None, help="write the lead-time scores as JSON")
+    return ap
+
+
+def main(argv=None):
+    a = build_parser().parse_args(argv)
     dev = torch.device("cuda:0")
-    model, p, _ = load_registry_model(a.registry, dev, trust_checkpoint=a.trust_checkpoint)
+    model, p, stats = load_registry_model(a.registry, dev, trust_checkpoint=a.trust_checkpoint)
     H, W = p["img_size"]
     n_invar = 2 * int(bool(p["add_landmask"])) + int(bool(p["add_orography"]))
     if a.init:
@@ -122,10 +187,41 @@ def main(argv=None):
         from .utils.data_loader_era5 import cos_zenith
         cz = torch.stack([cos_zenith(2018, 6.0 * (s + 1), H, W) for s in range(a.steps - 1)], 0).unsqueeze(0).expand(x0.shape[0], -1, -1, -1).to(dev) \
             if a.steps > 1 else None
+    if a.truth:
+        return _score_main(a, model, p, stats, x0, cz, n_invar)
     y = rollout(model, x0, a.steps, cz, n_invar)
     print(f"forecast {tuple(y.shape)}: per-step rms " + " ".join(f"{float(y[:, s].square().mean().sqrt()):.4f}" for s in range(a.steps)))
     if a.out:
         np.save(a.out, y.cpu().numpy())
+
+
+def _score_main(a, model, p, stats, x0, cz, n_invar):
+    """--truth: roll out, score every lead time, print the table of the tracked channels (default u10m, v10m as the Trainer)"""
+    H, W = p["img_size"]
+    chans = np.asarray(p["out_channels"])
+    reg_tm = os.path.join(a.registry, "time_means.npy")
+    pc = _Params(p)
+    pc["time_means_path"] = a.climatology or (reg_tm if os.path.isfile(reg_tm) else p.get("time_means_path"))
+    means, stds = stats if stats is not None else (None, None)
+    clim = load_climatology(pc, means=means, stds=stds)
+    scorer = ForecastScorer(H, W, len(chans), x0.device, climatology=clim, stds=None if stds is None else stds[0, chans, 0, 0])
+    truth = np.load(a.truth, mmap_mode="r")              # read step by step: the whole array need not fit in host memory
+    if truth.ndim != 5 or truth.shape[1] < a.steps:
+        raise ValueError(f"--truth: expected [B, >= {a.steps}, Cout, H, W], got {truth.shape}")
+    sc = score_rollout(model, x0, lambda s: torch.from_numpy(np.array(truth[:, s], dtype=np.float32)).to(x0.device), a.steps, cz, n_invar,
+                       scorer, keep_forecast=bool(a.out))
+    if "track_channels" in p and "channel_names" in p:
+        names = [(v, list(p["channel_names"]).index(v)) for v in p["track_channels"]]
+    else:
+        names = [(v, i) for i, v in enumerate(("u10m", "v10m")) if i < len(chans)]
+    print(f"scores in {'physical' if stds is not None else 'normalised'} units, {'with' if clim is not None else 'no climatology: without'} ACC")
+    print(lead_time_table(sc, names))
+    if a.scores_out:
+        with open(a.scores_out, "w") as f:
+            json.dump({"lead_hours": [6.0 * (s + 1) for s in range(a.steps)], "rmse": sc.rmse.cpu().tolist(),
+                       "acc": None if sc.acc is None else sc.acc.cpu().tolist(), "tracked": dict(names)}, f)
+    if a.out:
+        np.save(a.out, sc.forecast.cpu().numpy())
 
 
 if __name__ == "__main__":

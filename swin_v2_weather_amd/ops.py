@@ -414,6 +414,65 @@ def loss_grad(prd, tar, qw, coef, dprd):
     L.check(L.load().swv2_loss_grad(_p(prd), _p(tar), _p(qw), _p(coef), _p(dprd), B * Cc, H, W, _stream()), "swv2_loss_grad")
 
 
+def score_slices(planes: int, H: int, W: int) -> int:
+    """slices per plane of swv2_score_sums' plan (host-only)"""
+    return int(L.load().swv2_score_slices(planes, H, W))
+
+
+def score_workspace(planes: int, H: int, W: int, device) -> torch.Tensor:
+    """the caller's workspace of swv2_score_sums / swv2_score_finalize for `planes` = B * C planes: allocate once, reuse"""
+    return torch.empty(int(L.load().swv2_score_ws_bytes(planes, H, W)) // 4, dtype=torch.float32, device=device)
+
+
+def score_planes_ok(t: torch.Tensor) -> bool:
+    """what swv2_score_sums takes in place: a CUDA fp32 [B, C, H, W] tensor or channel block of one (contiguous planes, W % 4 == 0)"""
+    if not (t.is_cuda and t.dtype == torch.float32 and t.dim() == 4 and t.numel() > 0):
+        return False
+    B, Cc, H, W = t.shape
+    return W % 4 == 0 and tuple(t.stride()[1:]) == (H * W, W, 1) and t.data_ptr() % 16 == 0 and \
+        (B == 1 or (t.stride(0) % 4 == 0 and t.stride(0) >= Cc * H * W))
+
+
+def score_sums(prd, tar, w, ws, clim=None):
+    """the four weighted sums of every (b, c) plane of prd / tar (each [B, C, H, W] or a channel block `x[:, a:b]` of a wider contiguous
+    tensor, scored in place) as slice partials in ws (score_workspace); w [H] row weights, clim [C, H, W] or None"""
+    if not (score_planes_ok(prd) and score_planes_ok(tar)) or prd.shape != tar.shape:
+        raise L.Swv2Error(f"score_sums: expected two CUDA fp32 [B, C, H, W] tensors of one shape with contiguous planes and W % 4 == 0, got "
+                          f"{tuple(prd.shape)} {prd.dtype} strides {prd.stride()} / {tuple(tar.shape)} {tar.dtype} strides {tar.stride()}")
+    B, Cc, H, W = prd.shape
+    _chk(w, torch.float32, "row weights"); _chk(ws, torch.float32, "score workspace")
+    if w.numel() != H:
+        raise L.Swv2Error(f"score_sums: {w.numel()} row weights for {H} rows")
+    if clim is not None and (_chk(clim, torch.float32, "climatology").shape != (Cc, H, W)):
+        raise L.Swv2Error(f"score_sums: climatology {tuple(clim.shape)}, expected {(Cc, H, W)}")
+    L.check(L.load().swv2_score_sums(_p(prd), prd.stride(0) if B > 1 else Cc * H * W, _p(tar), tar.stride(0) if B > 1 else Cc * H * W,
+                                     _p(clim), _p(w), B, Cc, H, W, _p(ws), ws.numel() * 4, _stream()), "swv2_score_sums")
+
+
+def score_finalize(ws, B: int, Cc: int, H: int, W: int, scale=None):
+    """slice partials -> (sums [B, C, 4], rmse [B, C], acc [B, C], rmse_mean [C] (x scale [C] if given), acc_mean [C]), one launch;
+    the five results are views of one fresh buffer"""
+    _chk(ws, torch.float32, "score workspace")
+    if scale is not None and _chk(scale, torch.float32, "scale").numel() != Cc:
+        raise L.Swv2Error(f"score_finalize: scale of {scale.numel()} values for {Cc} channels")
+    n = B * Cc
+    buf = torch.empty(6 * n + 2 * Cc, dtype=torch.float32, device=ws.device)
+    sums, rmse, acc = buf[:4 * n].view(B, Cc, 4), buf[4 * n:5 * n].view(B, Cc), buf[5 * n:6 * n].view(B, Cc)
+    rmse_mean, acc_mean = buf[6 * n:6 * n + Cc], buf[6 * n + Cc:]
+    L.check(L.load().swv2_score_finalize(_p(ws), ws.numel() * 4, B, Cc, H, W, _p(scale), _p(sums), _p(rmse), _p(acc), _p(rmse_mean),
+                                         _p(acc_mean), _stream()), "swv2_score_finalize")
+    return sums, rmse, acc, rmse_mean, acc_mean
+
+
+def forecast_scores(prd, tar, w, clim=None, scale=None, ws=None):
+    """score_sums + score_finalize; ws: a score_workspace to reuse (allocated here otherwise)"""
+    B, Cc, H, W = prd.shape
+    if ws is None:
+        ws = score_workspace(B * Cc, H, W, prd.device)
+    score_sums(prd, tar, w, ws, clim)
+    return score_finalize(ws, B, Cc, H, W, scale)
+
+
 def era5_select_normalize(raw, out, chan, mean, std, coff=0, stream=None):
     """raw [B, S, Craw, Hraw, Wraw] fp32 -> out[:, coff : coff + S*len(chan)] = (raw[:, s, chan] - mean) / std, cropped to out's H, W"""
     B, S, Craw, Hraw, Wraw = raw.shape

@@ -39,7 +39,7 @@ from .utils import get_data_loader_distributed, logging_utils
 from .utils.YParams import YParams
 from .utils.losses import LossHandler
 from .utils.preprocess_utils import PreProcessor
-from .utils.weighted_acc_rmse import weighted_rmse_torch
+from .utils.weighted_acc_rmse import ForecastScorer, load_climatology, weighted_rmse_torch
 
 try:  # optional observability (absent in this image)
     import wandb
@@ -303,6 +303,8 @@ class Trainer():
         valid_loss = valid_buff[0].view(-1)
         valid_steps = valid_buff[2].view(-1)
         valid_weighted_rmse = torch.zeros((self.params.n_out_channels), dtype=torch.float32, device=self.device)
+        scorer = self._valid_scorer()
+        valid_acc = torch.zeros((self.params.n_out_channels), dtype=torch.float32, device=self.device) if scorer is not None else None
         valid_start = time.time()
         with torch.no_grad():
             for i, data in enumerate(self.valid_data_loader, 0):
@@ -313,9 +315,13 @@ class Trainer():
                 tar = tar[:, -self.params.n_out_channels:]
                 gen = gen[:, -self.params.n_out_channels:]
                 valid_weighted_rmse += weighted_rmse_torch(gen, tar)
+                if scorer is not None:
+                    valid_acc += scorer.score(gen, tar).acc_mean
         if dist.is_initialized():
             dist.all_reduce(valid_buff)
             dist.all_reduce(valid_weighted_rmse)
+            if valid_acc is not None:
+                dist.all_reduce(valid_acc)
         valid_buff[0:2] = valid_buff[0:2] / valid_buff[2]
         valid_weighted_rmse = valid_weighted_rmse / valid_buff[2]
         valid_weighted_rmse *= mult
@@ -331,9 +337,25 @@ class Trainer():
         for idx, var in zip(idxes, track_channels):
             if idx < len(valid_weighted_rmse_cpu):
                 logs.update({f'valid_rmse_{var}': valid_weighted_rmse_cpu[idx]})
+        if valid_acc is not None:
+            valid_acc_cpu = (valid_acc / valid_buff[2]).detach().cpu().numpy()
+            for idx, var in zip(idxes, track_channels):
+                if idx < len(valid_acc_cpu):
+                    logs.update({f'valid_acc_{var}': valid_acc_cpu[idx]})
         if self.log_to_wandb:
             wandb.log(logs, step=self.epoch)
         return valid_time, logs
+
+    def _valid_scorer(self):
+        """the ForecastScorer behind valid_acc_<var>: only when `time_means_path` is a file and the device is a GPU (None otherwise:
+        validation then logs exactly what it always did); built once"""
+        if not hasattr(self, "_scorer"):
+            clim = load_climatology(self.params) if self.device.type == 'cuda' else None
+            self._scorer = None
+            if clim is not None:
+                H, W = self.params['img_size']
+                self._scorer = ForecastScorer(H, W, self.params.n_out_channels, self.device, climatology=clim)
+        return self._scorer
 
     def save_checkpoint(self, checkpoint_path, model=None):
         if not model:

@@ -1,5 +1,9 @@
 """Validation metric used by the trainer (reference utils/weighted_acc_rmse.py:50-86): cos-latitude weighted RMSE.
 Validation only -- not on the timed training path -- so this is plain torch."""
+import os
+from collections import namedtuple
+
+import numpy as np
 import torch
 
 
@@ -11,3 +15,161 @@ def weighted_rmse_torch(pred: torch.Tensor, target: torch.Tensor) -> torch.Tenso
     coslat = torch.cos(3.1416 / 180.0 * (90.0 - j * 180.0 / float(num_lat - 1)))
     weight = (num_lat * coslat / coslat.sum()).reshape(1, 1, -1, 1)
     return torch.sqrt(torch.mean(weight * (pred - target) ** 2.0, dim=(-1, -2))).mean(dim=0)
+
+
+# ---- forecast scoring: RMSE and anomaly correlation per channel (reference utils/weighted_acc_rmse.py:50-115) ----------------
+# On CUDA fp32 inputs with contiguous planes and W % 4 == 0 the sums come from ONE pass of swv2_score_sums (csrc/score.hip) instead of
+# torch's ten; anything else (CPU tensors -- the host tests, the gloo trainer --, odd widths, other dtypes) runs plain torch.
+_WEIGHTS = {}
+
+
+def latitude_weights(num_lat: int, device=None) -> torch.Tensor:
+    """[num_lat] fp32: num_lat cos(3.1416 / 180 lat_j) / sum_j cos(..), lat_j = 90 - 180 j / (num_lat - 1).  Computed ONCE on the CPU
+    in fp32 and copied, cached per device: the CPU and GPU paths use bit-identical weights.  The tensor returned IS the cached one:
+    read it, never modify it in place."""
+    dev = torch.device(device) if device is not None else torch.device("cpu")
+    key = (int(num_lat), dev)
+    if key not in _WEIGHTS:
+        if (int(num_lat), torch.device("cpu")) not in _WEIGHTS:
+            j = torch.arange(0, num_lat)
+            coslat = torch.cos(3.1416 / 180.0 * (90.0 - j * 180.0 / float(num_lat - 1)))
+            _WEIGHTS[(int(num_lat), torch.device("cpu"))] = num_lat * coslat / coslat.sum()
+        _WEIGHTS[key] = _WEIGHTS[(int(num_lat), torch.device("cpu"))].to(dev)
+    return _WEIGHTS[key]
+
+
+def _row_weights(t: torch.Tensor, weighted: bool) -> torch.Tensor:
+    if weighted:
+        return latitude_weights(t.shape[2], t.device)
+    key = ("ones", int(t.shape[2]), t.device)
+    if key not in _WEIGHTS:
+        _WEIGHTS[key] = torch.ones(t.shape[2], dtype=torch.float32, device=t.device)
+    return _WEIGHTS[key]
+
+
+def _on_kernels(pred: torch.Tensor, target: torch.Tensor) -> bool:
+    if not (pred.is_cuda and target.is_cuda and pred.shape == target.shape):
+        return False
+    from .. import ops
+    return ops.score_planes_ok(pred) and ops.score_planes_ok(target)
+
+
+def _torch_sums(pred, target, w, clim=None):
+    """the four sums of csrc/score.hip in plain torch, in the inputs' dtype: [n, c] each"""
+    w = w.to(pred.dtype).reshape(1, 1, -1, 1)
+    pa, ta = (pred, target) if clim is None else (pred - clim, target - clim)
+    d = pred - target
+    return tuple(torch.sum(w * a * b, dim=(-1, -2)) for a, b in ((d, d), (pa, ta), (pa, pa), (ta, ta)))
+
+
+def _acc_channels(pred, target, weighted: bool):
+    w = _row_weights(pred, weighted)
+    if _on_kernels(pred, target):
+        from .. import ops
+        return ops.forecast_scores(pred, target, w)[2]
+    _, s_pt, s_pp, s_tt = _torch_sums(pred, target, w)
+    return s_pt / torch.sqrt(s_pp * s_tt)
+
+
+def weighted_rmse_torch_channels(pred: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
+    """[n, c, h, w] x2 -> [n, c]: sqrt(mean_hw(w_lat (pred - target)^2)).  Like the other drop-in names below this is a stateless call: on
+    the kernel path it takes a fresh workspace (n c slices 16 bytes, from torch's caching allocator) every time and computes all four
+    sums for the one it returns; a loop that scores many steps should hold a ForecastScorer, which owns and reuses its workspace."""
+    w = _row_weights(pred, True)
+    if _on_kernels(pred, target):
+        from .. import ops
+        return ops.forecast_scores(pred, target, w)[1]
+    return torch.sqrt(torch.mean(w.to(pred.dtype).reshape(1, 1, -1, 1) * (pred - target) ** 2.0, dim=(-1, -2)))
+
+
+def weighted_acc_torch_channels(pred: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
+    """[n, c, h, w] x2 (anomalies) -> [n, c]: sum(w p t) / sqrt(sum(w p p) sum(w t t))"""
+    return _acc_channels(pred, target, True)
+
+
+def weighted_acc_torch(pred: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
+    return torch.mean(weighted_acc_torch_channels(pred, target), dim=0)
+
+
+def unweighted_acc_torch_channels(pred: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
+    return _acc_channels(pred, target, False)
+
+
+def unweighted_acc_torch(pred: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
+    return torch.mean(unweighted_acc_torch_channels(pred, target), dim=0)
+
+
+def load_climatology(params, means=None, stds=None):
+    """The normalised climatology ACC needs, [C, H, W] fp32 numpy: (time_means[:, out_channels, :H, :W] - means) / stds with the
+    reference's files (`time_means_path` [1, Call, Hfull, Wfull]; means / stds [1, Call, 1, 1] from `global_means_path` /
+    `global_stds_path` unless given; a missing stats file means unit stds / zero means, as validation treats synthetic fields).
+    None when `time_means_path` is not a file."""
+    def get(k):
+        return params[k] if k in params else None
+    path = get("time_means_path")
+    if path is None or not os.path.isfile(str(path)):
+        return None
+    H, W = get("img_size")
+    chans = np.asarray(get("out_channels"))
+    tm = np.load(str(path))[:, chans, :H, :W].astype(np.float32)
+
+    def stat(given, key, default):
+        if given is None:
+            f = get(key)
+            if f is None or not os.path.isfile(str(f)):
+                return np.float32(default)
+            given = np.load(str(f))
+        return np.asarray(given, dtype=np.float32)[:, chans]
+    return np.ascontiguousarray(((tm - stat(means, "global_means_path", 0.0)) / stat(stds, "global_stds_path", 1.0))[0], dtype=np.float32)
+
+
+Scores = namedtuple("Scores", "rmse acc rmse_mean acc_mean sums")
+
+
+class ForecastScorer:
+    """Latitude-weighted RMSE and ACC of [B, C, H, W] forecasts against the verifying analysis, both normalised as the model sees them.
+    Owns the row weights, the normalised climatology [C, H, W] (None: no ACC) and the kernel workspace; `stds` [C] puts the batch-mean
+    RMSE into physical units.  One pass over prediction, truth and climatology per call on CUDA (csrc/score.hip), plain torch elsewhere."""
+
+    def __init__(self, H, W, n_channels, device, climatology=None, stds=None):
+        self.H, self.W, self.C = int(H), int(W), int(n_channels)
+        self.w = latitude_weights(self.H, device)
+        self.device = self.w.device                       # resolved: "cuda" names the current device, whose tensors say cuda:<index>
+        self.clim = None
+        if climatology is not None:
+            if isinstance(climatology, np.ndarray):
+                climatology = torch.from_numpy(np.array(climatology, dtype=np.float32))          # (a copy: the array may be read-only)
+            self.clim = torch.as_tensor(climatology, dtype=torch.float32).to(self.device).contiguous()
+            if self.clim.shape != (self.C, self.H, self.W):
+                raise ValueError(f"climatology {tuple(self.clim.shape)}, expected {(self.C, self.H, self.W)}")
+        self.scale = None if stds is None else torch.as_tensor(stds, dtype=torch.float32).reshape(-1).to(self.device).contiguous()
+        if self.scale is not None and self.scale.numel() != self.C:
+            raise ValueError(f"{self.scale.numel()} stds for {self.C} channels")
+        self._ws = {}
+
+    def score(self, prd, tar, coff_prd=0, coff_tar=0) -> Scores:
+        """channels coff_prd .. + C of prd against channels coff_tar .. + C of tar (scored in place, no copy) ->
+        Scores(rmse [B, C], acc [B, C] | None, rmse_mean [C] (x stds), acc_mean [C] | None, sums [B, C, 4])"""
+        p, t = prd[:, coff_prd:coff_prd + self.C], tar[:, coff_tar:coff_tar + self.C]
+        if p.shape != t.shape or p.shape[1:] != (self.C, self.H, self.W):
+            raise ValueError(f"score: blocks {tuple(p.shape)} / {tuple(t.shape)}, expected [B, {self.C}, {self.H}, {self.W}]")
+        if _on_kernels(p, t) and p.device == self.device:
+            from .. import ops
+            B = p.shape[0]
+            if B not in self._ws:
+                self._ws[B] = ops.score_workspace(B * self.C, self.H, self.W, self.device)
+            ops.score_sums(p, t, self.w, self._ws[B], self.clim)
+            sums, rmse, acc, rmse_mean, acc_mean = ops.score_finalize(self._ws[B], B, self.C, self.H, self.W, self.scale)
+        else:
+            w = self.w.to(p.device)
+            clim = None if self.clim is None else self.clim.to(device=p.device, dtype=p.dtype)
+            s = _torch_sums(p, t, w, clim)
+            sums = torch.stack(s, dim=-1)
+            rmse = torch.sqrt(s[0] / float(self.H * self.W))
+            acc = s[1] / torch.sqrt(s[2] * s[3])
+            rmse_mean, acc_mean = rmse.mean(dim=0), acc.mean(dim=0)
+            if self.scale is not None:
+                rmse_mean = rmse_mean * self.scale.to(device=p.device, dtype=p.dtype)
+        if self.clim is None:
+            acc = acc_mean = None
+        return Scores(rmse, acc, rmse_mean, acc_mean, sums)
