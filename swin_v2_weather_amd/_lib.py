@@ -97,6 +97,14 @@ class PrepItem(C.Structure):
                 ("out_rows", C.c_int), ("col_map", C.c_void_p), ("out_cols", C.c_int), ("out", C.c_void_p), ("out_f32", C.c_int)]
 
 
+class AdamItem(C.Structure):         # swv2_adam_item
+    _fields_ = [("p", C.c_void_p), ("g", C.c_void_p), ("m", C.c_void_p), ("v", C.c_void_p), ("n", C.c_long)]
+
+
+class LambItem(C.Structure):         # swv2_lamb_item
+    _fields_ = [("p", C.c_void_p), ("g", C.c_void_p), ("m", C.c_void_p), ("v", C.c_void_p), ("n", C.c_long), ("chunk0", C.c_long)]
+
+
 class WgradItem(C.Structure):
     _fields_ = [("dy", Operand), ("x", Operand), ("dW", C.c_void_p), ("db", C.c_void_p), ("nmap", C.c_void_p),
                 ("kmap", C.c_void_p), ("ldw", C.c_int)]

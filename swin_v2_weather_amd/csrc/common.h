@@ -34,6 +34,21 @@ __device__ __forceinline__ bf16x4 f2bf4(f32x4 v) {
     return __builtin_bit_cast(bf16x4, p);
 }
 
+// 8 floats <-> 8 packed bf16 (one 16-byte unit of a bf16 row)
+__device__ __forceinline__ uint4 pack8(const float* v) {
+    uint4 r;
+    r.x = f2bf2(v[0], v[1]); r.y = f2bf2(v[2], v[3]); r.z = f2bf2(v[4], v[5]); r.w = f2bf2(v[6], v[7]);
+    return r;
+}
+__device__ __forceinline__ void unpack8(uint4 c, float* v) {
+    const uint32_t w[4] = {c.x, c.y, c.z, c.w};
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        v[2 * i] = __uint_as_float(w[i] << 16);
+        v[2 * i + 1] = __uint_as_float(w[i] & 0xffff0000u);
+    }
+}
+
 // ---- MFMA wrappers (wave64) ---------------------------------------------------------------
 // v_mfma_f32_16x16x16_bf16: A[i=l&15][k=4*(l>>4)+j], B[k=4*(l>>4)+j][n=l&15], C[row=4*(l>>4)+r][col=l&15]
 __device__ __forceinline__ f32x4 mfma16(bf16x4 a, bf16x4 b, f32x4 c) {

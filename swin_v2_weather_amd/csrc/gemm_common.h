@@ -77,8 +77,9 @@ typedef unsigned short u16x2_t __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ uint16_t gelu_tab_arg(int i) { return (uint16_t)(((i / GT_HALF) << 15) | (GT_LO + i % GT_HALF)); }
 
 // two packed bf16 arguments -> byte offsets (packed u16 pair) into a table of `ESZ`-byte entries; `bad` is set when either
-// argument is outside the table (the offsets are then clamped and the caller must not use the looked-up values)
-template <int ESZ>
+// argument is outside the table (the offsets are then clamped and the caller must not use the looked-up values).  SIGNED = false: a
+// table that holds the POSITIVE arguments only (GT_HALF entries), offsets of |x|; the caller applies the sign symmetry
+template <int ESZ, bool SIGNED = true>
 __device__ __forceinline__ uint32_t gelu_tab_off2(uint32_t w, bool& bad) {
     const u16x2_t a = __builtin_bit_cast(u16x2_t, w & 0x7fff7fffu);
     const u16x2_t lo = {(unsigned short)GT_LO, (unsigned short)GT_LO};
@@ -86,37 +87,11 @@ __device__ __forceinline__ uint32_t gelu_tab_off2(uint32_t w, bool& bad) {
     const u16x2_t idx = a - lo;                                      // wraps for arguments below the table
     const u16x2_t idc = __builtin_elementwise_min(idx, mx);
     bad = bad || (__builtin_bit_cast(uint32_t, idx) != __builtin_bit_cast(uint32_t, idc));
+    if constexpr (!SIGNED) return __builtin_bit_cast(uint32_t, (u16x2_t)(idc * (unsigned short)ESZ));
     const u16x2_t sg = __builtin_bit_cast(u16x2_t, w) >> 15;         // 0 / 1 per half
     const u16x2_t half = {(unsigned short)GT_HALF, (unsigned short)GT_HALF};
     const u16x2_t off = (idc + sg * half) * (unsigned short)ESZ;
     return __builtin_bit_cast(uint32_t, off);
-}
-
-// the same for a table that holds the POSITIVE arguments only (GT_HALF entries): offsets of |x|; the caller applies the sign symmetry
-template <int ESZ>
-__device__ __forceinline__ uint32_t gelu_tab_off2_abs(uint32_t w, bool& bad) {
-    const u16x2_t a = __builtin_bit_cast(u16x2_t, w & 0x7fff7fffu);
-    const u16x2_t lo = {(unsigned short)GT_LO, (unsigned short)GT_LO};
-    const u16x2_t mx = {(unsigned short)(GT_HALF - 1), (unsigned short)(GT_HALF - 1)};
-    const u16x2_t idx = a - lo;
-    const u16x2_t idc = __builtin_elementwise_min(idx, mx);
-    bad = bad || (__builtin_bit_cast(uint32_t, idx) != __builtin_bit_cast(uint32_t, idc));
-    const u16x2_t off = idc * (unsigned short)ESZ;
-    return __builtin_bit_cast(uint32_t, off);
-}
-
-__device__ __forceinline__ uint4 pack8(const float* v) {
-    uint4 r;
-    r.x = f2bf2(v[0], v[1]); r.y = f2bf2(v[2], v[3]); r.z = f2bf2(v[4], v[5]); r.w = f2bf2(v[6], v[7]);
-    return r;
-}
-__device__ __forceinline__ void unpack8(uint4 c, float* v) {
-    const uint32_t w[4] = {c.x, c.y, c.z, c.w};
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        v[2 * i] = __uint_as_float(w[i] << 16);
-        v[2 * i + 1] = __uint_as_float(w[i] & 0xffff0000u);
-    }
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -282,32 +257,33 @@ template <> struct ALoad<A_HEADS> {
         if (m >= d.M || k0 >= d.K) return make_uint4(0, 0, 0, 0);
         return raw_unc(m, k0);
     }
-    __device__ __forceinline__ uint4 raw_unc(int m, int k0) const {
-        const int h = d.p0, Lp = d.p2, DP = d.p3, S = (int)d.ld;
-        const int bw = fdiv(m, Lp, d.mg0), t = m - bw * Lp;
-        const int ph = d.p1 >= 0 ? (k0 >> d.p1) : fdiv(k0, DP, d.mg2), j = k0 - ph * DP;      // p1 = log2(DP) or -1 (DP = 96), set by make_loader
-        const int part = (h == 1) ? ph : fdiv(ph, h, d.mg1), hd = ph - part * h;
-        return *(const uint4*)((const uint16_t*)d.ptr + ((((long)bw * h + hd) * S + part) * Lp + t) * DP + j);
-    }
-    // element offset of (row m, column k0) for callers that address with 32 bits (tensor below 2^32 bytes, checked by them)
-    __device__ __forceinline__ uint32_t elem_off(int m, int k0) const {
-        const int h = d.p0, Lp = d.p2, DP = d.p3, S = (int)d.ld;
+    // (row m, column k0) -> window, token, part, head, channel.  p1 = log2(DP) or -1 (DP = 96), set by make_loader
+    struct Split { int bw, t, part, hd, j; };
+    __device__ __forceinline__ Split split(int m, int k0) const {
+        const int h = d.p0, Lp = d.p2, DP = d.p3;
         const int bw = fdiv(m, Lp, d.mg0), t = m - bw * Lp;
         const int ph = d.p1 >= 0 ? (k0 >> d.p1) : fdiv(k0, DP, d.mg2), j = k0 - ph * DP;
         const int part = (h == 1) ? ph : fdiv(ph, h, d.mg1), hd = ph - part * h;
-        return (uint32_t)((((bw * h + hd) * S + part) * Lp + t) * DP + j);
+        return {bw, t, part, hd, j};
     }
+    __device__ __forceinline__ uint4 raw_unc(int m, int k0) const {
+        const int h = d.p0, Lp = d.p2, DP = d.p3, S = (int)d.ld;
+        const Split s = split(m, k0);
+        return *(const uint4*)((const uint16_t*)d.ptr + ((((long)s.bw * h + s.hd) * S + s.part) * Lp + s.t) * DP + s.j);
+    }
+    // element offset of (row m, column k0) for callers that address with 32 bits (tensor below 2^32 bytes, checked by them)
+    __device__ __forceinline__ uint32_t elem_off(const Split& s) const {
+        return (uint32_t)((((s.bw * d.p0 + s.hd) * (int)d.ld + s.part) * d.p2 + s.t) * d.p3 + s.j);
+    }
+    __device__ __forceinline__ uint32_t elem_off(int m, int k0) const { return elem_off(split(m, k0)); }
     // Walking rows m, m + 16, m + 32, ... of ONE chunk column (the weight-gradient kernel's staging): the window / token split
     // once per step (step_base), then adds -- a row block that runs past its window's Lp rows continues (h S - 1) Lp DP
     // elements further, in the same (head, part) slab of the next window.  Valid while a step spans at most one window
     // boundary (16 * chunks <= Lp, checked by the caller); 32-bit element offsets.
     struct Step { uint32_t off0; int t0; };
     __device__ __forceinline__ Step step_base(int m, int k0) const {
-        const int h = d.p0, Lp = d.p2, DP = d.p3, S = (int)d.ld;
-        const int bw = fdiv(m, Lp, d.mg0), t = m - bw * Lp;
-        const int ph = d.p1 >= 0 ? (k0 >> d.p1) : fdiv(k0, DP, d.mg2), j = k0 - ph * DP;
-        const int part = (h == 1) ? ph : fdiv(ph, h, d.mg1), hd = ph - part * h;
-        Step o = {(uint32_t)((((bw * h + hd) * S + part) * Lp + t) * DP + j), t};
+        const Split s = split(m, k0);
+        Step o = {elem_off(s), s.t};
         return o;
     }
     __device__ __forceinline__ uint32_t step_off(const Step& b, int i) const {

@@ -15,6 +15,7 @@
 // through LDS in chunks of 32 hidden units (W1[32][C] and W2[C][32], double buffered), shared by the 4 waves.
 #include <cstdlib>
 #include "gemm_common.h"
+#include "ln_common.h"
 
 namespace {
 
@@ -366,7 +367,7 @@ __global__ __launch_bounds__(256, (C >= 192 && MT == 2) ? 1 : 2) void mlp_bwd_ke
     constexpr int PY = C + 4;
     constexpr int ROWS = 64 * MT, PX = C + 8;          // rows per workgroup, pitch (bf16) of the staged da2 tile
     constexpr int XBYTES = ROWS * PX * 2;
-    constexpr int GBYTES = (256 / (C <= 32 ? 8 : C <= 64 ? 16 : C <= 128 ? 32 : 64)) * 2 * C * 4;      // d gamma / d beta row groups
+    constexpr int GBYTES = LnBwdShape<C, 256, ROWS>::RPP * 2 * C * 4;      // d gamma / d beta row groups
     // RECOMP: the fc1 bias sits behind the weight chunk buffers during the chunk loop (a global load inside the loop would drain
     // the weight prefetch, see the forward kernel); at C = 128 that tail of the prologue's region is free, so the LDS footprint
     // -- two workgroups per CU at 79.9 KB each -- does not grow
@@ -485,10 +486,8 @@ __global__ __launch_bounds__(256, (C >= 192 && MT == 2) ? 1 : 2) void mlp_bwd_ke
     // global (bf16, for the fc2 weight gradient) and to an LDS tile from which the waves pick up their B fragments.
     bf16x8 xf[MT][KS];
     {
-        constexpr int LPR = C <= 32 ? 8 : C <= 64 ? 16 : C <= 128 ? 32 : 64;      // lanes per row (power of two >= C / 4)
-        constexpr int RPP = 256 / LPR, NPASS = ROWS / RPP;
-        constexpr int BATCH = NPASS < 4 ? NPASS : 4;                               // passes whose loads are in flight together
-        static_assert(NPASS % BATCH == 0, "row passes must come in whole batches");
+        typedef LnBwdShape<C, 256, ROWS> Sh;
+        constexpr int LPR = Sh::LPR, RPP = Sh::RPP, NPASS = Sh::NPASS, BATCH = Sh::BATCH;
         const int lr = tid % LPR, rg = tid / LPR;
         const bool act = 4 * lr < C;
         const int c0 = act ? 4 * lr : 0;
@@ -622,8 +621,8 @@ __global__ __launch_bounds__(256, (C >= 192 && MT == 2) ? 1 : 2) void mlp_bwd_ke
                 // with gelu_grad_f, so bit-identical to the formula); the formula -- an exp, a reciprocal and a dozen
                 // fmas per value, 26 % of a wave's life -- only for the rare group with an argument outside the table
                 bool bad = false;
-                const uint32_t o0 = GHALF ? gelu_tab_off2_abs<4>(w0, bad) : gelu_tab_off2<4>(w0, bad);
-                const uint32_t o1 = GHALF ? gelu_tab_off2_abs<4>(w1, bad) : gelu_tab_off2<4>(w1, bad);
+                const uint32_t o0 = gelu_tab_off2<4, !GHALF>(w0, bad);
+                const uint32_t o1 = gelu_tab_off2<4, !GHALF>(w1, bad);
                 f32x4 gg;
                 if ((!GTAB && !GHALF) || __builtin_expect(__any((int)bad), 0)) {
                     gg[0] = gelu_grad_f(__uint_as_float(w0 << 16));

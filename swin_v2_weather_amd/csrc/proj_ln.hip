@@ -10,6 +10,7 @@
 // and its output tiles (rows = one head's 16 channels, column = token) store directly as 512-byte head-major runs.
 #include <cstdlib>
 #include "gemm_common.h"
+#include "ln_common.h"
 
 namespace {
 
@@ -194,10 +195,8 @@ template <int C, int MT, int HS = 16, int NW = 4>
 __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void proj_ln_bwd_kernel(const ProjLnBwd a) {
     constexpr int KS = C / 32, NT = 64 * NW, HDPM = 8 * HS;
     constexpr int ROWS = 16 * NW * MT, PX = C + 8, PW = C + 8;
-    constexpr int LPR = C <= 32 ? 8 : C <= 64 ? 16 : C <= 128 ? 32 : 64;
-    constexpr int RPP = NT / LPR, NPASS = ROWS / RPP;
-    constexpr int BATCH = NPASS < 4 ? NPASS : 4;
-    static_assert(NPASS % BATCH == 0, "row passes must come in whole batches");
+    typedef LnBwdShape<C, NT, ROWS> Sh;
+    constexpr int LPR = Sh::LPR, RPP = Sh::RPP, NPASS = Sh::NPASS, BATCH = Sh::BATCH;
     // d gamma / d beta partials of the RPP row groups: summed through LDS -- in two rounds (upper half of the row groups onto the
     // lower half, then across the lower half) where the one-round table would not fit beside the 102 KB weight (NW = 8)
     constexpr bool TWO_ROUNDS = NW == 8;

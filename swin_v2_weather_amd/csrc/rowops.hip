@@ -7,19 +7,6 @@ namespace {
 
 constexpr int LN_BLOCK = 256;
 
-__device__ __forceinline__ void unpack8f(uint4 c, float* v) {
-    const uint32_t w[4] = {c.x, c.y, c.z, c.w};
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        v[2 * i] = __uint_as_float(w[i] << 16);
-        v[2 * i + 1] = __uint_as_float(w[i] & 0xffff0000u);
-    }
-}
-__device__ __forceinline__ uint4 pack8f(const float* v) {
-    uint4 r;
-    r.x = f2bf2(v[0], v[1]); r.y = f2bf2(v[2], v[3]); r.z = f2bf2(v[4], v[5]); r.w = f2bf2(v[6], v[7]);
-    return r;
-}
 template <int G>
 __device__ __forceinline__ float group_sum(float v) { return group_allsum<G>(v); }       // (vector ALU only: common.h)
 
@@ -49,7 +36,7 @@ __global__ __launch_bounds__(LN_BLOCK) void ln_residual_fwd_kernel(
         for (int i = 0; i < CH; ++i) {
             const int c0 = (gl + i * G) * 8;
             if (c0 < C) {
-                unpack8f(*(const uint4*)(a + m * C + c0), v[i]);
+                unpack8(*(const uint4*)(a + m * C + c0), v[i]);
 #pragma unroll
                 for (int e = 0; e < 8; ++e) s += v[i][e];
             } else {
@@ -124,7 +111,7 @@ __global__ __launch_bounds__(LN_BLOCK) void ln_residual_bwd_kernel(
             const int c0 = (gl + i * G) * 8;
             if (c0 < C) {
                 float av[8];
-                unpack8f(*(const uint4*)(a + m * C + c0), av);
+                unpack8(*(const uint4*)(a + m * C + c0), av);
 #pragma unroll
                 for (int hlf = 0; hlf < 2; ++hlf) {
                     const f32x4 d4 = *(const f32x4*)(dy + dst * C + c0 + 4 * hlf);
@@ -155,7 +142,7 @@ __global__ __launch_bounds__(LN_BLOCK) void ln_residual_bwd_kernel(
             float o[8];
 #pragma unroll
             for (int e = 0; e < 8; ++e) o[e] = rs * (gg[i][e] - s1 - xh[i][e] * s2);
-            *(uint4*)(da + m * C + c0) = pack8f(o);
+            *(uint4*)(da + m * C + c0) = pack8(o);
         }
     }
     // block reduction of dgamma / dbeta: rows_per_block partial sums per column
@@ -489,16 +476,22 @@ __global__ __launch_bounds__(256) void loss_grad_kernel(const float* __restrict_
 
 // fused Adam over one flat fp32 buffer (torch.optim.Adam semantics, train.py:176: betas (0.9, 0.95), eps 1e-8,
 // no weight decay, bias correction).  step_size = lr / (1 - b1^t), bc2_sqrt = sqrt(1 - b2^t); inv_scale un-scales grads.
+// THE element update (adam_kernel, adam_multi_kernel's 16-byte walk); g is the un-scaled gradient.  adam_multi_kernel's scalar walk
+// keeps the same lines written out: with a call there the compiler contracts b1 m + (1 - b1) g of the 16-BYTE walk into the other of
+// its two possible fmas, and m changes in its last bit (LABNOTES, "Shared row-kernel rules: what could be written once").
+__device__ __forceinline__ void adam_update(float g, float& m, float& v, float& p, float b1, float b2, float eps, float step_size,
+                                            float bc2_sqrt) {
+    const float mi = b1 * m + (1.f - b1) * g;
+    const float vi = b2 * v + (1.f - b2) * g * g;
+    m = mi;
+    v = vi;
+    p -= step_size * mi / (sqrtf(vi) / bc2_sqrt + eps);
+}
 __global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                             float* __restrict__ v, long n, float b1, float b2, float eps, float step_size,
                             float bc2_sqrt, float inv_scale) {
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
-        const float gi = g[i] * inv_scale;
-        const float mi = b1 * m[i] + (1.f - b1) * gi;
-        const float vi = b2 * v[i] + (1.f - b2) * gi * gi;
-        m[i] = mi;
-        v[i] = vi;
-        p[i] -= step_size * mi / (sqrtf(vi) / bc2_sqrt + eps);
+        adam_update(g[i] * inv_scale, m[i], v[i], p[i], b1, b2, eps, step_size, bc2_sqrt);
     }
 }
 
@@ -523,9 +516,9 @@ __global__ __launch_bounds__(256) void adam_multi_kernel(const swv2_adam_item* _
             f32x4 mi = *(const f32x4*)(m + i), vi = *(const f32x4*)(v + i), pi = *(const f32x4*)(p + i);
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
-                mi[e] = b1 * mi[e] + (1.f - b1) * gi[e];
-                vi[e] = b2 * vi[e] + (1.f - b2) * gi[e] * gi[e];
-                pi[e] -= step_size * mi[e] / (sqrtf(vi[e]) / bc2_sqrt + eps);
+                float me = mi[e], ve = vi[e], pe = pi[e];          // (a reference cannot bind to a vector element)
+                adam_update(gi[e], me, ve, pe, b1, b2, eps, step_size, bc2_sqrt);
+                mi[e] = me; vi[e] = ve; pi[e] = pe;
             }
             *(f32x4*)(m + i) = mi; *(f32x4*)(v + i) = vi; *(f32x4*)(p + i) = pi;
         }
@@ -630,10 +623,10 @@ __global__ __launch_bounds__(256) void qk_normalize_kernel(uint16_t* __restrict_
     for (int cc = c; cc * 8 < DP; cc += 16) {                       // one chunk per lane at DP <= 128, two at 256
         uint16_t* row = qkvh + ((bh * 3 + part) * Lp + t) * DP + cc * 8;
         float v[8];
-        unpack8f(*(const uint4*)row, v);
+        unpack8(*(const uint4*)row, v);
 #pragma unroll
         for (int e = 0; e < 8; ++e) v[e] *= rn;
-        *(uint4*)row = pack8f(v);
+        *(uint4*)row = pack8(v);
     }
     if (c == 0) rnorm[i] = rn;
 }

@@ -21,15 +21,61 @@ import torch
 
 from .. import _lib as L
 
-
-class _Item(C.Structure):
-    _fields_ = [("p", C.c_void_p), ("g", C.c_void_p), ("m", C.c_void_p), ("v", C.c_void_p), ("n", C.c_long)]
+_Item, _LambItem = L.AdamItem, L.LambItem      # the names these mirrors had while they were defined here (still imported by older callers)
 
 
 def _dense(t: torch.Tensor) -> bool:
     """memory is one gap-free block (the kernel walks it linearly; p, grad, m, v must then only share the strides)"""
     return t.is_contiguous() or (t.dim() == 4 and t.is_contiguous(memory_format=torch.channels_last)) or \
         (t.dim() == 5 and t.is_contiguous(memory_format=torch.channels_last_3d))
+
+
+def _kernel_ok(p, s, dev) -> bool:
+    """the kernels walk raw memory: (p, grad, exp_avg, exp_avg_sq) must all be fp32 on `dev`, dense and laid out alike"""
+    g = p.grad
+    return (p.is_cuda and p.device == dev and p.dtype == torch.float32 and not g.is_sparse and g.dtype == torch.float32 and
+            g.device == dev and _dense(p) and g.stride() == p.stride() and
+            all(s[k].dtype == torch.float32 and s[k].device == dev and s[k].stride() == p.stride() for k in ("exp_avg", "exp_avg_sq")))
+
+
+def chunk_pairs(numels, chunk):
+    """(pairs, chunk0) of a multi-tensor launch: pairs = (item, chunk) for every chunk of `chunk` elements of every item, in order (one
+    workgroup each); chunk0[i] = the index of item i's first pair"""
+    pairs, chunk0 = [], []
+    for i, n in enumerate(numels):
+        chunk0.append(len(pairs))
+        pairs += [(i, c) for c in range((n + chunk - 1) // chunk)]
+    return pairs, chunk0
+
+
+class _LaunchTable:
+    """The device tables of a multi-tensor launch: the chunk pairs (static per parameter set) and the item rows of pointers, refreshed by
+    `upload` whenever a pointer moved (gradient buffers may move between steps).  The optimizers hang their own bookkeeping on it."""
+
+    def __init__(self, numels, chunk, item, dev):
+        pairs, self.chunk0 = chunk_pairs(numels, chunk)
+        self.n_items, self.n_chunks, self.words = len(numels), len(pairs), C.sizeof(item) // 8
+        nbytes = C.sizeof(item) * self.n_items
+        self.host = [torch.empty(nbytes, dtype=torch.uint8).pin_memory() for _ in range(2)]
+        self.events, self.flip, self.rows = [None, None], 0, None
+        self.dev = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        self.chunks = torch.tensor(pairs, dtype=torch.int32).to(dev)
+
+    def upload(self, rows):
+        """Two pinned staging buffers are used alternately, each guarded by an event recorded behind its H2D copy: the host may run
+        several steps ahead of the GPU (no per-step sync in bench.py / train.py), so a staging buffer is rewritten only after the copy
+        that last read it has executed (without the wait, step N's table could be overwritten with step N + 2's pointers
+        before step N's copy ran)."""
+        self.flip = 1 - self.flip
+        host, ev = self.host[self.flip], self.events
+        if ev[self.flip] is not None:
+            ev[self.flip].synchronize()
+        np.frombuffer(host.numpy(), dtype=np.int64).reshape(self.n_items, self.words)[:] = np.asarray(rows, dtype=np.int64)
+        self.dev.copy_(host, non_blocking=True)
+        e = torch.cuda.Event()
+        e.record(torch.cuda.current_stream(self.dev.device))
+        ev[self.flip] = e
+        self.rows = rows
 
 
 class HipAdam(torch.optim.Adam):
@@ -39,43 +85,14 @@ class HipAdam(torch.optim.Adam):
         super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=amsgrad, **kw)
         self._tables = {}       # group index -> cached launch tables
 
-    # ---- launch tables -------------------------------------------------------------------------------------
     def _table(self, gi, plist):
-        """(items host array, pinned staging, device items, device chunks, n_chunks); sizes are static per group, pointers
-        are refreshed by `_refresh` (gradient buffers may move between steps)."""
+        """the group's launch table; sizes are static per group, pointers are refreshed by `upload`"""
         key = tuple((p.data_ptr(), p.numel()) for p in plist)
         t = self._tables.get(gi)
-        if t is not None and t["key"] == key:
-            return t
-        dev = plist[0].device
-        chunk = L.load().swv2_adam_chunk()
-        pairs = []
-        for i, p in enumerate(plist):
-            pairs += [(i, c) for c in range((p.numel() + chunk - 1) // chunk)]
-        chunks = torch.tensor(pairs, dtype=torch.int32).to(dev)
-        nbytes = C.sizeof(_Item) * len(plist)
-        t = {"key": key, "host": [torch.empty(nbytes, dtype=torch.uint8).pin_memory() for _ in range(2)],
-             "dev": torch.empty(nbytes, dtype=torch.uint8, device=dev), "chunks": chunks, "n_chunks": len(pairs), "ptrs": None}
-        self._tables[gi] = t
+        if t is None or t.key != key:
+            t = self._tables[gi] = _LaunchTable([p.numel() for p in plist], L.load().swv2_adam_chunk(), L.AdamItem, plist[0].device)
+            t.key, t.step = key, None
         return t
-
-    @staticmethod
-    def _refresh(t, ptrs, n):
-        """upload the pointer table.  Two pinned staging buffers are used alternately, each guarded by an event recorded behind
-        its H2D copy: the host may run several steps ahead of the GPU (no per-step sync in bench.py / train.py), so a staging
-        buffer is rewritten only after the copy that last read it has executed (without the wait, step N's table
-        could be overwritten with step N + 2's pointers before step N's copy ran)."""
-        t["flip"] = 1 - t.get("flip", 0)
-        host = t["host"][t["flip"]]
-        ev = t.setdefault("events", [None, None])
-        if ev[t["flip"]] is not None:
-            ev[t["flip"]].synchronize()
-        np.frombuffer(host.numpy(), dtype=np.int64).reshape(n, 5)[:] = np.asarray(ptrs, dtype=np.int64)
-        t["dev"].copy_(host, non_blocking=True)
-        e = torch.cuda.Event()
-        e.record(torch.cuda.current_stream(t["dev"].device))
-        ev[t["flip"]] = e
-        t["ptrs"] = ptrs
 
     def load_state_dict(self, state_dict):
         super().load_state_dict(state_dict)
@@ -106,31 +123,27 @@ class HipAdam(torch.optim.Adam):
             t = self._table(gi, plist)
             ptrs = tuple((p.data_ptr(), p.grad.data_ptr(), s["exp_avg"].data_ptr(), s["exp_avg_sq"].data_ptr(), p.numel())
                          for p, s in zip(plist, states))
-            if ptrs != t["ptrs"]:
-                # new tensors: the kernel walks raw memory, so every (p, grad, m, v) must be fp32 on the GPU, dense and laid
-                # out alike, and the per-parameter step counters must agree; anything else keeps torch's exact path
-                ok = all(p.is_cuda and p.dtype == torch.float32 and p.grad.dtype == torch.float32 and not p.grad.is_sparse and
-                         _dense(p) and p.grad.stride() == p.stride() and
-                         s["exp_avg"].stride() == p.stride() and s["exp_avg_sq"].stride() == p.stride()
-                         for p, s in zip(plist, states))
-                if ok and t.get("step") is None:           # new table (first step, new parameters, restored state)
+            if ptrs != t.rows:
+                # new tensors: anything the kernel cannot walk, or per-parameter step counters that disagree, keeps torch's exact path
+                ok = all(_kernel_ok(p, s, plist[0].device) for p, s in zip(plist, states))
+                if ok and t.step is None:           # new table (first step, new parameters, restored state)
                     steps = {int(s["step"]) for s in states}
                     ok = len(steps) == 1
                     if ok:
-                        t["step"], t["step_tensors"] = steps.pop(), [s["step"] for s in states]
+                        t.step, t.step_tensors = steps.pop(), [s["step"] for s in states]
                 if not ok:
                     self._tables.pop(gi, None)
                     slow.append(gi)
                     continue
-                self._refresh(t, ptrs, len(plist))
-            t["step"] += 1
-            step = t["step"]
+                t.upload(ptrs)
+            t.step += 1
+            step = t.step
             stream = torch.cuda.current_stream(plist[0].device).cuda_stream
             b1, b2 = group["betas"]
-            L.check(L.load().swv2_adam_multi(t["dev"].data_ptr(), t["chunks"].data_ptr(), t["n_chunks"], float(group["lr"]),
+            L.check(L.load().swv2_adam_multi(t.dev.data_ptr(), t.chunks.data_ptr(), t.n_chunks, float(group["lr"]),
                                              float(b1), float(b2), float(group["eps"]), step, float(grad_inv_scale), stream),
                     "swv2_adam_multi")
-            torch._foreach_add_(t["step_tensors"], 1.0)      # state_dict() keeps torch's per-parameter `step` entries
+            torch._foreach_add_(t.step_tensors, 1.0)      # state_dict() keeps torch's per-parameter `step` entries
             # the kernel wrote the parameters behind autograd's back: bump their version counters like an in-place torch op
             # would (anything keyed on `Tensor._version` -- e.g. cached casts of the weights -- must see the change)
             torch.autograd.graph.increment_version(plist)
@@ -151,10 +164,6 @@ class HipAdam(torch.optim.Adam):
 # ---------------------------------------------------------------------------------------------------------------
 # LAMB
 # ---------------------------------------------------------------------------------------------------------------
-class _LambItem(C.Structure):
-    _fields_ = [("p", C.c_void_p), ("g", C.c_void_p), ("m", C.c_void_p), ("v", C.c_void_p), ("n", C.c_long), ("chunk0", C.c_long)]
-
-
 def _f32(x) -> float:
     """the fp32 value of a scalar, as a Python float: what the kernel receives (1 - beta2 formed from the DOUBLE 0.999 is off by 3e-5)"""
     return float(np.float32(x))
@@ -211,54 +220,23 @@ class HipLamb(torch.optim.Optimizer):
         super().load_state_dict(state_dict)
         self._table, self._torch_only = None, set()
 
-    # ---- launch tables -------------------------------------------------------------------------------------
-    @staticmethod
-    def _kernel_ok(p, s, dev):
-        g = p.grad
-        return (p.is_cuda and p.device == dev and p.dtype == torch.float32 and not g.is_sparse and g.dtype == torch.float32 and
-                g.device == dev and _dense(p) and g.stride() == p.stride() and
-                all(s[k].dtype == torch.float32 and s[k].device == dev and s[k].stride() == p.stride() for k in ("exp_avg", "exp_avg_sq")))
-
     def _tables_for(self, work, dev):
-        """ONE item table and ONE chunk table for the tensors of every group the kernels take (group = a range of both), the workspace and
-        the pinned staging; sizes are static per parameter set, pointers are refreshed by `_upload`."""
+        """ONE launch table for the tensors of every group the kernels take (group = a range of its items and chunks) and the workspace"""
         sig = tuple((gi, tuple((p.data_ptr(), p.numel()) for p in pl)) for gi, _, pl in work)
         t = self._table
-        if t is not None and t["sig"] == sig:
+        if t is not None and t.sig == sig:
             return t
         lib = L.load()
-        chunk = lib.swv2_lamb_chunk()
-        pairs, chunk0, ranges, n_items = [], [], {}, 0
+        t = _LaunchTable([p.numel() for _, _, pl in work for p in pl], lib.swv2_lamb_chunk(), L.LambItem, dev)
+        t.sig, t.params, t.ranges, i0 = sig, [p for _, _, pl in work for p in pl], {}, 0
         for gi, _, pl in work:
-            lo = (n_items, len(pairs))
-            for p in pl:
-                chunk0.append(len(pairs))
-                pairs += [(n_items, c) for c in range((p.numel() + chunk - 1) // chunk)]
-                n_items += 1
-            ranges[gi] = lo + (n_items, len(pairs))           # item_lo, chunk_lo, item_hi, chunk_hi
-        nbytes = C.sizeof(_LambItem) * n_items
-        ws_bytes = lib.swv2_lamb_ws_bytes(n_items, len(pairs))
-        t = {"sig": sig, "ranges": ranges, "chunk0": chunk0, "n_items": n_items, "n_chunks": len(pairs), "rows": None,
-             "host": [torch.empty(nbytes, dtype=torch.uint8).pin_memory() for _ in range(2)], "events": [None, None], "flip": 0,
-             "dev": torch.empty(nbytes, dtype=torch.uint8, device=dev), "chunks": torch.tensor(pairs, dtype=torch.int32).to(dev),
-             "ws": torch.zeros(ws_bytes // 4, dtype=torch.float32, device=dev), "ws_bytes": ws_bytes,
-             "params": [p for _, _, pl in work for p in pl]}
+            i1 = i0 + len(pl)
+            t.ranges[gi] = (i0, t.chunk0[i0], i1, t.chunk0[i1] if i1 < t.n_items else t.n_chunks)      # item_lo, chunk_lo, item_hi, chunk_hi
+            i0 = i1
+        t.ws_bytes = lib.swv2_lamb_ws_bytes(t.n_items, t.n_chunks)
+        t.ws = torch.zeros(t.ws_bytes // 4, dtype=torch.float32, device=dev)
         self._table = t
         return t
-
-    @staticmethod
-    def _upload(t, rows):
-        """the pointer table through two pinned buffers used alternately, each guarded by an event behind its copy (`HipAdam._refresh`)"""
-        t["flip"] = 1 - t["flip"]
-        host, ev = t["host"][t["flip"]], t["events"]
-        if ev[t["flip"]] is not None:
-            ev[t["flip"]].synchronize()
-        np.frombuffer(host.numpy(), dtype=np.int64).reshape(t["n_items"], 6)[:] = np.asarray(rows, dtype=np.int64)
-        t["dev"].copy_(host, non_blocking=True)
-        e = torch.cuda.Event()
-        e.record(torch.cuda.current_stream(t["dev"].device))
-        ev[t["flip"]] = e
-        t["rows"] = rows
 
     def kernel_norms(self):
         """(G^2, {parameter: float tensor (|p|^2, |u|^2, r)}) as the kernels of the last step stored them (device tensors, views of the
@@ -266,8 +244,8 @@ class HipLamb(torch.optim.Optimizer):
         t = self._table
         if t is None:
             return None
-        ws = t["ws"]
-        return ws[L.LAMB_WS_GNORM2], {p: ws[L.lamb_ws_item(i):L.lamb_ws_item(i) + 3] for i, p in enumerate(t["params"])}
+        ws = t.ws
+        return ws[L.LAMB_WS_GNORM2], {p: ws[L.lamb_ws_item(i):L.lamb_ws_item(i) + 3] for i, p in enumerate(t.params)}
 
     # ---- step ----------------------------------------------------------------------------------------------
     def _flags(self, group):
@@ -302,15 +280,15 @@ class HipLamb(torch.optim.Optimizer):
                 break
             t = self._tables_for(work, dev)
             rows = tuple((p.data_ptr(), p.grad.data_ptr(), self.state[p]["exp_avg"].data_ptr(), self.state[p]["exp_avg_sq"].data_ptr(),
-                          p.numel(), c0) for p, c0 in zip(t["params"], t["chunk0"]))
-            if rows == t["rows"]:
+                          p.numel(), c0) for p, c0 in zip(t.params, t.chunk0))
+            if rows == t.rows:
                 break
-            bad = {gi for gi, _, pl in work if not all(self._kernel_ok(p, self.state[p], dev) for p in pl)}
+            bad = {gi for gi, _, pl in work if not all(_kernel_ok(p, self.state[p], dev) for p in pl)}
             if not bad:
-                self._upload(t, rows)
+                t.upload(rows)
                 break
             self._torch_only |= bad
-        slow = [w for w in groups if t is None or w[0] not in t["ranges"]]
+        slow = [w for w in groups if t is None or w[0] not in t.ranges]
         # the slow groups' share of G^2 (float64), handed to the kernels as a device float
         extra = None
         for _, _, pl in slow:
@@ -322,16 +300,16 @@ class HipLamb(torch.optim.Optimizer):
             lib = L.load()
             stream = torch.cuda.current_stream(dev).cuda_stream
             extra_dev = extra.to(dev, torch.float32).reshape(1) if extra is not None else None
-            ws = t["ws"]
-            L.check(lib.swv2_lamb_grad_norm(t["dev"].data_ptr(), t["chunks"].data_ptr(), t["n_items"], t["n_chunks"], inv, ws.data_ptr(),
-                                            t["ws_bytes"], stream), "swv2_lamb_grad_norm")
+            ws = t.ws
+            L.check(lib.swv2_lamb_grad_norm(t.dev.data_ptr(), t.chunks.data_ptr(), t.n_items, t.n_chunks, inv, ws.data_ptr(),
+                                            t.ws_bytes, stream), "swv2_lamb_grad_norm")
             for gi, group, pl in work:
-                i0, c0, i1, c1 = t["ranges"][gi]
+                i0, c0, i1, c1 = t.ranges[gi]
                 b1, b2 = group["betas"]
-                L.check(lib.swv2_lamb_multi(t["dev"].data_ptr(), t["chunks"].data_ptr(), t["n_items"], t["n_chunks"], i0, i1, c0, c1,
+                L.check(lib.swv2_lamb_multi(t.dev.data_ptr(), t.chunks.data_ptr(), t.n_items, t.n_chunks, i0, i1, c0, c1,
                                             float(group["lr"]), float(b1), float(b2), float(group["eps"]), float(group["weight_decay"]), inv,
                                             max_norm, int(group["step"]), self._flags(group),
-                                            extra_dev.data_ptr() if extra_dev is not None else None, ws.data_ptr(), t["ws_bytes"], stream),
+                                            extra_dev.data_ptr() if extra_dev is not None else None, ws.data_ptr(), t.ws_bytes, stream),
                         "swv2_lamb_multi")
                 # the kernel wrote the parameters behind autograd's back: bump their version counters like an in-place torch op would
                 torch.autograd.graph.increment_version(pl)

@@ -63,8 +63,7 @@ def test_ctypes_structs_follow_the_header_field_order():
              "swv2_mlp_args": L.MlpArgs, "swv2_mlp_bwd_args": L.MlpBwdArgs, "swv2_proj_ln_args": L.ProjLnArgs,
              "swv2_proj_ln_bwd_args": L.ProjLnBwdArgs, "swv2_ln_args": L.LnArgs,
              "swv2_wgrad_item": L.WgradItem, "swv2_block_plan_t": L.BlockPlan, "swv2_attn_kernel_t": L.AttnKernelInfo}
-    from swin_v2_weather_amd.utils.optim import _Item
-    pairs["swv2_adam_item"] = _Item
+    pairs["swv2_adam_item"] = L.AdamItem
     for cname, cls in pairs.items():
         assert [f[0] for f in cls._fields_] == header_struct_fields(cname), cname
     doc = open(os.path.join(ROOT, "INTEGRATION.md")).read()

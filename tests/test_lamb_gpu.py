@@ -40,7 +40,7 @@ class Bed:
     and the workspace; `launch` is one optimizer step through the C ABI."""
 
     def __init__(self, dev, sizes, groups, shift=None):
-        from swin_v2_weather_amd.utils.optim import _LambItem
+        from swin_v2_weather_amd._lib import LambItem as _LambItem
         self.dev, self.sizes, self.groups = dev, sizes, groups
         self.order = [i for g in groups for i in g]
         self.buf, self.view = {}, {}

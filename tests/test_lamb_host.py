@@ -143,7 +143,7 @@ def test_other_dtypes_and_sparse_gradients_take_the_torch_path_too():
 
 
 def test_ctypes_item_follows_the_header_and_workspace_arithmetic():
-    from swin_v2_weather_amd.utils.optim import _LambItem
+    from swin_v2_weather_amd._lib import LambItem as _LambItem
     assert [f[0] for f in _LambItem._fields_] == header_struct_fields("swv2_lamb_item") == ["p", "g", "m", "v", "n", "chunk0"]
     assert ctypes.sizeof(_LambItem) == 48
     lib = L.load()
@@ -203,3 +203,30 @@ def test_cpu_trainer_with_fusedlamb_builds_hiplamb(tmp_path):
     loss = tr.train_step((torch.randn(2, 4, 24, 36, generator=g), torch.randn(2, 4, 24, 36, generator=g)))
     assert torch.isfinite(loss) and tr.optimizer.param_groups[0]["step"] == 1
     assert any(not torch.equal(a, b) for a, b in zip(before, tr.model.parameters()))
+
+
+def test_chunk_pairs_lists_every_chunk_once_and_matches_the_two_loops_it_replaced():
+    """utils/optim.chunk_pairs (the tables of HipAdam and HipLamb): tensors of 1 element, one short of a chunk, a chunk, one past it and
+    three chunks -- every (item, chunk) once and in order, chunk0 = the running sum of the chunk counts."""
+    from swin_v2_weather_amd.utils.optim import chunk_pairs
+    numels, chunk = [1, 4095, 4096, 4097, 3 * 4096], 4096
+    pairs, chunk0 = chunk_pairs(numels, chunk)
+    counts = [sum(1 for i, _ in pairs if i == k) for k in range(len(numels))]
+    assert counts == [1, 1, 1, 2, 3]
+    assert chunk0 == [0, 1, 2, 3, 5]
+    assert pairs == [(0, 0), (1, 0), (2, 0), (3, 0), (3, 1), (4, 0), (4, 1), (4, 2)]
+    assert pairs == sorted(set(pairs)) and len(pairs) == sum(counts)
+    for (i, c), n in ((pc, numels[pc[0]]) for pc in pairs):
+        assert 0 <= c * chunk < n                                     # every chunk starts inside its tensor
+    # HipAdam._table's loop, as it stood
+    adam = []
+    for i, n in enumerate(numels):
+        adam += [(i, c) for c in range((n + chunk - 1) // chunk)]
+    # HipLamb._tables_for's loop, as it stood (one group)
+    lamb, lamb0, n_items = [], [], 0
+    for n in numels:
+        lamb0.append(len(lamb))
+        lamb += [(n_items, c) for c in range((n + chunk - 1) // chunk)]
+        n_items += 1
+    assert pairs == adam == lamb and chunk0 == lamb0
+    assert chunk_pairs([], chunk) == ([], [])

@@ -164,12 +164,12 @@ def probe_optim():
             f"({44 * n / tl / 1e6:5.2f} TB/s of 44 B/param)")
     t = lamb._table
     lib, st = L.load(), torch.cuda.current_stream(dev).cuda_stream
-    tabs = (t["dev"].data_ptr(), t["chunks"].data_ptr(), t["n_items"], t["n_chunks"])
-    ws = (t["ws"].data_ptr(), t["ws_bytes"])
+    tabs = (t.dev.data_ptr(), t.chunks.data_ptr(), t.n_items, t.n_chunks)
+    ws = (t.ws.data_ptr(), t.ws_bytes)
     ta_ = adam._tables[0]
-    k_adam = lambda: L.check(lib.swv2_adam_multi(ta_["dev"].data_ptr(), ta_["chunks"].data_ptr(), ta_["n_chunks"], 1e-3, 0.9, 0.95, 1e-8, 7, 1.0, st))
+    k_adam = lambda: L.check(lib.swv2_adam_multi(ta_.dev.data_ptr(), ta_.chunks.data_ptr(), ta_.n_chunks, 1e-3, 0.9, 0.95, 1e-8, 7, 1.0, st))
     k_norm = lambda: L.check(lib.swv2_lamb_grad_norm(*tabs, 1.0, *ws, st))
-    k_multi = lambda: L.check(lib.swv2_lamb_multi(*tabs, 0, t["n_items"], 0, t["n_chunks"], 1e-3, 0.9, 0.999, 1e-6, 0.01, 1.0, 5.0, 7, 7, None, *ws, st))
+    k_multi = lambda: L.check(lib.swv2_lamb_multi(*tabs, 0, t.n_items, 0, t.n_chunks, 1e-3, 0.9, 0.999, 1e-6, 0.01, 1.0, 5.0, 7, 7, None, *ws, st))
     for rnd in range(3):                 # the entry points alone (no Python side), alternating
         tk, tg, tm = timeit(k_adam, 50), timeit(k_norm, 50), timeit(k_multi, 50)
         say(f"  round {rnd}: swv2_adam_multi {tk:6.1f} us ({28 * n / tk / 1e6:5.2f} TB/s of 28 B/param)   swv2_lamb_grad_norm {tg:6.1f} us "
