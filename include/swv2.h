@@ -34,7 +34,8 @@ extern "C" {
  * swv2_block_wgrad_kernel; 109: swv2_block_plan (+ swv2_block_plan_t, enum swv2_block_step, swv2_block_step_id / _name),
  * swv2_block_desc loses fuse_attn and wgrad_side_stream; 110: the attention kernel-selection queries swv2_attn_fwd_kernel /
  * swv2_attn_bwd_kernel (+ swv2_attn_kernel_t, SWV2_ATTN_K_*); 111: the LAMB optimizer, swv2_lamb_* (+ swv2_lamb_item, SWV2_LAMB_*);
- * 112: forecast scores, swv2_score_*. */
+ * 112: forecast scores, swv2_score_*.  The dataset statistics, swv2_stats_*, came later and are purely additive (new entry points only,
+ * no struct member moves): the revision stays 112. */
 #define SWV2_VERSION 112
 
 enum {
@@ -502,6 +503,28 @@ int swv2_score_sums(const float* prd, long prd_bstride, const float* tar, long t
                     int H, int W, void* ws, size_t ws_bytes, void* stream);
 int swv2_score_finalize(const void* ws, size_t ws_bytes, int B, int C, int H, int W, const float* scale, float* sums, float* rmse, float* acc,
                         float* rmse_mean, float* acc_mean, void* stream);
+
+/* Dataset statistics: the running sums behind global_means / global_stds / time_diff_stds / time_means, one pass per time slab while the
+ * year files stream through the device (utils/dataset_stats.py).  slab, prev: [C][H][W] fp32 on the device; everything accumulated is fp64.
+ *   x' = (double)x - pivot[c]     d = (double)x - (double)prev (only when prev != NULL: the previous slab of the SAME year file)
+ *   tsum [C][H][W] += x'          part [C][slices][6] += (sum x', sum x'^2, sum d, sum d^2, number of non-finite x, 0 (spare))
+ * swv2_stats_accumulate: one launch of C * swv2_stats_slices(C, H, W) workgroups; workgroup (c, slice) owns part[c][slice][0..5] and the tsum
+ * elements [H W sl / slices / 4 * 4, H W (sl + 1) / slices / 4 * 4) of plane c (the last slice to the end).  Slabs are serialised on the
+ * stream and every accumulator has one owner: no atomics.  first != 0 stores instead of adding (tsum and part alike): nothing to zero
+ * beforehand.  pivot [C] fp64 on the device, a value near the channel mean (an fp32 value, so that x' is exact), the same for every call.
+ * swv2_stats_finalize: folds the slices of each channel in one fixed order (two runs on the same inputs agree bit for bit) into
+ *   folded [C][6]     and writes     time_means [C][H][W] = (float)(pivot[c] + tsum / T),     T = the number of slabs accumulated.
+ * Means, variances and roots over the C channels are host arithmetic on `folded` (utils/dataset_stats.py::vectors_from_folded).
+ * Refused with SWV2_ERR_INVALID before any launch: a null pointer (prev may be NULL), C, H, W <= 0, C >= 2^20, H * W >= 2^30,
+ * H * W % 4 != 0, slab / prev / tsum / time_means not 16-byte aligned, pivot / part / folded not 8-byte aligned, a workspace (part) smaller
+ * than swv2_stats_ws_bytes, T <= 0.  swv2_stats_slices and swv2_stats_ws_bytes are host-only (no HIP call); both return 0 for a non-positive
+ * argument. */
+int swv2_stats_slices(int C, int H, int W);
+size_t swv2_stats_ws_bytes(int C, int H, int W);          /* C * swv2_stats_slices(C, H, W) * 6 * 8: the bytes of part */
+int swv2_stats_accumulate(const float* slab, const float* prev, const double* pivot, double* tsum, void* part, size_t part_bytes, int C, int H,
+                          int W, int first, void* stream);
+int swv2_stats_finalize(const void* part, size_t part_bytes, const double* tsum, const double* pivot, int C, int H, int W, long T,
+                        double* folded, float* time_means, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * ERA5 input assembly (the step BEFORE the model): raw time slabs staged on the device by async H2D copies

@@ -473,6 +473,44 @@ def forecast_scores(prd, tar, w, clim=None, scale=None, ws=None):
     return score_finalize(ws, B, Cc, H, W, scale)
 
 
+def stats_slices(Cc: int, H: int, W: int) -> int:
+    """slices per channel of swv2_stats_accumulate's plan (host-only)"""
+    return int(L.load().swv2_stats_slices(Cc, H, W))
+
+
+def stats_workspace(Cc: int, H: int, W: int, device) -> torch.Tensor:
+    """part [C, slices, 6] fp64 of swv2_stats_accumulate / swv2_stats_finalize; not zeroed: the first accumulate (first=True) stores"""
+    return torch.empty(int(L.load().swv2_stats_ws_bytes(Cc, H, W)) // 8, dtype=torch.float64, device=device).view(Cc, -1, 6)
+
+
+def stats_accumulate(slab, prev, pivot, tsum, part, first: bool, stream=None):
+    """one time slab [C, H, W] fp32 into the running fp64 sums: tsum [C, H, W] += slab - pivot[c], part [C, slices, 6] += the slice sums of
+    (x', x'^2, d, d^2, non-finite count, 0), d = slab - prev (prev None: no difference terms).  first: store instead of add."""
+    _chk(slab, torch.float32, "stats slab"); _chk(pivot, torch.float64, "stats pivot")
+    _chk(tsum, torch.float64, "stats tsum"); _chk(part, torch.float64, "stats workspace")
+    if slab.dim() != 3 or tsum.shape != slab.shape or pivot.numel() != slab.shape[0]:
+        raise L.Swv2Error(f"stats_accumulate: slab {tuple(slab.shape)}, tsum {tuple(tsum.shape)}, pivot {tuple(pivot.shape)}: expected "
+                          "[C, H, W], [C, H, W], [C]")
+    if prev is not None and _chk(prev, torch.float32, "stats prev").shape != slab.shape:
+        raise L.Swv2Error(f"stats_accumulate: prev {tuple(prev.shape)}, slab {tuple(slab.shape)}")
+    Cc, H, W = slab.shape
+    L.check(L.load().swv2_stats_accumulate(_p(slab), _p(prev), _p(pivot), _p(tsum), _p(part), part.numel() * 8, Cc, H, W, int(bool(first)),
+                                           stream if stream is not None else _stream()), "swv2_stats_accumulate")
+
+
+def stats_finalize(part, tsum, pivot, T: int, stream=None):
+    """-> (folded [C, 6] fp64: the slices of every channel added in a fixed order, time_means [C, H, W] fp32 = pivot + tsum / T)"""
+    _chk(part, torch.float64, "stats workspace"); _chk(tsum, torch.float64, "stats tsum"); _chk(pivot, torch.float64, "stats pivot")
+    if tsum.dim() != 3 or pivot.numel() != tsum.shape[0]:
+        raise L.Swv2Error(f"stats_finalize: tsum {tuple(tsum.shape)}, pivot {tuple(pivot.shape)}: expected [C, H, W], [C]")
+    Cc, H, W = tsum.shape
+    folded = torch.empty(Cc, 6, dtype=torch.float64, device=tsum.device)
+    time_means = torch.empty(Cc, H, W, dtype=torch.float32, device=tsum.device)
+    L.check(L.load().swv2_stats_finalize(_p(part), part.numel() * 8, _p(tsum), _p(pivot), Cc, H, W, int(T), _p(folded), _p(time_means),
+                                         stream if stream is not None else _stream()), "swv2_stats_finalize")
+    return folded, time_means
+
+
 def era5_select_normalize(raw, out, chan, mean, std, coff=0, stream=None):
     """raw [B, S, Craw, Hraw, Wraw] fp32 -> out[:, coff : coff + S*len(chan)] = (raw[:, s, chan] - mean) / std, cropped to out's H, W"""
     B, S, Craw, Hraw, Wraw = raw.shape

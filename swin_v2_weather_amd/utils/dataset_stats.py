@@ -1,0 +1,341 @@
+"""Dataset statistics: make the four statistics files every config of config/swin.yaml names from the year files.
+
+    global_means.npy, global_stds.npy   [1, C, 1, 1]   the z-score of utils/host_pipeline.py, inference, the Trainer's valid_rmse_*
+    time_diff_stds.npy                  [1, C, 1, 1]   utils/losses.py::load_stats (the step-1 value; losses.py scales it by sqrt(dt))
+    time_means.npy                      [1, C, H, W]   utils/weighted_acc_rmse.py::load_climatology (ACC)
+
+Over the year files y with N_y slabs x[y, t, c, i, j] (all C stored channels, the full stored grid, unweighted), T = sum N_y,
+N = T H W, N_d = sum (N_y - 1) H W:
+    global_means[c] = sum x / N                    global_stds[c] = sqrt(sum (x - global_means[c])^2 / N)      (population form)
+    time_means[c, i, j] = sum_{y, t} x / T         time_diff_stds[c] = population std of d[y, t] = x[y, t + 1] - x[y, t], t < N_y - 1
+Differences are taken inside a year file only.
+
+One pass, shifted: with a per-channel pivot p[c] near the mean (an fp32 value), x' = x - p[c] is exact in fp64 and
+    S1 = sum x', S2 = sum x'^2, D1 = sum d, D2 = sum d^2, tsum[c, i, j] = sum_t x'
+give mean = p + S1 / N, var = S2 / N - (S1 / N)^2 with nothing of size cancelling.  All sums are fp64.  On a CUDA device the slabs
+stream through the staging of Era5HostPipeline (pinned ring, copy stream, two alternating device slabs) into swv2_stats_accumulate
+(csrc/stats.hip); on `cpu` the same formulas run in numpy fp64.  There is no fallback from one to the other.
+
+States of disjoint sets of year files computed with the same pivot add up (`DatasetStats.merge`): eight processes can each take a
+subset of the years (`--years ... --partial-out`) and one `merge` call writes the files.
+
+    python -m swin_v2_weather_amd.utils.dataset_stats --data DIR --out DIR [--years 1979 1980 ...] [--device cuda:0|cpu]
+    python -m swin_v2_weather_amd.utils.dataset_stats --data DIR --years 1979 --partial-out 1979.npz
+    python -m swin_v2_weather_amd.utils.dataset_stats merge 1979.npz 1980.npz ... --out DIR
+"""
+from __future__ import annotations
+
+import argparse
+import os
+from collections import deque
+from concurrent.futures import ThreadPoolExecutor
+
+import numpy as np
+import torch
+
+from .host_pipeline import SyntheticYearSource, YearArraySource  # noqa: F401  (the sources this module streams)
+
+FILES = ("global_means.npy", "global_stds.npy", "time_diff_stds.npy", "time_means.npy")
+S1, S2, D1, D2, NONFINITE, SPARE = range(6)          # the six running values per channel (csrc/stats.hip)
+
+
+def vectors_from_folded(folded, pivot, T: int, N_d: int, H: int, W: int):
+    """folded [C, 6] fp64, pivot [C] fp64 -> (global_means, global_stds, time_diff_stds), each [C] fp64: the [C]-sized arithmetic every
+    path (kernels, numpy, merged states) shares"""
+    n = float(T) * H * W
+    m = folded[:, S1] / n
+    var = folded[:, S2] / n - m * m
+    md = folded[:, D1] / float(N_d)
+    var_d = folded[:, D2] / float(N_d) - md * md
+    return pivot + m, np.sqrt(np.maximum(var, 0.0)), np.sqrt(np.maximum(var_d, 0.0))
+
+
+def pivot_of(slab) -> np.ndarray:
+    """the pivot rule: the per-channel fp64 mean of a slab [C, H, W], rounded to fp32 (returned as fp64); 0 where that is not finite"""
+    p = np.asarray(slab, dtype=np.float64).mean(axis=(1, 2)).astype(np.float32).astype(np.float64)
+    return np.where(np.isfinite(p), p, 0.0)
+
+
+class DatasetStats:
+    """Running state of the statistics of [C, H, W] fp32 slabs.  `update(slab, prev)` takes one slab (prev: the previous slab of the
+    same year file, None at the first slab of a file); `finalize()` returns the four arrays.  device `cpu`: numpy fp64 on numpy /
+    CPU-tensor slabs; a CUDA device: the HIP kernels on CUDA-tensor slabs (H * W % 4 == 0 required, no fallback)."""
+
+    def __init__(self, C: int, H: int, W: int, device, pivot):
+        self.C, self.H, self.W = int(C), int(H), int(W)
+        self.device = torch.device(device)
+        self.pivot = np.ascontiguousarray(np.asarray(pivot, dtype=np.float64).reshape(-1))
+        if self.pivot.shape != (self.C,) or not np.all(np.isfinite(self.pivot)):
+            raise ValueError(f"DatasetStats: pivot must be {self.C} finite values, got shape {np.asarray(pivot).shape}")
+        self.T, self.N_d = 0, 0
+        self.on_kernels = self.device.type == "cuda"
+        if self.on_kernels:
+            if (self.H * self.W) % 4 != 0:
+                raise ValueError(f"DatasetStats on {self.device}: H * W = {self.H * self.W} is not a multiple of 4 (swv2_stats_accumulate); "
+                                 "use device='cpu' for this grid")
+            from .. import ops
+            self._ops = ops
+            self._pivot_dev = torch.from_numpy(self.pivot).to(self.device)
+            self._tsum = torch.empty(self.C, self.H, self.W, dtype=torch.float64, device=self.device)
+            self._part = ops.stats_workspace(self.C, self.H, self.W, self.device)
+            self._first = True
+        else:
+            self._folded = np.zeros((self.C, 6), np.float64)
+            self._tsum = np.zeros((self.C, self.H, self.W), np.float64)
+
+    # -- accumulation
+    def update(self, slab, prev=None, stream=None):
+        shape = (self.C, self.H, self.W)
+        if tuple(slab.shape) != shape or (prev is not None and tuple(prev.shape) != shape):
+            raise ValueError(f"DatasetStats.update: slab {tuple(slab.shape)}, expected {shape}")
+        if self.on_kernels:
+            self._ops.stats_accumulate(slab, prev, self._pivot_dev, self._tsum, self._part, self._first,
+                                       stream if stream is not None else torch.cuda.current_stream(self.device).cuda_stream)
+            self._first = False
+        else:
+            x = np.asarray(slab)
+            if x.dtype != np.float32:
+                raise ValueError(f"DatasetStats.update: fp32 slabs expected, got {x.dtype}")
+            x64 = x.astype(np.float64)
+            f = self._folded
+            with np.errstate(invalid="ignore", over="ignore"):    # non-finite data is counted here and refused in finalize()
+                xs = x64 - self.pivot[:, None, None]
+                self._tsum += xs
+                f[:, S1] += xs.sum(axis=(1, 2))
+                f[:, S2] += (xs * xs).sum(axis=(1, 2))
+                if prev is not None:
+                    d = x64 - np.asarray(prev).astype(np.float64)
+                    f[:, D1] += d.sum(axis=(1, 2))
+                    f[:, D2] += (d * d).sum(axis=(1, 2))
+            f[:, NONFINITE] += (~np.isfinite(x)).sum(axis=(1, 2))
+        self.T += 1
+        if prev is not None:
+            self.N_d += self.H * self.W
+
+    # -- state
+    def _fold(self):
+        """-> (folded [C, 6] numpy fp64, time_means [C, H, W] numpy fp32 | None when T == 0)"""
+        if not self.on_kernels:
+            tm = None if self.T == 0 else (self.pivot[:, None, None] + self._tsum / float(self.T)).astype(np.float32)
+            return self._folded.copy(), tm
+        if self._first:
+            return np.zeros((self.C, 6), np.float64), None
+        with torch.cuda.device(self.device):
+            folded, tm = self._ops.stats_finalize(self._part, self._tsum, self._pivot_dev, max(self.T, 1),
+                                                  torch.cuda.current_stream(self.device).cuda_stream)
+            return folded.cpu().numpy(), (tm.cpu().numpy() if self.T else None)
+
+    def state(self) -> dict:
+        """everything needed to go on or to merge, in fp64 numpy: pivot [C], T, N_d, folded [C, 6], tsum [C, H, W]"""
+        if self.on_kernels:
+            torch.cuda.synchronize(self.device)
+            tsum = np.zeros((self.C, self.H, self.W), np.float64) if self._first else self._tsum.cpu().numpy()
+        else:
+            tsum = self._tsum.copy()
+        return dict(pivot=self.pivot.copy(), T=int(self.T), N_d=int(self.N_d), folded=self._fold()[0], tsum=tsum)
+
+    def load_state(self, state) -> "DatasetStats":
+        pivot, folded, tsum = (np.asarray(state[k], dtype=np.float64) for k in ("pivot", "folded", "tsum"))
+        if tsum.shape != (self.C, self.H, self.W) or folded.shape != (self.C, 6):
+            raise ValueError(f"DatasetStats.load_state: state of shape {tsum.shape}, this object is {(self.C, self.H, self.W)}")
+        if pivot.shape != self.pivot.shape or pivot.tobytes() != self.pivot.tobytes():
+            raise ValueError("DatasetStats.load_state: the state was computed with another pivot")
+        self.T, self.N_d = int(state["T"]), int(state["N_d"])
+        if self.on_kernels:
+            self._tsum.copy_(torch.from_numpy(np.ascontiguousarray(tsum)))
+            self._part.zero_()
+            self._part[:, 0].copy_(torch.from_numpy(np.ascontiguousarray(folded)))     # slice 0 carries the channel's sums so far
+            self._first = False
+        else:
+            self._folded, self._tsum = folded.copy(), tsum.copy()
+        return self
+
+    @staticmethod
+    def merge(states, device="cpu") -> "DatasetStats":
+        """the sum of states of disjoint sets of slabs (added in the order given); raises unless every state has the same shape and the
+        same pivot, bit for bit"""
+        states = list(states)
+        if not states:
+            raise ValueError("DatasetStats.merge: no states")
+        first = states[0]
+        p0, t0 = np.asarray(first["pivot"], dtype=np.float64), np.asarray(first["tsum"])
+        folded, tsum, T, N_d = np.zeros((p0.size, 6), np.float64), np.zeros(t0.shape, np.float64), 0, 0
+        for i, s in enumerate(states):
+            p, t = np.asarray(s["pivot"], dtype=np.float64), np.asarray(s["tsum"], dtype=np.float64)
+            if t.shape != t0.shape or t.ndim != 3 or np.asarray(s["folded"]).shape != folded.shape:
+                raise ValueError(f"DatasetStats.merge: state {i} has shape {t.shape}, state 0 has {t0.shape}")
+            if p.shape != p0.shape or p.tobytes() != p0.tobytes():
+                raise ValueError(f"DatasetStats.merge: state {i} was computed with another pivot than state 0 (shards must take the pivot "
+                                 "from the same slab: the first file of the whole folder)")
+            folded += np.asarray(s["folded"], dtype=np.float64)
+            tsum += t
+            T += int(s["T"])
+            N_d += int(s["N_d"])
+        out = DatasetStats(t0.shape[0], t0.shape[1], t0.shape[2], device, p0)
+        return out.load_state(dict(pivot=p0, T=T, N_d=N_d, folded=folded, tsum=tsum))
+
+    # -- results
+    def finalize(self) -> dict:
+        """-> {"global_means", "global_stds", "time_diff_stds": [1, C, 1, 1] fp32, "time_means": [1, C, H, W] fp32}"""
+        if self.T == 0:
+            raise ValueError("DatasetStats.finalize: no slab was accumulated (T == 0)")
+        if self.N_d == 0:
+            raise ValueError(f"DatasetStats.finalize: no time difference inside a year file ({self.T} slabs, every file holds one): "
+                             "time_diff_stds is undefined")
+        folded, tm = self._fold()
+        bad = np.nonzero(folded[:, NONFINITE] != 0)[0]
+        if bad.size:
+            raise ValueError("DatasetStats.finalize: non-finite values in the data, no file is written: " +
+                             ", ".join(f"channel {int(c)}: {int(folded[c, NONFINITE])}" for c in bad))
+        gm, gs, td = vectors_from_folded(folded, self.pivot, self.T, self.N_d, self.H, self.W)
+        vec = lambda a: a.astype(np.float32).reshape(1, self.C, 1, 1)
+        return dict(global_means=vec(gm), global_stds=vec(gs), time_diff_stds=vec(td), time_means=tm.reshape(1, self.C, self.H, self.W))
+
+
+# ---- streaming a source ----------------------------------------------------------------------------------------
+def select_years(source, years=None):
+    """indices of the year files of `source` to stream: all, or those whose four-digit stem is in `years`"""
+    if years is None:
+        return list(range(len(source.years)))
+    years = [int(y) for y in years]
+    missing = [y for y in years if y not in source.years]
+    if missing:
+        raise ValueError(f"no year file for {missing}: the folder holds {source.years}")
+    return [i for i, y in enumerate(source.years) if y in years]
+
+
+def source_pivot(source) -> np.ndarray:
+    """the pivot of a source: from slab 0 of its FIRST year file, whichever years are selected, so that shards agree"""
+    if hasattr(source, "slab"):
+        return pivot_of(source.slab(0, 0).numpy())
+    buf = np.empty(source.shape, np.float32)
+    source.read(0, 0, buf)
+    return pivot_of(buf)
+
+
+def accumulate_source(source, device, pivot, year_idx=None, ring=3, workers=None) -> DatasetStats:
+    """every slab of the selected year files of `source`, in order, into a DatasetStats on `device`"""
+    device = torch.device(device)
+    C, H, W = source.shape
+    st = DatasetStats(C, H, W, device, pivot)
+    items = [(y, t) for y in (range(len(source.years)) if year_idx is None else year_idx) for t in range(source.n_samples_year[y])]
+    if device.type != "cuda":
+        bufs = [np.empty((C, H, W), np.float32) for _ in range(2)]
+        for i, (y, t) in enumerate(items):
+            source.read(y, t, bufs[i % 2])
+            st.update(bufs[i % 2], bufs[(i - 1) % 2] if t > 0 else None)
+        return st
+    direct = bool(getattr(source, "pinned", False))              # a page-locked source is copied from in place
+    ring = max(2, int(ring))
+    dev = [torch.empty((C, H, W), dtype=torch.float32, device=device) for _ in range(2)]
+    pin = [] if direct else [torch.empty((C, H, W), dtype=torch.float32, pin_memory=True) for _ in range(ring)]
+    cs = torch.cuda.Stream(device=device)
+    pool = ThreadPoolExecutor(max_workers=workers or ring)
+    free, pending, inflight, nxt = deque(range(ring)), deque(), deque(), 0     # pinned slots / reads under way / H2D copies under way
+    try:
+        for i, (y, t) in enumerate(items):
+            if direct:
+                host = source.slab(y, t)
+            else:
+                while inflight and inflight[0][0].query():       # copies that have completed give their pinned slab back
+                    free.append(inflight.popleft()[1])
+                if not free and not pending:                     # every slab of the ring is waiting for its copy
+                    ev, slot = inflight.popleft()
+                    ev.synchronize()
+                    free.append(slot)
+                while free and nxt < len(items):                 # producers: one read per free slab, in slab order
+                    slot = free.popleft()
+                    pending.append((slot, pool.submit(source.read, items[nxt][0], items[nxt][1], pin[slot].numpy())))
+                    nxt += 1
+                slot, fut = pending.popleft()
+                fut.result()                                     # a producer's exception surfaces here and fails the call
+                host = pin[slot]
+            with torch.cuda.stream(cs):
+                dev[i % 2].copy_(host, non_blocking=True)
+                # the same stream: this kernel follows its copy, and the next copy into the other slab follows the kernel that read it
+                st.update(dev[i % 2], dev[(i - 1) % 2] if t > 0 else None, stream=cs.cuda_stream)
+                if not direct:
+                    ev = torch.cuda.Event()
+                    ev.record(cs)
+                    inflight.append((ev, slot))
+        cs.synchronize()
+    finally:
+        for _, fut in pending:
+            fut.cancel()
+        pool.shutdown(wait=True)
+        cs.synchronize()
+    return st
+
+
+def compute_stats(location, device, years=None, ring=3, workers=None, source=None) -> DatasetStats:
+    """The running state over the year files under `location` (`*.npy` or `*.h5`; or over `source`, an object with the interface of
+    YearArraySource), restricted to `years` (four-digit file stems) when given.  `.finalize()` gives the four arrays, `.state()` a
+    partial result for `DatasetStats.merge`."""
+    source = YearArraySource(location) if source is None else source
+    return accumulate_source(source, device, source_pivot(source), select_years(source, years), ring=ring, workers=workers)
+
+
+# ---- files and the command line --------------------------------------------------------------------------------
+def write_files(stats: dict, out_dir) -> list:
+    os.makedirs(out_dir, exist_ok=True)
+    paths = []
+    for name in FILES:
+        paths.append(os.path.join(out_dir, name))
+        np.save(paths[-1], stats[name[:-4]])
+    return paths
+
+
+def save_state(state: dict, path) -> None:
+    with open(path, "wb") as f:                                  # (a file object: np.savez would append .npz to a bare name)
+        np.savez(f, pivot=state["pivot"], T=np.int64(state["T"]), N_d=np.int64(state["N_d"]), folded=state["folded"], tsum=state["tsum"])
+
+
+def load_state_file(path) -> dict:
+    with np.load(path) as z:
+        return dict(pivot=z["pivot"], T=int(z["T"]), N_d=int(z["N_d"]), folded=z["folded"], tsum=z["tsum"])
+
+
+def build_parser() -> argparse.ArgumentParser:
+    ap = argparse.ArgumentParser(prog="python -m swin_v2_weather_amd.utils.dataset_stats", description=__doc__.split("\n\n")[0])
+    ap.add_argument("--data", required=True, help="folder of year files (*.npy or *.h5, [N, C, H, W] fp32)")
+    ap.add_argument("--out", help="folder the four statistics files are written to")
+    ap.add_argument("--partial-out", help="write the running state (.npz) of the selected years instead, for `merge`")
+    ap.add_argument("--years", type=int, nargs="+", help="only these year files (four-digit file stems)")
+    ap.add_argument("--device", default="cuda:0" if torch.cuda.is_available() else "cpu")
+    ap.add_argument("--ring", type=int, default=3, help="pinned staging slabs")
+    ap.add_argument("--workers", type=int, default=None, help="producer threads")
+    return ap
+
+
+def build_merge_parser() -> argparse.ArgumentParser:
+    ap = argparse.ArgumentParser(prog="python -m swin_v2_weather_amd.utils.dataset_stats merge")
+    ap.add_argument("states", nargs="+", help="state files written with --partial-out")
+    ap.add_argument("--out", required=True)
+    return ap
+
+
+def main(argv=None):
+    import sys
+    argv = list(sys.argv[1:] if argv is None else argv)
+    if argv and argv[0] == "merge":
+        a = build_merge_parser().parse_args(argv[1:])
+        st = DatasetStats.merge([load_state_file(p) for p in a.states])
+        paths = write_files(st.finalize(), a.out)
+        print(f"merged {len(a.states)} states ({st.T} slabs): wrote " + ", ".join(paths))
+        return 0
+    ap = build_parser()
+    a = ap.parse_args(argv)
+    if bool(a.out) == bool(a.partial_out):
+        ap.error("give exactly one of --out and --partial-out")
+    st = compute_stats(a.data, a.device, years=a.years, ring=a.ring, workers=a.workers)
+    if a.partial_out:
+        save_state(st.state(), a.partial_out)
+        print(f"{st.T} slabs on {a.device}: wrote the state to {a.partial_out}")
+    else:
+        paths = write_files(st.finalize(), a.out)
+        print(f"{st.T} slabs on {a.device}: wrote " + ", ".join(paths))
+    return 0
+
+
+if __name__ == "__main__":
+    raise SystemExit(main())
