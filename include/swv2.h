@@ -35,7 +35,7 @@ extern "C" {
  * swv2_block_desc loses fuse_attn and wgrad_side_stream; 110: the attention kernel-selection queries swv2_attn_fwd_kernel /
  * swv2_attn_bwd_kernel (+ swv2_attn_kernel_t, SWV2_ATTN_K_*); 111: the LAMB optimizer, swv2_lamb_* (+ swv2_lamb_item, SWV2_LAMB_*);
  * 112: forecast scores, swv2_score_*.  The dataset statistics, swv2_stats_*, came later and are purely additive (new entry points only,
- * no struct member moves): the revision stays 112. */
+ * no struct member moves): the revision stays 112.  So are the plane order statistics, swv2_quantile_ws_bytes / swv2_plane_order_stats. */
 #define SWV2_VERSION 112
 
 enum {
@@ -525,6 +525,29 @@ int swv2_stats_accumulate(const float* slab, const float* prev, const double* pi
                           int W, int first, void* stream);
 int swv2_stats_finalize(const void* part, size_t part_bytes, const double* tsum, const double* pivot, int C, int H, int W, long T,
                         double* folded, float* time_means, void* stream);
+
+/* Order statistics of every (sample, channel) plane (csrc/quantile.hip): the values at K given ranks of the sorted plane, by a multi-rank
+ * radix select on order-preserving 32-bit keys (digits of 12, 5, 5, 5, 5 bits) -- five streaming passes, no sort, no plane-sized temporary.
+ * Behind the extremes metric top_quantiles_error_torch (reference utils/weighted_acc_rmse.py:117-126).
+ *   x          C planes of [H][W] fp32 per sample, sample b at x + b * bstride (elements): a channel block of a wider tensor is read in place
+ *   ranks      [K] device ints, distinct, ascending, in [0, H W): the same ranks for every plane (the caller builds them)
+ *   out        [K][B * C] fp32: out[k][b * C + c] = the element of rank ranks[k] of plane (b, c) in ascending order.  NaNs sort last (as in
+ *              torch.sort) and come back as NaN; -0.0 sorts directly below +0.0.
+ *   nan_count  [B * C] ints: the number of NaNs of the plane
+ *   ws         swv2_quantile_ws_bytes(B * C, H, W, K) bytes = planes * 35 856: per plane 8192 integer counters, the active prefixes, and the
+ *              slot and residual of every rank.  The op zeroes what it counts into and writes all state before reading it: the caller
+ *              zeroes nothing, a dirty workspace gives the bits of a clean one.
+ * One call is a fixed sequence of launches on `stream` without host synchronisation: a memset of the workspace, then per digit one count
+ * launch of B * C * slices workgroups (the plan of swv2_score_sums: slices = planes >= 2048 ? 1 : 2048 / planes, slice bounds on 16-byte
+ * vectors) that folds its LDS histogram into the plane's counters with integer atomics, and one resolve launch of B * C workgroups.  Integer
+ * counters: the result does not depend on arrival order, two runs agree bit for bit.
+ * Refused with SWV2_ERR_INVALID before any launch: a null pointer, B, C, H, W <= 0, B * C >= 2^20, H * W >= 2^30, H * W % 4 != 0, x / ws not
+ * 16-byte aligned, ranks / out / nan_count not 4-byte aligned, a batch stride that is not a multiple of 4 or (B > 1) smaller than C H W,
+ * K < 1 or K > 256, a workspace smaller than swv2_quantile_ws_bytes.  swv2_quantile_ws_bytes is host-only (no HIP call) and returns 0 for a
+ * non-positive argument. */
+size_t swv2_quantile_ws_bytes(int planes, int H, int W, int K);
+int swv2_plane_order_stats(const float* x, long bstride, int B, int C, int H, int W, const int* ranks, int K, float* out, int* nan_count,
+                           void* ws, size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * ERA5 input assembly (the step BEFORE the model): raw time slabs staged on the device by async H2D copies

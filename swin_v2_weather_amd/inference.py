@@ -12,10 +12,11 @@ loads the weights with any of the prefixes the reference produces (`module.model
 prediction fed back, next cos-zenith channel and the invariant channels re-appended.
 
 `score_rollout` is the same loop with every step scored against the verifying analysis as soon as it is written
-(utils/weighted_acc_rmse.ForecastScorer: latitude-weighted RMSE and ACC per channel and lead time, one pass per step).
+(utils/weighted_acc_rmse.ForecastScorer: latitude-weighted RMSE and ACC per channel and lead time, one pass per step; with
+extremes=True also the top-quantile error, ForecastScorer.quantile_error).
 
     python -m swin_v2_weather_amd.inference --registry DIR --steps 8 [--init x0.npy] [--out forecast.npy]
-                                            [--truth truth.npy [--climatology time_means.npy] [--scores-out scores.json]]
+                                            [--truth truth.npy [--climatology time_means.npy] [--scores-out scores.json] [--extremes]]
 """
 from __future__ import annotations
 
@@ -116,17 +117,19 @@ def rollout(model, x0: torch.Tensor, n_steps: int, coszen: torch.Tensor | None =
     return out.view(B, n_steps, Cout, H, W)
 
 
-RolloutScores = namedtuple("RolloutScores", "rmse acc rmse_samples acc_samples forecast")
+RolloutScores = namedtuple("RolloutScores", "rmse acc rmse_samples acc_samples forecast tqe", defaults=(None,))
 
 
 @torch.no_grad()
 def score_rollout(model, x0: torch.Tensor, truth, n_steps: int, coszen: torch.Tensor | None = None, n_invar: int = 0,
-                  scorer: ForecastScorer | None = None, keep_forecast: bool = False) -> RolloutScores:
+                  scorer: ForecastScorer | None = None, keep_forecast: bool = False, extremes: bool = False) -> RolloutScores:
     """`rollout` with every step's prediction scored against truth[:, s] as soon as it is written.  truth: [B, n_steps, Cout, H, W]
     (normalised as the model's output) or a callable s -> [B, Cout, H, W].  scorer: a ForecastScorer (default: no climatology, so
     no ACC; normalised units).  Unless keep_forecast, the predictions live in a two-slot ring [B, 2 Cout, H, W]: memory does not grow
     with n_steps.  -> RolloutScores(rmse [n_steps, Cout] and acc [n_steps, Cout] | None: batch means (rmse x the scorer's stds);
-    rmse_samples, acc_samples [n_steps, B, Cout]; forecast [B, n_steps, Cout, H, W] | None).  The predictions are `rollout`'s, bit for bit."""
+    rmse_samples, acc_samples [n_steps, B, Cout]; forecast [B, n_steps, Cout, H, W] | None;
+    tqe [n_steps, B, Cout] | None).  extremes: every step's prediction also goes through scorer.quantile_error against that step's truth
+    (the top-quantile error, tqe).  The predictions are `rollout`'s, bit for bit."""
     net = model.model if hasattr(model, "model") else model
     B, _, H, W = x0.shape
     Cout = net.out_chans
@@ -138,22 +141,29 @@ def score_rollout(model, x0: torch.Tensor, truth, n_steps: int, coszen: torch.Te
     rmse = torch.empty(n_steps, Cout, dtype=torch.float32, device=x0.device)
     rmse_s = torch.empty(n_steps, B, Cout, dtype=torch.float32, device=x0.device)
     acc, acc_s = (torch.empty_like(rmse), torch.empty_like(rmse_s)) if scorer.clim is not None else (None, None)
+    tqe = torch.empty_like(rmse_s) if extremes else None
     for s in _rollout_steps(net, x0, n_steps, coszen, n_invar, out, coff_of):
-        tar = truth(s) if callable(truth) else truth[:, s]
-        r = scorer.score(out, tar.to(x0.device), coff_prd=coff_of(s))
+        tar = (truth(s) if callable(truth) else truth[:, s]).to(x0.device)
+        r = scorer.score(out, tar, coff_prd=coff_of(s))
+        if extremes:
+            tqe[s] = scorer.quantile_error(out, tar, coff_prd=coff_of(s))
         rmse[s], rmse_s[s] = r.rmse_mean, r.rmse
         if acc is not None:
             acc[s], acc_s[s] = r.acc_mean, r.acc
-    return RolloutScores(rmse, acc, rmse_s, acc_s, out.view(B, n_steps, Cout, H, W) if keep_forecast else None)
+    return RolloutScores(rmse, acc, rmse_s, acc_s, out.view(B, n_steps, Cout, H, W) if keep_forecast else None, tqe)
 
 
 def lead_time_table(scores: RolloutScores, names, hours_per_step: float = 6.0) -> str:
-    """one line per lead time: RMSE (and ACC) of the named channels; names: [(column title, channel index)]"""
+    """one line per lead time: RMSE (and ACC, and the batch-mean top-quantile error when scored) of the named channels;
+    names: [(column title, channel index)]"""
     rm, ac = scores.rmse.cpu().numpy(), None if scores.acc is None else scores.acc.cpu().numpy()
-    cols = [f"rmse_{n}" for n, _ in names] + ([f"acc_{n}" for n, _ in names] if ac is not None else [])
+    tq = None if scores.tqe is None else scores.tqe.mean(dim=1).cpu().numpy()
+    cols = [f"rmse_{n}" for n, _ in names] + ([f"acc_{n}" for n, _ in names] if ac is not None else []) + \
+        ([f"tqe_{n}" for n, _ in names] if tq is not None else [])
     lines = ["lead_h " + " ".join(f"{c:>12s}" for c in cols)]
     for s in range(rm.shape[0]):
-        vals = [rm[s, i] for _, i in names] + ([ac[s, i] for _, i in names] if ac is not None else [])
+        vals = [rm[s, i] for _, i in names] + ([ac[s, i] for _, i in names] if ac is not None else []) + \
+            ([tq[s, i] for _, i in names] if tq is not None else [])
         lines.append(f"{hours_per_step * (s + 1):6.0f} " + " ".join(f"{v:12.5f}" for v in vals))
     return "\n".join(lines)
 
@@ -169,6 +179,7 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--climatology", default=None, help=".npy time means [1, Call, Hfull, Wfull] for ACC (default: the registry's time_means.npy, "
                                                         "else the hyper-parameters' time_means_path)")
     ap.add_argument("--scores-out", default=None, help="write the lead-time scores as JSON")
+    ap.add_argument("--extremes", action="store_true", help="with --truth: also score the top-quantile error (tqe_<name> columns, \"tqe\" key)")
     return ap
 
 
@@ -209,7 +220,7 @@ def _score_main(a, model, p, stats, x0, cz, n_invar):
     if truth.ndim != 5 or truth.shape[1] < a.steps:
         raise ValueError(f"--truth: expected [B, >= {a.steps}, Cout, H, W], got {truth.shape}")
     sc = score_rollout(model, x0, lambda s: torch.from_numpy(np.array(truth[:, s], dtype=np.float32)).to(x0.device), a.steps, cz, n_invar,
-                       scorer, keep_forecast=bool(a.out))
+                       scorer, keep_forecast=bool(a.out), extremes=a.extremes)
     if "track_channels" in p and "channel_names" in p:
         names = [(v, list(p["channel_names"]).index(v)) for v in p["track_channels"]]
     else:
@@ -217,9 +228,12 @@ def _score_main(a, model, p, stats, x0, cz, n_invar):
     print(f"scores in {'physical' if stds is not None else 'normalised'} units, {'with' if clim is not None else 'no climatology: without'} ACC")
     print(lead_time_table(sc, names))
     if a.scores_out:
+        doc = {"lead_hours": [6.0 * (s + 1) for s in range(a.steps)], "rmse": sc.rmse.cpu().tolist(),
+               "acc": None if sc.acc is None else sc.acc.cpu().tolist(), "tracked": dict(names)}
+        if sc.tqe is not None:
+            doc["tqe"] = sc.tqe.mean(dim=1).cpu().tolist()
         with open(a.scores_out, "w") as f:
-            json.dump({"lead_hours": [6.0 * (s + 1) for s in range(a.steps)], "rmse": sc.rmse.cpu().tolist(),
-                       "acc": None if sc.acc is None else sc.acc.cpu().tolist(), "tracked": dict(names)}, f)
+            json.dump(doc, f)
     if a.out:
         np.save(a.out, sc.forecast.cpu().numpy())
 

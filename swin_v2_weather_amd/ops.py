@@ -473,6 +473,47 @@ def forecast_scores(prd, tar, w, clim=None, scale=None, ws=None):
     return score_finalize(ws, B, Cc, H, W, scale)
 
 
+QUANTILE_MAX_RANKS = 256      # the K cap of swv2_plane_order_stats
+
+
+def quantile_workspace(planes: int, H: int, W: int, K: int, device) -> torch.Tensor:
+    """the caller's workspace of swv2_plane_order_stats for `planes` = B * C planes and K ranks: allocate once, reuse; never zeroed"""
+    return torch.empty(int(L.load().swv2_quantile_ws_bytes(planes, H, W, K)) // 4, dtype=torch.int32, device=device)
+
+
+def quantile_planes_ok(t: torch.Tensor) -> bool:
+    """what swv2_plane_order_stats reads in place: a CUDA fp32 [B, C, H, W] tensor or channel block of one (contiguous planes,
+    H * W % 4 == 0)"""
+    if not (t.is_cuda and t.dtype == torch.float32 and t.dim() == 4 and t.numel() > 0):
+        return False
+    B, Cc, H, W = t.shape
+    return (H * W) % 4 == 0 and H * W < 2 ** 30 and tuple(t.stride()[1:]) == (H * W, W, 1) and t.data_ptr() % 16 == 0 and \
+        (B == 1 or (t.stride(0) % 4 == 0 and t.stride(0) >= Cc * H * W))
+
+
+def plane_order_stats(x, ranks, ws=None):
+    """-> (values [K, B, C]: the element of rank ranks[k] of every plane of x in ascending order, NaNs last; nan_count [B, C] int32).
+    x: [B, C, H, W] or a channel block of a wider tensor, read in place; ranks: [K] int32 on x's device, distinct, ascending, in
+    [0, H * W), K <= QUANTILE_MAX_RANKS (the caller's promise: utils/weighted_acc_rmse.quantile_ranks builds them); ws: a
+    quantile_workspace to reuse (allocated here otherwise)."""
+    if not quantile_planes_ok(x):
+        raise L.Swv2Error(f"plane_order_stats: expected a CUDA fp32 [B, C, H, W] tensor with contiguous planes and H * W % 4 == 0, got "
+                          f"{tuple(x.shape)} {x.dtype} strides {x.stride()}")
+    B, Cc, H, W = x.shape
+    _chk(ranks, torch.int32, "ranks")
+    K = ranks.numel()
+    if ranks.dim() != 1 or ranks.device != x.device:
+        raise L.Swv2Error(f"plane_order_stats: ranks {tuple(ranks.shape)} on {ranks.device}, expected [K] on {x.device}")
+    if ws is None:
+        ws = quantile_workspace(B * Cc, H, W, K, x.device)
+    _chk(ws, torch.int32, "quantile workspace")
+    out = torch.empty(K, B, Cc, dtype=torch.float32, device=x.device)
+    nan_count = torch.empty(B, Cc, dtype=torch.int32, device=x.device)
+    L.check(L.load().swv2_plane_order_stats(_p(x), x.stride(0) if B > 1 else Cc * H * W, B, Cc, H, W, _p(ranks), K, _p(out), _p(nan_count),
+                                            _p(ws), ws.numel() * 4, _stream()), "swv2_plane_order_stats")
+    return out, nan_count
+
+
 def stats_slices(Cc: int, H: int, W: int) -> int:
     """slices per channel of swv2_stats_accumulate's plan (host-only)"""
     return int(L.load().swv2_stats_slices(Cc, H, W))

@@ -99,6 +99,85 @@ def unweighted_acc_torch(pred: torch.Tensor, target: torch.Tensor) -> torch.Tens
     return torch.mean(unweighted_acc_torch_channels(pred, target), dim=0)
 
 
+# ---- forecast extremes: top-quantile error (reference utils/weighted_acc_rmse.py:36-47, 117-126) -----------------------------------
+# torch.quantile sorts every plane; the 100 levels need at most 200 order statistics, the same ranks in every plane.  On CUDA fp32 inputs
+# with contiguous planes and H * W % 4 == 0 they come from swv2_plane_order_stats (csrc/quantile.hip: a five-pass radix select, exact);
+# anything else runs torch.quantile.
+def quantile_levels(qlim=3, qcut=0.1, qs=100) -> torch.Tensor:
+    """[qs] fp32: 1 - logspace(-qlim, -qcut, qs), the reference's levels, log-spaced toward the upper tail (0.2057 .. 0.999)"""
+    return 1.0 - torch.logspace(-qlim, -qcut, steps=qs)
+
+
+def quantile_ranks(n: int, q: torch.Tensor):
+    """The order statistics torch.quantile(x, q) of n values reads, WITH ITS ARITHMETIC: pos = q * (n - 1) in fp32, lo = floor(pos),
+    hi = ceil(pos), weight = pos - lo (an fp64 product gives other floors at n = 721 * 1440).  All on the CPU ->
+    (ranks [K] int32: the distinct lo and hi, ascending; i_lo, i_hi [len(q)] int64: where each level's two ranks sit in `ranks`;
+    weight [len(q)] fp32)."""
+    q = torch.as_tensor(q, dtype=torch.float32, device="cpu").reshape(-1)
+    if q.numel() == 0 or bool(((q < 0) | (q > 1)).any()):
+        raise ValueError("quantile_ranks: levels must lie in [0, 1]")
+    pos = q * (n - 1)
+    lo, hi = pos.floor(), pos.ceil()
+    weight = pos - lo
+    lo, hi = lo.long().clamp_(0, n - 1), hi.long().clamp_(0, n - 1)
+    ranks = torch.unique(torch.cat([lo, hi]))                  # sorted
+    return ranks.int(), torch.searchsorted(ranks, lo), torch.searchsorted(ranks, hi), weight
+
+
+class _QuantilePlan:
+    """the ranks of quantile_ranks and the gather indices on one device"""
+
+    def __init__(self, n, q, device):
+        ranks, i_lo, i_hi, weight = quantile_ranks(n, q)
+        self.K = ranks.numel()
+        self.ranks, self.i_lo, self.i_hi = ranks.to(device), i_lo.to(device), i_hi.to(device)
+        self.weight = weight.to(device).reshape(-1, 1, 1)
+
+    def quantiles(self, x, ws=None):
+        from .. import ops
+        v, nan_count = ops.plane_order_stats(x, self.ranks, ws)
+        out = torch.lerp(v[self.i_lo], v[self.i_hi], self.weight)
+        return out.masked_fill_((nan_count > 0).unsqueeze(0), float("nan"))           # as torch.quantile: a NaN poisons its plane
+
+
+def _quantiles_on_kernels(x: torch.Tensor) -> bool:
+    if not (x.is_cuda and x.dim() == 4):
+        return False
+    from .. import ops
+    return ops.quantile_planes_ok(x)
+
+
+def plane_quantiles(x: torch.Tensor, q: torch.Tensor) -> torch.Tensor:
+    """[B, C, H, W], levels [Q] -> [Q, B, C]: torch.quantile(x.view(B, C, H W), q, dim=-1) (linear interpolation).  A stateless call (a
+    fresh workspace each time on the kernel path); a loop should hold a ForecastScorer."""
+    q = torch.as_tensor(q, dtype=torch.float32).reshape(-1)
+    if _quantiles_on_kernels(x):
+        from .. import ops
+        step = ops.QUANTILE_MAX_RANKS // 2                     # two ranks per level at most: every chunk of levels fits one call
+        parts = [_QuantilePlan(x.shape[2] * x.shape[3], q[i:i + step], x.device).quantiles(x) for i in range(0, q.numel(), step)]
+        return parts[0] if len(parts) == 1 else torch.cat(parts, dim=0)
+    B, Cc = x.shape[:2]
+    return torch.quantile(x.reshape(B, Cc, -1), q.to(device=x.device, dtype=x.dtype), dim=-1)
+
+
+def top_quantiles_error_torch(pred: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
+    """[n, c, h, w] x2 -> [n, c]: the mean over the 100 levels of quantile(pred) - quantile(target), per plane: negative where the
+    forecast blurs its extremes"""
+    q = quantile_levels()
+    return torch.mean(plane_quantiles(pred, q) - plane_quantiles(target, q), dim=0)
+
+
+def top_quantiles_error(pred, target):
+    """the numpy form, CPU only: [n, h, w] (or [h, w]) x2 -> [n], levels 1 - logspace(-5, -0.1, 100) in fp64"""
+    pred, target = np.asarray(pred), np.asarray(target)
+    if pred.ndim == 2:
+        pred = np.expand_dims(pred, 0)
+    if target.ndim == 2:
+        target = np.expand_dims(target, 0)
+    qtile = 1.0 - np.logspace(-5, -0.1, num=100)
+    return np.mean(np.quantile(pred, q=qtile, axis=(1, 2)) - np.quantile(target, q=qtile, axis=(1, 2)), axis=0)
+
+
 def load_climatology(params, means=None, stds=None):
     """The normalised climatology ACC needs, [C, H, W] fp32 numpy: (time_means[:, out_channels, :H, :W] - means) / stds with the
     reference's files (`time_means_path` [1, Call, Hfull, Wfull]; means / stds [1, Call, 1, 1] from `global_means_path` /
@@ -146,6 +225,7 @@ class ForecastScorer:
         if self.scale is not None and self.scale.numel() != self.C:
             raise ValueError(f"{self.scale.numel()} stds for {self.C} channels")
         self._ws = {}
+        self._qplan, self._qws = None, {}
 
     def score(self, prd, tar, coff_prd=0, coff_tar=0) -> Scores:
         """channels coff_prd .. + C of prd against channels coff_tar .. + C of tar (scored in place, no copy) ->
@@ -173,3 +253,20 @@ class ForecastScorer:
         if self.clim is None:
             acc = acc_mean = None
         return Scores(rmse, acc, rmse_mean, acc_mean, sums)
+
+    def quantile_error(self, prd, tar, coff_prd=0, coff_tar=0) -> torch.Tensor:
+        """top_quantiles_error_torch of channels coff_prd .. + C of prd against channels coff_tar .. + C of tar (read in place) -> [B, C].
+        The rank tensor and the workspace (one per B) are made once and reused."""
+        p, t = prd[:, coff_prd:coff_prd + self.C], tar[:, coff_tar:coff_tar + self.C]
+        if p.shape != t.shape or p.shape[1:] != (self.C, self.H, self.W):
+            raise ValueError(f"quantile_error: blocks {tuple(p.shape)} / {tuple(t.shape)}, expected [B, {self.C}, {self.H}, {self.W}]")
+        q = quantile_levels()
+        if not (_quantiles_on_kernels(p) and _quantiles_on_kernels(t) and p.device == self.device == t.device):
+            return torch.mean(plane_quantiles(p, q) - plane_quantiles(t, q), dim=0)
+        from .. import ops
+        if self._qplan is None:
+            self._qplan = _QuantilePlan(self.H * self.W, q, self.device)
+        B = p.shape[0]
+        if B not in self._qws:
+            self._qws[B] = ops.quantile_workspace(B * self.C, self.H, self.W, self._qplan.K, self.device)
+        return torch.mean(self._qplan.quantiles(p, self._qws[B]) - self._qplan.quantiles(t, self._qws[B]), dim=0)
