@@ -35,7 +35,8 @@ extern "C" {
  * swv2_block_desc loses fuse_attn and wgrad_side_stream; 110: the attention kernel-selection queries swv2_attn_fwd_kernel /
  * swv2_attn_bwd_kernel (+ swv2_attn_kernel_t, SWV2_ATTN_K_*); 111: the LAMB optimizer, swv2_lamb_* (+ swv2_lamb_item, SWV2_LAMB_*);
  * 112: forecast scores, swv2_score_*.  The dataset statistics, swv2_stats_*, came later and are purely additive (new entry points only,
- * no struct member moves): the revision stays 112.  So are the plane order statistics, swv2_quantile_ws_bytes / swv2_plane_order_stats. */
+ * no struct member moves): the revision stays 112.  So are the plane order statistics, swv2_quantile_ws_bytes / swv2_plane_order_stats,
+ * and the ensemble scores, swv2_ens_*. */
 #define SWV2_VERSION 112
 
 enum {
@@ -548,6 +549,37 @@ int swv2_stats_finalize(const void* part, size_t part_bytes, const double* tsum,
 size_t swv2_quantile_ws_bytes(int planes, int H, int W, int K);
 int swv2_plane_order_stats(const float* x, long bstride, int B, int C, int H, int W, const int* ranks, int K, float* out, int* nan_count,
                            void* ws, size_t ws_bytes, void* stream);
+
+/* Ensemble scores (csrc/ensemble.hip): CRPS, fair CRPS, spread, ensemble-mean RMSE and the rank histogram of M forecast members against the
+ * verifying analysis, per (sample, channel) plane, from ONE pass in which every thread holds the M values of its grid points in registers.
+ * All fields fp32.
+ *   ens       member m, sample b, channel c at ens + m * ens_mstride + b * ens_bstride + c * H * W (elements): a ring slot or a channel block of
+ *             a member-major [M * B, channels, H, W] tensor is scored in place (ens_mstride = B * ens_bstride)
+ *   tar       the truth, sample b at tar + b * tar_bstride, C planes of [H][W];  w: [H] row weights, the vector swv2_score_sums takes
+ *   per grid point, every term from differences of inputs:   xbar = (1 / M) sum_m x_m    s2 = (1 / (M - 1)) sum_m (x_m - xbar)^2
+ *             e1 = sum_m |x_m - y|    e2 = sum_{m<n} |x_m - x_n| (as the gaps of the sorted members)    rank = #{m : x_m < y}  (strict, 0 .. M)
+ *   per plane  S_mse = sum w[h] (xbar - y)^2    S_var = sum w[h] s2    S_1 = sum w[h] e1    S_2 = sum w[h] e2    hist[r] = #{points with rank r}
+ * swv2_ens_sums: one launch of B * C * swv2_score_slices(B * C, H, W) workgroups (the plan and slice bounds of swv2_score_sums); workgroup
+ * (plane, slice) stores four float partials at ws[(plane * slices + slice) * 4 ..] and, behind all of those, M + 1 integer counts at
+ * ((int*)ws)[planes * slices * 4 + (plane * slices + slice) * (M + 1) ..].  No float atomics, nothing to zero beforehand; a slice without
+ * elements stores zeros.  The kernel is chosen by M alone: register slots for M rounded up to a multiple of 8.
+ * swv2_ens_finalize: one launch; folds the slices of each plane in a fixed order (two runs on the same inputs agree bit for bit, counts
+ * included) and writes, with N = H W,
+ *   sums [B][C][4] = (S_mse, S_var, S_1, S_2)    hist [B][C][M + 1] (its entries add up to N exactly)
+ *   ens_rmse = sqrt(S_mse / N)   spread = sqrt(S_var / N)   crps = (S_1 / M - S_2 / M^2) / N   fair_crps = (S_1 / M - S_2 / (M (M - 1))) / N   [B][C] each
+ *   means [4][C] = the batch means of ens_rmse, spread, crps, fair_crps in ascending b; scale[c] (may be NULL: the physical-unit stds)
+ *   multiplies the first three.
+ * A NaN in a member or in the truth makes the four scores of that plane (and that channel's means) NaN and touches no other plane; the
+ * plane's hist is then unspecified except that it still adds up to N.
+ * Refused with SWV2_ERR_INVALID before any launch: a null pointer (scale may be NULL), M outside 2 .. 64, W % 4 != 0, ens / tar / ws / sums not
+ * 16-byte aligned, a member or batch stride that is not a multiple of 4 or (B > 1) a batch stride smaller than C H W, B * C >= 2^20,
+ * H * W >= 2^30, a workspace smaller than swv2_ens_ws_bytes.  swv2_ens_ws_bytes is host-only (no HIP call) and returns 0 for a non-positive
+ * argument or M outside 2 .. 64. */
+size_t swv2_ens_ws_bytes(int planes, int H, int W, int M);      /* planes * swv2_score_slices(planes, H, W) * (16 + 4 (M + 1)) */
+int swv2_ens_sums(const float* ens, long ens_mstride, long ens_bstride, const float* tar, long tar_bstride, const float* w, int M, int B, int C,
+                  int H, int W, void* ws, size_t ws_bytes, void* stream);
+int swv2_ens_finalize(const void* ws, size_t ws_bytes, int M, int B, int C, int H, int W, const float* scale, float* sums, int* hist,
+                      float* ens_rmse, float* spread, float* crps, float* fair_crps, float* means, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * ERA5 input assembly (the step BEFORE the model): raw time slabs staged on the device by async H2D copies

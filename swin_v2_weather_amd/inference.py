@@ -15,8 +15,13 @@ prediction fed back, next cos-zenith channel and the invariant channels re-appen
 (utils/weighted_acc_rmse.ForecastScorer: latitude-weighted RMSE and ACC per channel and lead time, one pass per step; with
 extremes=True also the top-quantile error, ForecastScorer.quantile_error).
 
+`ensemble_rollout` perturbs the initial condition (`perturb_initial_condition`: member 0 is the unperturbed control), rolls the M
+members out in the same loop and scores every step as an ensemble (ForecastScorer.ensemble_score: CRPS, fair CRPS, spread,
+ensemble-mean RMSE and the rank histogram per channel and lead time, one pass over the members per step).
+
     python -m swin_v2_weather_amd.inference --registry DIR --steps 8 [--init x0.npy] [--out forecast.npy]
-                                            [--truth truth.npy [--climatology time_means.npy] [--scores-out scores.json] [--extremes]]
+                                            [--truth truth.npy [--climatology time_means.npy] [--scores-out scores.json] [--extremes]
+                                             [--ensemble M --perturbation A [--seed S] [--member-batch K]]]
 """
 from __future__ import annotations
 
@@ -31,7 +36,7 @@ import torch
 
 from .networks.helpers import get_model
 from .utils.YParams import load_yaml
-from .utils.weighted_acc_rmse import ForecastScorer, load_climatology
+from .utils.weighted_acc_rmse import ForecastScorer, load_climatology, spread_skill_ratio
 
 
 class _Params(dict):
@@ -153,23 +158,131 @@ def score_rollout(model, x0: torch.Tensor, truth, n_steps: int, coszen: torch.Te
     return RolloutScores(rmse, acc, rmse_s, acc_s, out.view(B, n_steps, Cout, H, W) if keep_forecast else None, tqe)
 
 
-def lead_time_table(scores: RolloutScores, names, hours_per_step: float = 6.0) -> str:
+def perturb_initial_condition(x0: torch.Tensor, n_members: int, amplitude: float, seed: int, n_fields: int) -> torch.Tensor:
+    """x0 [B, Cin, H, W] (fields | zenith | invariants) -> the M = n_members initial conditions [M B, Cin, H, W], member-major (row m B + b).
+    Member 0 is x0 bit for bit (the control); the members 1 .. M - 1 add
+        amplitude * torch.randn((M - 1) B, n_fields, H, W, generator=torch.Generator(x0.device).manual_seed(seed))
+    to the first n_fields channels.  The other channels (cos-zenith, invariants) are x0's bit for bit in every member."""
+    M = int(n_members)
+    B, Cin, H, W = x0.shape
+    if M < 1 or not 0 <= n_fields <= Cin:
+        raise ValueError(f"perturb_initial_condition: {M} members, {n_fields} fields of {Cin} channels")
+    out = x0.repeat(M, 1, 1, 1)
+    if M > 1 and n_fields:
+        gen = torch.Generator(device=x0.device).manual_seed(int(seed))
+        noise = torch.randn((M - 1) * B, n_fields, H, W, generator=gen, device=x0.device, dtype=x0.dtype)
+        out[B:, :n_fields] += amplitude * noise
+    return out
+
+
+EnsembleRolloutScores = namedtuple("EnsembleRolloutScores", "crps fair_crps spread ens_rmse crps_samples fair_crps_samples spread_samples "
+                                   "ens_rmse_samples hist forecast control", defaults=(None,))
+
+
+@torch.no_grad()
+def ensemble_rollout(model, x0: torch.Tensor, truth, n_steps: int, n_members: int, amplitude: float, seed: int = 0,
+                     coszen: torch.Tensor | None = None, n_invar: int = 0, scorer: ForecastScorer | None = None,
+                     member_batch: int | None = None, keep_forecast: bool = False, n_fields: int | None = None,
+                     score_control: bool = False) -> EnsembleRolloutScores:
+    """`score_rollout` for an ensemble: x0 [B, Cin, H, W] is perturbed into M = n_members initial conditions (perturb_initial_condition;
+    n_fields defaults to Cin - n_invar - (1 if coszen is given)), all members are rolled out and every step is scored against truth[:, s]
+    by scorer.ensemble_score as soon as all members have written it.  truth, scorer: as in score_rollout; coszen [B, n_steps - 1, H, W] is
+    repeated for every member.  Unless keep_forecast the predictions live in a two-slot ring [M B, 2 Cout, H, W], scored where they lie.
+    member_batch: members per model call (default: all M at once); the chunks advance in lockstep, one step at a time.  With one chunk
+    the forecasts are rollout(model, perturb_initial_condition(...), n_steps, coszen.repeat(M, 1, 1, 1), n_invar)'s bit for bit.
+    -> EnsembleRolloutScores(crps, fair_crps, spread, ens_rmse [n_steps, Cout]: batch means (the scorer's stds on crps, spread, ens_rmse);
+    their _samples [n_steps, B, Cout]; hist [n_steps, B, Cout, M + 1] int32; forecast [M B, n_steps, Cout, H, W] | None;
+    control: with score_control, the RolloutScores of member 0 -- the deterministic forecast -- from scorer.score, else None)."""
+    net = model.model if hasattr(model, "model") else model
+    B, Cin, H, W = x0.shape
+    M, Cout = int(n_members), net.out_chans
+    if M < 2:
+        raise ValueError(f"ensemble_rollout: {M} members (an ensemble has at least 2)")
+    K = M if member_batch is None else int(member_batch)
+    if K < 1:
+        raise ValueError(f"ensemble_rollout: member_batch {member_batch}")
+    if scorer is None:
+        scorer = ForecastScorer(H, W, Cout, x0.device)
+    if n_fields is None:
+        n_fields = Cin - n_invar - int(coszen is not None)
+    xe = perturb_initial_condition(x0, M, amplitude, seed, n_fields)
+    slots = n_steps if keep_forecast else 2
+    out = torch.empty(M * B, slots * Cout, H, W, dtype=torch.float32, device=x0.device)
+    coff_of = (lambda s: s * Cout) if keep_forecast else (lambda s: (s % 2) * Cout)
+    chunks = []
+    for m0 in range(0, M, K):
+        r0, r1 = m0 * B, min(m0 + K, M) * B
+        cz = None if coszen is None else coszen.repeat((r1 - r0) // B, 1, 1, 1)
+        chunks.append(_rollout_steps(net, xe[r0:r1], n_steps, cz, n_invar, out[r0:r1], coff_of))
+    mean = {k: torch.empty(n_steps, Cout, dtype=torch.float32, device=x0.device) for k in ("crps", "fair_crps", "spread", "ens_rmse")}
+    samp = {k: torch.empty(n_steps, B, Cout, dtype=torch.float32, device=x0.device) for k in mean}
+    hist = torch.empty(n_steps, B, Cout, M + 1, dtype=torch.int32, device=x0.device)
+    ctl = None
+    if score_control:
+        ctl = [torch.empty(n_steps, Cout, dtype=torch.float32, device=x0.device), torch.empty(n_steps, B, Cout, dtype=torch.float32, device=x0.device)]
+        ctl += [torch.empty_like(t) for t in ctl] if scorer.clim is not None else [None, None]
+    for s in range(n_steps):
+        for ch in chunks:
+            next(ch)
+        tar = (truth(s) if callable(truth) else truth[:, s]).to(x0.device)
+        r = scorer.ensemble_score(out, tar, M, coff_ens=coff_of(s))
+        for k in mean:
+            mean[k][s], samp[k][s] = getattr(r, k + "_mean"), getattr(r, k)
+        hist[s] = r.hist
+        if score_control:
+            c = scorer.score(out[:B], tar, coff_prd=coff_of(s))
+            ctl[0][s], ctl[1][s] = c.rmse_mean, c.rmse
+            if ctl[2] is not None:
+                ctl[2][s], ctl[3][s] = c.acc_mean, c.acc
+    control = None if ctl is None else RolloutScores(ctl[0], ctl[2], ctl[1], ctl[3], None)
+    return EnsembleRolloutScores(mean["crps"], mean["fair_crps"], mean["spread"], mean["ens_rmse"], samp["crps"], samp["fair_crps"], samp["spread"],
+                                 samp["ens_rmse"], hist, out.view(M * B, n_steps, Cout, H, W) if keep_forecast else None, control)
+
+
+def lead_time_table(scores: RolloutScores, names, hours_per_step: float = 6.0, ensemble: EnsembleRolloutScores | None = None) -> str:
     """one line per lead time: RMSE (and ACC, and the batch-mean top-quantile error when scored) of the named channels;
-    names: [(column title, channel index)]"""
+    names: [(column title, channel index)].  ensemble: the crps_, spread_ and ens_rmse_ columns of an ensemble_rollout follow."""
     rm, ac = scores.rmse.cpu().numpy(), None if scores.acc is None else scores.acc.cpu().numpy()
     tq = None if scores.tqe is None else scores.tqe.mean(dim=1).cpu().numpy()
     cols = [f"rmse_{n}" for n, _ in names] + ([f"acc_{n}" for n, _ in names] if ac is not None else []) + \
         ([f"tqe_{n}" for n, _ in names] if tq is not None else [])
+    ens = [] if ensemble is None else [(k, getattr(ensemble, k).cpu().numpy()) for k in ("crps", "spread", "ens_rmse")]
+    cols += [f"{k}_{n}" for k, _ in ens for n, _ in names]
     lines = ["lead_h " + " ".join(f"{c:>12s}" for c in cols)]
     for s in range(rm.shape[0]):
         vals = [rm[s, i] for _, i in names] + ([ac[s, i] for _, i in names] if ac is not None else []) + \
-            ([tq[s, i] for _, i in names] if tq is not None else [])
+            ([tq[s, i] for _, i in names] if tq is not None else []) + [v[s, i] for _, v in ens for _, i in names]
         lines.append(f"{hours_per_step * (s + 1):6.0f} " + " ".join(f"{v:12.5f}" for v in vals))
     return "\n".join(lines)
 
 
+class _Parser(argparse.ArgumentParser):
+    """the flags that only make sense together are checked where the command line is parsed: a wrong combination is a parser error"""
+
+    def parse_args(self, args=None, namespace=None):
+        a = super().parse_args(args, namespace)
+        if a.ensemble is None:
+            for flag, v in (("--perturbation", a.perturbation), ("--seed", a.seed), ("--member-batch", a.member_batch)):
+                if v is not None:
+                    self.error(f"{flag} needs --ensemble")
+            return a
+        if not a.truth:
+            self.error("--ensemble scores the members against the verifying analysis: it needs --truth")
+        if a.out:
+            self.error("--ensemble keeps no forecast: it cannot be combined with --out")
+        if a.extremes:
+            self.error("--extremes is scored for a single forecast: run it without --ensemble")
+        if not 2 <= a.ensemble <= 64:
+            self.error("--ensemble: 2 .. 64 members")
+        if a.perturbation is None:
+            self.error("--ensemble needs --perturbation (the amplitude of the initial-condition noise, in normalised units)")
+        if a.member_batch is not None and a.member_batch < 1:
+            self.error("--member-batch: at least one member per model call")
+        return a
+
+
 def build_parser() -> argparse.ArgumentParser:
-    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap = _Parser(description=__doc__.split("\n")[0])
     ap.add_argument("--registry", required=True, help="model folder with hyperparams.yaml + weights.tar")
     ap.add_argument("--steps", type=int, default=4)
     ap.add_argument("--init", default=None, help=".npy [B, Cin, H, W] normalised initial condition (default: seeded N(0,1))")
@@ -180,6 +293,12 @@ def build_parser() -> argparse.ArgumentParser:
                                                         "else the hyper-parameters' time_means_path)")
     ap.add_argument("--scores-out", default=None, help="write the lead-time scores as JSON")
     ap.add_argument("--extremes", action="store_true", help="with --truth: also score the top-quantile error (tqe_<name> columns, \"tqe\" key)")
+    ap.add_argument("--ensemble", type=int, default=None, metavar="M", help="with --truth: roll out M members from perturbed initial conditions "
+                                                                            "(member 0 is the control) and score CRPS, spread and ensemble-mean RMSE "
+                                                                            "(crps_/spread_/ens_rmse_<name> columns, \"ensemble\" key)")
+    ap.add_argument("--perturbation", type=float, default=None, metavar="A", help="with --ensemble: amplitude of the N(0, 1) noise added to the fields")
+    ap.add_argument("--seed", type=int, default=None, help="with --ensemble: seed of the noise (default 0)")
+    ap.add_argument("--member-batch", type=int, default=None, metavar="K", help="with --ensemble: members per model call (default: all at once)")
     return ap
 
 
@@ -219,19 +338,30 @@ def _score_main(a, model, p, stats, x0, cz, n_invar):
     truth = np.load(a.truth, mmap_mode="r")              # read step by step: the whole array need not fit in host memory
     if truth.ndim != 5 or truth.shape[1] < a.steps:
         raise ValueError(f"--truth: expected [B, >= {a.steps}, Cout, H, W], got {truth.shape}")
-    sc = score_rollout(model, x0, lambda s: torch.from_numpy(np.array(truth[:, s], dtype=np.float32)).to(x0.device), a.steps, cz, n_invar,
-                       scorer, keep_forecast=bool(a.out), extremes=a.extremes)
+    truth_of = lambda s: torch.from_numpy(np.array(truth[:, s], dtype=np.float32)).to(x0.device)      # noqa: E731
+    ens = None
+    if a.ensemble is not None:
+        # one rollout of all members: member 0 is the unperturbed forecast, scored as score_rollout scores it
+        ens = ensemble_rollout(model, x0, truth_of, a.steps, a.ensemble, a.perturbation, a.seed or 0, cz, n_invar, scorer,
+                               member_batch=a.member_batch, n_fields=len(p["in_channels"]), score_control=True)
+        sc = ens.control
+    else:
+        sc = score_rollout(model, x0, truth_of, a.steps, cz, n_invar, scorer, keep_forecast=bool(a.out), extremes=a.extremes)
     if "track_channels" in p and "channel_names" in p:
         names = [(v, list(p["channel_names"]).index(v)) for v in p["track_channels"]]
     else:
         names = [(v, i) for i, v in enumerate(("u10m", "v10m")) if i < len(chans)]
     print(f"scores in {'physical' if stds is not None else 'normalised'} units, {'with' if clim is not None else 'no climatology: without'} ACC")
-    print(lead_time_table(sc, names))
+    print(lead_time_table(sc, names, ensemble=ens))
     if a.scores_out:
         doc = {"lead_hours": [6.0 * (s + 1) for s in range(a.steps)], "rmse": sc.rmse.cpu().tolist(),
                "acc": None if sc.acc is None else sc.acc.cpu().tolist(), "tracked": dict(names)}
         if sc.tqe is not None:
             doc["tqe"] = sc.tqe.mean(dim=1).cpu().tolist()
+        if ens is not None:
+            doc["ensemble"] = {"members": a.ensemble, "crps": ens.crps.cpu().tolist(), "fair_crps": ens.fair_crps.cpu().tolist(),
+                               "spread": ens.spread.cpu().tolist(), "ens_rmse": ens.ens_rmse.cpu().tolist(),
+                               "spread_skill": spread_skill_ratio(ens.spread, ens.ens_rmse, a.ensemble).cpu().tolist()}
         with open(a.scores_out, "w") as f:
             json.dump(doc, f)
     if a.out:

@@ -473,6 +473,60 @@ def forecast_scores(prd, tar, w, clim=None, scale=None, ws=None):
     return score_finalize(ws, B, Cc, H, W, scale)
 
 
+ENS_MAX_MEMBERS = 64          # the M cap of swv2_ens_sums
+
+
+def ens_workspace(planes: int, H: int, W: int, M: int, device) -> torch.Tensor:
+    """the caller's workspace of swv2_ens_sums / swv2_ens_finalize for `planes` = B * C planes and M members: allocate once, reuse"""
+    n = int(L.load().swv2_ens_ws_bytes(planes, H, W, M))
+    if n == 0:
+        raise L.Swv2Error(f"ens_workspace: planes {planes}, H {H}, W {W} must be positive and M = {M} within 2 .. {ENS_MAX_MEMBERS}")
+    return torch.empty(n // 4, dtype=torch.float32, device=device)
+
+
+def ens_members_ok(t: torch.Tensor) -> bool:
+    """what swv2_ens_sums reads in place as the members: a CUDA fp32 [M, B, C, H, W] view (contiguous planes, W % 4 == 0, 2 <= M <= 64,
+    member and batch strides multiples of 4) -- a channel block of a member-major [M * B, channels, H, W] tensor viewed that way"""
+    if not (t.is_cuda and t.dtype == torch.float32 and t.dim() == 5 and t.numel() > 0):
+        return False
+    M, B, Cc, H, W = t.shape
+    return 2 <= M <= ENS_MAX_MEMBERS and W % 4 == 0 and tuple(t.stride()[2:]) == (H * W, W, 1) and t.data_ptr() % 16 == 0 and \
+        t.stride(0) % 4 == 0 and (B == 1 or (t.stride(1) % 4 == 0 and t.stride(1) >= Cc * H * W))
+
+
+def ens_sums(ens, tar, w, ws):
+    """the partial sums and rank counts of every (b, c) plane of the members ens [M, B, C, H, W] against tar [B, C, H, W] (both may be
+    channel blocks of wider tensors, read in place) into ws (ens_workspace); w [H] row weights"""
+    if not (ens_members_ok(ens) and score_planes_ok(tar)) or ens.shape[1:] != tar.shape or ens.device != tar.device:
+        raise L.Swv2Error(f"ens_sums: expected CUDA fp32 members [M, B, C, H, W] (2 <= M <= {ENS_MAX_MEMBERS}) and truth [B, C, H, W] with contiguous "
+                          f"planes and W % 4 == 0, got {tuple(ens.shape)} {ens.dtype} strides {ens.stride()} / {tuple(tar.shape)} {tar.dtype} "
+                          f"strides {tar.stride()}")
+    M, B, Cc, H, W = ens.shape
+    _chk(w, torch.float32, "row weights"); _chk(ws, torch.float32, "ensemble workspace")
+    if w.numel() != H:
+        raise L.Swv2Error(f"ens_sums: {w.numel()} row weights for {H} rows")
+    span = Cc * H * W
+    L.check(L.load().swv2_ens_sums(_p(ens), ens.stride(0), ens.stride(1) if B > 1 else span, _p(tar), tar.stride(0) if B > 1 else span, _p(w),
+                                   M, B, Cc, H, W, _p(ws), ws.numel() * 4, _stream()), "swv2_ens_sums")
+
+
+def ens_finalize(ws, M: int, B: int, Cc: int, H: int, W: int, scale=None):
+    """slice partials -> (sums [B, C, 4] = (S_mse, S_var, S_1, S_2), hist [B, C, M + 1] int32, ens_rmse, spread, crps, fair_crps [B, C] each,
+    means [4, C]: their batch means, the first three x scale [C] if given), one launch; the float results are views of one fresh buffer"""
+    _chk(ws, torch.float32, "ensemble workspace")
+    if scale is not None and _chk(scale, torch.float32, "scale").numel() != Cc:
+        raise L.Swv2Error(f"ens_finalize: scale of {scale.numel()} values for {Cc} channels")
+    n = B * Cc
+    buf = torch.empty(8 * n + 4 * Cc, dtype=torch.float32, device=ws.device)
+    hist = torch.empty(B, Cc, M + 1, dtype=torch.int32, device=ws.device)
+    sums = buf[:4 * n].view(B, Cc, 4)
+    er, sp, cr, fc = (buf[(4 + k) * n:(5 + k) * n].view(B, Cc) for k in range(4))
+    means = buf[8 * n:].view(4, Cc)
+    L.check(L.load().swv2_ens_finalize(_p(ws), ws.numel() * 4, M, B, Cc, H, W, _p(scale), _p(sums), _p(hist), _p(er), _p(sp), _p(cr), _p(fc),
+                                       _p(means), _stream()), "swv2_ens_finalize")
+    return sums, hist, er, sp, cr, fc, means
+
+
 QUANTILE_MAX_RANKS = 256      # the K cap of swv2_plane_order_stats
 
 

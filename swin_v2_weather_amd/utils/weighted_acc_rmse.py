@@ -203,6 +203,7 @@ def load_climatology(params, means=None, stds=None):
 
 
 Scores = namedtuple("Scores", "rmse acc rmse_mean acc_mean sums")
+EnsembleScores = namedtuple("EnsembleScores", "sums hist ens_rmse spread crps fair_crps ens_rmse_mean spread_mean crps_mean fair_crps_mean")
 
 
 class ForecastScorer:
@@ -226,6 +227,7 @@ class ForecastScorer:
             raise ValueError(f"{self.scale.numel()} stds for {self.C} channels")
         self._ws = {}
         self._qplan, self._qws = None, {}
+        self._ews = {}
 
     def score(self, prd, tar, coff_prd=0, coff_tar=0) -> Scores:
         """channels coff_prd .. + C of prd against channels coff_tar .. + C of tar (scored in place, no copy) ->
@@ -270,3 +272,78 @@ class ForecastScorer:
         if B not in self._qws:
             self._qws[B] = ops.quantile_workspace(B * self.C, self.H, self.W, self._qplan.K, self.device)
         return torch.mean(self._qplan.quantiles(p, self._qws[B]) - self._qplan.quantiles(t, self._qws[B]), dim=0)
+
+    def ensemble_score(self, ens, tar, n_members, coff_ens=0, coff_tar=0) -> EnsembleScores:
+        """n_members forecasts against one truth.  ens: [M B, Cany, H, W] with a member-major batch (row m B + b) or [M, B, Cany, H, W];
+        channels coff_ens .. + C of it against channels coff_tar .. + C of tar [B, Cany', H, W], all read in place (a ring slot of
+        inference.ensemble_rollout) -> EnsembleScores(sums [B, C, 4] = (S_mse, S_var, S_1, S_2), hist [B, C, M + 1] int32, ens_rmse, spread,
+        crps, fair_crps [B, C], and their batch means [C]; the scorer's stds multiply ens_rmse_mean, spread_mean and crps_mean).  One
+        workspace per (M, B) is kept and reused."""
+        M = int(n_members)
+        if ens.dim() == 4:
+            if M < 1 or ens.shape[0] % M:
+                raise ValueError(f"ensemble_score: a batch of {ens.shape[0]} rows does not hold {M} members")
+            ens = ens.unflatten(0, (M, ens.shape[0] // M))                    # always a view: row m B + b -> [m, b]
+        e, t = ens[:, :, coff_ens:coff_ens + self.C], tar[:, coff_tar:coff_tar + self.C]
+        if e.dim() != 5 or e.shape[0] != M or M < 2 or e.shape[1:] != t.shape or t.shape[1:] != (self.C, self.H, self.W):
+            raise ValueError(f"ensemble_score: members {tuple(e.shape)} / truth {tuple(t.shape)}, expected [{M} >= 2, B, {self.C}, {self.H}, {self.W}] "
+                             f"/ [B, {self.C}, {self.H}, {self.W}]")
+        from .. import ops
+        if e.is_cuda and t.is_cuda and e.device == self.device == t.device and ops.ens_members_ok(e) and ops.score_planes_ok(t):
+            B = t.shape[0]
+            if (M, B) not in self._ews:
+                self._ews[(M, B)] = ops.ens_workspace(B * self.C, self.H, self.W, M, self.device)
+            ops.ens_sums(e, t, self.w, self._ews[(M, B)])
+            sums, hist, er, sp, cr, fc, means = ops.ens_finalize(self._ews[(M, B)], M, B, self.C, self.H, self.W, self.scale)
+            return EnsembleScores(sums, hist, er, sp, cr, fc, means[0], means[1], means[2], means[3])
+        return ensemble_scores_torch(e, t, self.w, self.scale)
+
+
+# ---- ensemble scores: CRPS, spread, ensemble-mean RMSE, rank histogram (what Earth2MIP reports for perturbed-initial-condition runs) ----
+# M members x_m against the truth y, per grid point (every term from differences of inputs, so the rounding error of a sum is relative to
+# that sum of non-negative terms and not to the magnitude of the fields):
+#     xbar = mean_m x_m    s2 = sum_m (x_m - xbar)^2 / (M - 1)    e1 = sum_m |x_m - y|    e2 = sum_{m<n} |x_m - x_n|    rank = #{m : x_m < y}
+# per plane, with row weights w[h] and N = H W:
+#     S_mse = sum w (xbar - y)^2    S_var = sum w s2    S_1 = sum w e1    S_2 = sum w e2    hist[r] = #{points of rank r}
+#     ens_rmse = sqrt(S_mse / N)    spread = sqrt(S_var / N)    crps = (S_1 / M - S_2 / M^2) / N    fair_crps = (S_1 / M - S_2 / (M (M - 1))) / N
+# On CUDA fp32 members with contiguous planes and W % 4 == 0 the sums come from ONE pass of swv2_ens_sums (csrc/ensemble.hip: the M
+# values of a grid point in registers); anything else runs ensemble_scores_torch.
+
+
+def spread_skill_ratio(spread: torch.Tensor, ens_rmse: torch.Tensor, n_members: int) -> torch.Tensor:
+    """sqrt((M + 1) / M) spread / ens_rmse: 1 for a statistically consistent ensemble"""
+    return float(np.sqrt((n_members + 1.0) / n_members)) * spread / ens_rmse
+
+
+def ensemble_scores_torch(ens: torch.Tensor, tar: torch.Tensor, w=None, scale=None) -> EnsembleScores:
+    """ens [M, B, C, H, W], tar [B, C, H, W], w [H] (default: the latitude weights) -> EnsembleScores, in plain torch on any device and
+    for any W: sort over the member axis, e2 from the gaps of the sorted members, the variance from deviations.  scale [C] multiplies the
+    first three batch means."""
+    M, B, Cc, H, W = ens.shape
+    if M < 2 or tar.shape != ens.shape[1:]:
+        raise ValueError(f"ensemble_scores_torch: members {tuple(ens.shape)} / truth {tuple(tar.shape)}, expected [M >= 2, B, C, H, W] / [B, C, H, W]")
+    w = (latitude_weights(H, ens.device) if w is None else w).to(device=ens.device, dtype=ens.dtype).reshape(1, 1, -1, 1)
+    n = float(H * W)
+    d = ens - tar.unsqueeze(0)
+    e1 = d.abs().sum(dim=0)
+    rank = (ens < tar.unsqueeze(0)).sum(dim=0)
+    a = ens - ens[0:1]
+    abar = a.mean(dim=0)
+    vv = ((a - abar.unsqueeze(0)) ** 2).sum(dim=0)
+    em = d[0] + abar
+    gaps = torch.diff(torch.sort(ens, dim=0).values, dim=0)
+    i = torch.arange(1, M, device=ens.device, dtype=ens.dtype)
+    e2 = ((i * (M - i)).reshape(-1, 1, 1, 1, 1) * gaps).sum(dim=0)
+    s_mse, s_vv, s_1, s_2 = (torch.sum(w * t, dim=(-1, -2)) for t in (em * em, vv, e1, e2))
+    s_var = s_vv / (M - 1.0)
+    hist = torch.zeros(B, Cc, M + 1, dtype=torch.int64, device=ens.device)
+    hist.scatter_add_(2, rank.reshape(B, Cc, H * W), torch.ones(B, Cc, H * W, dtype=torch.int64, device=ens.device))
+    ens_rmse, spread = torch.sqrt(s_mse / n), torch.sqrt(s_var / n)
+    spread = torch.where(torch.isnan(s_1), s_1, spread)        # a NaN in the truth poisons the plane's spread too, as every other score
+    crps, fair = (s_1 / M - s_2 / float(M * M)) / n, (s_1 / M - s_2 / float(M * (M - 1))) / n
+    means = [v.mean(dim=0) for v in (ens_rmse, spread, crps, fair)]
+    if scale is not None:
+        sc = scale.to(device=ens.device, dtype=ens.dtype)
+        means = [m * sc for m in means[:3]] + means[3:]
+    return EnsembleScores(torch.stack((s_mse, s_var, s_1, s_2), dim=-1), hist.to(torch.int32), ens_rmse, spread, crps, fair, *means)
+

@@ -1,0 +1,406 @@
+"""GPU (-m gpu): swv2_ens_sums / swv2_ens_finalize through the C ABI, judged element by element against the fp64 statement of
+tests/ensemble_reference.py (every bound is derived there; the rank histogram must be exact), then the Python layer on top of them:
+ForecastScorer.ensemble_score, inference.ensemble_rollout and the --ensemble command line."""
+import functools
+import json
+import os
+from types import SimpleNamespace
+
+import numpy as np
+import pytest
+import torch
+
+from tests import ensemble_reference as R
+
+pytestmark = pytest.mark.gpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+SENTINEL = 0x7FC0BEEF                                                                   # a NaN payload no kernel produces, as int32
+GUARD = 64                                                                              # words in front of and behind every output
+NAMES = R.NAMES
+
+# (M, B, C, H, W): the smallest shapes that reach each branch.  Capacities 8 / 16 / 32 / 64 hold M <= 8 / 16 / 32 / 64 (they set the points per
+# thread); both M == capacity and M == capacity / 2 + 1 appear for every capacity.
+SHAPES = [(2, 1, 1, 1, 4),           # the smallest ensemble, a single vector: 2047 empty slices
+          (3, 2, 3, 5, 8),           # slices that cut rows
+          (16, 1, 2, 33, 132),       # capacity 16 full; 4356 elements over 1024 slices: mostly empty slices or a single vector
+          (17, 3, 5, 16, 32),        # the first M of capacity 32 (= 32 / 2 + 1)
+          (33, 1, 3, 9, 12),         # the first M of capacity 64 (= 64 / 2 + 1): one point per thread and iteration
+          (64, 1, 2, 16, 32),        # capacity 64 full
+          (2, 1, 2100, 2, 4),        # B * C above the slice threshold: one slice per plane
+          (5, 2, 2, 3, 8),           # capacity 8 at 8 / 2 + 1
+          (9, 2, 3, 5, 12),          # capacity 16 at 16 / 2 + 1
+          (32, 1, 3, 6, 8),          # capacity 32 full
+          # the register slots come in steps of 8 with one kernel for M == slots and one for slots - 8 < M < slots: the remaining
+          # first and last M of every step, and the 50 members of the operational ensembles
+          (24, 1, 2, 5, 8), (25, 1, 2, 5, 8), (40, 1, 2, 5, 8), (41, 1, 2, 5, 8), (48, 1, 2, 5, 8), (49, 1, 2, 5, 8), (50, 2, 2, 5, 8),
+          (56, 1, 2, 5, 8), (57, 1, 2, 5, 8),
+          # One shape per capacity whose slices are long enough for a thread to go through the kernel's one loop (`for (i = lo + tid * PTS;
+          # i < hi; i += 256 * PTS)`, members loaded and scored per iteration) more than once: 2048 planes of one slice each, the slice
+          # longer than 256 * PTS elements (PTS = 4, 4, 1, 1 points per thread at capacity 8, 16, 32, 64).
+          (8, 1, 2048, 4, 260),      # capacity 8 full:  1040 elements = 260 groups of 4: threads 0 .. 3 iterate twice
+          (9, 1, 2048, 4, 260),      # capacity 16:      the same plane, M below the capacity
+          (16, 1, 2048, 4, 260),     # capacity 16 full
+          (17, 1, 2048, 4, 132),     # capacity 32:      528 elements, one per thread: three iterations for threads 0 .. 15, two for the rest
+          (33, 1, 2048, 4, 68)]      # capacity 64:      272 elements, one per thread: threads 0 .. 15 iterate twice
+
+
+@pytest.fixture(scope="module")
+def dev():
+    assert torch.cuda.is_available(), "GPU tests need an MI355X"
+    return torch.device("cuda:0")
+
+
+@pytest.fixture(scope="module")
+def lib():
+    from swin_v2_weather_amd import _lib as L
+    return L.load()                                  # fails loudly if libswv2.so is missing: no fallback exists
+
+
+def _weights(H):
+    from swin_v2_weather_amd.utils.weighted_acc_rmse import latitude_weights
+    return latitude_weights(H).numpy() if H > 1 else np.ones(1, np.float32)          # (the formula divides by H - 1)
+
+
+@functools.lru_cache(maxsize=None)
+def _fields(M, B, C, H, W, offset=0.0, quantum=0.0, seed=0):
+    """members [M, B, C, H, W] and truth [B, C, H, W]: N(0, 1) around a smooth field (+ offset; rounded to multiples of `quantum`), as
+    numpy fp32, generated once per shape and never modified"""
+    rng = np.random.default_rng(1000 * seed + 31 * M + 7 * B + 3 * C + H + W)
+    y, x = np.linspace(0, np.pi, H)[:, None], np.linspace(0, 2 * np.pi, W)[None, :]
+    base = (offset + (1.0 + np.arange(C)[:, None, None] % 5) * np.sin(y + 0.3 * np.arange(C)[:, None, None]) * np.cos(2 * x)).astype(np.float32)
+    ens = base[None, None] + rng.standard_normal((M, B, C, H, W), dtype=np.float32)
+    tar = base[None] + rng.standard_normal((B, C, H, W), dtype=np.float32)
+    if quantum:
+        ens, tar = np.round(ens / quantum) * quantum, np.round(tar / quantum) * quantum
+    ens, tar = ens.astype(np.float32), tar.astype(np.float32)
+    for a in (ens, tar):
+        a.setflags(write=False)
+    return ens, tar, _weights(H)
+
+
+class Guarded:
+    """32-bit device buffers carved out of one sentinel-filled allocation, each 16-byte aligned with GUARD sentinel words on both sides"""
+
+    def __init__(self, dev, **sizes):
+        self.off, n = {}, GUARD
+        for k, v in sizes.items():
+            self.off[k] = (n, v)
+            n += (v + 3) // 4 * 4 + GUARD
+        self.raw = torch.full((n,), SENTINEL, dtype=torch.int32, device=dev)
+        self.sizes = sizes
+
+    def ints(self, k):
+        o, v = self.off[k]
+        return self.raw[o:o + v]
+
+    def __getitem__(self, k):
+        return self.ints(k).view(torch.float32)
+
+    def guards_intact(self):
+        keep = torch.ones(self.raw.numel(), dtype=torch.bool, device=self.raw.device)
+        for o, v in self.off.values():
+            keep[o:o + v] = False
+        return bool((self.raw[keep] == SENTINEL).all())
+
+    def written(self, k):
+        return bool((self.ints(k) != SENTINEL).all())
+
+
+def _launch(lib, dev, ens, tar, w, scale=None, ws_fill=None):
+    """ens [M, B, C, H, W], tar [B, C, H, W]: device tensors or channel-block views; -> (Guarded with ws / sums / hist / the four scores /
+    means, slices)"""
+    from swin_v2_weather_amd import _lib as L
+    M, B, C, H, W = ens.shape
+    slices = lib.swv2_score_slices(B * C, H, W)
+    wsb = lib.swv2_ens_ws_bytes(B * C, H, W, M)
+    assert wsb == B * C * slices * (16 + 4 * (M + 1))
+    g = Guarded(dev, ws=wsb // 4, sums=B * C * 4, hist=B * C * (M + 1), ens_rmse=B * C, spread=B * C, crps=B * C, fair_crps=B * C, means=4 * C)
+    if ws_fill is not None:
+        g.ints("ws").fill_(ws_fill)
+    st = torch.cuda.current_stream().cuda_stream
+    span = C * H * W
+    L.check(lib.swv2_ens_sums(ens.data_ptr(), ens.stride(0), ens.stride(1) if B > 1 else span, tar.data_ptr(), tar.stride(0) if B > 1 else span,
+                              w.data_ptr(), M, B, C, H, W, g["ws"].data_ptr(), wsb, st), "swv2_ens_sums")
+    L.check(lib.swv2_ens_finalize(g["ws"].data_ptr(), wsb, M, B, C, H, W, None if scale is None else scale.data_ptr(), g["sums"].data_ptr(),
+                                  g["hist"].data_ptr(), g["ens_rmse"].data_ptr(), g["spread"].data_ptr(), g["crps"].data_ptr(),
+                                  g["fair_crps"].data_ptr(), g["means"].data_ptr(), st), "swv2_ens_finalize")
+    torch.cuda.synchronize()
+    return g, slices
+
+
+def _got(g, M, B, C):
+    out = {k: g[k].cpu().numpy().reshape(B, C) for k in NAMES}
+    out["sums"] = g["sums"].cpu().numpy().reshape(B, C, 4)
+    out["hist"] = g.ints("hist").cpu().numpy().reshape(B, C, M + 1)
+    out["means"] = g["means"].cpu().numpy().reshape(4, C)
+    return out
+
+
+def _verdict(g, slices, ens, tar, w, scale=None, tag=""):
+    """the element-by-element judgement of one launch pair (numpy inputs); asserts every bound, the exact histogram, the guards and the
+    written slots"""
+    M, B, C, H, W = ens.shape
+    assert g.guards_intact(), "a kernel wrote outside its outputs"
+    for k in g.sizes:
+        assert g.written(k), f"{k}: slots the plan names were left unwritten"
+    got = _got(g, M, B, C)
+    R.judge(got, ens, tar, w, R.chain_length(H, W, slices, M), scale, tag)
+    return got
+
+
+def _dev(dev, *arrays):
+    return [torch.tensor(a).to(dev) for a in arrays]
+
+
+@pytest.mark.parametrize("shape", SHAPES, ids=lambda s: "x".join(map(str, s)))
+def test_kernels_element_by_element_against_fp64(dev, lib, shape):
+    ens, tar, w = _fields(*shape)
+    d = _dev(dev, ens, tar, w)
+    g, slices = _launch(lib, dev, *d)
+    _verdict(g, slices, ens, tar, w, tag=f"{shape}")
+
+
+@pytest.mark.parametrize("M", [16, 50])
+def test_offset_fields_keep_the_bounds_of_the_differences(dev, lib, M):
+    """mean 1e4, spread 1: the bounds are relative to sums of differences, so they are as tight as for centred fields -- a badly conditioned
+    e2 (raw sorted values times 2 i - M - 1) or variance (sum x^2 - M xbar^2) is off by hundreds of them here"""
+    shape = (M, 2, 2, 9, 16)
+    ens, tar, w = _fields(*shape, offset=1.0e4)
+    assert abs(float(ens.mean()) - 1.0e4) < 1.0 and 0.5 < float(ens.std(axis=0).mean()) < 1.5
+    g, slices = _launch(lib, dev, *_dev(dev, ens, tar, w))
+    _verdict(g, slices, ens, tar, w, tag=f"offset 1e4 {shape}")
+
+
+@pytest.mark.parametrize("M", [7, 16, 20])
+def test_ties_and_zeros_rank_by_the_strict_compare(dev, lib, M):
+    """fields on a grid of 0.25 with the truth equal to a member at many points (and many exact zeros): ranks count x_m < y strictly"""
+    shape = (M, 2, 3, 6, 16)
+    ens, tar, w = _fields(*shape, quantum=0.25)
+    tar = tar.copy()
+    tar[:, :, ::2] = ens[M // 2][:, :, ::2]                   # every other row: the truth IS member M / 2
+    tar[:, 0, 1] = 0.0
+    ens = ens.copy()
+    ens[:3, :, 0, 1] = 0.0                                    # zeros against zeros (+0 and -0 compare equal)
+    ens[1, :, 0, 1, ::2] = -0.0
+    assert (ens == tar[None]).mean() > 0.05
+    g, slices = _launch(lib, dev, *_dev(dev, ens, tar, w))
+    got = _verdict(g, slices, ens, tar, w, tag=f"ties {shape}")
+    assert got["hist"][..., M].sum() < got["hist"].sum()      # (not everything sits in one bin)
+
+
+def test_constant_ensemble_has_no_spread_exactly(dev, lib):
+    """all members equal: S_var and S_2 are exactly zero and crps N = S_1 / M"""
+    M, B, C, H, W = 4, 2, 3, 6, 16
+    one, tar, w = _fields(1, B, C, H, W)
+    ens = np.ascontiguousarray(np.broadcast_to(one, (M, B, C, H, W)))
+    g, slices = _launch(lib, dev, *_dev(dev, ens, tar, w))
+    got = _verdict(g, slices, ens, tar, w, tag="constant ensemble")
+    assert np.all(got["sums"][..., 1] == 0.0) and np.all(got["sums"][..., 3] == 0.0) and np.all(got["spread"] == 0.0)
+    S, dS, _ = R.sums(ens, tar, w, R.chain_length(H, W, slices, M))
+    ref, b = R.crps_score(S, dS, M, H * W, False)
+    assert np.all(S[..., 3] == 0.0) and np.all(np.abs(got["crps"].astype(np.float64) * (H * W) - S[..., 2] / M) <= b * (H * W))
+    assert np.array_equal(got["crps"], got["fair_crps"])
+
+
+def test_nan_in_one_member_of_one_plane_only(dev, lib):
+    M, B, C, H, W = 6, 3, 4, 16, 32
+    ens, tar, w = _fields(M, B, C, H, W)
+    ens = ens.copy()
+    ens[4, 1, 2, 7, 9] = np.nan
+    scale = np.array([2.0, 0.5, 3.0, 7.25], np.float32)
+    g, slices = _launch(lib, dev, *_dev(dev, ens, tar, w, scale))
+    got = _verdict(g, slices, ens, tar, w, scale, tag="nan plane")          # NaN exactly where the reference has it, hist sums to N everywhere
+    for k in NAMES:
+        nan = np.isnan(got[k])
+        assert nan[1, 2] and nan.sum() == 1, k
+    assert np.isnan(got["means"][:, 2]).all() and np.isnan(got["means"]).sum() == 4
+    assert got["hist"][1, 2].sum() == H * W
+    # the truth instead of a member
+    tar2 = tar.copy()
+    tar2[0, 3, 0, 0] = np.nan
+    ens2, _, _ = _fields(M, B, C, H, W)
+    g2, _ = _launch(lib, dev, *_dev(dev, ens2, tar2, w))
+    got2 = _verdict(g2, slices, ens2, tar2, w, tag="nan truth")
+    assert all(np.isnan(got2[k][0, 3]) and np.isnan(got2[k]).sum() == 1 for k in NAMES)
+
+
+@pytest.mark.parametrize("shape", [(16, 2, 3, 17, 40), (50, 1, 2, 9, 16)], ids=lambda s: "x".join(map(str, s)))
+def test_reruns_and_a_dirty_workspace_give_the_same_bits(dev, lib, shape):
+    ens, tar, w = _fields(*shape)
+    scale = np.linspace(0.5, 2.0, shape[2]).astype(np.float32)
+    d = _dev(dev, ens, tar, w, scale)
+    g1, _ = _launch(lib, dev, *d)
+    g2, _ = _launch(lib, dev, *d)
+    assert torch.equal(g1.raw, g2.raw)                        # workspace, sums, hist, scores and means, bit for bit
+    g3, _ = _launch(lib, dev, *d, ws_fill=-1)                 # a workspace full of 0xFF bytes: nothing is accumulated into, all is stored
+    assert torch.equal(g1.raw, g3.raw)
+    g4, _ = _launch(lib, dev, d[0], d[1], d[2], None)         # the scale reaches the first three means only
+    for k in g1.sizes:
+        if k != "means":
+            assert torch.equal(g4.ints(k), g1.ints(k)), k
+    m1, m4 = g1["means"].view(4, -1), g4["means"].view(4, -1)
+    assert torch.equal(m4[3], m1[3]) and not torch.equal(m4[:3], m1[:3])
+
+
+def test_channel_block_of_member_major_rows_in_place(dev, lib):
+    """members as the rows of [M B, 15, H, W], channels 5:10, against channels 7:12 of an 18-channel truth: nothing is copied"""
+    M, B, C, H, W = 5, 2, 5, 9, 12
+    ens_w, _, w = _fields(M, B, 15, H, W)
+    tar_w = _fields(1, B, 18, H, W, seed=1)[1]
+    rows = torch.tensor(ens_w).to(dev).view(M * B, 15, H, W)
+    dt = torch.tensor(tar_w).to(dev)
+    ve, vt = rows.unflatten(0, (M, B))[:, :, 5:10], dt[:, 7:12]
+    assert ve.stride() == (B * 15 * H * W, 15 * H * W, H * W, W, 1) and vt.stride(0) == 18 * H * W
+    assert ve.data_ptr() == rows.data_ptr() + 5 * H * W * 4 and ve.data_ptr() % 16 == 0 and vt.data_ptr() % 16 == 0
+    g, slices = _launch(lib, dev, ve, vt, torch.tensor(w).to(dev))
+    assert slices == 204
+    _verdict(g, slices, ens_w[:, :, 5:10], tar_w[:, 7:12], w, tag="block 5:10 / 7:12")
+
+
+# ---- the Python layer ------------------------------------------------------------------------------------------------------
+def _scores_as_got(r):
+    out = {k: getattr(r, k).cpu().numpy() for k in NAMES + ("sums", "hist")}
+    out["means"] = np.stack([getattr(r, k + "_mean").cpu().numpy() for k in NAMES])
+    return out
+
+
+def test_forecast_scorer_ensemble_score_against_fp64(dev, lib):
+    from swin_v2_weather_amd import ops
+    from swin_v2_weather_amd.utils.weighted_acc_rmse import EnsembleScores, ForecastScorer
+    M, B, C, H, W = 5, 2, 5, 9, 12
+    ens_w, _, w = _fields(M, B, 15, H, W)
+    tar_w = _fields(1, B, 18, H, W, seed=1)[1]
+    stds = np.array([1.5, 2.0, 0.25, 9.0, 4.0], np.float32)
+    rows, dt = torch.tensor(ens_w).to(dev).view(M * B, 15, H, W), torch.tensor(tar_w).to(dev)
+    sc = ForecastScorer(H, W, C, dev, stds=stds)
+    before = sc.score(rows[:B], dt, coff_prd=5, coff_tar=7)
+    r = sc.ensemble_score(rows, dt, M, coff_ens=5, coff_tar=7)
+    assert isinstance(r, EnsembleScores) and r.hist.dtype == torch.int32 and tuple(r.hist.shape) == (B, C, M + 1) and len(sc._ews) == 1
+    assert ops.ens_members_ok(rows.unflatten(0, (M, B))[:, :, 5:10])                 # the kernel path
+    n = R.chain_length(H, W, ops.score_slices(B * C, H, W), M)
+    R.judge(_scores_as_got(r), ens_w[:, :, 5:10], tar_w[:, 7:12], w, n, stds, "ensemble_score, kernels")
+    r5 = sc.ensemble_score(rows.view(M, B, 15, H, W), dt, M, coff_ens=5, coff_tar=7)   # the five-dimensional form, the workspace reused
+    assert all(torch.equal(a, b) for a, b in zip(r, r5)) and len(sc._ews) == 1 and r5.crps.data_ptr() != r.crps.data_ptr()
+    after = sc.score(rows[:B], dt, coff_prd=5, coff_tar=7)
+    assert all(torch.equal(a, b) for a, b in zip(before[:1] + before[2:3] + before[4:], after[:1] + after[2:3] + after[4:]))      # score() is untouched
+    # odd width: the torch path on the device, judged as sums in any order (chain H W M)
+    Wo = 10
+    eo, to_ = np.ascontiguousarray(ens_w[..., :Wo]), np.ascontiguousarray(tar_w[..., :Wo])
+    so = ForecastScorer(H, Wo, C, dev, stds=stds)
+    ro = so.ensemble_score(torch.tensor(eo).to(dev).view(M * B, 15, H, Wo), torch.tensor(to_).to(dev), M, 5, 7)
+    assert len(so._ews) == 0 and ro.hist.dtype == torch.int32
+    R.judge(_scores_as_got(ro), eo[:, :, 5:10], to_[:, 7:12], w, H * Wo * M, stds, "ensemble_score, torch path")
+    with pytest.raises(ValueError):
+        sc.ensemble_score(rows, dt, 3, coff_ens=5, coff_tar=7)                       # 10 rows do not hold 3 members
+    with pytest.raises(ValueError):
+        sc.ensemble_score(rows, dt, M, coff_ens=12, coff_tar=7)                      # only three channels are left from there
+
+
+def _registry_model(dev, tmp_path):
+    """the tiny registry folder of tests/test_score_gpu.py (same construction)"""
+    import yaml
+    from swin_v2_weather_amd import inference
+    from swin_v2_weather_amd.networks import helpers
+    hp = dict(nettype="swin", img_size=[48, 72], patch_size=4, depth=2, num_heads=2, embed_dim=24, window_ratio=8,
+              drop_path_rate=0.1, full_pos_embed=True, rel_pos=True, mlp_ratio=4, activation_ckpt=False, residual=True,
+              in_channels=list(range(5)), out_channels=list(range(5)), add_zenith=True, add_orography=True, add_landmask=True,
+              n_in_channels=9, n_out_channels=5, n_future=2, lr="1E-3")
+    reg = tmp_path / "swin_test_registry"
+    reg.mkdir()
+    yaml.safe_dump(hp, open(reg / "hyperparams.yaml", "w"))
+    torch.manual_seed(31)
+    ms = helpers.get_model(SimpleNamespace(**hp))
+    with torch.no_grad():
+        for n_, p_ in ms.named_parameters():
+            if n_.endswith("norm1.weight") or n_.endswith("norm2.weight"):
+                p_.uniform_(0.5, 1.5)
+    torch.save({"iters": 7, "epoch": 1, "model_state": {"module." + k: v for k, v in ms.state_dict().items()},
+                "optimizer_state_dict": {}}, reg / "weights.tar")
+    np.save(reg / "global_means.npy", np.zeros((1, 73, 1, 1), np.float32))
+    np.save(reg / "global_stds.npy", np.full((1, 73, 1, 1), 2.0, np.float32))
+    model, p, _ = inference.load_registry_model(str(reg), dev)
+    return model
+
+
+SCORE_FIELDS = ("crps", "fair_crps", "spread", "ens_rmse")
+
+
+def test_ensemble_rollout_equals_rollout_of_the_perturbed_batch_and_the_scorer(dev, lib, tmp_path):
+    from swin_v2_weather_amd import inference
+    from swin_v2_weather_amd.utils.weighted_acc_rmse import ForecastScorer
+    model = _registry_model(dev, tmp_path)
+    M, B, Cout, H, W, steps, amp, seed = 4, 2, 5, 48, 72, 3, 0.05, 11
+    g = torch.Generator(device=dev).manual_seed(3)
+    x0 = torch.randn(B, 9, H, W, device=dev, generator=g)
+    cz = torch.rand(B, steps - 1, H, W, device=dev, generator=g) * 2 - 1
+    truth = torch.randn(B, steps, Cout, H, W, device=dev, generator=g)
+    stds = torch.tensor([1.0, 2.0, 3.0, 4.0, 5.0], device=dev)
+    scorer = ForecastScorer(H, W, Cout, dev, stds=stds)
+    xe = inference.perturb_initial_condition(x0, M, amp, seed, 5)
+    noise = torch.randn((M - 1) * B, 5, H, W, generator=torch.Generator(device=dev).manual_seed(seed), device=dev)
+    assert torch.equal(xe[:B], x0) and torch.equal(xe[B:, 5:], x0.repeat(M - 1, 1, 1, 1)[:, 5:])
+    assert torch.equal(xe[B:, :5], x0.repeat(M - 1, 1, 1, 1)[:, :5] + amp * noise)
+    y = inference.rollout(model, xe, steps, cz.repeat(M, 1, 1, 1), n_invar=3)
+    kept = inference.ensemble_rollout(model, x0, truth, steps, M, amp, seed, cz, 3, scorer, keep_forecast=True)
+    assert torch.equal(kept.forecast, y)                                         # the forecasts are rollout's on the perturbed batch, bit for bit
+    assert kept.crps.shape == (steps, Cout) and kept.crps_samples.shape == (steps, B, Cout) and kept.hist.shape == (steps, B, Cout, M + 1)
+    assert kept.hist.dtype == torch.int32 and bool((kept.hist.sum(dim=-1) == H * W).all()) and kept.control is None
+    for s in range(steps):                                                       # scores = the scorer on the stored forecast, bit for bit
+        r = scorer.ensemble_score(y[:, s], truth[:, s], M)
+        for k in SCORE_FIELDS:
+            assert torch.equal(getattr(kept, k)[s], getattr(r, k + "_mean")) and torch.equal(getattr(kept, k + "_samples")[s], getattr(r, k)), (s, k)
+        assert torch.equal(kept.hist[s], r.hist)
+    assert bool((kept.spread > 0).all()) and bool((kept.crps > kept.fair_crps).all())
+    ring = inference.ensemble_rollout(model, x0, truth, steps, M, amp, seed, cz, 3, scorer)
+    fn = inference.ensemble_rollout(model, x0, lambda s: truth[:, s].clone(), steps, M, amp, seed, cz, 3, scorer, score_control=True)
+    assert ring.forecast is None and fn.forecast is None
+    for other in (ring, fn):                                                     # the two-slot ring and a callable truth change nothing
+        for a, b in zip(other[:9], kept[:9]):
+            assert torch.equal(a, b)
+    ctl = inference.score_rollout(model, x0, truth, steps, cz, n_invar=3, scorer=scorer)      # member 0 is the deterministic forecast
+    assert torch.equal(fn.control.rmse_samples, ctl.rmse_samples) and torch.equal(fn.control.rmse, ctl.rmse) and fn.control.acc is None
+    # two members per model call: the chunks advance in lockstep and each is a rollout of its own
+    halves = [inference.rollout(model, xe[i * 2 * B:(i + 1) * 2 * B], steps, cz.repeat(2, 1, 1, 1), n_invar=3) for i in range(2)]
+    mb = inference.ensemble_rollout(model, x0, truth, steps, M, amp, seed, cz, 3, scorer, member_batch=2, keep_forecast=True)
+    assert torch.equal(mb.forecast, torch.cat(halves, dim=0))
+    for s in range(steps):
+        r = scorer.ensemble_score(torch.cat([h[:, s] for h in halves], dim=0), truth[:, s], M)
+        for k in SCORE_FIELDS:
+            assert torch.equal(getattr(mb, k + "_samples")[s], getattr(r, k)) and torch.equal(getattr(mb, k)[s], getattr(r, k + "_mean")), (s, k)
+        assert torch.equal(mb.hist[s], r.hist)
+    # no perturbation: every member is the control, no spread at all
+    flat = inference.ensemble_rollout(model, x0, truth, steps, M, 0.0, seed, cz, 3, scorer)
+    assert bool((flat.spread_samples == 0).all()) and bool((flat.spread == 0).all())
+    assert torch.equal(flat.crps_samples, flat.fair_crps_samples)
+
+
+def test_cli_scores_an_ensemble_per_lead_time(dev, lib, tmp_path, capsys):
+    """python -m swin_v2_weather_amd.inference --truth ... --ensemble 4 --perturbation A: the table and the JSON hold ensemble_rollout's numbers"""
+    from swin_v2_weather_amd import inference
+    from swin_v2_weather_amd.utils.data_loader_era5 import cos_zenith
+    from swin_v2_weather_amd.utils.weighted_acc_rmse import ForecastScorer, spread_skill_ratio
+    model = _registry_model(dev, tmp_path)
+    reg = tmp_path / "swin_test_registry"
+    rng = np.random.default_rng(11)
+    B, Cout, H, W, steps, M = 2, 5, 48, 72, 3, 4
+    x0, truth = rng.standard_normal((B, 9, H, W)).astype(np.float32), rng.standard_normal((B, steps, Cout, H, W)).astype(np.float32)
+    np.save(tmp_path / "x0.npy", x0); np.save(tmp_path / "truth.npy", truth)
+    inference.main(["--registry", str(reg), "--steps", str(steps), "--init", str(tmp_path / "x0.npy"), "--truth", str(tmp_path / "truth.npy"),
+                    "--scores-out", str(tmp_path / "scores.json"), "--ensemble", str(M), "--perturbation", "0.1", "--seed", "5", "--member-batch", "2"])
+    out = capsys.readouterr().out.splitlines()
+    js = json.load(open(tmp_path / "scores.json"))
+    scorer = ForecastScorer(H, W, Cout, dev, stds=np.full(Cout, 2.0, np.float32))
+    cz = torch.stack([cos_zenith(2018, 6.0 * (s + 1), H, W) for s in range(steps - 1)], 0).unsqueeze(0).expand(B, -1, -1, -1).to(dev)
+    want = inference.ensemble_rollout(model, torch.tensor(x0).to(dev), torch.tensor(truth).to(dev), steps, M, 0.1, 5, cz, 3, scorer,
+                                      member_batch=2, n_fields=5, score_control=True)
+    e = js["ensemble"]
+    assert e["members"] == M and js["lead_hours"] == [6.0, 12.0, 18.0] and js["rmse"] == want.control.rmse.cpu().tolist() and js["acc"] is None
+    for k in SCORE_FIELDS:
+        assert e[k] == getattr(want, k).cpu().tolist(), k
+    assert e["spread_skill"] == spread_skill_ratio(want.spread, want.ens_rmse, M).cpu().tolist()
+    assert out[1].split() == ["lead_h", "rmse_u10m", "rmse_v10m", "crps_u10m", "crps_v10m", "spread_u10m", "spread_v10m", "ens_rmse_u10m", "ens_rmse_v10m"]
+    assert len(out) == 2 + steps
+    row = [float(v) for v in out[3].split()]
+    assert row[1:] == pytest.approx([js["rmse"][1][0], js["rmse"][1][1], e["crps"][1][0], e["crps"][1][1], e["spread"][1][0], e["spread"][1][1],
+                                     e["ens_rmse"][1][0], e["ens_rmse"][1][1]], abs=1e-5)
