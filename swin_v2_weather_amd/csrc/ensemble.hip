@@ -28,35 +28,25 @@
 // and one code path is kept); the network needs no runtime index, and min / max are exact, so the only roundings of e2 are the M - 1
 // gaps and their fma chain.
 //
-// Plan (that of score.hip): slices = planes >= 2048 ? 1 : 2048 / planes workgroups of 256 threads per plane, slice sl covering the
-// elements [plane_size * sl / slices / 4 * 4, plane_size * (sl + 1) / slices / 4 * 4) (the last one to the end); a slice without
-// elements stores zeros.  Workgroup index = (c * slices + sl) * B + b.  A workgroup reads its piece of the truth and of every member
-// once; the neighbours in launch order share the row weights only.
+// Plan and sums: plane_stream.h, with the workgroup index (c * slices + sl) * B + b; a slice without elements stores zeros.  A
+// workgroup reads its piece of the truth and of every member once; the neighbours in launch order share the row weights only.  The
+// thread's own running sum takes PTS ceil(g / 256) fma, one per grid point, g = groups of PTS elements in the largest slice
+// (tests/ensemble_reference.py::chain_length).
 //
-// Workspace: float part[planes * slices][4], then int cnt[planes * slices][M + 1].  No float atomics, nothing to zero beforehand: the
-// counts are added up in LDS with integer adds (order-independent) and stored by their workgroup.
+// Workspace: float part[planes * slices][4], then int cnt[planes * slices][M + 1].  Nothing to zero beforehand: the counts are added
+// up in LDS with integer adds (order-independent) and stored by their workgroup.
 //
-// Sums: the order is fixed by the plan alone, so two runs on the same inputs agree bit for bit.  On its way into a plane's sum a
-// term passes through at most
-//     PTS ceil(g / 256)  the thread's own running sum (one fma per grid point), g = groups of PTS elements in the largest slice
-//     6                  wave64 butterfly
-//     2                  the four waves through LDS, (w0 + w1) + (w2 + w3)
-//     ceil(slices / 64)  the lane's running sum over the slice partials in swv2_ens_finalize (slices sl = lane, lane + 64, ...)
-//     6                  wave64 butterfly
-// fp32 additions (tests/ensemble_reference.py::chain_length states the same count).  Per-term roundings, as written below:
+// Per-term roundings, as written below:
 //     e1   d_m: 1; M - 1 additions                                         e2   gap: 1; M - 1 fma (the coefficients i (M - i) are exact)
 //     v_m  a_m: 1; abar: M - 1 additions + the reciprocal + the product; the subtraction: 1; M fma for sum v^2
 //     e    d_0: 1; abar as above; the addition: 1; q e: 1
 #include <cmath>
 
-#include "common.h"
+#include "plane_stream.h"
 
 namespace {
 
-constexpr int ENS_MAX_BLOCKS = 2048;          // the plan of score.hip
 constexpr int ENS_MAX_M = 64;
-
-__host__ __device__ inline int ens_slices(long planes) { return planes >= ENS_MAX_BLOCKS ? 1 : (int)(ENS_MAX_BLOCKS / planes); }
 
 template <int PTS> struct ens_vec;
 template <> struct ens_vec<4> { using type = f32x4; };
@@ -106,8 +96,8 @@ __global__ __launch_bounds__(256) void ens_sums_kernel(const ens_coef_t coef, co
     const int M = FULL ? MB : Mrt;
     const int b = blockIdx.x % B, cs = blockIdx.x / B, c = cs / slices, sl = cs - c * slices;
     const uint32_t plane = (uint32_t)H * W;                   // < 2^30 (checked by the host)
-    const uint32_t lo = (uint32_t)((uint64_t)plane * sl / slices) / 4 * 4;
-    const uint32_t hi = (sl + 1 == slices) ? plane : (uint32_t)((uint64_t)plane * (sl + 1) / slices) / 4 * 4;
+    uint32_t lo, hi;
+    plane_slice_range(plane, sl, slices, lo, hi);
     const float* x0p = ens + b * ens_bs + (long)c * plane;
     const float* t = tar + b * tar_bs + (long)c * plane;
     __shared__ int hist[ENS_MAX_M + 1];
@@ -165,25 +155,20 @@ __global__ __launch_bounds__(256) void ens_sums_kernel(const ens_coef_t coef, co
             atomicAdd(&hist[rank], 1);                         // LDS, integer: 0 <= rank <= M
         }
     }
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        s[k] = wave_sum(s[k]);
-        if ((threadIdx.x & 63) == 0) r[k][threadIdx.x >> 6] = s[k];
-    }
-    __syncthreads();                                           // the wave sums and every count of this workgroup are in LDS
+    plane_block_stage(s, r);                                   // after its barrier the wave sums and every count of this workgroup are in LDS
     const size_t slot = (size_t)(b * C + c) * slices + sl;
     if (threadIdx.x == 0) {
         f32x4 o;
 #pragma unroll
-        for (int k = 0; k < 4; ++k) o[k] = (r[k][0] + r[k][1]) + (r[k][2] + r[k][3]);
+        for (int k = 0; k < 4; ++k) o[k] = plane_block_total(r[k]);
         *(f32x4*)(part + slot * 4) = o;
     }
     if ((int)threadIdx.x <= M) cnt[slot * (size_t)(M + 1) + threadIdx.x] = hist[threadIdx.x];
 }
 
-// One workgroup per channel: wave v folds the planes b = v, v + 4, ...: the float partials as score_finalize_kernel does (lane l adds
-// the slices l, l + 64, ... in ascending order, then the butterfly), the counts with lane = rank (integers: any order gives the same);
-// lane 0 writes the plane's sums and scores; thread 0 then adds the B values of the channel in ascending b for the batch means.
+// One workgroup per channel: wave v folds the planes b = v, v + 4, ...: the float partials by plane_fold_slices, the counts with
+// lane = rank (integers: any order gives the same); lane 0 writes the plane's sums and scores; thread 0 then adds the B values of the
+// channel in ascending b for the batch means.
 __global__ __launch_bounds__(256) void ens_finalize_kernel(const float* __restrict__ part, const int* __restrict__ cnt, int slices, int M, int B, int C,
                                                            float npix, const float* __restrict__ scale, float* __restrict__ sums,
                                                            int* __restrict__ hist, float* ens_rmse, float* spread, float* crps, float* fair_crps,
@@ -197,10 +182,8 @@ __global__ __launch_bounds__(256) void ens_finalize_kernel(const float* __restri
             for (int sl = 0; sl < slices; ++sl) n += cnt[(pl * slices + sl) * (size_t)(M + 1) + k];
             hist[pl * (M + 1) + k] = n;
         }
-        f32x4 a = {0.f, 0.f, 0.f, 0.f};
-        for (int sl = lane; sl < slices; sl += 64) a += *(const f32x4*)(part + (pl * slices + sl) * 4);
-#pragma unroll
-        for (int k = 0; k < 4; ++k) a[k] = wave_sum(a[k]);
+        f32x4 a;
+        plane_fold_slices<1>((const f32x4*)part, pl, slices, lane, &a);
         if (lane == 0) {
             a[1] = a[1] / (fm - 1.0f);
             *(f32x4*)(sums + pl * 4) = a;
@@ -223,10 +206,6 @@ __global__ __launch_bounds__(256) void ens_finalize_kernel(const float* __restri
     }
 }
 
-inline bool ens_shape_ok(int M, int B, int C, int H, int W) {
-    return M >= 2 && M <= ENS_MAX_M && B > 0 && C > 0 && H > 0 && W > 0 && (long)B * C < (1L << 31) / ENS_MAX_BLOCKS && (long)H * W < (1L << 30);
-}
-
 template <int MB, int PTS>
 void ens_launch(dim3 grid, hipStream_t st, const float* ens, long ms, long bs, const float* tar, long tbs, const float* w, float* part, int* cnt,
                 int M, int B, int C, int H, int W, int slices) {
@@ -242,21 +221,20 @@ void ens_launch(dim3 grid, hipStream_t st, const float* ens, long ms, long bs, c
 
 extern "C" size_t swv2_ens_ws_bytes(int planes, int H, int W, int M) {
     if (planes <= 0 || H <= 0 || W <= 0 || M < 2 || M > ENS_MAX_M) return 0;
-    return (size_t)planes * ens_slices(planes) * (4 * sizeof(float) + (size_t)(M + 1) * sizeof(int));
+    return (size_t)planes * plane_slices(planes) * (4 * sizeof(float) + (size_t)(M + 1) * sizeof(int));
 }
 
 extern "C" int swv2_ens_sums(const float* ens, long ens_mstride, long ens_bstride, const float* tar, long tar_bstride, const float* w, int M, int B,
                              int C, int H, int W, void* ws, size_t ws_bytes, void* stream) {
     SWV2_CHECK_ARG(ens && tar && w && ws, "ens_sums: null pointer");
     SWV2_CHECK_ARG(M >= 2 && M <= ENS_MAX_M, "ens_sums: members M outside 2 .. 64");
-    SWV2_CHECK_ARG(ens_shape_ok(M, B, C, H, W), "ens_sums: bad shape (B, C, H, W > 0, B * C < 2^20, H * W < 2^30)");
+    SWV2_CHECK_ARG(B > 0 && C > 0 && plane_shape_ok((long)B * C, H, W), "ens_sums: bad shape (B, C, H, W > 0, B * C < 2^20, H * W < 2^30)");
     SWV2_CHECK_ARG(W % 4 == 0, "ens_sums: W % 4 != 0");
-    SWV2_CHECK_ARG((((uintptr_t)ens | (uintptr_t)tar | (uintptr_t)ws) & 15) == 0, "ens_sums: pointer not 16-byte aligned");
-    SWV2_CHECK_ARG(ens_mstride % 4 == 0 && ens_bstride % 4 == 0 && tar_bstride % 4 == 0, "ens_sums: member or batch stride not a multiple of 4");
-    const long span = (long)C * H * W;
-    SWV2_CHECK_ARG(B == 1 || (ens_bstride >= span && tar_bstride >= span), "ens_sums: batch stride smaller than the C planes of a sample");
-    SWV2_CHECK_ARG(ws_bytes >= swv2_ens_ws_bytes(B * C, H, W, M), "ens_sums: workspace too small (swv2_ens_ws_bytes)");
-    const int slices = ens_slices((long)B * C);
+    SWV2_CHECK_ARG(ens_mstride % 4 == 0, "ens_sums: member stride not a multiple of 4");
+    if (!plane_operands_ok("ens_sums", {ens, tar, ws}, {ens_bstride, tar_bstride}, B, (long)C * H * W, ws_bytes, swv2_ens_ws_bytes(B * C, H, W, M),
+                           "swv2_ens_ws_bytes"))
+        return SWV2_ERR_INVALID;
+    const int slices = plane_slices((long)B * C);
     const size_t slots = (size_t)B * C * slices;
     const dim3 grid((unsigned)slots);
     float* part = (float*)ws;
@@ -283,10 +261,10 @@ extern "C" int swv2_ens_finalize(const void* ws, size_t ws_bytes, int M, int B, 
                                  float* ens_rmse, float* spread, float* crps, float* fair_crps, float* means, void* stream) {
     SWV2_CHECK_ARG(ws && sums && hist && ens_rmse && spread && crps && fair_crps && means, "ens_finalize: null pointer");
     SWV2_CHECK_ARG(M >= 2 && M <= ENS_MAX_M, "ens_finalize: members M outside 2 .. 64");
-    SWV2_CHECK_ARG(ens_shape_ok(M, B, C, H, W), "ens_finalize: bad shape (B, C, H, W > 0, B * C < 2^20, H * W < 2^30)");
-    SWV2_CHECK_ARG((((uintptr_t)ws | (uintptr_t)sums) & 15) == 0, "ens_finalize: pointer not 16-byte aligned (ws, sums)");
-    SWV2_CHECK_ARG(ws_bytes >= swv2_ens_ws_bytes(B * C, H, W, M), "ens_finalize: workspace too small (swv2_ens_ws_bytes)");
-    const int slices = ens_slices((long)B * C);
+    SWV2_CHECK_ARG(B > 0 && C > 0 && plane_shape_ok((long)B * C, H, W), "ens_finalize: bad shape (B, C, H, W > 0, B * C < 2^20, H * W < 2^30)");
+    if (!plane_operands_ok("ens_finalize", {ws, sums}, {}, 1, 0, ws_bytes, swv2_ens_ws_bytes(B * C, H, W, M), "swv2_ens_ws_bytes"))
+        return SWV2_ERR_INVALID;
+    const int slices = plane_slices((long)B * C);
     const float* part = (const float*)ws;
     const int* cnt = (const int*)(part + (size_t)B * C * slices * 4);
     hipLaunchKernelGGL(ens_finalize_kernel, dim3(C), dim3(256), 0, (hipStream_t)stream, part, cnt, slices, M, B, C, (float)((long)H * W), scale, sums,

@@ -14,8 +14,8 @@
 // Launches of one swv2_plane_order_stats, all on the caller's stream, no host synchronisation in between:
 //     memset(hist)   count<0> resolve   count<1> resolve   count<2> resolve   count<3> resolve   count<4> resolve(last)
 //
-// count<L>: workgroup (plane, slice) of the swv2_score_sums plan (slices = planes >= 2048 ? 1 : 2048 / planes, slice bounds on 16-byte
-// vectors, an empty slice adds nothing) streams its slice with four 16-byte loads in flight per thread.  Level 0 counts the top digit of
+// count<L>: workgroup (plane, slice) of the plan of plane_stream.h (workgroup index plane * slices + sl; an empty slice adds nothing)
+// streams its slice with four 16-byte loads in flight per thread.  Level 0 counts the top digit of
 // every element.  Level L > 0 looks the element's prefix key >> (25 - 5 L) up among the plane's active prefixes (at most K, sorted, held
 // in LDS and padded to 256 with 0xffffffff: an 8-step lower bound) and counts its next digit into hist[slot][digit]; an element under
 // no active prefix counts nowhere.  The lanes of a wave that hit the same counter as its first lane (all of them in a constant plane, most
@@ -32,13 +32,12 @@
 // itself (one memset up front, resolve afterwards) and writes every state word before reading it: a dirty workspace gives the bits of a
 // clean one.  Counters are integers: the result does not depend on the order in which workgroups or lanes arrive, two runs agree bit
 // for bit.  One counter can hold a whole plane (H W < 2^30).
-#include "common.h"
+#include "plane_stream.h"
 
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
 namespace {
 
-constexpr int Q_MAX_BLOCKS = 2048;            // the plan of swv2_score_sums
 constexpr int Q_MAX_K = 256;
 constexpr int Q_BITS0 = 12, Q_BITS = 5, Q_LEVELS = 5;
 constexpr int Q_HIST = Q_MAX_K << Q_BITS;     // 8192 counters per plane: >= 1 << Q_BITS0
@@ -47,8 +46,6 @@ constexpr uint32_t Q_NONE = 0xffffffffu;
 
 static_assert(Q_BITS0 + (Q_LEVELS - 1) * Q_BITS == 32, "the digits cover the key");
 static_assert((1 << Q_BITS0) <= Q_HIST, "level 0 fits the plane's histogram");
-
-__host__ __device__ inline int q_slices(long planes) { return planes >= Q_MAX_BLOCKS ? 1 : (int)(Q_MAX_BLOCKS / planes); }
 
 __device__ __forceinline__ uint32_t float_key(float v) {
     const uint32_t u = __float_as_uint(v);
@@ -105,8 +102,8 @@ __global__ __launch_bounds__(256) void quantile_count_kernel(const float* __rest
     for (int i = threadIdx.x; i < n; i += 256) hist[i] = 0;
     __syncthreads();
     const uint32_t plane = (uint32_t)H * W;                   // < 2^30, a multiple of 4 (checked by the host)
-    const uint32_t lo = (uint32_t)((uint64_t)plane * sl / slices) / 4 * 4;
-    const uint32_t hi = (sl + 1 == slices) ? plane : (uint32_t)((uint64_t)plane * (sl + 1) / slices) / 4 * 4;
+    uint32_t lo, hi;
+    plane_slice_range(plane, sl, slices, lo, hi);
     const float* p = x + b * bstride + (long)c * plane;
     uint32_t i = lo + threadIdx.x * 4;
     for (; i + 3 * 1024 < hi; i += 4 * 1024) {
@@ -215,18 +212,17 @@ extern "C" size_t swv2_quantile_ws_bytes(int planes, int H, int W, int K) {
 extern "C" int swv2_plane_order_stats(const float* x, long bstride, int B, int C, int H, int W, const int* ranks, int K, float* out,
                                       int* nan_count, void* ws, size_t ws_bytes, void* stream) {
     SWV2_CHECK_ARG(x && ranks && out && nan_count && ws, "plane_order_stats: null pointer");
-    SWV2_CHECK_ARG(B > 0 && C > 0 && H > 0 && W > 0 && (long)B * C < (1L << 31) / Q_MAX_BLOCKS && (long)H * W < (1L << 30),
-                   "plane_order_stats: bad shape (B, C, H, W > 0, B * C < 2^20, H * W < 2^30)");
+    SWV2_CHECK_ARG(B > 0 && C > 0 && plane_shape_ok((long)B * C, H, W), "plane_order_stats: bad shape (B, C, H, W > 0, B * C < 2^20, H * W < 2^30)");
     SWV2_CHECK_ARG((long)H * W % 4 == 0, "plane_order_stats: H * W % 4 != 0");
     SWV2_CHECK_ARG(K >= 1 && K <= Q_MAX_K, "plane_order_stats: K outside 1 .. 256");
-    SWV2_CHECK_ARG((((uintptr_t)x | (uintptr_t)ws) & 15) == 0 && (((uintptr_t)ranks | (uintptr_t)out | (uintptr_t)nan_count) & 3) == 0,
-                   "plane_order_stats: pointer not aligned (x, ws: 16 bytes; ranks, out, nan_count: 4)");
-    SWV2_CHECK_ARG(bstride % 4 == 0, "plane_order_stats: batch stride not a multiple of 4");
-    SWV2_CHECK_ARG(B == 1 || bstride >= (long)C * H * W, "plane_order_stats: batch stride smaller than the C planes of a sample");
+    SWV2_CHECK_ARG((((uintptr_t)ranks | (uintptr_t)out | (uintptr_t)nan_count) & 3) == 0,
+                   "plane_order_stats: pointer not 4-byte aligned (ranks, out, nan_count)");
     const int planes = B * C;
-    SWV2_CHECK_ARG(ws_bytes >= swv2_quantile_ws_bytes(planes, H, W, K), "plane_order_stats: workspace too small (swv2_quantile_ws_bytes)");
+    if (!plane_operands_ok("plane_order_stats", {x, ws}, {bstride}, B, (long)C * H * W, ws_bytes, swv2_quantile_ws_bytes(planes, H, W, K),
+                           "swv2_quantile_ws_bytes"))
+        return SWV2_ERR_INVALID;
     const hipStream_t st = (hipStream_t)stream;
-    const int slices = q_slices(planes);
+    const int slices = plane_slices(planes);
     uint32_t* w = (uint32_t*)ws;
     if (hipMemsetAsync(w, 0, (size_t)planes * (Q_HIST + Q_STATE) * sizeof(uint32_t), st) != hipSuccess) {
         swv2_set_error("plane_order_stats: hipMemsetAsync failed");

@@ -2,6 +2,7 @@
 // un-roll scatter), its backward, weight preparation, batch sums, the geometric l2 loss, fused Adam.
 // All of them stream rows with 16-byte accesses; G lanes cooperate on one row (G = 16/32/64 by channel count).
 #include "common.h"
+#include "plane_stream.h"
 
 namespace {
 
@@ -699,8 +700,7 @@ extern "C" int swv2_merge_ln_bwd(const float* x, const void* dn_bf16, const floa
 extern "C" int swv2_loss_sums(const float* prd, const float* tar, const float* quad_w, float* sums, int BC, int H, int W,
                               void* stream) {
     SWV2_CHECK_ARG(prd && tar && quad_w && sums && BC > 0 && H > 0 && W > 0 && W % 4 == 0, "loss_sums: bad argument (W % 4)");
-    // at most 2048 workgroups = one round at 8 per CU (7 .. 56 slices at B * C = 146 all run at 4.5 TB/s: the read stream is the bound)
-    const int slices = BC >= 2048 ? 1 : 2048 / BC;
+    const int slices = plane_slices(BC);                      // the slice count of plane_stream.h (loss_sums_kernel holds the same bounds in 64-bit form)
     hipLaunchKernelGGL(loss_sums_kernel, dim3(BC * slices), dim3(256), 0, (hipStream_t)stream, prd, tar, quad_w, sums, H, W,
                        slices);
     SWV2_CHECK_LAUNCH("swv2_loss_sums");

@@ -10,27 +10,12 @@
 //     p' = p - clim[c][h][w], t' = t - clim[c][h][w]  (p, t themselves without a climatology);  d = p - t is formed from p and t,
 //     never as p' - t': RMSE does not depend on the climatology.
 //
-// Plan (swv2_score_slices, the same rule as swv2_loss_sums): slices = planes >= 2048 ? 1 : 2048 / planes workgroups of 256 threads
-// per plane, slice sl covering the elements [plane_size * sl / slices / 4 * 4, plane_size * (sl + 1) / slices / 4 * 4) (the last
-// one to the end).  A slice without elements stores four zeros.  Workgroup index = (c * slices + sl) * B + b: the B workgroups
-// that read the same piece of the climatology are neighbours in launch order, so that piece is fetched from HBM once and
-// served from the memory-side cache to the others.
-//
-// Sums: no atomics and no pre-zeroed output; the order is fixed by the plan alone, so two runs on the same inputs agree bit for
-// bit.  On its way into a plane's sum a term passes through at most
-//     4 ceil(v / 256)   the thread's own running sum (fma), v = 16-byte vectors of the largest slice
-//     6                 wave64 butterfly
-//     2                 the four waves through LDS, (w0 + w1) + (w2 + w3)
-//     ceil(slices / 64) the lane's running sum over the slice partials in swv2_score_finalize (slices sl = lane, lane + 64, ...)
-//     6                 wave64 butterfly
-// fp32 additions (tests/score_reference.py::chain_length states the same count).
-#include "common.h"
+// Plan and sums: plane_stream.h, with the workgroup index (c * slices + sl) * B + b (the climatology is the shared operand) and
+// 4 ceil(v / 256) fma in the thread's own running sum, v = 16-byte vectors of the largest slice (tests/score_reference.py::chain_length).
+// A slice without elements stores four zeros.
+#include "plane_stream.h"
 
 namespace {
-
-constexpr int SCORE_MAX_BLOCKS = 2048;        // one round at 8 workgroups per CU, as swv2_loss_sums
-
-__host__ __device__ inline int score_slices(long planes) { return planes >= SCORE_MAX_BLOCKS ? 1 : (int)(SCORE_MAX_BLOCKS / planes); }
 
 template <bool CLIM>
 __device__ __forceinline__ void score_vec(const f32x4 a, const f32x4 b, const f32x4 m, const float q, float (&s)[4]) {
@@ -52,8 +37,8 @@ __global__ __launch_bounds__(256) void score_sums_kernel(const float* __restrict
                                                          int B, int C, int H, int W, int slices) {
     const int b = blockIdx.x % B, cs = blockIdx.x / B, c = cs / slices, sl = cs - c * slices;
     const uint32_t plane = (uint32_t)H * W;                   // < 2^30 (checked by the host)
-    const uint32_t lo = (uint32_t)((uint64_t)plane * sl / slices) / 4 * 4;
-    const uint32_t hi = (sl + 1 == slices) ? plane : (uint32_t)((uint64_t)plane * (sl + 1) / slices) / 4 * 4;
+    uint32_t lo, hi;
+    plane_slice_range(plane, sl, slices, lo, hi);
     const float* p = prd + b * prd_bs + (long)c * plane;
     const float* t = tar + b * tar_bs + (long)c * plane;
     const float* m = CLIM ? clim + (long)c * plane : nullptr;
@@ -78,23 +63,17 @@ __global__ __launch_bounds__(256) void score_sums_kernel(const float* __restrict
         score_vec<CLIM>(a, bb, mm, w[i / (uint32_t)W], s);      // W % 4 == 0: the 4 elements share a latitude row
     }
     __shared__ float r[4][4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        s[k] = wave_sum(s[k]);
-        if ((threadIdx.x & 63) == 0) r[k][threadIdx.x >> 6] = s[k];
-    }
-    __syncthreads();
+    plane_block_stage(s, r);
     if (threadIdx.x == 0) {
         f32x4 o;
 #pragma unroll
-        for (int k = 0; k < 4; ++k) o[k] = (r[k][0] + r[k][1]) + (r[k][2] + r[k][3]);
+        for (int k = 0; k < 4; ++k) o[k] = plane_block_total(r[k]);
         *(f32x4*)(ws + ((size_t)(b * C + c) * slices + sl) * 4) = o;
     }
 }
 
-// One workgroup per channel: wave v folds the slice partials of the planes b = v, v + 4, ... (lane l adds the slices l, l + 64, ...
-// in ascending order, then the butterfly) and writes that plane's sums, RMSE and ACC; thread 0 then adds the B values of the channel
-// in ascending b for the batch means.
+// One workgroup per channel: wave v folds the slice partials of the planes b = v, v + 4, ... (plane_fold_slices) and writes that
+// plane's sums, RMSE and ACC; thread 0 then adds the B values of the channel in ascending b for the batch means.
 __global__ __launch_bounds__(256) void score_finalize_kernel(const float* __restrict__ ws, int slices, int B, int C, float npix,
                                                              const float* __restrict__ scale, float* __restrict__ sums,
                                                              float* rmse, float* acc,
@@ -102,10 +81,8 @@ __global__ __launch_bounds__(256) void score_finalize_kernel(const float* __rest
     const int c = blockIdx.x, lane = threadIdx.x & 63;
     for (int b = threadIdx.x >> 6; b < B; b += 4) {
         const size_t pl = (size_t)b * C + c;
-        f32x4 a = {0.f, 0.f, 0.f, 0.f};
-        for (int sl = lane; sl < slices; sl += 64) a += *(const f32x4*)(ws + (pl * slices + sl) * 4);
-#pragma unroll
-        for (int k = 0; k < 4; ++k) a[k] = wave_sum(a[k]);
+        f32x4 a;
+        plane_fold_slices<1>((const f32x4*)ws, pl, slices, lane, &a);
         if (lane == 0) {
             *(f32x4*)(sums + pl * 4) = a;
             rmse[pl] = sqrtf(a[0] / npix);
@@ -122,33 +99,27 @@ __global__ __launch_bounds__(256) void score_finalize_kernel(const float* __rest
     }
 }
 
-inline bool score_shape_ok(int B, int C, int H, int W) {
-    return B > 0 && C > 0 && H > 0 && W > 0 && (long)B * C < (1L << 31) / SCORE_MAX_BLOCKS && (long)H * W < (1L << 30);
-}
-
 }  // namespace
 
 extern "C" int swv2_score_slices(int planes, int H, int W) {
     if (planes <= 0 || H <= 0 || W <= 0) return 0;
-    return score_slices(planes);
+    return plane_slices(planes);
 }
 
 extern "C" size_t swv2_score_ws_bytes(int planes, int H, int W) {
     if (planes <= 0 || H <= 0 || W <= 0) return 0;
-    return (size_t)planes * score_slices(planes) * 4 * sizeof(float);
+    return (size_t)planes * plane_slices(planes) * 4 * sizeof(float);
 }
 
 extern "C" int swv2_score_sums(const float* prd, long prd_bstride, const float* tar, long tar_bstride, const float* clim, const float* w,
                                int B, int C, int H, int W, void* ws, size_t ws_bytes, void* stream) {
     SWV2_CHECK_ARG(prd && tar && w && ws, "score_sums: null pointer");
-    SWV2_CHECK_ARG(score_shape_ok(B, C, H, W), "score_sums: bad shape (B, C, H, W > 0, B * C < 2^20, H * W < 2^30)");
+    SWV2_CHECK_ARG(B > 0 && C > 0 && plane_shape_ok((long)B * C, H, W), "score_sums: bad shape (B, C, H, W > 0, B * C < 2^20, H * W < 2^30)");
     SWV2_CHECK_ARG(W % 4 == 0, "score_sums: W % 4 != 0");
-    SWV2_CHECK_ARG((((uintptr_t)prd | (uintptr_t)tar | (uintptr_t)clim | (uintptr_t)ws) & 15) == 0, "score_sums: pointer not 16-byte aligned");
-    SWV2_CHECK_ARG(prd_bstride % 4 == 0 && tar_bstride % 4 == 0, "score_sums: batch stride not a multiple of 4");
-    const long span = (long)C * H * W;
-    SWV2_CHECK_ARG(B == 1 || (prd_bstride >= span && tar_bstride >= span), "score_sums: batch stride smaller than the C planes of a sample");
-    SWV2_CHECK_ARG(ws_bytes >= swv2_score_ws_bytes(B * C, H, W), "score_sums: workspace too small (swv2_score_ws_bytes)");
-    const int slices = score_slices((long)B * C);
+    if (!plane_operands_ok("score_sums", {prd, tar, clim, ws}, {prd_bstride, tar_bstride}, B, (long)C * H * W, ws_bytes,
+                           swv2_score_ws_bytes(B * C, H, W), "swv2_score_ws_bytes"))
+        return SWV2_ERR_INVALID;
+    const int slices = plane_slices((long)B * C);
     const dim3 grid((unsigned)((long)B * C * slices));
     if (clim)
         hipLaunchKernelGGL(score_sums_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, prd, prd_bstride, tar, tar_bstride, clim, w,
@@ -163,10 +134,10 @@ extern "C" int swv2_score_sums(const float* prd, long prd_bstride, const float* 
 extern "C" int swv2_score_finalize(const void* ws, size_t ws_bytes, int B, int C, int H, int W, const float* scale, float* sums, float* rmse,
                                    float* acc, float* rmse_mean, float* acc_mean, void* stream) {
     SWV2_CHECK_ARG(ws && sums && rmse && acc && rmse_mean && acc_mean, "score_finalize: null pointer");
-    SWV2_CHECK_ARG(score_shape_ok(B, C, H, W), "score_finalize: bad shape (B, C, H, W > 0, B * C < 2^20, H * W < 2^30)");
-    SWV2_CHECK_ARG((((uintptr_t)ws | (uintptr_t)sums) & 15) == 0, "score_finalize: pointer not 16-byte aligned (ws, sums)");
-    SWV2_CHECK_ARG(ws_bytes >= swv2_score_ws_bytes(B * C, H, W), "score_finalize: workspace too small (swv2_score_ws_bytes)");
-    hipLaunchKernelGGL(score_finalize_kernel, dim3(C), dim3(256), 0, (hipStream_t)stream, (const float*)ws, score_slices((long)B * C), B, C,
+    SWV2_CHECK_ARG(B > 0 && C > 0 && plane_shape_ok((long)B * C, H, W), "score_finalize: bad shape (B, C, H, W > 0, B * C < 2^20, H * W < 2^30)");
+    if (!plane_operands_ok("score_finalize", {ws, sums}, {}, 1, 0, ws_bytes, swv2_score_ws_bytes(B * C, H, W), "swv2_score_ws_bytes"))
+        return SWV2_ERR_INVALID;
+    hipLaunchKernelGGL(score_finalize_kernel, dim3(C), dim3(256), 0, (hipStream_t)stream, (const float*)ws, plane_slices((long)B * C), B, C,
                        (float)((long)H * W), scale, sums, rmse, acc, rmse_mean, acc_mean);
     SWV2_CHECK_LAUNCH("swv2_score_finalize");
     return SWV2_OK;

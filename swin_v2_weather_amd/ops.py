@@ -424,13 +424,19 @@ def score_workspace(planes: int, H: int, W: int, device) -> torch.Tensor:
     return torch.empty(int(L.load().swv2_score_ws_bytes(planes, H, W)) // 4, dtype=torch.float32, device=device)
 
 
+def _planes_in_place(t: torch.Tensor, lead: int) -> bool:
+    """a CUDA fp32 block of planes a plane-streaming kernel (csrc/plane_stream.h) reads in place: `lead` leading dimensions ([B] or
+    [M, B]), then [C, H, W] with contiguous planes, 16-byte aligned; the batch stride, unless B == 1, a multiple of 4 that steps over the
+    C planes of a sample"""
+    if not (t.is_cuda and t.dtype == torch.float32 and t.dim() == lead + 3 and t.numel() > 0):
+        return False
+    B, (Cc, H, W), bs = t.shape[lead - 1], t.shape[lead:], t.stride(lead - 1)
+    return tuple(t.stride()[lead:]) == (H * W, W, 1) and t.data_ptr() % 16 == 0 and (B == 1 or (bs % 4 == 0 and bs >= Cc * H * W))
+
+
 def score_planes_ok(t: torch.Tensor) -> bool:
     """what swv2_score_sums takes in place: a CUDA fp32 [B, C, H, W] tensor or channel block of one (contiguous planes, W % 4 == 0)"""
-    if not (t.is_cuda and t.dtype == torch.float32 and t.dim() == 4 and t.numel() > 0):
-        return False
-    B, Cc, H, W = t.shape
-    return W % 4 == 0 and tuple(t.stride()[1:]) == (H * W, W, 1) and t.data_ptr() % 16 == 0 and \
-        (B == 1 or (t.stride(0) % 4 == 0 and t.stride(0) >= Cc * H * W))
+    return _planes_in_place(t, 1) and t.shape[3] % 4 == 0
 
 
 def score_sums(prd, tar, w, ws, clim=None):
@@ -487,11 +493,7 @@ def ens_workspace(planes: int, H: int, W: int, M: int, device) -> torch.Tensor:
 def ens_members_ok(t: torch.Tensor) -> bool:
     """what swv2_ens_sums reads in place as the members: a CUDA fp32 [M, B, C, H, W] view (contiguous planes, W % 4 == 0, 2 <= M <= 64,
     member and batch strides multiples of 4) -- a channel block of a member-major [M * B, channels, H, W] tensor viewed that way"""
-    if not (t.is_cuda and t.dtype == torch.float32 and t.dim() == 5 and t.numel() > 0):
-        return False
-    M, B, Cc, H, W = t.shape
-    return 2 <= M <= ENS_MAX_MEMBERS and W % 4 == 0 and tuple(t.stride()[2:]) == (H * W, W, 1) and t.data_ptr() % 16 == 0 and \
-        t.stride(0) % 4 == 0 and (B == 1 or (t.stride(1) % 4 == 0 and t.stride(1) >= Cc * H * W))
+    return _planes_in_place(t, 2) and 2 <= t.shape[0] <= ENS_MAX_MEMBERS and t.shape[4] % 4 == 0 and t.stride(0) % 4 == 0
 
 
 def ens_sums(ens, tar, w, ws):
@@ -538,11 +540,7 @@ def quantile_workspace(planes: int, H: int, W: int, K: int, device) -> torch.Ten
 def quantile_planes_ok(t: torch.Tensor) -> bool:
     """what swv2_plane_order_stats reads in place: a CUDA fp32 [B, C, H, W] tensor or channel block of one (contiguous planes,
     H * W % 4 == 0)"""
-    if not (t.is_cuda and t.dtype == torch.float32 and t.dim() == 4 and t.numel() > 0):
-        return False
-    B, Cc, H, W = t.shape
-    return (H * W) % 4 == 0 and H * W < 2 ** 30 and tuple(t.stride()[1:]) == (H * W, W, 1) and t.data_ptr() % 16 == 0 and \
-        (B == 1 or (t.stride(0) % 4 == 0 and t.stride(0) >= Cc * H * W))
+    return _planes_in_place(t, 1) and (t.shape[2] * t.shape[3]) % 4 == 0 and t.shape[2] * t.shape[3] < 2 ** 30
 
 
 def plane_order_stats(x, ranks, ws=None):

@@ -225,23 +225,31 @@ class ForecastScorer:
         self.scale = None if stds is None else torch.as_tensor(stds, dtype=torch.float32).reshape(-1).to(self.device).contiguous()
         if self.scale is not None and self.scale.numel() != self.C:
             raise ValueError(f"{self.scale.numel()} stds for {self.C} channels")
-        self._ws = {}
-        self._qplan, self._qws = None, {}
-        self._ews = {}
+        self._qplan = None
+        self._ws = {}                                     # (kind, ...) -> the kernel workspace of that call shape, made once and reused
+
+    def _workspace(self, key, make, *args):
+        if key not in self._ws:
+            self._ws[key] = make(*args, self.device)
+        return self._ws[key]
+
+    def _blocks(self, who, prd, tar, coff_prd, coff_tar):
+        """the [B, C, H, W] channel blocks of prd and tar at their offsets, as views"""
+        p, t = prd[:, coff_prd:coff_prd + self.C], tar[:, coff_tar:coff_tar + self.C]
+        if p.shape != t.shape or p.shape[1:] != (self.C, self.H, self.W):
+            raise ValueError(f"{who}: blocks {tuple(p.shape)} / {tuple(t.shape)}, expected [B, {self.C}, {self.H}, {self.W}]")
+        return p, t
 
     def score(self, prd, tar, coff_prd=0, coff_tar=0) -> Scores:
         """channels coff_prd .. + C of prd against channels coff_tar .. + C of tar (scored in place, no copy) ->
         Scores(rmse [B, C], acc [B, C] | None, rmse_mean [C] (x stds), acc_mean [C] | None, sums [B, C, 4])"""
-        p, t = prd[:, coff_prd:coff_prd + self.C], tar[:, coff_tar:coff_tar + self.C]
-        if p.shape != t.shape or p.shape[1:] != (self.C, self.H, self.W):
-            raise ValueError(f"score: blocks {tuple(p.shape)} / {tuple(t.shape)}, expected [B, {self.C}, {self.H}, {self.W}]")
+        p, t = self._blocks("score", prd, tar, coff_prd, coff_tar)
         if _on_kernels(p, t) and p.device == self.device:
             from .. import ops
             B = p.shape[0]
-            if B not in self._ws:
-                self._ws[B] = ops.score_workspace(B * self.C, self.H, self.W, self.device)
-            ops.score_sums(p, t, self.w, self._ws[B], self.clim)
-            sums, rmse, acc, rmse_mean, acc_mean = ops.score_finalize(self._ws[B], B, self.C, self.H, self.W, self.scale)
+            ws = self._workspace(("score", B), ops.score_workspace, B * self.C, self.H, self.W)
+            ops.score_sums(p, t, self.w, ws, self.clim)
+            sums, rmse, acc, rmse_mean, acc_mean = ops.score_finalize(ws, B, self.C, self.H, self.W, self.scale)
         else:
             w = self.w.to(p.device)
             clim = None if self.clim is None else self.clim.to(device=p.device, dtype=p.dtype)
@@ -259,9 +267,7 @@ class ForecastScorer:
     def quantile_error(self, prd, tar, coff_prd=0, coff_tar=0) -> torch.Tensor:
         """top_quantiles_error_torch of channels coff_prd .. + C of prd against channels coff_tar .. + C of tar (read in place) -> [B, C].
         The rank tensor and the workspace (one per B) are made once and reused."""
-        p, t = prd[:, coff_prd:coff_prd + self.C], tar[:, coff_tar:coff_tar + self.C]
-        if p.shape != t.shape or p.shape[1:] != (self.C, self.H, self.W):
-            raise ValueError(f"quantile_error: blocks {tuple(p.shape)} / {tuple(t.shape)}, expected [B, {self.C}, {self.H}, {self.W}]")
+        p, t = self._blocks("quantile_error", prd, tar, coff_prd, coff_tar)
         q = quantile_levels()
         if not (_quantiles_on_kernels(p) and _quantiles_on_kernels(t) and p.device == self.device == t.device):
             return torch.mean(plane_quantiles(p, q) - plane_quantiles(t, q), dim=0)
@@ -269,9 +275,8 @@ class ForecastScorer:
         if self._qplan is None:
             self._qplan = _QuantilePlan(self.H * self.W, q, self.device)
         B = p.shape[0]
-        if B not in self._qws:
-            self._qws[B] = ops.quantile_workspace(B * self.C, self.H, self.W, self._qplan.K, self.device)
-        return torch.mean(self._qplan.quantiles(p, self._qws[B]) - self._qplan.quantiles(t, self._qws[B]), dim=0)
+        ws = self._workspace(("quantile", B), ops.quantile_workspace, B * self.C, self.H, self.W, self._qplan.K)
+        return torch.mean(self._qplan.quantiles(p, ws) - self._qplan.quantiles(t, ws), dim=0)
 
     def ensemble_score(self, ens, tar, n_members, coff_ens=0, coff_tar=0) -> EnsembleScores:
         """n_members forecasts against one truth.  ens: [M B, Cany, H, W] with a member-major batch (row m B + b) or [M, B, Cany, H, W];
@@ -291,10 +296,9 @@ class ForecastScorer:
         from .. import ops
         if e.is_cuda and t.is_cuda and e.device == self.device == t.device and ops.ens_members_ok(e) and ops.score_planes_ok(t):
             B = t.shape[0]
-            if (M, B) not in self._ews:
-                self._ews[(M, B)] = ops.ens_workspace(B * self.C, self.H, self.W, M, self.device)
-            ops.ens_sums(e, t, self.w, self._ews[(M, B)])
-            sums, hist, er, sp, cr, fc, means = ops.ens_finalize(self._ews[(M, B)], M, B, self.C, self.H, self.W, self.scale)
+            ws = self._workspace(("ensemble", M, B), ops.ens_workspace, B * self.C, self.H, self.W, M)
+            ops.ens_sums(e, t, self.w, ws)
+            sums, hist, er, sp, cr, fc, means = ops.ens_finalize(ws, M, B, self.C, self.H, self.W, self.scale)
             return EnsembleScores(sums, hist, er, sp, cr, fc, means[0], means[1], means[2], means[3])
         return ensemble_scores_torch(e, t, self.w, self.scale)
 

@@ -42,7 +42,8 @@ import math
 
 import numpy as np
 
-from tests.score_reference import U, batch_mean, gamma, plan_slices, slice_bounds, worst  # noqa: F401  (re-exported)
+from tests.plane_reference import U, gamma, plan_slices, slice_bounds, worst  # noqa: F401  (re-exported)
+from tests.score_reference import batch_mean  # noqa: F401  (re-exported)
 
 CAPACITIES = (8, 16, 32, 64)
 CHUNK = 128

@@ -19,11 +19,7 @@ Bounds, none of them taken from the code under test:
 import numpy as np
 import torch
 
-U = 2.0 ** -24
-
-
-def gamma(n):
-    return n * U / (1.0 - n * U)
+from tests.plane_reference import U, gamma, worst  # noqa: F401  (re-exported)
 
 
 def levels(qlim=3, qcut=0.1, qs=100):
@@ -70,13 +66,3 @@ def top_quantiles_error(pred, target):
     (p, bp), (t, bt) = quantiles(pred, q), quantiles(target, q)
     gap = p.astype(np.float64) - t.astype(np.float64)
     return gap.mean(axis=0), (bp + bt).mean(axis=0) + gamma(100) * np.abs(gap).mean(axis=0)
-
-
-def worst(err, bound):
-    """max of err / bound with 0 / 0 = 0 and x / 0 = inf"""
-    err, bound = np.asarray(err, np.float64), np.asarray(bound, np.float64)
-    if err.size == 0:
-        return 0.0
-    with np.errstate(divide="ignore", invalid="ignore"):
-        r = np.where(err == 0, 0.0, err / bound)
-    return float(np.max(r))

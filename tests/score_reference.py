@@ -41,25 +41,9 @@ import math
 
 import numpy as np
 
-U = 2.0 ** -24
+from tests.plane_reference import BLOCKS, U, gamma, plan_slices, slice_bounds, worst  # noqa: F401  (re-exported)
+
 C_TERM = 4
-BLOCKS = 2048          # SCORE_MAX_BLOCKS of csrc/score.hip
-
-
-def gamma(k: float) -> float:
-    assert k * U < 0.01
-    return k * U / (1.0 - k * U)
-
-
-def plan_slices(planes: int) -> int:
-    """swv2_score_slices: the published plan"""
-    return 1 if planes >= BLOCKS else BLOCKS // planes
-
-
-def slice_bounds(plane: int, slices: int):
-    """element range [lo, hi) of every slice of a plane of `plane` elements"""
-    lo = [plane * s // slices // 4 * 4 for s in range(slices)]
-    return list(zip(lo, lo[1:] + [plane]))
 
 
 def chain_length(H: int, W: int, slices: int) -> int:
@@ -118,14 +102,6 @@ def batch_mean(v, scale=None):
     B = v.shape[0]
     s = 1.0 if scale is None else scale.astype(np.float64)
     return v.mean(axis=0) * s, gamma(B + 1) * np.abs(v).sum(axis=0) / B * np.abs(s)
-
-
-def worst(err, bound) -> float:
-    """largest error / bound ratio (0 / 0 counts as 0): what every test prints before it asserts"""
-    err, bound = np.asarray(err, dtype=np.float64), np.asarray(bound, dtype=np.float64)
-    with np.errstate(invalid="ignore", divide="ignore"):
-        r = np.where(err == 0, 0.0, err / bound)
-    return float(np.max(r)) if r.size else 0.0
 
 
 def judge(got_sums, got_rmse, got_acc, prd, tar, w, clim, n: int, tag=""):

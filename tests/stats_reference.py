@@ -36,9 +36,11 @@ import math
 
 import numpy as np
 
-U = 2.0 ** -53
+from tests import plane_reference as P
+from tests.plane_reference import BLOCKS, plan_slices, slice_bounds, worst  # noqa: F401  (re-exported)
+
+U = 2.0 ** -53         # the sums are fp64
 C_TERM = 2
-BLOCKS = 2048          # STATS_MAX_BLOCKS of csrc/stats.hip
 LD = np.longdouble
 
 # (C, H, W) -> T: the smallest shapes that reach each branch of the plan
@@ -52,19 +54,7 @@ SHAPES = {(1, 1, 4): 3,            # a single vector: 2047 empty slices
 
 
 def gamma(k: float) -> float:
-    assert k * U < 0.01
-    return k * U / (1.0 - k * U)
-
-
-def plan_slices(C: int) -> int:
-    """swv2_stats_slices: the published plan"""
-    return 1 if C >= BLOCKS else BLOCKS // C
-
-
-def slice_bounds(plane: int, slices: int):
-    """element range [lo, hi) of every slice of a plane of `plane` elements"""
-    lo = [plane * s // slices // 4 * 4 for s in range(slices)]
-    return list(zip(lo, lo[1:] + [plane]))
+    return P.gamma(k, U)
 
 
 def chain_length(H: int, W: int, slices: int, T: int) -> int:
@@ -138,14 +128,6 @@ def state(years, pivot):
         A[c] = np.abs(xs).sum(), (xs * xs).sum(), np.abs(D).sum(), (D * D).sum()
         ts[c], At[c] = xs.sum(axis=0), np.abs(xs).sum(axis=0)
     return S, A, ts, At
-
-
-def worst(err, bound) -> float:
-    """largest error / bound ratio (0 / 0 counts as 0): what every test prints before it asserts"""
-    err, bound = np.asarray(err, dtype=np.float64), np.asarray(bound, dtype=np.float64)
-    with np.errstate(invalid="ignore", divide="ignore"):
-        r = np.where(err == 0, 0.0, err / bound)
-    return float(np.max(r)) if r.size else 0.0
 
 
 def judge_state(folded, tsum, ref_state, n: int, T: int, c_term: int = C_TERM, tag=""):

@@ -6,52 +6,9 @@ import pytest
 import torch
 
 from tests import stats_reference as R
+from tests.plane_harness import SENTINEL, Guarded, dev, lib  # noqa: F401  (dev, lib: fixtures)
 
 pytestmark = pytest.mark.gpu
-
-SENTINEL = 0x7FC0BEEF                                    # as int32; two of them make an fp64 NaN no kernel produces
-GUARD = 64                                               # int32 words in front of and behind every buffer
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "GPU tests need an MI355X"
-    return torch.device("cuda:0")
-
-
-@pytest.fixture(scope="module")
-def lib():
-    from swin_v2_weather_amd import _lib as L
-    return L.load()                                      # fails loudly if libswv2.so is missing: no fallback exists
-
-
-class Guarded:
-    """device buffers carved out of one int32 allocation filled with `fill`, each 16-byte aligned with GUARD words on both sides;
-    sizes in elements of the given dtype (torch.float32 / torch.float64)"""
-
-    def __init__(self, dev, fill=SENTINEL, **specs):
-        self.off, n = {}, GUARD
-        for k, (count, dtype) in specs.items():
-            words = count * (2 if dtype == torch.float64 else 1)
-            self.off[k] = (n, words, dtype)
-            n += (words + 3) // 4 * 4 + GUARD
-        self.raw = torch.full((n,), fill, dtype=torch.int32, device=dev)
-        self.fill = fill
-        assert self.raw.data_ptr() % 16 == 0
-
-    def __getitem__(self, k):
-        o, words, dtype = self.off[k]
-        return self.raw[o:o + words].view(dtype)
-
-    def guards_intact(self):
-        keep = torch.ones(self.raw.numel(), dtype=torch.bool, device=self.raw.device)
-        for o, words, _ in self.off.values():
-            keep[o:o + words] = False
-        return bool((self.raw[keep] == self.fill).all())
-
-    def written(self, k):
-        o, words, _ = self.off[k]
-        return bool((self.raw[o:o + words] != SENTINEL).all())
 
 
 def _run(lib, dev, slabs, pivot, fill=SENTINEL):

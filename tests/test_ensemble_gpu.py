@@ -11,12 +11,11 @@ import pytest
 import torch
 
 from tests import ensemble_reference as R
+from tests.plane_harness import Guarded, _weights, dev, lib  # noqa: F401  (dev, lib: fixtures)
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SENTINEL = 0x7FC0BEEF                                                                   # a NaN payload no kernel produces, as int32
-GUARD = 64                                                                              # words in front of and behind every output
 NAMES = R.NAMES
 
 # (M, B, C, H, W): the smallest shapes that reach each branch.  Capacities 8 / 16 / 32 / 64 hold M <= 8 / 16 / 32 / 64 (they set the points per
@@ -45,23 +44,6 @@ SHAPES = [(2, 1, 1, 1, 4),           # the smallest ensemble, a single vector: 2
           (33, 1, 2048, 4, 68)]      # capacity 64:      272 elements, one per thread: threads 0 .. 15 iterate twice
 
 
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "GPU tests need an MI355X"
-    return torch.device("cuda:0")
-
-
-@pytest.fixture(scope="module")
-def lib():
-    from swin_v2_weather_amd import _lib as L
-    return L.load()                                  # fails loudly if libswv2.so is missing: no fallback exists
-
-
-def _weights(H):
-    from swin_v2_weather_amd.utils.weighted_acc_rmse import latitude_weights
-    return latitude_weights(H).numpy() if H > 1 else np.ones(1, np.float32)          # (the formula divides by H - 1)
-
-
 @functools.lru_cache(maxsize=None)
 def _fields(M, B, C, H, W, offset=0.0, quantum=0.0, seed=0):
     """members [M, B, C, H, W] and truth [B, C, H, W]: N(0, 1) around a smooth field (+ offset; rounded to multiples of `quantum`), as
@@ -77,34 +59,6 @@ def _fields(M, B, C, H, W, offset=0.0, quantum=0.0, seed=0):
     for a in (ens, tar):
         a.setflags(write=False)
     return ens, tar, _weights(H)
-
-
-class Guarded:
-    """32-bit device buffers carved out of one sentinel-filled allocation, each 16-byte aligned with GUARD sentinel words on both sides"""
-
-    def __init__(self, dev, **sizes):
-        self.off, n = {}, GUARD
-        for k, v in sizes.items():
-            self.off[k] = (n, v)
-            n += (v + 3) // 4 * 4 + GUARD
-        self.raw = torch.full((n,), SENTINEL, dtype=torch.int32, device=dev)
-        self.sizes = sizes
-
-    def ints(self, k):
-        o, v = self.off[k]
-        return self.raw[o:o + v]
-
-    def __getitem__(self, k):
-        return self.ints(k).view(torch.float32)
-
-    def guards_intact(self):
-        keep = torch.ones(self.raw.numel(), dtype=torch.bool, device=self.raw.device)
-        for o, v in self.off.values():
-            keep[o:o + v] = False
-        return bool((self.raw[keep] == SENTINEL).all())
-
-    def written(self, k):
-        return bool((self.ints(k) != SENTINEL).all())
 
 
 def _launch(lib, dev, ens, tar, w, scale=None, ws_fill=None):
@@ -276,12 +230,12 @@ def test_forecast_scorer_ensemble_score_against_fp64(dev, lib):
     sc = ForecastScorer(H, W, C, dev, stds=stds)
     before = sc.score(rows[:B], dt, coff_prd=5, coff_tar=7)
     r = sc.ensemble_score(rows, dt, M, coff_ens=5, coff_tar=7)
-    assert isinstance(r, EnsembleScores) and r.hist.dtype == torch.int32 and tuple(r.hist.shape) == (B, C, M + 1) and len(sc._ews) == 1
+    assert isinstance(r, EnsembleScores) and r.hist.dtype == torch.int32 and tuple(r.hist.shape) == (B, C, M + 1) and set(sc._ws) == {("score", B), ("ensemble", M, B)}
     assert ops.ens_members_ok(rows.unflatten(0, (M, B))[:, :, 5:10])                 # the kernel path
     n = R.chain_length(H, W, ops.score_slices(B * C, H, W), M)
     R.judge(_scores_as_got(r), ens_w[:, :, 5:10], tar_w[:, 7:12], w, n, stds, "ensemble_score, kernels")
     r5 = sc.ensemble_score(rows.view(M, B, 15, H, W), dt, M, coff_ens=5, coff_tar=7)   # the five-dimensional form, the workspace reused
-    assert all(torch.equal(a, b) for a, b in zip(r, r5)) and len(sc._ews) == 1 and r5.crps.data_ptr() != r.crps.data_ptr()
+    assert all(torch.equal(a, b) for a, b in zip(r, r5)) and set(sc._ws) == {("score", B), ("ensemble", M, B)} and r5.crps.data_ptr() != r.crps.data_ptr()
     after = sc.score(rows[:B], dt, coff_prd=5, coff_tar=7)
     assert all(torch.equal(a, b) for a, b in zip(before[:1] + before[2:3] + before[4:], after[:1] + after[2:3] + after[4:]))      # score() is untouched
     # odd width: the torch path on the device, judged as sums in any order (chain H W M)
@@ -289,7 +243,7 @@ def test_forecast_scorer_ensemble_score_against_fp64(dev, lib):
     eo, to_ = np.ascontiguousarray(ens_w[..., :Wo]), np.ascontiguousarray(tar_w[..., :Wo])
     so = ForecastScorer(H, Wo, C, dev, stds=stds)
     ro = so.ensemble_score(torch.tensor(eo).to(dev).view(M * B, 15, H, Wo), torch.tensor(to_).to(dev), M, 5, 7)
-    assert len(so._ews) == 0 and ro.hist.dtype == torch.int32
+    assert len(so._ws) == 0 and ro.hist.dtype == torch.int32
     R.judge(_scores_as_got(ro), eo[:, :, 5:10], to_[:, 7:12], w, H * Wo * M, stds, "ensemble_score, torch path")
     with pytest.raises(ValueError):
         sc.ensemble_score(rows, dt, 3, coff_ens=5, coff_tar=7)                       # 10 rows do not hold 3 members

@@ -133,7 +133,7 @@ def test_forecast_scorer_ensemble_score_torch_path_in_place_blocks():
     ens, tar = rows.reshape(m, B, C + 2, H, W)[:, :, 1:4], wide[:, 2:5]
     R.judge(_as_got(r), ens, tar, M.latitude_weights(H).numpy(), H * W * m, stds, "ensemble_score on cpu")
     r5 = sc.ensemble_score(torch.from_numpy(rows).view(m, B, C + 2, H, W), torch.from_numpy(wide), m, 1, 2)
-    assert all(torch.equal(a, b) for a, b in zip(r, r5)) and len(sc._ews) == 0
+    assert all(torch.equal(a, b) for a, b in zip(r, r5)) and len(sc._ws) == 0
     plain = M.ForecastScorer(H, W, C, "cpu").ensemble_score(torch.from_numpy(rows), torch.from_numpy(wide), m, 1, 2)
     assert torch.equal(plain.fair_crps_mean, r.fair_crps_mean) and torch.equal(plain.crps, r.crps)
     assert torch.equal(r.crps_mean, plain.crps_mean * torch.from_numpy(stds)) and torch.equal(r.spread_mean, plain.spread_mean * torch.from_numpy(stds))

@@ -10,25 +10,12 @@ import pytest
 import torch
 
 from tests import quantile_reference as R
+from tests.plane_harness import SENTINEL, Guarded, dev, lib  # noqa: F401  (dev, lib: fixtures)
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLD = np.load(os.path.join(ROOT, "tests", "golden", "quantiles.npz"))
-SENTINEL = 0x7FC0BEEF                                  # a NaN payload no kernel produces, as int32
-GUARD = 64
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "GPU tests need an MI355X"
-    return torch.device("cuda:0")
-
-
-@pytest.fixture(scope="module")
-def lib():
-    from swin_v2_weather_amd import _lib as L
-    return L.load()                                  # fails loudly if libswv2.so is missing: no fallback exists
 
 
 def _case(name):
@@ -79,28 +66,6 @@ def _ranks_for(n):
     return np.array(sorted(r), np.int32)
 
 
-class Guarded:
-    """int32 device buffers carved out of one sentinel-filled allocation, each 16-byte aligned with GUARD sentinel words on both sides"""
-
-    def __init__(self, dev, **sizes):
-        self.off, n = {}, GUARD
-        for k, v in sizes.items():
-            self.off[k] = (n, v)
-            n += (v + 3) // 4 * 4 + GUARD
-        self.raw = torch.full((n,), SENTINEL, dtype=torch.int32, device=dev)
-        self.sizes = sizes
-
-    def __getitem__(self, k):
-        o, v = self.off[k]
-        return self.raw[o:o + v]
-
-    def guards_intact(self):
-        keep = torch.ones(self.raw.numel(), dtype=torch.bool, device=self.raw.device)
-        for o, v in self.off.values():
-            keep[o:o + v] = False
-        return bool((self.raw[keep] == SENTINEL).all())
-
-
 def _launch(lib, dev, x, ranks, ws_fill=SENTINEL):
     """x: device tensor or channel-block view [B, C, H, W]; ranks: numpy int32 -> (values [K, B, C] numpy, nan_count [B, C] numpy, Guarded)"""
     from swin_v2_weather_amd import _lib as L
@@ -108,7 +73,7 @@ def _launch(lib, dev, x, ranks, ws_fill=SENTINEL):
     K = len(ranks)
     wsb = lib.swv2_quantile_ws_bytes(B * C, H, W, K)
     assert wsb == B * C * 35856
-    g = Guarded(dev, ws=wsb // 4, out=K * B * C, nan_count=B * C)
+    g = Guarded(dev, dtype=torch.int32, ws=wsb // 4, out=K * B * C, nan_count=B * C)
     if ws_fill != SENTINEL:
         g["ws"].fill_(ws_fill)
     d_ranks = torch.tensor(ranks, dtype=torch.int32).to(dev)
@@ -247,12 +212,12 @@ def test_forecast_scorer_quantile_error_with_offsets_reuses_its_workspace(dev, l
     got = sc.quantile_error(dp, dt, coff_prd=20, coff_tar=7)
     want = M.top_quantiles_error_torch(dp[:, 20:25].contiguous(), dt[:, 7:12].contiguous())
     assert torch.equal(got, want) and tuple(got.shape) == (2, 5)
-    ws, ranks = sc._qws[2], sc._qplan.ranks
+    ws, ranks = sc._ws[("quantile", 2)], sc._qplan.ranks
     again = sc.quantile_error(dp, dt, coff_prd=20, coff_tar=7)
     assert torch.equal(again, got) and again.data_ptr() != got.data_ptr()
-    assert len(sc._qws) == 1 and sc._qws[2] is ws and sc._qplan.ranks is ranks
+    assert len(sc._ws) == 1 and sc._ws[("quantile", 2)] is ws and sc._qplan.ranks is ranks
     one = sc.quantile_error(dp[:1], dt[:1], coff_prd=20, coff_tar=7)
-    assert torch.equal(one, M.top_quantiles_error_torch(dp[:1, 20:25].contiguous(), dt[:1, 7:12].contiguous())) and set(sc._qws) == {1, 2}
+    assert torch.equal(one, M.top_quantiles_error_torch(dp[:1, 20:25].contiguous(), dt[:1, 7:12].contiguous())) and set(sc._ws) == {("quantile", 1), ("quantile", 2)}
     r = sc.score(dp, dt, coff_prd=20, coff_tar=7)                                                # Scores and score() are what they were
     assert type(r)._fields == ("rmse", "acc", "rmse_mean", "acc_mean", "sums")
 
@@ -262,7 +227,7 @@ def test_refusals_are_made_on_the_host_before_any_launch(dev, lib):
     K = 67
     ranks = torch.arange(K, dtype=torch.int32, device=dev)
     wsb = lib.swv2_quantile_ws_bytes(6, 8, 16, K)
-    g = Guarded(dev, ws=wsb // 4, out=256 * 6, nan_count=6)
+    g = Guarded(dev, dtype=torch.int32, ws=wsb // 4, out=256 * 6, nan_count=6)
     st = torch.cuda.current_stream().cuda_stream
 
     def call(xp=x.data_ptr(), H=8, W=16, K=K, ws=g["ws"].data_ptr(), wb=wsb):

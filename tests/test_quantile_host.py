@@ -87,7 +87,7 @@ def test_forecast_scorer_quantile_error_on_the_cpu_equals_the_function():
     wide_p[:, 2:5], wide_t[:, 4:7] = pred, target
     sc = M.ForecastScorer(9, 16, 3, "cpu")
     got = sc.quantile_error(wide_p, wide_t, coff_prd=2, coff_tar=4)
-    assert np.array_equal(got.numpy(), GOLD["top_quantiles_error_torch"]) and sc._qws == {}
+    assert np.array_equal(got.numpy(), GOLD["top_quantiles_error_torch"]) and sc._ws == {}
     with pytest.raises(ValueError):
         sc.quantile_error(wide_p, wide_t, coff_prd=5)
     assert M.Scores._fields == ("rmse", "acc", "rmse_mean", "acc_mean", "sums")

@@ -10,12 +10,11 @@ import pytest
 import torch
 
 from tests import score_reference as R
+from tests.plane_harness import Guarded, _weights, dev, lib  # noqa: F401  (dev, lib: fixtures)
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SENTINEL = 0x7FC0BEEF                                                                   # a NaN payload no kernel produces, as int32
-GUARD = 64                                                                              # floats in front of and behind every output
 
 # (B, C, H, W): the smallest shapes that reach each branch of the plan (slices: tests/test_score_host.py::PLAN)
 SHAPES = [(1, 1, 1, 4),            # a single vector: 2047 empty slices
@@ -30,23 +29,6 @@ SHAPES = [(1, 1, 1, 4),            # a single vector: 2047 empty slices
                                    # rows, 1024 elements = 2.13 rows apart) + a tail for threads 0 .. 8, and the batch stride inside the loop
 
 
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "GPU tests need an MI355X"
-    return torch.device("cuda:0")
-
-
-@pytest.fixture(scope="module")
-def lib():
-    from swin_v2_weather_amd import _lib as L
-    return L.load()                                  # fails loudly if libswv2.so is missing: no fallback exists
-
-
-def _weights(H):
-    from swin_v2_weather_amd.utils.weighted_acc_rmse import latitude_weights
-    return latitude_weights(H).numpy() if H > 1 else np.ones(1, np.float32)          # (the formula divides by H - 1)
-
-
 @functools.lru_cache(maxsize=None)
 def _fields(B, C, H, W, seed=0):
     """N(0, 1) fields on a smooth climatology, as numpy fp32 (generated once per shape, never modified)"""
@@ -58,32 +40,6 @@ def _fields(B, C, H, W, seed=0):
     for a in (clim, prd, tar):
         a.setflags(write=False)
     return prd, tar, clim, _weights(H)
-
-
-class Guarded:
-    """fp32 device buffers carved out of one sentinel-filled allocation, each 16-byte aligned with GUARD sentinel floats on both sides"""
-
-    def __init__(self, dev, **sizes):
-        self.off, n = {}, GUARD
-        for k, v in sizes.items():
-            self.off[k] = (n, v)
-            n += (v + 3) // 4 * 4 + GUARD
-        self.raw = torch.full((n,), SENTINEL, dtype=torch.int32, device=dev)
-        self.sizes = sizes
-
-    def __getitem__(self, k):
-        o, v = self.off[k]
-        return self.raw[o:o + v].view(torch.float32)
-
-    def guards_intact(self):
-        keep = torch.ones(self.raw.numel(), dtype=torch.bool, device=self.raw.device)
-        for o, v in self.off.values():
-            keep[o:o + v] = False
-        return bool((self.raw[keep] == SENTINEL).all())
-
-    def written(self, k):
-        o, v = self.off[k]
-        return bool((self.raw[o:o + v] != SENTINEL).all())
 
 
 def _launch(lib, dev, prd, tar, w, clim, scale=None):
