@@ -36,7 +36,7 @@ extern "C" {
  * swv2_attn_bwd_kernel (+ swv2_attn_kernel_t, SWV2_ATTN_K_*); 111: the LAMB optimizer, swv2_lamb_* (+ swv2_lamb_item, SWV2_LAMB_*);
  * 112: forecast scores, swv2_score_*.  The dataset statistics, swv2_stats_*, came later and are purely additive (new entry points only,
  * no struct member moves): the revision stays 112.  So are the plane order statistics, swv2_quantile_ws_bytes / swv2_plane_order_stats,
- * and the ensemble scores, swv2_ens_*. */
+ * and the ensemble scores, swv2_ens_*, and the l1 loss family, swv2_l1_*. */
 #define SWV2_VERSION 112
 
 enum {
@@ -580,6 +580,32 @@ int swv2_ens_sums(const float* ens, long ens_mstride, long ens_bstride, const fl
                   int H, int W, void* ws, size_t ws_bytes, void* stream);
 int swv2_ens_finalize(const void* ws, size_t ws_bytes, int M, int B, int C, int H, int W, const float* scale, float* sums, int* hist,
                       float* ens_rmse, float* spread, float* crps, float* fair_crps, float* means, void* stream);
+
+/* Geometric l1 loss (csrc/loss_l1.hip; reference utils/losses.py:114-120 with p = 1) and the latitude-weighted mean absolute error: per
+ * (sample, channel) plane, from ONE pass over prediction and target.  All tensors fp32.
+ *   prd, tar  C planes of [H][W] per sample, sample b at ptr + b * bstride (elements), as swv2_score_sums takes them;  w: [H] row weights
+ *   S0 = sum w[h] |p - t|      S1 = sum w[h] |t|
+ * swv2_l1_sums: one launch of B * C * swv2_score_slices(B * C, H, W) workgroups (the plan and slice bounds of swv2_score_sums); workgroup
+ * (plane, slice) stores (S0, S1) of its slice at ws[(plane * slices + slice) * 2 ..], plane = b * C + c.  No atomics, nothing to zero
+ * beforehand; a slice without elements stores zeros.
+ * swv2_l1_finalize: one launch of one workgroup; folds the slices of each plane in a fixed order and writes sums [B][C][2] = (S0, S1).
+ * With chw != NULL ([C] channel weights) it also writes
+ *   loss [1] = sum_bc chw[c] norm[b][c],   norm = S0 (absolute != 0) or S0 / S1,   the B C terms added in an order fixed by the code
+ *   coef [B][C] = d loss / d S0 = chw[c] (absolute) or chw[c] / S1[b][c]
+ * (loss and coef are not touched and may be NULL when chw is NULL).  Two runs on the same inputs agree bit for bit in every output.  A
+ * NaN in a plane makes that plane's sums and the loss NaN and touches no other plane's sums.
+ * swv2_l1_grad: dprd[b][c][h][w] = coef[b][c] * w[h] (one fp32 product) with the sign of p - t, taken from the comparisons p > t and
+ * p < t: +-that product, or 0 where p == t or either is NaN.  prd, tar, dprd contiguous [B C][H][W]; the grid of swv2_loss_grad.
+ * Refused with SWV2_ERR_INVALID before any launch: a null pointer, W % 4 != 0, prd / tar / ws / dprd not 16-byte aligned, sums not 8-byte
+ * aligned, a batch stride that is not a multiple of 4 or (B > 1) smaller than C H W, a workspace smaller than swv2_l1_ws_bytes,
+ * B * C >= 2^20 (swv2_l1_grad: B * C > 65535), H * W >= 2^30.  swv2_l1_ws_bytes is host-only (no HIP call) and returns 0 for a
+ * non-positive argument. */
+size_t swv2_l1_ws_bytes(int planes, int H, int W);        /* planes * swv2_score_slices(planes, H, W) * 8 */
+int swv2_l1_sums(const float* prd, long prd_bstride, const float* tar, long tar_bstride, const float* w, int B, int C, int H, int W, void* ws,
+                 size_t ws_bytes, void* stream);
+int swv2_l1_finalize(const void* ws, size_t ws_bytes, int B, int C, int H, int W, const float* chw, int absolute, float* sums, float* loss,
+                     float* coef, void* stream);
+int swv2_l1_grad(const float* prd, const float* tar, const float* quad_w, const float* coef, float* dprd, int BC, int H, int W, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * ERA5 input assembly (the step BEFORE the model): raw time slabs staged on the device by async H2D copies

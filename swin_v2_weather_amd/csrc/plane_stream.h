@@ -1,5 +1,5 @@
 // The plan of the plane-streaming kernels, stated once: forecast scores (score.hip), dataset statistics (stats.hip), order statistics
-// (quantile.hip), ensemble scores (ensemble.hip); swv2_loss_sums (rowops.hip) takes its slice count from here.  Each of them reads
+// (quantile.hip), ensemble scores (ensemble.hip), the l1 loss (loss_l1.hip); swv2_loss_sums (rowops.hip) takes its slice count from here.  Each of them reads
 // `planes` planes of H x W fp32 values once (planes = B * C, or C for the statistics) and leaves a few numbers per plane.
 //
 // Slices.  A plane is cut into  slices = planes >= 2048 ? 1 : 2048 / planes  pieces, one workgroup of 256 threads each: at most 2048
@@ -10,7 +10,7 @@
 //
 // Workgroup index.  (c * slices + sl) * B + b where a per-channel operand is shared (the climatology of score.hip, the row weights of
 // ensemble.hip): the B workgroups that read the same piece of it are neighbours in launch order, so it comes from HBM once and from
-// the memory-side cache afterwards.  plane * slices + sl where nothing is shared (stats.hip, quantile.hip).
+// the memory-side cache afterwards.  plane * slices + sl where nothing is shared (stats.hip, quantile.hip) or the row weights only (loss_l1.hip).
 //
 // Sums.  No float atomics and no pre-zeroed output: every partial sum has ONE owner, and the order of the additions is fixed by the
 // plan alone, so two runs on the same inputs agree bit for bit.  On its way into a plane's sum a term passes through

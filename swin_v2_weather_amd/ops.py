@@ -479,6 +479,50 @@ def forecast_scores(prd, tar, w, clim=None, scale=None, ws=None):
     return score_finalize(ws, B, Cc, H, W, scale)
 
 
+def l1_workspace(planes: int, H: int, W: int, device) -> torch.Tensor:
+    """the caller's workspace of swv2_l1_sums / swv2_l1_finalize for `planes` = B * C planes: allocate once, reuse"""
+    return torch.empty(int(L.load().swv2_l1_ws_bytes(planes, H, W)) // 4, dtype=torch.float32, device=device)
+
+
+def l1_sums(prd, tar, w, ws):
+    """S0 = sum w |prd - tar| and S1 = sum w |tar| of every (b, c) plane (prd / tar as score_sums takes them: [B, C, H, W] or a channel
+    block of a wider contiguous tensor, read in place) as slice partials in ws (l1_workspace); w [H] row weights"""
+    if not (score_planes_ok(prd) and score_planes_ok(tar)) or prd.shape != tar.shape:
+        raise L.Swv2Error(f"l1_sums: expected two CUDA fp32 [B, C, H, W] tensors of one shape with contiguous planes and W % 4 == 0, got "
+                          f"{tuple(prd.shape)} {prd.dtype} strides {prd.stride()} / {tuple(tar.shape)} {tar.dtype} strides {tar.stride()}")
+    B, Cc, H, W = prd.shape
+    _chk(w, torch.float32, "row weights"); _chk(ws, torch.float32, "l1 workspace")
+    if w.numel() != H:
+        raise L.Swv2Error(f"l1_sums: {w.numel()} row weights for {H} rows")
+    L.check(L.load().swv2_l1_sums(_p(prd), prd.stride(0) if B > 1 else Cc * H * W, _p(tar), tar.stride(0) if B > 1 else Cc * H * W, _p(w),
+                                  B, Cc, H, W, _p(ws), ws.numel() * 4, _stream()), "swv2_l1_sums")
+
+
+def l1_finalize(ws, B: int, Cc: int, H: int, W: int, chw=None, absolute: bool = False):
+    """slice partials -> sums [B, C, 2] = (S0, S1); with chw [C] also (loss [1], coef [B, C] = d loss / d S0), else (None, None).  One
+    launch; the results are views of one fresh buffer"""
+    _chk(ws, torch.float32, "l1 workspace")
+    if chw is not None and _chk(chw, torch.float32, "channel weights").numel() != Cc:
+        raise L.Swv2Error(f"l1_finalize: {chw.numel()} channel weights for {Cc} channels")
+    n = B * Cc
+    buf = torch.empty(3 * n + 2, dtype=torch.float32, device=ws.device)
+    sums = buf[:2 * n].view(B, Cc, 2)
+    coef, loss = (buf[2 * n:3 * n].view(B, Cc), buf[3 * n:3 * n + 1]) if chw is not None else (None, None)
+    L.check(L.load().swv2_l1_finalize(_p(ws), ws.numel() * 4, B, Cc, H, W, _p(chw), int(absolute), _p(sums), _p(loss), _p(coef), _stream()),
+            "swv2_l1_finalize")
+    return sums, loss, coef
+
+
+def l1_grad(prd, tar, qw, coef, dprd):
+    """dprd = coef[b, c] * qw[h] * sign(prd - tar); prd, tar, dprd contiguous fp32 [B, C, H, W]"""
+    for t, what in ((prd, "prediction"), (tar, "target"), (dprd, "gradient"), (qw, "row weights"), (coef, "coef")):
+        _chk(t, torch.float32, what)
+    B, Cc, H, W = prd.shape
+    if tar.shape != prd.shape or dprd.shape != prd.shape or coef.numel() != B * Cc or qw.numel() != H:
+        raise L.Swv2Error(f"l1_grad: shapes {tuple(prd.shape)} / {tuple(tar.shape)} / {tuple(dprd.shape)}, coef {coef.numel()}, weights {qw.numel()}")
+    L.check(L.load().swv2_l1_grad(_p(prd), _p(tar), _p(qw), _p(coef), _p(dprd), B * Cc, H, W, _stream()), "swv2_l1_grad")
+
+
 ENS_MAX_MEMBERS = 64          # the M cap of swv2_ens_sums
 
 

@@ -1,7 +1,9 @@
-"""Quadrature weights on the lat-lon grid (reference utils/grids.py:62-117, 'naive' rule only: the other rules need
-torch_harmonics and are selected by no config)."""
+"""Quadrature weights on the lat-lon grid (reference utils/grids.py:62-117): the 'naive' rule and the Gauss-Legendre rule
+('legendre-gauss', what model_grid_type: legendre_gauss selects; computed with numpy, no torch_harmonics).  'clenshaw-curtiss' is
+reachable from no config and is not provided."""
 import math
 
+import numpy as np
 import torch
 
 
@@ -17,15 +19,29 @@ def naive_quadrature_weights(H: int, W: int, normalize: bool = True) -> torch.Te
     return q
 
 
+def legendre_gauss_quadrature_weights(H: int, W: int, normalize: bool = True) -> torch.Tensor:
+    """[H] latitude weights of the Gauss-Legendre rule on H nodes in cos(colatitude) (grids.py:83-88, 93-94): q[h] = w[h] * 2 pi / W
+    with w the Gauss-Legendre weights on [-1, 1] (their sum is 2, so the [H, W] grid sums to 4 pi), / 4 pi if `normalize`.  Computed in
+    fp64 by numpy.polynomial.legendre.leggauss and stored in fp32, one value per row."""
+    _, w = np.polynomial.legendre.leggauss(int(H))
+    q = w * (2.0 * math.pi / W)
+    if normalize:
+        q = q / (4.0 * math.pi)
+    return torch.from_numpy(q.astype(np.float32))
+
+
+QUADRATURE_RULES = {'naive': naive_quadrature_weights, 'legendre-gauss': legendre_gauss_quadrature_weights}
+
+
 class GridQuadrature(torch.nn.Module):
     """Integrates over the last two axes with the latitude weights (grids.py:62-117).  Host-side helper; the training
     loss uses the fused kernels in losses.py."""
 
     def __init__(self, quadrature_rule, img_shape, crop_shape=None, crop_offset=(0, 0), normalize=False, pole_mask=None):
         super().__init__()
-        if quadrature_rule != 'naive':
-            raise ValueError(f"Unknown quadrature rule {quadrature_rule} (only 'naive' is available without torch_harmonics)")
-        q = naive_quadrature_weights(img_shape[0], img_shape[1], normalize).unsqueeze(1).repeat(1, img_shape[1])
+        if quadrature_rule not in QUADRATURE_RULES:
+            raise ValueError(f"Unknown quadrature rule {quadrature_rule} (available: {sorted(QUADRATURE_RULES)})")
+        q = QUADRATURE_RULES[quadrature_rule](img_shape[0], img_shape[1], normalize).unsqueeze(1).repeat(1, img_shape[1])
         if pole_mask:
             q[:pole_mask, :] = 0.0
             q[img_shape[0] - pole_mask:, :] = 0.0

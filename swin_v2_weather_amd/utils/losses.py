@@ -3,7 +3,19 @@
 The O(B*C*H*W) work -- the latitude-weighted sums of (prd - tar)^2 and tar^2 per (sample, channel) plane and the
 gradient d loss / d prd -- is two HIP kernels (swv2_loss_sums / swv2_loss_grad); the remaining arithmetic is on
 [B, C] tensors.  Supported: the 'l2' family used by every entry of config/swin.yaml ('l2', 'squared geometric l2',
-'weighted absolute|relative temp-std squared geometric l2').  l1 / geometric h1 are not selected by any config.
+'weighted absolute|relative temp-std squared geometric l2') and the 'l1' family (every string with the word l1 and
+without l2: losses.py:114-120 builds the same class with p = 1).
+
+l1: S0 = sum q[h] |prd - tar|, S1 = sum q[h] |tar| per plane, loss = sum_bc chw[c] (S0 or S0 / S1).  The reference never
+forwards `squared` for p = 1 and x ** (1 / 1) is the identity, so 'l1', 'geometric l1' and 'squared geometric l1' are one
+number; the word `squared` still squares the temp-std channel factor.  `geometric_l1_torch` is the readable definition
+(any device, any dtype, differentiable by autograd); on CUDA fp32 tensors with W % 4 == 0 value and gradient come from
+one autograd node over swv2_l1_sums / swv2_l1_finalize / swv2_l1_grad (csrc/loss_l1.hip), in training, validation and
+rollouts alike.  The head epilogue evaluates squared residuals, so `fused_with` is a no-op for l1.
+
+Quadrature: the 'naive' rule, or Gauss-Legendre rows (utils/grids.py) when model_grid_type is 'legendre_gauss' and the
+string contains `geometric` (losses.py:102-120), for l1 and l2 alike: the kernels take per-row weights.
+geometric h1 (a spherical-harmonics transform) and pole-masked (an undefined name in the reference) raise.
 """
 import math
 
@@ -14,7 +26,40 @@ import torch
 from torch import nn
 
 from .. import ops
-from .grids import naive_quadrature_weights
+from .grids import legendre_gauss_quadrature_weights, naive_quadrature_weights
+
+
+def geometric_l1_torch(prd, tar, quad_rows, chw, absolute):
+    """The geometric l1 loss in plain torch (losses.py:188-240 with p = 1): prd, tar [B, C, H, W], quad_rows [H] normalised row
+    weights, chw [C] (or [1, C]) channel weights -> sum_bc chw[c] S0[b, c] (absolute) or chw[c] S0[b, c] / S1[b, c], with
+    S0 = sum_hw q[h] |prd - tar| and S1 = sum_hw q[h] |tar|.  In the inputs' dtype, on their device."""
+    q = quad_rows.to(device=prd.device, dtype=prd.dtype).reshape(1, 1, -1, 1)
+    B = prd.shape[0]
+    norms = torch.sum(torch.abs(prd - tar) * q, dim=(-2, -1)).reshape(B, -1)
+    if not absolute:
+        norms = norms / torch.sum(torch.abs(tar) * q, dim=(-2, -1)).reshape(B, -1)
+    return torch.sum(chw.to(device=prd.device, dtype=prd.dtype).reshape(1, -1) * norms)
+
+
+class _GeoL1(torch.autograd.Function):
+    """The l1 LossHandler value as one node: l1_sums (one pass over prd / tar), l1_finalize (the slices, the [B, C] arithmetic and
+    the backward coefficients), and in backward one l1_grad pass.  `ws`: the caller's workspace for this shape."""
+
+    @staticmethod
+    def forward(ctx, prd, tar, qw, chw, absolute, ws):
+        prd, tar = prd.contiguous(), tar.contiguous()
+        B, C, H, W = prd.shape
+        ops.l1_sums(prd, tar, qw, ws)
+        _, loss, coef = ops.l1_finalize(ws, B, C, H, W, chw, absolute)
+        ctx.save_for_backward(prd, tar, qw, coef)
+        return loss.view(())
+
+    @staticmethod
+    def backward(ctx, gout):
+        prd, tar, qw, coef = ctx.saved_tensors
+        dprd = torch.empty_like(prd)
+        ops.l1_grad(prd, tar, qw, (coef * gout).contiguous(), dprd)
+        return dprd, None, None, None, None, None
 
 
 class _QuadSums(torch.autograd.Function):
@@ -181,8 +226,12 @@ class LossHandler(nn.Module):
         flags = set(params.loss.split())
         if 'pole-masked' in flags:
             raise ValueError("pole-masked losses hit an undefined name in the reference (grids.py:97-99)")
-        if 'l2' not in flags:
-            raise ValueError(f"Unknown / unsupported loss function: {self.loss_type} (l2 family only)")
+        if 'l2' in flags:                      # l2 wins when both words occur, as the reference's if / elif (losses.py:107-120)
+            self.p = 2
+        elif 'l1' in flags:
+            self.p = 1
+        else:
+            raise ValueError(f"Unknown / unsupported loss function: {self.loss_type} (l2 and l1 families only)")
         if 'weighted' in flags:
             if params.channel_weights == 'auto':
                 cw = auto_channel_weights(params.channel_names, params.n_out_channels)
@@ -206,9 +255,12 @@ class LossHandler(nn.Module):
                 tvw = tvw ** 2
             cw = cw * tvw
         self.register_buffer('channel_weights', cw.float())
-        if getattr(params, 'model_grid_type', 'equiangular') == 'legendre_gauss':
-            raise ValueError("legendre-gauss quadrature needs torch_harmonics (not used by config/swin.yaml)")
-        self.register_buffer('quad_rows', naive_quadrature_weights(self.img_shape[0], self.img_shape[1], True).contiguous())
+        # the non-geometric strings never forward the rule (losses.py:112-113, 119-120): naive rows whatever the grid
+        rule = naive_quadrature_weights
+        if getattr(params, 'model_grid_type', 'equiangular') == 'legendre_gauss' and 'geometric' in flags:
+            rule = legendre_gauss_quadrature_weights
+        self.register_buffer('quad_rows', rule(self.img_shape[0], self.img_shape[1], True).contiguous())
+        self._l1_ws = {}                       # (device, B, C) -> the l1 kernels' workspace of that shape, made once and reused
         ms = torch.ones(self.n_future + 1, dtype=torch.float32) / float(self.n_future + 1)
         self.register_buffer('multistep_weight', ms.reshape(-1, 1, 1, 1))
 
@@ -224,7 +276,8 @@ class LossHandler(nn.Module):
 
         @contextlib.contextmanager
         def cm():
-            net = _core_net(model) if (self.training and os.environ.get("SWV2_LOSS_IN_HEAD", "1") != "0") else None
+            # (l1: the head epilogue evaluates squared residuals -- no hand-over, the two-pass l1 kernels run)
+            net = _core_net(model) if (self.p == 2 and self.training and os.environ.get("SWV2_LOSS_IN_HEAD", "1") != "0") else None
             # (rollouts: every step's head takes its channel block of the target; SWV2_LOSS_IN_HEAD_ROLLOUT=0 keeps the two-pass kernels)
             if net is None or (self.n_future != 0 and os.environ.get("SWV2_LOSS_IN_HEAD_ROLLOUT", "1") == "0"):
                 yield
@@ -237,8 +290,31 @@ class LossHandler(nn.Module):
                 net._loss_ctx = None
         return cm()
 
+    def _chw_now(self):
+        """[1, C (n_future + 1)] in training (the multistep weight per step), [1, C] in eval (losses.py:145-148)"""
+        chw = self.channel_weights
+        if self.training:
+            return (chw * self.multistep_weight).reshape(1, -1)
+        return chw.reshape(1, -1)
+
+    def _forward_l1(self, prd, tar):
+        chw = self._chw_now()
+        on_kernels = (prd.is_cuda and tar.is_cuda and prd.device == tar.device == self.quad_rows.device and
+                      prd.dtype == tar.dtype == torch.float32 and prd.dim() == 4 and prd.shape == tar.shape and
+                      not tar.requires_grad and prd.shape[3] % 4 == 0 and prd.shape[2] == self.quad_rows.numel() and
+                      chw.numel() == prd.shape[1] and prd.shape[0] * prd.shape[1] <= 65535 and prd.shape[2] * prd.shape[3] < 2 ** 30)
+        if not on_kernels:
+            return geometric_l1_torch(prd, tar, self.quad_rows, chw, self.absolute)
+        B, C, H, W = prd.shape
+        key = (prd.device, B, C)
+        if key not in self._l1_ws:
+            self._l1_ws[key] = ops.l1_workspace(B * C, H, W, prd.device)
+        return _GeoL1.apply(prd, tar, self.quad_rows, chw.reshape(-1).contiguous().float(), self.absolute, self._l1_ws[key])
+
     def forward(self, prd: torch.Tensor, tar: torch.Tensor, inp: torch.Tensor = None):
         lc, self._fused = self._fused, None
+        if self.p == 1:
+            return self._forward_l1(prd, tar)
         rsums = None
         if lc is not None and lc.steps and lc.tar is tar and self.training and prd.dtype == torch.float32:
             rsums = lc.rollout_sums(prd, prd.shape[1] // (self.n_future + 1))
@@ -250,11 +326,7 @@ class LossHandler(nn.Module):
                 self._chw_flat = (self.channel_weights * self.multistep_weight).reshape(-1).contiguous().float()
                 self._chw_key = key
             return _FusedGeoL2.apply(lc.sums if rsums is None else rsums, self._chw_flat, self.absolute, self.squared)
-        chw = self.channel_weights
-        if self.training:
-            chw = (chw * self.multistep_weight).reshape(1, -1)
-        else:
-            chw = chw.reshape(1, -1)
+        chw = self._chw_now()
         if prd.is_cuda and prd.requires_grad and not tar.requires_grad and os.environ.get("SWV2_LOSS_FUSED", "1") != "0":
             return _GeoL2.apply(prd, tar, self.quad_rows, chw.reshape(-1).contiguous().float(), self.absolute, self.squared)
         sums = _QuadSums.apply(prd, tar, self.quad_rows)

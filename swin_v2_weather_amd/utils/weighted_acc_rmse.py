@@ -203,6 +203,7 @@ def load_climatology(params, means=None, stds=None):
 
 
 Scores = namedtuple("Scores", "rmse acc rmse_mean acc_mean sums")
+MaeScores = namedtuple("MaeScores", "mae mae_mean sums")
 EnsembleScores = namedtuple("EnsembleScores", "sums hist ens_rmse spread crps fair_crps ens_rmse_mean spread_mean crps_mean fair_crps_mean")
 
 
@@ -263,6 +264,27 @@ class ForecastScorer:
         if self.clim is None:
             acc = acc_mean = None
         return Scores(rmse, acc, rmse_mean, acc_mean, sums)
+
+    def mae(self, prd, tar, coff_prd=0, coff_tar=0) -> MaeScores:
+        """latitude-weighted mean absolute error of channels coff_prd .. + C of prd against channels coff_tar .. + C of tar (read in
+        place) -> MaeScores(mae [B, C] = S0 / (H W), mae_mean [C] = mean_b mae (x stds), sums [B, C, 2] = (S0, S1)) with
+        S0 = sum w[h] |prd - tar|, S1 = sum w[h] |tar|.  One pass of swv2_l1_sums (csrc/loss_l1.hip) on CUDA, plain torch elsewhere."""
+        p, t = self._blocks("mae", prd, tar, coff_prd, coff_tar)
+        n = float(self.H * self.W)
+        if _on_kernels(p, t) and p.device == self.device:
+            from .. import ops
+            B = p.shape[0]
+            ws = self._workspace(("l1", B), ops.l1_workspace, B * self.C, self.H, self.W)
+            ops.l1_sums(p, t, self.w, ws)
+            sums = ops.l1_finalize(ws, B, self.C, self.H, self.W)[0]
+        else:
+            w = self.w.to(device=p.device, dtype=p.dtype).reshape(1, 1, -1, 1)
+            sums = torch.stack((torch.sum(w * torch.abs(p - t), dim=(-1, -2)), torch.sum(w * torch.abs(t), dim=(-1, -2))), dim=-1)
+        mae = sums[..., 0] / n
+        mae_mean = mae.mean(dim=0)
+        if self.scale is not None:
+            mae_mean = mae_mean * self.scale.to(device=p.device, dtype=p.dtype)
+        return MaeScores(mae, mae_mean, sums)
 
     def quantile_error(self, prd, tar, coff_prd=0, coff_tar=0) -> torch.Tensor:
         """top_quantiles_error_torch of channels coff_prd .. + C of prd against channels coff_tar .. + C of tar (read in place) -> [B, C].
