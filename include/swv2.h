@@ -36,7 +36,7 @@ extern "C" {
  * swv2_attn_bwd_kernel (+ swv2_attn_kernel_t, SWV2_ATTN_K_*); 111: the LAMB optimizer, swv2_lamb_* (+ swv2_lamb_item, SWV2_LAMB_*);
  * 112: forecast scores, swv2_score_*.  The dataset statistics, swv2_stats_*, came later and are purely additive (new entry points only,
  * no struct member moves): the revision stays 112.  So are the plane order statistics, swv2_quantile_ws_bytes / swv2_plane_order_stats,
- * and the ensemble scores, swv2_ens_*, and the l1 loss family, swv2_l1_*. */
+ * and the ensemble scores, swv2_ens_*, and the l1 loss family, swv2_l1_*, and the spherical-harmonic degree spectra, swv2_sht_*. */
 #define SWV2_VERSION 112
 
 enum {
@@ -606,6 +606,29 @@ int swv2_l1_sums(const float* prd, long prd_bstride, const float* tar, long tar_
 int swv2_l1_finalize(const void* ws, size_t ws_bytes, int B, int C, int H, int W, const float* chw, int absolute, float* sums, float* loss,
                      float* coef, void* stream);
 int swv2_l1_grad(const float* prd, const float* tar, const float* quad_w, const float* coef, float* dprd, int BC, int H, int W, void* stream);
+
+/* Spherical-harmonic degree spectra (csrc/sht.hip; the RealSHT + |c|^2 sums of reference utils/losses.py:272-307): the Legendre stage of
+ * the transform and the degree power  P[plane][l] = sum_m w_m |c[m][l][plane]|^2,  w_0 = 1, else 2.  All tensors fp32.
+ *   table   [mmax][lmax][nlat]      quadrature-weighted orthonormal associated Legendre functions; rows l < m are never read
+ *   X, dX   [mmax][2 planes][nlat]  the longitude transform of the planes, column n = 2 plane + (0: real part, 1: imaginary part)
+ *   coeffs  [mmax][2 planes][lmax]  c[m][n][l] = sum_k table[m][l][k] X[m][n][k]; ONLY l >= m is written (and read by the adjoint)
+ *   power   [planes][lmax]          gpower: the gradient with respect to it, same shape
+ * swv2_sht_power: the products on the f32-input MFMA (fp32 accumulation, the k-ordered fma chain), skipping whole 32-row blocks of l
+ * below m; per-run partial sums in ws (swv2_sht_ws_bytes), folded by a second launch in ascending order -- no atomics, nothing to zero
+ * beforehand, two runs agree bit for bit.  coeffs may be NULL (nothing kept; the forward then writes power and ws only).
+ * swv2_sht_adjoint: dX[m][n][k] = sum_{l >= m} table[m][l][k] (2 w_m gpower[plane][l]) c[m][n][l]; every element of dX is written
+ * (zeros for m >= lmax).  Refused with SWV2_ERR_INVALID before any launch: a null pointer (coeffs of swv2_sht_power excepted), a
+ * non-positive size, planes > 2^20, nlat or lmax > 2^15, mmax > 65535, a workspace smaller than swv2_sht_ws_bytes.  No alignment is
+ * asked of any pointer beyond that of a float.  swv2_sht_ws_bytes is host-only and returns 0 for a non-positive argument.
+ * swv2_sht_repack: the transposing copy between the layout torch.fft.rfft leaves, F [planes][nlat][mmax][2] (re, im innermost), and the
+ * operand layout: X[m][2 p + ri][k] = scale F[p][k][m][ri], or with backward != 0 dst[p][k][m][ri] = scale src[m][2 p + ri][k] (the same
+ * map read the other way: the gradient's way back).  Every element of dst is written.  planes <= 65535. */
+size_t swv2_sht_ws_bytes(int planes, int lmax, int mmax);       /* ceil(min(mmax, lmax) / 8) * planes * lmax * 4 */
+int swv2_sht_power(const float* table, const float* X, float* power, float* coeffs, int planes, int nlat, int lmax, int mmax, void* ws,
+                   size_t ws_bytes, void* stream);
+int swv2_sht_adjoint(const float* table, const float* coeffs, const float* gpower, float* dX, int planes, int nlat, int lmax, int mmax,
+                     void* stream);
+int swv2_sht_repack(const float* src, float* dst, int planes, int nlat, int mmax, float scale, int backward, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * ERA5 input assembly (the step BEFORE the model): raw time slabs staged on the device by async H2D copies

@@ -13,7 +13,7 @@ import threading
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB_PATH = os.environ.get("SWV2_LIB") or os.path.join(HERE, "libswv2.so")     # SWV2_LIB: a privately built variant (tools/ab_macro.sh)
-SOURCES = ["capi.hip", "attn.hip", "attn2.hip", "attn_bwd_stream.hip", "attn_wide.hip", "attn_d256.hip", "gemm.hip", "gemm_tn.hip", "gemm_tn_slab.hip", "rowops.hip", "lamb.hip", "block.hip", "cpb.hip", "mlp.hip", "proj_ln.hip", "dataio.hip", "score.hip", "stats.hip", "quantile.hip", "ensemble.hip", "loss_l1.hip"]
+SOURCES = ["capi.hip", "attn.hip", "attn2.hip", "attn_bwd_stream.hip", "attn_wide.hip", "attn_d256.hip", "gemm.hip", "gemm_tn.hip", "gemm_tn_slab.hip", "rowops.hip", "lamb.hip", "block.hip", "cpb.hip", "mlp.hip", "proj_ln.hip", "dataio.hip", "score.hip", "stats.hip", "quantile.hip", "ensemble.hip", "loss_l1.hip", "sht.hip"]
 
 ABI_VERSION = 112          # SWV2_VERSION of the include/swv2.h these ctypes mirrors were written against (checked in load())
 
@@ -152,6 +152,7 @@ ATTN_FIRST_GEN, ATTN_PLAIN_STATS, ATTN_BWD_TWO_PHASE = 16, 8192, 32      # swv2_
 LOSS_PART_SLICES = 8          # SWV2_LOSS_PART_SLICES
 LOSS_GROUP_ROWS = 32          # SWV2_LOSS_GROUP_ROWS
 LOSS_DUMP_BYTES = 2048        # SWV2_LOSS_DUMP_BYTES
+SHT_MRUN = 8                  # adjacent m per forward workgroup of swv2_sht_power (csrc/sht.hip); sizes swv2_sht_ws_bytes
 
 
 def loss_resid_pitch(n: int) -> int:
@@ -279,6 +280,10 @@ SYMBOLS = {
     "swv2_l1_sums": (_I, [_P, _L, _P, _L, _P, _I, _I, _I, _I, _P, C.c_size_t, _P]),
     "swv2_l1_finalize": (_I, [_P, C.c_size_t, _I, _I, _I, _I, _P, _I, _P, _P, _P, _P]),
     "swv2_l1_grad": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _P]),
+    "swv2_sht_ws_bytes": (C.c_size_t, [_I, _I, _I]),
+    "swv2_sht_power": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P, C.c_size_t, _P]),
+    "swv2_sht_adjoint": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P]),
+    "swv2_sht_repack": (_I, [_P, _P, _I, _I, _I, _F, _I, _P]),
     "swv2_era5_select_normalize": (_I, [_P, _P, _P, _P, _P] + [_I] * 10 + [_P]),
     "swv2_era5_zenith": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P]),
     "swv2_era5_static": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P]),

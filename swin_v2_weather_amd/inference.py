@@ -13,7 +13,8 @@ prediction fed back, next cos-zenith channel and the invariant channels re-appen
 
 `score_rollout` is the same loop with every step scored against the verifying analysis as soon as it is written
 (utils/weighted_acc_rmse.ForecastScorer: latitude-weighted RMSE and ACC per channel and lead time, one pass per step; with
-extremes=True also the top-quantile error, ForecastScorer.quantile_error).
+extremes=True also the top-quantile error, ForecastScorer.quantile_error; with spectrum=True also the spherical-harmonic degree power
+of forecast and analysis, ForecastScorer.power_spectrum, and the small-scale power ratio that shows a rollout blurring).
 
 `ensemble_rollout` perturbs the initial condition (`perturb_initial_condition`: member 0 is the unperturbed control), rolls the M
 members out in the same loop and scores every step as an ensemble (ForecastScorer.ensemble_score: CRPS, fair CRPS, spread,
@@ -21,6 +22,7 @@ ensemble-mean RMSE and the rank histogram per channel and lead time, one pass ov
 
     python -m swin_v2_weather_amd.inference --registry DIR --steps 8 [--init x0.npy] [--out forecast.npy]
                                             [--truth truth.npy [--climatology time_means.npy] [--scores-out scores.json] [--extremes]
+                                             [--spectrum] [--spectrum-out spectrum.npz]
                                              [--ensemble M --perturbation A [--seed S] [--member-batch K]]]
 """
 from __future__ import annotations
@@ -36,7 +38,7 @@ import torch
 
 from .networks.helpers import get_model
 from .utils.YParams import load_yaml
-from .utils.weighted_acc_rmse import ForecastScorer, load_climatology, spread_skill_ratio
+from .utils.weighted_acc_rmse import ForecastScorer, load_climatology, small_scale_power_ratio, spread_skill_ratio
 
 
 class _Params(dict):
@@ -122,19 +124,33 @@ def rollout(model, x0: torch.Tensor, n_steps: int, coszen: torch.Tensor | None =
     return out.view(B, n_steps, Cout, H, W)
 
 
-RolloutScores = namedtuple("RolloutScores", "rmse acc rmse_samples acc_samples forecast tqe", defaults=(None,))
+# degree power of forecast and analysis per lead time (batch means [n_steps, Cout, lmax]) and small_scale_power_ratio [n_steps, B, Cout]
+RolloutSpectrum = namedtuple("RolloutSpectrum", "pred truth ratio")
+
+
+class RolloutScores(namedtuple("RolloutScores", "rmse acc rmse_samples acc_samples forecast tqe", defaults=(None,))):
+    """score_rollout's answer.  The tuple keeps its six fields (callers unpack and build it positionally); `spectrum` rides along as an
+    attribute: None, or the RolloutSpectrum of score_rollout(..., spectrum=True).  (_replace builds a new tuple: carry it over by hand.)"""
+    spectrum = None
+
+    def with_spectrum(self, spectrum):
+        self.spectrum = spectrum
+        return self
 
 
 @torch.no_grad()
 def score_rollout(model, x0: torch.Tensor, truth, n_steps: int, coszen: torch.Tensor | None = None, n_invar: int = 0,
-                  scorer: ForecastScorer | None = None, keep_forecast: bool = False, extremes: bool = False) -> RolloutScores:
+                  scorer: ForecastScorer | None = None, keep_forecast: bool = False, extremes: bool = False,
+                  spectrum: bool = False) -> RolloutScores:
     """`rollout` with every step's prediction scored against truth[:, s] as soon as it is written.  truth: [B, n_steps, Cout, H, W]
     (normalised as the model's output) or a callable s -> [B, Cout, H, W].  scorer: a ForecastScorer (default: no climatology, so
     no ACC; normalised units).  Unless keep_forecast, the predictions live in a two-slot ring [B, 2 Cout, H, W]: memory does not grow
     with n_steps.  -> RolloutScores(rmse [n_steps, Cout] and acc [n_steps, Cout] | None: batch means (rmse x the scorer's stds);
     rmse_samples, acc_samples [n_steps, B, Cout]; forecast [B, n_steps, Cout, H, W] | None;
     tqe [n_steps, B, Cout] | None).  extremes: every step's prediction also goes through scorer.quantile_error against that step's truth
-    (the top-quantile error, tqe).  The predictions are `rollout`'s, bit for bit."""
+    (the top-quantile error, tqe).  spectrum: every step's prediction and truth also go through scorer.power_spectrum ->
+    spectrum = RolloutSpectrum(pred, truth [n_steps, Cout, lmax = H]: batch-mean degree power in the scorer's normalised units; ratio
+    [n_steps, B, Cout]: small_scale_power_ratio per sample), else None.  The predictions are `rollout`'s, bit for bit."""
     net = model.model if hasattr(model, "model") else model
     B, _, H, W = x0.shape
     Cout = net.out_chans
@@ -147,15 +163,22 @@ def score_rollout(model, x0: torch.Tensor, truth, n_steps: int, coszen: torch.Te
     rmse_s = torch.empty(n_steps, B, Cout, dtype=torch.float32, device=x0.device)
     acc, acc_s = (torch.empty_like(rmse), torch.empty_like(rmse_s)) if scorer.clim is not None else (None, None)
     tqe = torch.empty_like(rmse_s) if extremes else None
+    spec = None
+    if spectrum:
+        spec = RolloutSpectrum(torch.empty(n_steps, Cout, H, dtype=torch.float32, device=x0.device),
+                               torch.empty(n_steps, Cout, H, dtype=torch.float32, device=x0.device), torch.empty_like(rmse_s))
     for s in _rollout_steps(net, x0, n_steps, coszen, n_invar, out, coff_of):
         tar = (truth(s) if callable(truth) else truth[:, s]).to(x0.device)
         r = scorer.score(out, tar, coff_prd=coff_of(s))
         if extremes:
             tqe[s] = scorer.quantile_error(out, tar, coff_prd=coff_of(s))
+        if spectrum:
+            ps = scorer.power_spectrum(out, tar, coff_prd=coff_of(s))
+            spec.pred[s], spec.truth[s], spec.ratio[s] = ps.pred.mean(dim=0), ps.truth.mean(dim=0), small_scale_power_ratio(ps.pred, ps.truth)
         rmse[s], rmse_s[s] = r.rmse_mean, r.rmse
         if acc is not None:
             acc[s], acc_s[s] = r.acc_mean, r.acc
-    return RolloutScores(rmse, acc, rmse_s, acc_s, out.view(B, n_steps, Cout, H, W) if keep_forecast else None, tqe)
+    return RolloutScores(rmse, acc, rmse_s, acc_s, out.view(B, n_steps, Cout, H, W) if keep_forecast else None, tqe).with_spectrum(spec)
 
 
 def perturb_initial_condition(x0: torch.Tensor, n_members: int, amplitude: float, seed: int, n_fields: int) -> torch.Tensor:
@@ -240,18 +263,20 @@ def ensemble_rollout(model, x0: torch.Tensor, truth, n_steps: int, n_members: in
 
 
 def lead_time_table(scores: RolloutScores, names, hours_per_step: float = 6.0, ensemble: EnsembleRolloutScores | None = None) -> str:
-    """one line per lead time: RMSE (and ACC, and the batch-mean top-quantile error when scored) of the named channels;
+    """one line per lead time: RMSE (and ACC, and the batch-mean top-quantile error and small-scale power ratio when scored) of the named channels;
     names: [(column title, channel index)].  ensemble: the crps_, spread_ and ens_rmse_ columns of an ensemble_rollout follow."""
     rm, ac = scores.rmse.cpu().numpy(), None if scores.acc is None else scores.acc.cpu().numpy()
     tq = None if scores.tqe is None else scores.tqe.mean(dim=1).cpu().numpy()
+    sr = None if scores.spectrum is None else scores.spectrum.ratio.mean(dim=1).cpu().numpy()
     cols = [f"rmse_{n}" for n, _ in names] + ([f"acc_{n}" for n, _ in names] if ac is not None else []) + \
-        ([f"tqe_{n}" for n, _ in names] if tq is not None else [])
+        ([f"tqe_{n}" for n, _ in names] if tq is not None else []) + ([f"ssr_{n}" for n, _ in names] if sr is not None else [])
     ens = [] if ensemble is None else [(k, getattr(ensemble, k).cpu().numpy()) for k in ("crps", "spread", "ens_rmse")]
     cols += [f"{k}_{n}" for k, _ in ens for n, _ in names]
     lines = ["lead_h " + " ".join(f"{c:>12s}" for c in cols)]
     for s in range(rm.shape[0]):
         vals = [rm[s, i] for _, i in names] + ([ac[s, i] for _, i in names] if ac is not None else []) + \
-            ([tq[s, i] for _, i in names] if tq is not None else []) + [v[s, i] for _, v in ens for _, i in names]
+            ([tq[s, i] for _, i in names] if tq is not None else []) + ([sr[s, i] for _, i in names] if sr is not None else []) + \
+            [v[s, i] for _, v in ens for _, i in names]
         lines.append(f"{hours_per_step * (s + 1):6.0f} " + " ".join(f"{v:12.5f}" for v in vals))
     return "\n".join(lines)
 
@@ -261,6 +286,8 @@ class _Parser(argparse.ArgumentParser):
 
     def parse_args(self, args=None, namespace=None):
         a = super().parse_args(args, namespace)
+        if a.spectrum_out and not a.spectrum:
+            self.error("--spectrum-out needs --spectrum")
         if a.ensemble is None:
             for flag, v in (("--perturbation", a.perturbation), ("--seed", a.seed), ("--member-batch", a.member_batch)):
                 if v is not None:
@@ -272,6 +299,8 @@ class _Parser(argparse.ArgumentParser):
             self.error("--ensemble keeps no forecast: it cannot be combined with --out")
         if a.extremes:
             self.error("--extremes is scored for a single forecast: run it without --ensemble")
+        if a.spectrum:
+            self.error("--spectrum is scored for a single forecast: run it without --ensemble")
         if not 2 <= a.ensemble <= 64:
             self.error("--ensemble: 2 .. 64 members")
         if a.perturbation is None:
@@ -293,6 +322,10 @@ def build_parser() -> argparse.ArgumentParser:
                                                         "else the hyper-parameters' time_means_path)")
     ap.add_argument("--scores-out", default=None, help="write the lead-time scores as JSON")
     ap.add_argument("--extremes", action="store_true", help="with --truth: also score the top-quantile error (tqe_<name> columns, \"tqe\" key)")
+    ap.add_argument("--spectrum", action="store_true", help="with --truth: also the spherical-harmonic degree power of forecast and analysis; "
+                                                            "ssr_<name> columns (small-scale power ratio), \"ssr\" key")
+    ap.add_argument("--spectrum-out", default=None, metavar="FILE.npz", help="with --spectrum: write the arrays degree [lmax], pred and truth "
+                                                                             "[steps, Cout, lmax] (batch-mean degree power)")
     ap.add_argument("--ensemble", type=int, default=None, metavar="M", help="with --truth: roll out M members from perturbed initial conditions "
                                                                             "(member 0 is the control) and score CRPS, spread and ensemble-mean RMSE "
                                                                             "(crps_/spread_/ens_rmse_<name> columns, \"ensemble\" key)")
@@ -346,7 +379,7 @@ def _score_main(a, model, p, stats, x0, cz, n_invar):
                                member_batch=a.member_batch, n_fields=len(p["in_channels"]), score_control=True)
         sc = ens.control
     else:
-        sc = score_rollout(model, x0, truth_of, a.steps, cz, n_invar, scorer, keep_forecast=bool(a.out), extremes=a.extremes)
+        sc = score_rollout(model, x0, truth_of, a.steps, cz, n_invar, scorer, keep_forecast=bool(a.out), extremes=a.extremes, spectrum=a.spectrum)
     if "track_channels" in p and "channel_names" in p:
         names = [(v, list(p["channel_names"]).index(v)) for v in p["track_channels"]]
     else:
@@ -358,12 +391,16 @@ def _score_main(a, model, p, stats, x0, cz, n_invar):
                "acc": None if sc.acc is None else sc.acc.cpu().tolist(), "tracked": dict(names)}
         if sc.tqe is not None:
             doc["tqe"] = sc.tqe.mean(dim=1).cpu().tolist()
+        if sc.spectrum is not None:
+            doc["ssr"] = sc.spectrum.ratio.mean(dim=1).cpu().tolist()
         if ens is not None:
             doc["ensemble"] = {"members": a.ensemble, "crps": ens.crps.cpu().tolist(), "fair_crps": ens.fair_crps.cpu().tolist(),
                                "spread": ens.spread.cpu().tolist(), "ens_rmse": ens.ens_rmse.cpu().tolist(),
                                "spread_skill": spread_skill_ratio(ens.spread, ens.ens_rmse, a.ensemble).cpu().tolist()}
         with open(a.scores_out, "w") as f:
             json.dump(doc, f)
+    if a.spectrum_out:
+        np.savez(a.spectrum_out, degree=np.arange(H), pred=sc.spectrum.pred.cpu().numpy(), truth=sc.spectrum.truth.cpu().numpy())
     if a.out:
         np.save(a.out, sc.forecast.cpu().numpy())
 

@@ -523,6 +523,49 @@ def l1_grad(prd, tar, qw, coef, dprd):
     L.check(L.load().swv2_l1_grad(_p(prd), _p(tar), _p(qw), _p(coef), _p(dprd), B * Cc, H, W, _stream()), "swv2_l1_grad")
 
 
+def sht_power(table, X, keep_coeffs: bool = False):
+    """degree power [planes, lmax] of the spectral operand X [mmax, 2 planes, nlat] under table [mmax, lmax, nlat] (swv2_sht_power);
+    with keep_coeffs also the coefficients [mmax, 2 planes, lmax] (l >= m written) for sht_adjoint, else None"""
+    _chk(table, torch.float32, "sht table"); _chk(X, torch.float32, "sht operand")
+    if table.dim() != 3 or X.dim() != 3 or X.shape[0] != table.shape[0] or X.shape[2] != table.shape[2] or X.shape[1] % 2:
+        raise L.Swv2Error(f"sht_power: table {tuple(table.shape)} [mmax, lmax, nlat] against operand {tuple(X.shape)} [mmax, 2 planes, nlat]")
+    mmax, lmax, nlat = table.shape
+    planes = X.shape[1] // 2
+    lib = L.load()
+    nb = lib.swv2_sht_ws_bytes(planes, lmax, mmax)
+    ws = _scratch(nb, X.device, "sht_power")
+    power = torch.empty(planes, lmax, dtype=torch.float32, device=X.device)
+    coef = torch.empty(mmax, 2 * planes, lmax, dtype=torch.float32, device=X.device) if keep_coeffs else None
+    L.check(_timed("sht_power", lib.swv2_sht_power, _p(table), _p(X), _p(power), _p(coef), planes, nlat, lmax, mmax, _p(ws), nb, _stream()),
+            "swv2_sht_power")
+    return power, coef
+
+
+def sht_repack(src, planes: int, nlat: int, mmax: int, scale: float, backward: bool = False):
+    """rfft's layout F [planes, nlat, mmax, 2] -> the operand X [mmax, 2 planes, nlat] times scale; backward: the same map from X to F"""
+    _chk(src, torch.float32, "sht repack source")
+    if src.numel() != planes * nlat * mmax * 2:
+        raise L.Swv2Error(f"sht_repack: {src.numel()} elements for planes {planes}, nlat {nlat}, mmax {mmax}")
+    dst = torch.empty((planes, nlat, mmax, 2) if backward else (mmax, 2 * planes, nlat), dtype=torch.float32, device=src.device)
+    L.check(_timed("sht_repack", L.load().swv2_sht_repack, _p(src), _p(dst), planes, nlat, mmax, float(scale), int(backward), _stream()),
+            "swv2_sht_repack")
+    return dst
+
+
+def sht_adjoint(table, coef, gpower):
+    """dX [mmax, 2 planes, nlat]: the gradient of sht_power's operand from gpower [planes, lmax] and the kept coefficients"""
+    for t, what in ((table, "sht table"), (coef, "sht coefficients"), (gpower, "power gradient")):
+        _chk(t, torch.float32, what)
+    mmax, lmax, nlat = table.shape
+    planes = coef.shape[1] // 2
+    if tuple(coef.shape) != (mmax, 2 * planes, lmax) or tuple(gpower.shape) != (planes, lmax):
+        raise L.Swv2Error(f"sht_adjoint: table {tuple(table.shape)}, coefficients {tuple(coef.shape)}, gradient {tuple(gpower.shape)}")
+    dX = torch.empty(mmax, 2 * planes, nlat, dtype=torch.float32, device=coef.device)
+    L.check(_timed("sht_adjoint", L.load().swv2_sht_adjoint, _p(table), _p(coef), _p(gpower), _p(dX), planes, nlat, lmax, mmax, _stream()),
+            "swv2_sht_adjoint")
+    return dX
+
+
 ENS_MAX_MEMBERS = 64          # the M cap of swv2_ens_sums
 
 

@@ -15,7 +15,8 @@ rollouts alike.  The head epilogue evaluates squared residuals, so `fused_with` 
 
 Quadrature: the 'naive' rule, or Gauss-Legendre rows (utils/grids.py) when model_grid_type is 'legendre_gauss' and the
 string contains `geometric` (losses.py:102-120), for l1 and l2 alike: the kernels take per-row weights.
-geometric h1 (a spherical-harmonics transform) and pole-masked (an undefined name in the reference) raise.
+pole-masked (an undefined name in the reference) raises, and so do the geometric h1 strings of LossHandler; the class behind them,
+GeometricH1Loss, is here on its own (utils/sht.py, csrc/sht.hip).
 """
 import math
 
@@ -39,6 +40,62 @@ def geometric_l1_torch(prd, tar, quad_rows, chw, absolute):
     if not absolute:
         norms = norms / torch.sum(torch.abs(tar) * q, dim=(-2, -1)).reshape(B, -1)
     return torch.sum(chw.to(device=prd.device, dtype=prd.dtype).reshape(1, -1) * norms)
+
+
+class GeometricH1Loss(nn.Module):
+    """The weighted H1 loss on the sphere (reference utils/losses.py:244-338): with P[b, c, l] the degree power of prd - tar
+    (utils/sht.py::degree_power; HIP kernels on contiguous fp32 CUDA tensors), per sample
+
+        l2 = sum_{c, l} P          h1 = sum_{c, l} l (l + 1) P
+        norm = alpha sqrt(l2) + (1 - alpha) sqrt(h1)        (squared: alpha l2 + (1 - alpha) h1)
+
+    absolute: the norms [B]; relative: divided by the same norm of tar, then times `mask` when one is given.  reduction sums (or, with
+    size_average, averages: the mean, or sum / sum(mask) in the relative form with a mask) over what is left; reduction=False returns
+    it.  `p` is accepted and unused, and the absolute form ignores `mask`, both as in the reference.  Everything after the degree
+    power is torch on [B, C, lmax]; `retval * mask` broadcasts or fails exactly as torch does for the reference.
+
+    LossHandler does not build this class: its 'geometric h1' strings raise.  The reference's dispatch hands the channel weights
+    [1, C] to `mask`, and the relative form then multiplies [B] by [1, C], which torch rejects unless B is 1 or C (and mis-weights when
+    it does not reject).  The transform is pinned by its definition, not compared with torch_harmonics (utils/sht.py)."""
+
+    def __init__(self, img_shape, p=2., size_average=False, reduction=True, absolute=False, squared=False, alpha=0.5):
+        super().__init__()
+        self.img_shape = tuple(img_shape)
+        self.reduction, self.size_average, self.absolute, self.squared, self.alpha = reduction, size_average, absolute, squared, alpha
+        h1_weights = torch.arange(self.img_shape[0]).float()                  # lmax = nlat
+        self.register_buffer("h1_weights", h1_weights * (h1_weights + 1))
+
+    def _norms(self, field):
+        from .sht import degree_power
+        if tuple(field.shape[-2:]) != self.img_shape:
+            raise ValueError(f"GeometricH1Loss for a {self.img_shape} grid got a field of {tuple(field.shape[-2:])}")
+        num_examples = field.size()[0]
+        norm2 = degree_power(field)
+        l2_norm2 = norm2.reshape(num_examples, -1).sum(dim=-1)
+        h1_norm2 = (norm2 * self.h1_weights.to(norm2.dtype)).reshape(num_examples, -1).sum(dim=-1)
+        if not self.squared:
+            return self.alpha * torch.sqrt(l2_norm2) + (1 - self.alpha) * torch.sqrt(h1_norm2)
+        return self.alpha * l2_norm2 + (1 - self.alpha) * h1_norm2
+
+    def abs(self, prd, tar):
+        all_norms = self._norms(prd - tar)
+        if self.reduction:
+            return torch.mean(all_norms) if self.size_average else torch.sum(all_norms)
+        return all_norms
+
+    def rel(self, prd, tar, mask=None):
+        retval = self._norms(prd - tar) / self._norms(tar)
+        if mask is not None:
+            retval = retval * mask
+        if self.reduction:
+            if self.size_average:
+                retval = torch.mean(retval) if mask is None else torch.sum(retval) / torch.sum(mask)
+            else:
+                retval = torch.sum(retval)
+        return retval
+
+    def forward(self, prd, tar, mask=None):
+        return self.abs(prd, tar) if self.absolute else self.rel(prd, tar, mask)
 
 
 class _GeoL1(torch.autograd.Function):

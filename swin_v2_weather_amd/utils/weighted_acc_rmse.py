@@ -205,6 +205,15 @@ def load_climatology(params, means=None, stds=None):
 Scores = namedtuple("Scores", "rmse acc rmse_mean acc_mean sums")
 MaeScores = namedtuple("MaeScores", "mae mae_mean sums")
 EnsembleScores = namedtuple("EnsembleScores", "sums hist ens_rmse spread crps fair_crps ens_rmse_mean spread_mean crps_mean fair_crps_mean")
+PowerSpectrum = namedtuple("PowerSpectrum", "pred truth")
+
+
+def small_scale_power_ratio(pred: torch.Tensor, truth: torch.Tensor) -> torch.Tensor:
+    """degree power [..., lmax] x2 -> [...]: sum_{l >= lmax // 2} pred / sum_{l >= lmax // 2} truth, the share of the truth's power in the
+    upper half of the degrees that the forecast keeps.  This project's own scalar for the blurring of long rollouts (1: as sharp as the
+    analysis, below 1: blurred); the reference has no counterpart."""
+    lo = pred.shape[-1] // 2
+    return pred[..., lo:].sum(dim=-1) / truth[..., lo:].sum(dim=-1)
 
 
 class ForecastScorer:
@@ -285,6 +294,19 @@ class ForecastScorer:
         if self.scale is not None:
             mae_mean = mae_mean * self.scale.to(device=p.device, dtype=p.dtype)
         return MaeScores(mae, mae_mean, sums)
+
+    def power_spectrum(self, prd, tar=None, coff_prd=0, coff_tar=0) -> PowerSpectrum:
+        """spherical-harmonic degree power (utils/sht.py::degree_power: csrc/sht.hip on CUDA fp32) of channels coff_prd .. + C of prd and,
+        with tar, of channels coff_tar .. + C of tar, both read in place -> PowerSpectrum(pred [B, C, lmax = H], truth [B, C, lmax] | None),
+        in the scorer's normalised units (squared)"""
+        from .sht import degree_power
+        p = prd[:, coff_prd:coff_prd + self.C]
+        if p.shape[1:] != (self.C, self.H, self.W):
+            raise ValueError(f"power_spectrum: block {tuple(p.shape)}, expected [B, {self.C}, {self.H}, {self.W}]")
+        if tar is None:
+            return PowerSpectrum(degree_power(p), None)
+        p, t = self._blocks("power_spectrum", prd, tar, coff_prd, coff_tar)
+        return PowerSpectrum(degree_power(p), degree_power(t))
 
     def quantile_error(self, prd, tar, coff_prd=0, coff_tar=0) -> torch.Tensor:
         """top_quantiles_error_torch of channels coff_prd .. + C of prd against channels coff_tar .. + C of tar (read in place) -> [B, C].
