@@ -622,13 +622,24 @@ int swv2_l1_grad(const float* prd, const float* tar, const float* quad_w, const 
  * asked of any pointer beyond that of a float.  swv2_sht_ws_bytes is host-only and returns 0 for a non-positive argument.
  * swv2_sht_repack: the transposing copy between the layout torch.fft.rfft leaves, F [planes][nlat][mmax][2] (re, im innermost), and the
  * operand layout: X[m][2 p + ri][k] = scale F[p][k][m][ri], or with backward != 0 dst[p][k][m][ri] = scale src[m][2 p + ri][k] (the same
- * map read the other way: the gradient's way back).  Every element of dst is written.  planes <= 65535. */
+ * map read the other way: the gradient's way back).  Every element of dst is written.  planes <= 65535.
+ * swv2_sht_synth: the synthesis, from coefficients back to the longitude transform of a field, with a per-degree response,
+ *   S[m][n][k] = rweights[k] sum_{l = m}^{lmax - 1} table[m][l][k] (f_m h(n / 2, l)) coeffs[m][n][l]
+ *   f_m = scale_m0 for m = 0, else scale_m;  h(p, l) = response[p response_stride + l], or 1 if response is NULL
+ * rweights [nlat] is 1 / w_k of the quadrature weights the table carries (fp32), so rweights[k] table[m][l][k] is the Legendre function
+ * itself: the same product as swv2_sht_adjoint on the same table.  response_stride is 0 (one response [lmax] for all planes) or lmax
+ * ([planes][lmax]).  S has X's layout and every element is written: zeros for m >= lmax, and exact zeros in the imaginary rows (n odd) of
+ * m = 0 and, for an even nlon, of m = nlon / 2, whose coefficients are not read (an inverse real FFT ignores them).  Coefficients with
+ * l < m are never read.  No atomics: two runs agree bit for bit.  Refused like swv2_sht_adjoint, and also for a null rweights, another
+ * response_stride, nlon < 1. */
 size_t swv2_sht_ws_bytes(int planes, int lmax, int mmax);       /* ceil(min(mmax, lmax) / 8) * planes * lmax * 4 */
 int swv2_sht_power(const float* table, const float* X, float* power, float* coeffs, int planes, int nlat, int lmax, int mmax, void* ws,
                    size_t ws_bytes, void* stream);
 int swv2_sht_adjoint(const float* table, const float* coeffs, const float* gpower, float* dX, int planes, int nlat, int lmax, int mmax,
                      void* stream);
 int swv2_sht_repack(const float* src, float* dst, int planes, int nlat, int mmax, float scale, int backward, void* stream);
+int swv2_sht_synth(const float* table, const float* rweights, const float* coeffs, const float* response, int response_stride, float scale_m0,
+                   float scale_m, float* S, int planes, int nlat, int lmax, int mmax, int nlon, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * ERA5 input assembly (the step BEFORE the model): raw time slabs staged on the device by async H2D copies

@@ -284,6 +284,7 @@ SYMBOLS = {
     "swv2_sht_power": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P, C.c_size_t, _P]),
     "swv2_sht_adjoint": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P]),
     "swv2_sht_repack": (_I, [_P, _P, _I, _I, _I, _F, _I, _P]),
+    "swv2_sht_synth": (_I, [_P, _P, _P, _P, _I, _F, _F, _P, _I, _I, _I, _I, _I, _P]),
     "swv2_era5_select_normalize": (_I, [_P, _P, _P, _P, _P] + [_I] * 10 + [_P]),
     "swv2_era5_zenith": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P]),
     "swv2_era5_static": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P]),

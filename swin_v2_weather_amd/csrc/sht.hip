@@ -5,6 +5,8 @@
 //                                  partial[run][plane][l] = sum_{m in run} w_m (re^2 + im^2),  w_0 = 1, else 2
 //             sht_fold_kernel      power[plane][l] = sum_run partial[run][plane][l], runs in ascending order
 //   backward  sht_adjoint_kernel   dX[m][n][k] = sum_{l >= m} T[m][l][k] (2 w_m g[plane][l]) c[m][n][l]
+//   inverse   sht_synth_kernel     S[m][n][k] = (1 / w_k) sum_{l >= m} T[m][l][k] (f_m h[plane][l]) c[m][n][l]: the adjoint's product with
+//                                  another operand scale and the row weight taken out again in the epilogue (utils/sht.py: filter, noise)
 //   both      sht_repack_kernel    rfft's layout [plane][k][m][re, im] <-> the operand layout [m][n][k], times 2 pi
 //
 // Layouts.  T [mmax][lmax][nlat] dense (entries l < m are zero and never read); X and dX [mmax][2 planes][nlat]; the coefficients
@@ -49,6 +51,19 @@ struct GradScale {
     int lmax;
     float w2;
     __device__ __forceinline__ float operator()(float v, int n, int l) const { return (w2 * g[(size_t)(n >> 1) * lmax + l]) * v; }
+};
+
+// the synthesis' A operand: c[n][l] times f_m h[plane][l] (hs = 0: one response for all planes; without H: h = 1)
+template <bool H>
+struct SynthScale {
+    const float* h;          // [planes][lmax] or [lmax]
+    int hs;
+    float f;
+    bool real;               // this m's imaginary rows (n odd) count as zeros
+    __device__ __forceinline__ float operator()(float v, int n, int l) const {
+        const float s = H ? f * h[(size_t)(n >> 1) * hs + l] : f;          // (loaded under the caller's predicate only: the select comes last)
+        return real && (n & 1) ? 0.f : s * v;
+    }
 };
 
 // One operand stage, global -> registers: OUT x SHT_RT elements, element (o, r) at src[(o0 + o) * ld + r] (TR: contiguous along r) or
@@ -188,10 +203,10 @@ __global__ __launch_bounds__(256) void sht_fold_kernel(const float* __restrict__
     power[i] = s;
 }
 
-// grid (k tiles of 128, n tiles of 64, mmax)
-__global__ __launch_bounds__(256, 2) void sht_adjoint_kernel(const float* __restrict__ T, const float* __restrict__ coef, const float* __restrict__ g,
-                                                          float* __restrict__ dX, int planes, int nlat, int lmax) {
-    __shared__ float As[SHT_RT * SHT_PA], Bs[SHT_RT * SHT_PB];
+// The product both ways back share: out[m][n][k] = (RW ? rw[k] : 1) sum_{l >= m} T[m][l][k] fa(c[m][n][l]).  grid (k tiles of 128, n tiles of 64, mmax)
+template <bool RW, class FA>
+__device__ __forceinline__ void back_tile(const float* __restrict__ T, const float* __restrict__ coef, FA fa, const float* __restrict__ rw,
+                                          float* __restrict__ out, int planes, int nlat, int lmax, float* __restrict__ As, float* __restrict__ Bs) {
     const int k0 = blockIdx.x * SHT_TO, n0 = blockIdx.y * SHT_TN, m = blockIdx.z, N = 2 * planes;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int kw = k0 + (wave >> 1) * 64, nw = n0 + (wave & 1) * 32 + 4 * (lane >> 5);
@@ -203,21 +218,37 @@ __global__ __launch_bounds__(256, 2) void sht_adjoint_kernel(const float* __rest
 #pragma unroll
         for (int q = 0; q < 16; ++q) acc[j][q] = 0.f;
     }
-    if (m < lmax) {                                            // (uniform) else no degree has this m: the gradient is zero
-        const GradScale gs{g, lmax, m == 0 ? 2.f : 4.f};
-        tile_product<true, false>(acc, use, coef + (size_t)m * N * lmax, lmax, n0, N, gs, T + (size_t)m * lmax * nlat, nlat, k0, 0,
-                                  nlat, m, lmax, As, Bs);
-    }
+    if (m < lmax)                                              // (uniform) else no degree has this m: the result is zero
+        tile_product<true, false>(acc, use, coef + (size_t)m * N * lmax, lmax, n0, N, fa, T + (size_t)m * lmax * nlat, nlat, k0, 0, nlat, m, lmax,
+                                  As, Bs);
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
         const int k = kw + 32 * j + (lane & 31);
         if (k >= nlat) continue;
+        const float r = RW ? rw[k] : 1.f;                      // one load per accumulator column
 #pragma unroll
         for (int q = 0; q < 16; ++q) {
             const int n = nw + (q & 3) + 8 * (q >> 2);
-            if (n < N) dX[((size_t)m * N + n) * nlat + k] = acc[j][q];
+            if (n < N) out[((size_t)m * N + n) * nlat + k] = RW ? r * acc[j][q] : acc[j][q];
         }
     }
+}
+
+__global__ __launch_bounds__(256, 2) void sht_adjoint_kernel(const float* __restrict__ T, const float* __restrict__ coef, const float* __restrict__ g,
+                                                          float* __restrict__ dX, int planes, int nlat, int lmax) {
+    __shared__ float As[SHT_RT * SHT_PA], Bs[SHT_RT * SHT_PB];
+    back_tile<false>(T, coef, GradScale{g, lmax, blockIdx.z == 0 ? 2.f : 4.f}, nullptr, dX, planes, nlat, lmax, As, Bs);
+}
+
+// S[m][n][k] = rw[k] sum_{l >= m} T[m][l][k] (f_m h[plane][l]) c[m][n][l]; the imaginary rows of m = 0 and of m = m_nyq (nlon / 2 for an even
+// nlon, else -1) are not read and leave as zeros
+template <bool H>
+__global__ __launch_bounds__(256, 2) void sht_synth_kernel(const float* __restrict__ T, const float* __restrict__ rw, const float* __restrict__ coef,
+                                                        const float* __restrict__ h, int hs, float f0, float fm, int m_nyq, float* __restrict__ S,
+                                                        int planes, int nlat, int lmax) {
+    __shared__ float As[SHT_RT * SHT_PA], Bs[SHT_RT * SHT_PB];
+    const int m = blockIdx.z;
+    back_tile<true>(T, coef, SynthScale<H>{h, hs, m == 0 ? f0 : fm, m == 0 || m == m_nyq}, rw, S, planes, nlat, lmax, As, Bs);
 }
 
 // The longitude transform as torch.fft.rfft leaves it, F [planes][nlat][mmax][2] (m, then re / im, innermost), <-> the operand layout:
@@ -298,6 +329,25 @@ extern "C" int swv2_sht_adjoint(const float* table, const float* coeffs, const f
     hipLaunchKernelGGL(sht_adjoint_kernel, dim3(cdiv(nlat, SHT_TO), cdiv(2L * planes, SHT_TN), mmax), dim3(256), 0, (hipStream_t)stream, table, coeffs,
                        gpower, dX, planes, nlat, lmax);
     SWV2_CHECK_LAUNCH("swv2_sht_adjoint");
+    return SWV2_OK;
+}
+
+extern "C" int swv2_sht_synth(const float* table, const float* rweights, const float* coeffs, const float* response, int response_stride,
+                              float scale_m0, float scale_m, float* S, int planes, int nlat, int lmax, int mmax, int nlon, void* stream) {
+    SWV2_CHECK_ARG(table && rweights && coeffs && S, "sht_synth: null pointer");
+    SWV2_CHECK_ARG(sht_shape_ok(planes, nlat, lmax, mmax), "sht_synth: bad shape (planes, nlat, lmax, mmax > 0; planes <= 2^20, nlat, lmax <= 2^15, mmax < 2^16)");
+    SWV2_CHECK_ARG(cdiv(2L * planes, SHT_TN) <= 65535, "sht_synth: too many planes for one launch");
+    SWV2_CHECK_ARG(response_stride == 0 || response_stride == lmax, "sht_synth: response_stride is 0 (one response) or lmax (one per plane)");
+    SWV2_CHECK_ARG(nlon >= 1, "sht_synth: nlon < 1");
+    const dim3 grid(cdiv(nlat, SHT_TO), cdiv(2L * planes, SHT_TN), mmax);
+    const int m_nyq = nlon % 2 == 0 ? nlon / 2 : -1;
+    if (response)
+        hipLaunchKernelGGL(sht_synth_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, table, rweights, coeffs, response, response_stride,
+                           scale_m0, scale_m, m_nyq, S, planes, nlat, lmax);
+    else
+        hipLaunchKernelGGL(sht_synth_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, table, rweights, coeffs, response, response_stride,
+                           scale_m0, scale_m, m_nyq, S, planes, nlat, lmax);
+    SWV2_CHECK_LAUNCH("swv2_sht_synth");
     return SWV2_OK;
 }
 

@@ -23,7 +23,7 @@ ensemble-mean RMSE and the rank histogram per channel and lead time, one pass ov
     python -m swin_v2_weather_amd.inference --registry DIR --steps 8 [--init x0.npy] [--out forecast.npy]
                                             [--truth truth.npy [--climatology time_means.npy] [--scores-out scores.json] [--extremes]
                                              [--spectrum] [--spectrum-out spectrum.npz]
-                                             [--ensemble M --perturbation A [--seed S] [--member-batch K]]]
+                                             [--ensemble M --perturbation A [--seed S] [--member-batch K] [--perturbation-scale KM]]]
 """
 from __future__ import annotations
 
@@ -181,20 +181,35 @@ def score_rollout(model, x0: torch.Tensor, truth, n_steps: int, coszen: torch.Te
     return RolloutScores(rmse, acc, rmse_s, acc_s, out.view(B, n_steps, Cout, H, W) if keep_forecast else None, tqe).with_spectrum(spec)
 
 
-def perturb_initial_condition(x0: torch.Tensor, n_members: int, amplitude: float, seed: int, n_fields: int) -> torch.Tensor:
+def perturb_initial_condition(x0: torch.Tensor, n_members: int, amplitude: float, seed: int, n_fields: int, kind: str = "white",
+                              length_scale_km: float | None = None) -> torch.Tensor:
     """x0 [B, Cin, H, W] (fields | zenith | invariants) -> the M = n_members initial conditions [M B, Cin, H, W], member-major (row m B + b).
     Member 0 is x0 bit for bit (the control); the members 1 .. M - 1 add
         amplitude * torch.randn((M - 1) B, n_fields, H, W, generator=torch.Generator(x0.device).manual_seed(seed))
-    to the first n_fields channels.  The other channels (cos-zenith, invariants) are x0's bit for bit in every member."""
+    to the first n_fields channels.  The other channels (cos-zenith, invariants) are x0's bit for bit in every member.
+    kind="spherical": isotropic noise on the sphere with a Gaussian correlation of length_scale_km, zero global mean and unit variance at
+    every point (utils/sht.py::gaussian_noise_spectrum, spherical_noise) in place of the white noise.  The rows r = (member - 1) B + b
+    are drawn one at a time in ascending order from the same single generator,
+        z = torch.randn(W // 2 + 1, 2 n_fields, H, generator=gen)          fp32, the coefficient layout [mmax, 2 planes, lmax]
+    and amplitude * spherical_noise(z, sigma, W) is added to the row's field channels."""
     M = int(n_members)
     B, Cin, H, W = x0.shape
     if M < 1 or not 0 <= n_fields <= Cin:
         raise ValueError(f"perturb_initial_condition: {M} members, {n_fields} fields of {Cin} channels")
+    if kind not in ("white", "spherical") or (kind == "spherical") != (length_scale_km is not None):
+        raise ValueError(f"perturb_initial_condition: kind {kind!r} with length_scale_km {length_scale_km} (\"white\" takes none, \"spherical\" needs one)")
     out = x0.repeat(M, 1, 1, 1)
     if M > 1 and n_fields:
         gen = torch.Generator(device=x0.device).manual_seed(int(seed))
-        noise = torch.randn((M - 1) * B, n_fields, H, W, generator=gen, device=x0.device, dtype=x0.dtype)
-        out[B:, :n_fields] += amplitude * noise
+        if kind == "white":
+            noise = torch.randn((M - 1) * B, n_fields, H, W, generator=gen, device=x0.device, dtype=x0.dtype)
+            out[B:, :n_fields] += amplitude * noise
+        else:
+            from .utils import sht
+            sigma = sht.gaussian_noise_spectrum(H, W, length_scale_km)
+            for r in range((M - 1) * B):
+                z = torch.randn(W // 2 + 1, 2 * n_fields, H, generator=gen, device=x0.device, dtype=torch.float32)
+                out[B + r, :n_fields] += (amplitude * sht.spherical_noise(z, sigma, W)).to(x0.dtype)
     return out
 
 
@@ -206,9 +221,10 @@ EnsembleRolloutScores = namedtuple("EnsembleRolloutScores", "crps fair_crps spre
 def ensemble_rollout(model, x0: torch.Tensor, truth, n_steps: int, n_members: int, amplitude: float, seed: int = 0,
                      coszen: torch.Tensor | None = None, n_invar: int = 0, scorer: ForecastScorer | None = None,
                      member_batch: int | None = None, keep_forecast: bool = False, n_fields: int | None = None,
-                     score_control: bool = False) -> EnsembleRolloutScores:
-    """`score_rollout` for an ensemble: x0 [B, Cin, H, W] is perturbed into M = n_members initial conditions (perturb_initial_condition;
-    n_fields defaults to Cin - n_invar - (1 if coszen is given)), all members are rolled out and every step is scored against truth[:, s]
+                     score_control: bool = False, perturbation_kind: str = "white",
+                     length_scale_km: float | None = None) -> EnsembleRolloutScores:
+    """`score_rollout` for an ensemble: x0 [B, Cin, H, W] is perturbed into M = n_members initial conditions (perturb_initial_condition,
+    which perturbation_kind and length_scale_km are handed to; n_fields defaults to Cin - n_invar - (1 if coszen is given)), all members are rolled out and every step is scored against truth[:, s]
     by scorer.ensemble_score as soon as all members have written it.  truth, scorer: as in score_rollout; coszen [B, n_steps - 1, H, W] is
     repeated for every member.  Unless keep_forecast the predictions live in a two-slot ring [M B, 2 Cout, H, W], scored where they lie.
     member_batch: members per model call (default: all M at once); the chunks advance in lockstep, one step at a time.  With one chunk
@@ -228,7 +244,7 @@ def ensemble_rollout(model, x0: torch.Tensor, truth, n_steps: int, n_members: in
         scorer = ForecastScorer(H, W, Cout, x0.device)
     if n_fields is None:
         n_fields = Cin - n_invar - int(coszen is not None)
-    xe = perturb_initial_condition(x0, M, amplitude, seed, n_fields)
+    xe = perturb_initial_condition(x0, M, amplitude, seed, n_fields, perturbation_kind, length_scale_km)
     slots = n_steps if keep_forecast else 2
     out = torch.empty(M * B, slots * Cout, H, W, dtype=torch.float32, device=x0.device)
     coff_of = (lambda s: s * Cout) if keep_forecast else (lambda s: (s % 2) * Cout)
@@ -289,7 +305,8 @@ class _Parser(argparse.ArgumentParser):
         if a.spectrum_out and not a.spectrum:
             self.error("--spectrum-out needs --spectrum")
         if a.ensemble is None:
-            for flag, v in (("--perturbation", a.perturbation), ("--seed", a.seed), ("--member-batch", a.member_batch)):
+            for flag, v in (("--perturbation", a.perturbation), ("--seed", a.seed), ("--member-batch", a.member_batch),
+                            ("--perturbation-scale", a.perturbation_scale)):
                 if v is not None:
                     self.error(f"{flag} needs --ensemble")
             return a
@@ -307,6 +324,8 @@ class _Parser(argparse.ArgumentParser):
             self.error("--ensemble needs --perturbation (the amplitude of the initial-condition noise, in normalised units)")
         if a.member_batch is not None and a.member_batch < 1:
             self.error("--member-batch: at least one member per model call")
+        if a.perturbation_scale is not None and not a.perturbation_scale > 0:
+            self.error("--perturbation-scale: a correlation length in km, above 0")
         return a
 
 
@@ -332,6 +351,8 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--perturbation", type=float, default=None, metavar="A", help="with --ensemble: amplitude of the N(0, 1) noise added to the fields")
     ap.add_argument("--seed", type=int, default=None, help="with --ensemble: seed of the noise (default 0)")
     ap.add_argument("--member-batch", type=int, default=None, metavar="K", help="with --ensemble: members per model call (default: all at once)")
+    ap.add_argument("--perturbation-scale", type=float, default=None, metavar="KM", help="with --ensemble: the noise is isotropic on the sphere with a "
+                                                                                        "Gaussian correlation of this length (default: white per grid point)")
     return ap
 
 
@@ -376,7 +397,8 @@ def _score_main(a, model, p, stats, x0, cz, n_invar):
     if a.ensemble is not None:
         # one rollout of all members: member 0 is the unperturbed forecast, scored as score_rollout scores it
         ens = ensemble_rollout(model, x0, truth_of, a.steps, a.ensemble, a.perturbation, a.seed or 0, cz, n_invar, scorer,
-                               member_batch=a.member_batch, n_fields=len(p["in_channels"]), score_control=True)
+                               member_batch=a.member_batch, n_fields=len(p["in_channels"]), score_control=True,
+                               perturbation_kind="white" if a.perturbation_scale is None else "spherical", length_scale_km=a.perturbation_scale)
         sc = ens.control
     else:
         sc = score_rollout(model, x0, truth_of, a.steps, cz, n_invar, scorer, keep_forecast=bool(a.out), extremes=a.extremes, spectrum=a.spectrum)

@@ -523,9 +523,10 @@ def l1_grad(prd, tar, qw, coef, dprd):
     L.check(L.load().swv2_l1_grad(_p(prd), _p(tar), _p(qw), _p(coef), _p(dprd), B * Cc, H, W, _stream()), "swv2_l1_grad")
 
 
-def sht_power(table, X, keep_coeffs: bool = False):
+def sht_power(table, X, keep_coeffs: bool = False, zero_coeffs: bool = False):
     """degree power [planes, lmax] of the spectral operand X [mmax, 2 planes, nlat] under table [mmax, lmax, nlat] (swv2_sht_power);
-    with keep_coeffs also the coefficients [mmax, 2 planes, lmax] (l >= m written) for sht_adjoint, else None"""
+    with keep_coeffs also the coefficients [mmax, 2 planes, lmax] (l >= m written; the rest zeros with zero_coeffs, else whatever the
+    allocation held) for sht_adjoint and sht_synth, else None"""
     _chk(table, torch.float32, "sht table"); _chk(X, torch.float32, "sht operand")
     if table.dim() != 3 or X.dim() != 3 or X.shape[0] != table.shape[0] or X.shape[2] != table.shape[2] or X.shape[1] % 2:
         raise L.Swv2Error(f"sht_power: table {tuple(table.shape)} [mmax, lmax, nlat] against operand {tuple(X.shape)} [mmax, 2 planes, nlat]")
@@ -535,7 +536,7 @@ def sht_power(table, X, keep_coeffs: bool = False):
     nb = lib.swv2_sht_ws_bytes(planes, lmax, mmax)
     ws = _scratch(nb, X.device, "sht_power")
     power = torch.empty(planes, lmax, dtype=torch.float32, device=X.device)
-    coef = torch.empty(mmax, 2 * planes, lmax, dtype=torch.float32, device=X.device) if keep_coeffs else None
+    coef = (torch.zeros if zero_coeffs else torch.empty)(mmax, 2 * planes, lmax, dtype=torch.float32, device=X.device) if keep_coeffs else None
     L.check(_timed("sht_power", lib.swv2_sht_power, _p(table), _p(X), _p(power), _p(coef), planes, nlat, lmax, mmax, _p(ws), nb, _stream()),
             "swv2_sht_power")
     return power, coef
@@ -564,6 +565,28 @@ def sht_adjoint(table, coef, gpower):
     L.check(_timed("sht_adjoint", L.load().swv2_sht_adjoint, _p(table), _p(coef), _p(gpower), _p(dX), planes, nlat, lmax, mmax, _stream()),
             "swv2_sht_adjoint")
     return dX
+
+
+def sht_synth(table, rweights, coef, response=None, scales=(1.0, 1.0), *, nlon: int):
+    """S [mmax, 2 planes, nlat] = rweights[k] sum_{l >= m} table[m, l, k] f_m h[plane, l] coef[m, n, l] (swv2_sht_synth): the synthesis from
+    coefficients [mmax, 2 planes, lmax] back to the longitude transform of a field of nlon points per row.  response: None, [lmax] or
+    [planes, lmax]; scales = (f_0, f_m for m >= 1)"""
+    for t, what in ((table, "sht table"), (rweights, "inverse row weights"), (coef, "sht coefficients")):
+        _chk(t, torch.float32, what)
+    mmax, lmax, nlat = table.shape
+    planes = coef.shape[1] // 2
+    if tuple(coef.shape) != (mmax, 2 * planes, lmax) or tuple(rweights.shape) != (nlat,):
+        raise L.Swv2Error(f"sht_synth: table {tuple(table.shape)}, coefficients {tuple(coef.shape)}, inverse weights {tuple(rweights.shape)}")
+    stride = 0
+    if response is not None:
+        _chk(response, torch.float32, "degree response")
+        if tuple(response.shape) not in ((lmax,), (planes, lmax)):
+            raise L.Swv2Error(f"sht_synth: response {tuple(response.shape)} for {planes} planes of {lmax} degrees")
+        stride = lmax if response.dim() == 2 else 0
+    S = torch.empty(mmax, 2 * planes, nlat, dtype=torch.float32, device=coef.device)
+    L.check(_timed("sht_synth", L.load().swv2_sht_synth, _p(table), _p(rweights), _p(coef), _p(response), stride, float(scales[0]), float(scales[1]),
+                   _p(S), planes, nlat, lmax, mmax, int(nlon), _stream()), "swv2_sht_synth")
+    return S
 
 
 ENS_MAX_MEMBERS = 64          # the M cap of swv2_ens_sums
