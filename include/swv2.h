@@ -660,6 +660,34 @@ int swv2_era5_select_normalize(const float* raw, float* out, const int* chan, co
 int swv2_era5_zenith(float* out, const float* sun, int B, int nz, int H, int W, int Cout_total, int coff, void* stream);
 int swv2_era5_static(const float* stat, float* out, int B, int Cs, int H, int W, int Cout_total, int coff, void* stream);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * int16-packed year files (utils/packed.py; purely additive, the revision stays 112).  A (year file, channel) is stored as 16-bit codes
+ * with one fp32 offset and one fp32 scale:
+ *   pack     q  = clamp(rint((x - offset) / scale), -32767, 32767)          q = -32768 for a non-finite x
+ *   unpack   xh = (float(q) * scale) + offset                               xh = NaN for q = -32768
+ * each step one fp32 operation (no fused multiply-add, IEEE division, round half to even): numpy reproduces every result bit for bit.
+ *
+ * swv2_era5_select_normalize_i16: swv2_era5_select_normalize with the unpack in front.  raw [B][S][Craw][Hraw][Wraw] int16;
+ *   out[b][coff + s*Csel + c][i][j] = (xh - mean[c]) / std[c], xh unpacked with offset / scale[slab_row[b*S + s] * Craw + chan[c]]:
+ *   offset, scale are tables [rows][Craw] fp32 of every year file's parameters, slab_row [B][S] int32 names the row of each slab, so the
+ *   samples of one batch may come from different years.  Equal, bit for bit, to swv2_era5_select_normalize on the unpacked slab.
+ * swv2_era5_unpack_i16 / swv2_era5_pack_i16: a whole slab [C][H][W] with one parameter row offset [C], scale [C].
+ * swv2_pack_range: per-channel minimum and maximum of the finite values of slab [C][H][W] fp32 and the number of the others, folded into
+ *   the running range [C][2] fp32 (min, max) and missing [C] int64 of a year file; first != 0 overwrites them.  A channel without a
+ *   finite value so far holds (+inf, -inf).  Minima, maxima and counts do not depend on order: two runs agree bit for bit.  ws: at least
+ *   swv2_pack_range_ws_bytes(C, H, W) bytes (host-only; 0 for a non-positive size), not zeroed by the caller.
+ * Refused with SWV2_ERR_INVALID before any launch: a null pointer, a non-positive size, W % 4 or Wraw % 4 != 0, H > Hraw, W > Wraw, an
+ * int16 pointer not 8-byte aligned, an fp32 slab / out pointer not 16-byte aligned, a channel range outside the output, more than 65535
+ * planes in one call (C of a slab; B * S * Csel), H * W >= 2^30, ws / missing not 8-byte aligned, a workspace smaller than its _ws_bytes.
+ * ------------------------------------------------------------------------------------------------------------ */
+int swv2_era5_select_normalize_i16(const int16_t* raw, float* out, const int* chan, const float* mean, const float* stdv, const float* offset,
+                                   const float* scale, const int* slab_row, int B, int S, int Csel, int Craw, int Hraw, int Wraw, int H, int W,
+                                   int Cout_total, int coff, void* stream);
+int swv2_era5_unpack_i16(const int16_t* raw, float* out, const float* offset, const float* scale, int C, int H, int W, void* stream);
+int swv2_era5_pack_i16(const float* slab, int16_t* out, const float* offset, const float* scale, int C, int H, int W, void* stream);
+size_t swv2_pack_range_ws_bytes(int C, int H, int W);     /* C * slices of the plan * 16 */
+int swv2_pack_range(const float* slab, int C, int H, int W, int first, float* range, int64_t* missing, void* ws, size_t ws_bytes, void* stream);
+
 /* Output projection of the attention branch fused with LayerNorm1 (swinv2_global.py:318-319, 468-476, 490):
  *   forward : y[dst] = x[dst] + scale[b] * LN(merge_heads(oh) Wp^T + bp),  dst = rowidx[m] (negative = padded row, skipped);
  *             saves a1 = bf16(proj output) [Bw*Lp][C] (window order), mean, rstd            (replaces swv2_linear + swv2_ln_residual_fwd)

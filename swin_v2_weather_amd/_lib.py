@@ -13,7 +13,7 @@ import threading
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB_PATH = os.environ.get("SWV2_LIB") or os.path.join(HERE, "libswv2.so")     # SWV2_LIB: a privately built variant (tools/ab_macro.sh)
-SOURCES = ["capi.hip", "attn.hip", "attn2.hip", "attn_bwd_stream.hip", "attn_wide.hip", "attn_d256.hip", "gemm.hip", "gemm_tn.hip", "gemm_tn_slab.hip", "rowops.hip", "lamb.hip", "block.hip", "cpb.hip", "mlp.hip", "proj_ln.hip", "dataio.hip", "score.hip", "stats.hip", "quantile.hip", "ensemble.hip", "loss_l1.hip", "sht.hip"]
+SOURCES = ["capi.hip", "attn.hip", "attn2.hip", "attn_bwd_stream.hip", "attn_wide.hip", "attn_d256.hip", "gemm.hip", "gemm_tn.hip", "gemm_tn_slab.hip", "rowops.hip", "lamb.hip", "block.hip", "cpb.hip", "mlp.hip", "proj_ln.hip", "dataio.hip", "packed.hip", "score.hip", "stats.hip", "quantile.hip", "ensemble.hip", "loss_l1.hip", "sht.hip"]
 
 ABI_VERSION = 112          # SWV2_VERSION of the include/swv2.h these ctypes mirrors were written against (checked in load())
 
@@ -288,6 +288,11 @@ SYMBOLS = {
     "swv2_era5_select_normalize": (_I, [_P, _P, _P, _P, _P] + [_I] * 10 + [_P]),
     "swv2_era5_zenith": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P]),
     "swv2_era5_static": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P]),
+    "swv2_era5_select_normalize_i16": (_I, [_P] * 8 + [_I] * 10 + [_P]),
+    "swv2_era5_unpack_i16": (_I, [_P, _P, _P, _P, _I, _I, _I, _P]),
+    "swv2_era5_pack_i16": (_I, [_P, _P, _P, _P, _I, _I, _I, _P]),
+    "swv2_pack_range_ws_bytes": (C.c_size_t, [_I, _I, _I]),
+    "swv2_pack_range": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, C.c_size_t, _P]),
     "swv2_proj_ln_supported": (_I, [_I, _I, _I]),
     "swv2_proj_ln_bwd_ws_floats": (C.c_size_t, [_I, _I]),
     "swv2_proj_ln_fwd": (_I, [C.POINTER(ProjLnArgs), _P]),

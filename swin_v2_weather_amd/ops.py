@@ -723,6 +723,63 @@ def era5_select_normalize(raw, out, chan, mean, std, coff=0, stream=None):
                                                 H, W, Ct, coff, stream if stream is not None else _stream()), "swv2_era5_select_normalize")
 
 
+def era5_select_normalize_i16(raw, out, chan, mean, std, offset, scale, slab_row, coff=0, stream=None):
+    """era5_select_normalize over int16-packed slabs (utils/packed.py): raw [B, S, Craw, Hraw, Wraw] int16, offset / scale [rows, Craw] fp32
+    (every year file's parameters), slab_row [B, S] int32 (the row of each slab).  Bit for bit what era5_select_normalize gives on the
+    unpacked slabs."""
+    B, S, Craw, Hraw, Wraw = raw.shape
+    _, Ct, H, W = out.shape
+    _chk(raw, torch.int16, "era5 packed raw"); _chk(out, torch.float32, "era5 out")
+    _chk(offset, torch.float32, "era5 pack offset"); _chk(scale, torch.float32, "era5 pack scale"); _chk(slab_row, torch.int32, "era5 slab_row")
+    if offset.dim() != 2 or offset.shape[1] != Craw or scale.shape != offset.shape or slab_row.numel() != B * S:
+        raise L.Swv2Error(f"era5_select_normalize_i16: offset {tuple(offset.shape)}, scale {tuple(scale.shape)}, slab_row {tuple(slab_row.shape)}: "
+                          f"expected [rows, {Craw}] twice and [{B}, {S}]")
+    L.check(L.load().swv2_era5_select_normalize_i16(_p(raw), _p(out), _p(chan), _p(mean), _p(std), _p(offset), _p(scale), _p(slab_row), B, S,
+                                                    chan.numel(), Craw, Hraw, Wraw, H, W, Ct, coff,
+                                                    stream if stream is not None else _stream()), "swv2_era5_select_normalize_i16")
+
+
+def _pack_slab_args(who, i16, f32, offset, scale):
+    _chk(i16, torch.int16, who + " int16 slab"); _chk(f32, torch.float32, who + " fp32 slab")
+    _chk(offset, torch.float32, who + " offset"); _chk(scale, torch.float32, who + " scale")
+    if f32.dim() != 3 or i16.shape != f32.shape or offset.numel() != f32.shape[0] or scale.numel() != f32.shape[0]:
+        raise L.Swv2Error(f"{who}: int16 {tuple(i16.shape)}, fp32 {tuple(f32.shape)}, offset {tuple(offset.shape)}, scale {tuple(scale.shape)}: "
+                          "expected [C, H, W] twice and [C] twice")
+    return f32.shape
+
+
+def era5_unpack_i16(raw, out, offset, scale, stream=None):
+    """raw [C, H, W] int16 -> out [C, H, W] fp32 = raw * scale[c] + offset[c] (NaN for the code -32768), utils/packed.py::unpack_array"""
+    Cc, H, W = _pack_slab_args("era5_unpack_i16", raw, out, offset, scale)
+    L.check(L.load().swv2_era5_unpack_i16(_p(raw), _p(out), _p(offset), _p(scale), Cc, H, W,
+                                          stream if stream is not None else _stream()), "swv2_era5_unpack_i16")
+
+
+def era5_pack_i16(slab, out, offset, scale, stream=None):
+    """slab [C, H, W] fp32 -> out [C, H, W] int16, utils/packed.py::pack_array"""
+    Cc, H, W = _pack_slab_args("era5_pack_i16", out, slab, offset, scale)
+    L.check(L.load().swv2_era5_pack_i16(_p(slab), _p(out), _p(offset), _p(scale), Cc, H, W,
+                                        stream if stream is not None else _stream()), "swv2_era5_pack_i16")
+
+
+def pack_range_workspace(Cc: int, H: int, W: int, device) -> torch.Tensor:
+    """the slice partials of swv2_pack_range (bytes; not zeroed: every launch stores all of them)"""
+    return torch.empty(int(L.load().swv2_pack_range_ws_bytes(Cc, H, W)), dtype=torch.uint8, device=device)
+
+
+def pack_range(slab, rng, missing, ws, first: bool, stream=None):
+    """slab [C, H, W] fp32 into the running rng [C, 2] fp32 (min, max of the finite values) and missing [C] int64 (the others);
+    first: overwrite them"""
+    _chk(slab, torch.float32, "pack_range slab"); _chk(rng, torch.float32, "pack_range range"); _chk(missing, torch.int64, "pack_range missing")
+    _chk(ws, torch.uint8, "pack_range workspace")
+    if slab.dim() != 3 or tuple(rng.shape) != (slab.shape[0], 2) or missing.numel() != slab.shape[0]:
+        raise L.Swv2Error(f"pack_range: slab {tuple(slab.shape)}, range {tuple(rng.shape)}, missing {tuple(missing.shape)}: expected [C, H, W], "
+                          "[C, 2], [C]")
+    Cc, H, W = slab.shape
+    L.check(L.load().swv2_pack_range(_p(slab), Cc, H, W, int(bool(first)), _p(rng), _p(missing), _p(ws), ws.numel(),
+                                     stream if stream is not None else _stream()), "swv2_pack_range")
+
+
 def era5_zenith(out, sun, coff, stream=None):
     """sun [B, nz, 3] fp32 = (sin dec, cos dec, hour angle at longitude 0) per time point (utils/data_loader_era5.sun_position)
     -> out[:, coff : coff + nz] = cos of the solar zenith angle"""

@@ -5,7 +5,8 @@
     inp [B, n_in, H, W], tar [B, n_out*(n_future+1), H, W]  (+ zen_inp [B,1,H,W], zen_tar [B,n_future+1,H,W] if add_zenith)
 and the reference's dataset index arithmetic (year / local index, year-boundary wrap :158-160, target slab :164-165).
 Data sources, in the order `get_data_loader` tries them:
-  * year files under `files_pattern` (`*.npy` memmaps, or `*.h5` with h5py -- the reference's format) -> the host pipeline of
+  * year files under `files_pattern` (`*.npy` memmaps, fp32 or int16-packed by utils/pack_dataset.py, or `*.h5` with h5py -- the
+    reference's format) -> the host pipeline of
     utils/host_pipeline.py: pinned staging ring, async H2D, crop / z-score / zenith / invariants assembled by HIP kernels;
   * `params.synthetic_host_samples > 0`: the same pipeline over an in-memory synthetic year array (PCIe-inclusive benchmarks);
   * `params.synthetic_device_pool > 0` (default of the bench configs): `DevicePoolLoader`, K batches generated ON THE DEVICE once
@@ -190,11 +191,12 @@ class _PipelineDataset:
 def get_data_loader(params, files_pattern, distributed, train):
     host_n = _get(params, 'synthetic_host_samples', 0)
     if _year_files(files_pattern) or host_n:
-        from .host_pipeline import Era5HostPipeline, SyntheticYearSource, YearArraySource
+        from .host_pipeline import Era5HostPipeline, SyntheticYearSource
+        from .packed import open_year_source
         from .preprocess_utils import build_static_features
         device = torch.device('cuda', torch.cuda.current_device())
         if _year_files(files_pattern):
-            source = YearArraySource(str(files_pattern))
+            source = open_year_source(str(files_pattern))       # int16-packed .npy files (utils/packed.py) or the fp32 year files
         else:
             source = SyntheticYearSource(n_years=1, n_samples=int(host_n), seed=_get(params, 'seed', None) or 333,
                                          pinned=bool(_get(params, 'synthetic_host_pinned', False)))

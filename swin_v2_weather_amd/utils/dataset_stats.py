@@ -206,6 +206,10 @@ def select_years(source, years=None):
 
 def source_pivot(source) -> np.ndarray:
     """the pivot of a source: from slab 0 of its FIRST year file, whichever years are selected, so that shards agree"""
+    if getattr(source, "packed", False):                         # int16-packed (utils/packed.py): the pivot of the unpacked slab
+        buf = np.empty(source.shape, np.float32)
+        source.read_f32(0, 0, buf)
+        return pivot_of(buf)
     if hasattr(source, "slab"):
         return pivot_of(source.slab(0, 0).numpy())
     buf = np.empty(source.shape, np.float32)
@@ -213,22 +217,18 @@ def source_pivot(source) -> np.ndarray:
     return pivot_of(buf)
 
 
-def accumulate_source(source, device, pivot, year_idx=None, ring=3, workers=None) -> DatasetStats:
-    """every slab of the selected year files of `source`, in order, into a DatasetStats on `device`"""
+def staged_slabs(source, items, device, ring=3, workers=None):
+    """The slabs `items` = [(year_idx, t), ...] of `source` on `device`, in order, through the staging of Era5HostPipeline: producer
+    threads fill a ring of pinned slabs (a page-locked source is copied from in place), a copy stream moves them into two alternating
+    device slabs.  Yields (i, slab, previous slab, copy stream) with the H2D copy of slab i enqueued on the copy stream: the consumer
+    enqueues its kernels on THAT stream, so they follow the copy, and the next copy into the other slab follows the kernels that read
+    it.  Slabs are fp32, or int16 for a packed source (utils/packed.py).  A producer's exception fails the iteration."""
     device = torch.device(device)
-    C, H, W = source.shape
-    st = DatasetStats(C, H, W, device, pivot)
-    items = [(y, t) for y in (range(len(source.years)) if year_idx is None else year_idx) for t in range(source.n_samples_year[y])]
-    if device.type != "cuda":
-        bufs = [np.empty((C, H, W), np.float32) for _ in range(2)]
-        for i, (y, t) in enumerate(items):
-            source.read(y, t, bufs[i % 2])
-            st.update(bufs[i % 2], bufs[(i - 1) % 2] if t > 0 else None)
-        return st
+    dt = torch.int16 if getattr(source, "packed", False) else torch.float32
     direct = bool(getattr(source, "pinned", False))              # a page-locked source is copied from in place
     ring = max(2, int(ring))
-    dev = [torch.empty((C, H, W), dtype=torch.float32, device=device) for _ in range(2)]
-    pin = [] if direct else [torch.empty((C, H, W), dtype=torch.float32, pin_memory=True) for _ in range(ring)]
+    dev = [torch.empty(tuple(source.shape), dtype=dt, device=device) for _ in range(2)]
+    pin = [] if direct else [torch.empty(tuple(source.shape), dtype=dt, pin_memory=True) for _ in range(ring)]
     cs = torch.cuda.Stream(device=device)
     pool = ThreadPoolExecutor(max_workers=workers or ring)
     free, pending, inflight, nxt = deque(range(ring)), deque(), deque(), 0     # pinned slots / reads under way / H2D copies under way
@@ -252,26 +252,55 @@ def accumulate_source(source, device, pivot, year_idx=None, ring=3, workers=None
                 host = pin[slot]
             with torch.cuda.stream(cs):
                 dev[i % 2].copy_(host, non_blocking=True)
-                # the same stream: this kernel follows its copy, and the next copy into the other slab follows the kernel that read it
-                st.update(dev[i % 2], dev[(i - 1) % 2] if t > 0 else None, stream=cs.cuda_stream)
-                if not direct:
-                    ev = torch.cuda.Event()
-                    ev.record(cs)
-                    inflight.append((ev, slot))
+            yield i, dev[i % 2], dev[(i - 1) % 2], cs
+            if not direct:
+                ev = torch.cuda.Event()
+                ev.record(cs)
+                inflight.append((ev, slot))
         cs.synchronize()
     finally:
         for _, fut in pending:
             fut.cancel()
         pool.shutdown(wait=True)
         cs.synchronize()
+
+
+def accumulate_source(source, device, pivot, year_idx=None, ring=3, workers=None) -> DatasetStats:
+    """every slab of the selected year files of `source`, in order, into a DatasetStats on `device`.  A packed source (utils/packed.py)
+    is unpacked on the way: by swv2_era5_unpack_i16 after the int16 H2D copy on a CUDA device, by `read_f32` on the cpu."""
+    device = torch.device(device)
+    C, H, W = source.shape
+    st = DatasetStats(C, H, W, device, pivot)
+    packed = bool(getattr(source, "packed", False))
+    items = [(y, t) for y in (range(len(source.years)) if year_idx is None else year_idx) for t in range(source.n_samples_year[y])]
+    if device.type != "cuda":
+        bufs = [np.empty((C, H, W), np.float32) for _ in range(2)]
+        read = source.read_f32 if packed else source.read
+        for i, (y, t) in enumerate(items):
+            read(y, t, bufs[i % 2])
+            st.update(bufs[i % 2], bufs[(i - 1) % 2] if t > 0 else None)
+        return st
+    if packed:
+        from .. import ops
+        from .packed import param_tables
+        off, sc = (torch.from_numpy(a).to(device) for a in param_tables(source))
+        f32 = [torch.empty((C, H, W), dtype=torch.float32, device=device) for _ in range(2)]
+    for i, slab, prev, cs in staged_slabs(source, items, device, ring=ring, workers=workers):
+        y, t = items[i]
+        if packed:                                               # (the fp32 slab i - 1 was unpacked into the other buffer one step ago)
+            ops.era5_unpack_i16(slab, f32[i % 2], off[y], sc[y], stream=cs.cuda_stream)
+            slab, prev = f32[i % 2], f32[(i - 1) % 2]
+        st.update(slab, prev if t > 0 else None, stream=cs.cuda_stream)
     return st
 
 
 def compute_stats(location, device, years=None, ring=3, workers=None, source=None) -> DatasetStats:
-    """The running state over the year files under `location` (`*.npy` or `*.h5`; or over `source`, an object with the interface of
-    YearArraySource), restricted to `years` (four-digit file stems) when given.  `.finalize()` gives the four arrays, `.state()` a
+    """The running state over the year files under `location` (`*.npy`, fp32 or int16-packed, or `*.h5`; or over `source`, an object with
+    the interface of YearArraySource), restricted to `years` (four-digit file stems) when given.  `.finalize()` gives the four arrays, `.state()` a
     partial result for `DatasetStats.merge`."""
-    source = YearArraySource(location) if source is None else source
+    if source is None:
+        from .packed import open_year_source
+        source = open_year_source(location)
     return accumulate_source(source, device, source_pivot(source), select_years(source, years), ring=ring, workers=workers)
 
 
@@ -297,7 +326,7 @@ def load_state_file(path) -> dict:
 
 def build_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(prog="python -m swin_v2_weather_amd.utils.dataset_stats", description=__doc__.split("\n\n")[0])
-    ap.add_argument("--data", required=True, help="folder of year files (*.npy or *.h5, [N, C, H, W] fp32)")
+    ap.add_argument("--data", required=True, help="folder of year files (*.npy or *.h5, [N, C, H, W] fp32; or int16-packed *.npy)")
     ap.add_argument("--out", help="folder the four statistics files are written to")
     ap.add_argument("--partial-out", help="write the running state (.npz) of the selected years instead, for `merge`")
     ap.add_argument("--years", type=int, nargs="+", help="only these year files (four-digit file stems)")

@@ -2,7 +2,8 @@
 (utils/data_loader_era5_dali.py + utils/dali_era5_es_helper.py) and of the per-sample host work of its PyTorch loader
 (utils/data_loader_era5.py:149-177), SURVEY 8(f) row 3.
 
-    year files (fields[N, 73, 721, 1440] fp32: .npy memmaps, HDF5 if h5py is importable, or an in-memory synthetic array)
+    year files (fields[N, 73, 721, 1440] fp32: .npy memmaps, HDF5 if h5py is importable, or an in-memory synthetic array; or int16-packed
+    .npy files, utils/packed.py: half the bytes through every stage below, unpacked by swv2_era5_select_normalize_i16)
       -> producer threads copy whole, UNCROPPED time slabs into a ring of pinned staging buffers   (dali_era5_es_helper.py:92-103)
       -> hipMemcpyAsync on a copy stream into a double-buffered device slab
       -> swv2_era5_select_normalize / _zenith / _static on the same stream: crop + channel select + z-score + cos-zenith +
@@ -148,11 +149,20 @@ class Era5HostPipeline:
         slab = (self.Craw, self.Hraw, self.Wraw)
         self.ring = ring
         self.direct = bool(getattr(source, "pinned", False))
+        # an int16-packed source (utils/packed.py): the slabs stay int16 up to the assembly kernel, which unpacks them with the
+        # parameters of their year file (tables [years, Craw], uploaded once; the year index of every slab travels like `hours`)
+        self.packed = bool(getattr(source, "packed", False))
+        raw_dt = torch.int16 if self.packed else torch.float32
+        if self.packed:
+            from .packed import param_tables
+            off, sc = param_tables(source)
+            self.pack_offset, self.pack_scale = dev_t(off, torch.float32).contiguous(), dev_t(sc, torch.float32).contiguous()
+            self.rows = [torch.empty(self.B, 1 + self.S, dtype=torch.int32, pin_memory=True) for _ in range(ring + 1)]
         if not self.direct:      # per slot: the input slab and the S target slabs of every sample (separate, contiguous tensors)
-            self.pin = [(torch.empty((self.B, 1) + slab, dtype=torch.float32, pin_memory=True),
-                         torch.empty((self.B, self.S) + slab, dtype=torch.float32, pin_memory=True)) for _ in range(ring)]
-        self.raw = [(torch.empty((self.B, 1) + slab, dtype=torch.float32, device=device),
-                     torch.empty((self.B, self.S) + slab, dtype=torch.float32, device=device)) for _ in range(2)]
+            self.pin = [(torch.empty((self.B, 1) + slab, dtype=raw_dt, pin_memory=True),
+                         torch.empty((self.B, self.S) + slab, dtype=raw_dt, pin_memory=True)) for _ in range(ring)]
+        self.raw = [(torch.empty((self.B, 1) + slab, dtype=raw_dt, device=device),
+                     torch.empty((self.B, self.S) + slab, dtype=raw_dt, device=device)) for _ in range(2)]
         self.out = [(torch.empty(self.B, self.Cin_total, self.H, self.W, device=device),
                      torch.empty(self.B, self.S * self.n_out, self.H, self.W, device=device),
                      torch.empty(self.B, self.S, self.H, self.W, device=device) if self.add_zenith else None) for _ in range(2)]
@@ -161,7 +171,7 @@ class Era5HostPipeline:
         self.pool = ThreadPoolExecutor(max_workers=workers or max(1, int(g('num_data_workers', 8))))
         logging.info("ERA5 host pipeline: %d samples (%d years), shard %d/%d, %d steps/epoch, %s staging",
                      self.n_total, len(source.years), self.shard_id, self.shards, self.steps,
-                     "zero-copy (page-locked source)" if self.direct else f"{ring} pinned slabs")
+                     ("zero-copy (page-locked source)" if self.direct else f"{ring} pinned slabs") + (", int16-packed" if self.packed else ""))
 
     def __len__(self):
         return self.steps
@@ -205,8 +215,18 @@ class Era5HostPipeline:
                 raw_in.copy_(self.pin[slot_pin][0], non_blocking=True)
                 raw_tar.copy_(self.pin[slot_pin][1], non_blocking=True)
             st = cs.cuda_stream
-            ops.era5_select_normalize(raw_in, inp, self.in_chan, self.in_mean, self.in_std, 0, stream=st)
-            ops.era5_select_normalize(raw_tar, tar, self.out_chan, self.tar_mean, self.tar_std, 0, stream=st)
+            if self.packed:
+                rows = self.rows[slot_pin]
+                for b, (y, _) in enumerate(locs):
+                    rows[b, :] = y
+                rd = rows.to(self.dev, non_blocking=True)
+                ops.era5_select_normalize_i16(raw_in, inp, self.in_chan, self.in_mean, self.in_std, self.pack_offset, self.pack_scale,
+                                              rd[:, :1].contiguous(), 0, stream=st)
+                ops.era5_select_normalize_i16(raw_tar, tar, self.out_chan, self.tar_mean, self.tar_std, self.pack_offset, self.pack_scale,
+                                              rd[:, 1:].contiguous(), 0, stream=st)
+            else:
+                ops.era5_select_normalize(raw_in, inp, self.in_chan, self.in_mean, self.in_std, 0, stream=st)
+                ops.era5_select_normalize(raw_tar, tar, self.out_chan, self.tar_mean, self.tar_std, 0, stream=st)
             c = self.n_in
             if self.add_zenith:
                 hd = hrs.to(self.dev, non_blocking=True)
