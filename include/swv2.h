@@ -36,8 +36,9 @@ extern "C" {
  * swv2_attn_bwd_kernel (+ swv2_attn_kernel_t, SWV2_ATTN_K_*); 111: the LAMB optimizer, swv2_lamb_* (+ swv2_lamb_item, SWV2_LAMB_*);
  * 112: forecast scores, swv2_score_*.  The dataset statistics, swv2_stats_*, came later and are purely additive (new entry points only,
  * no struct member moves): the revision stays 112.  So are the plane order statistics, swv2_quantile_ws_bytes / swv2_plane_order_stats,
- * and the ensemble scores, swv2_ens_*, and the l1 loss family, swv2_l1_*, and the spherical-harmonic degree spectra, swv2_sht_*. */
-#define SWV2_VERSION 112
+ * and the ensemble scores, swv2_ens_*, and the l1 loss family, swv2_l1_*, and the spherical-harmonic degree spectra, swv2_sht_*;
+ * 113: swv2_loss_sums takes a workspace (+ swv2_loss_ws_bytes) and no longer needs zeroed sums. */
+#define SWV2_VERSION 113
 
 enum {
     SWV2_OK = 0,
@@ -389,10 +390,19 @@ int swv2_merge_stats(const float* x, float* mean, float* rstd, int B, int H, int
 int swv2_merge_ln_bwd(const float* x, const void* dn_bf16, const float* gamma, const float* mean, const float* rstd,
                       float* dx, float* dgamma, float* dbeta, int B, int H, int W, int C, void* stream);
 
-/* Geometric l2 loss (utils/losses.py:188-232, utils/grids.py:115-117): one pass produces, per (b,c) plane,
- * sums[2*bc] += sum q[h](prd-tar)^2 and sums[2*bc+1] += sum q[h] tar^2 (caller zeroes sums);
- * the backward is dprd = coef[bc] * q[h] * (prd - tar) with coef from the chain rule of the chosen variant. */
-int swv2_loss_sums(const float* prd, const float* tar, const float* quad_w, float* sums, int BC, int H, int W, void* stream);
+/* Geometric l2 loss (csrc/loss_l2.hip; utils/losses.py:188-232, utils/grids.py:115-117): one pass over prd and tar (contiguous [BC][H][W])
+ * produces, per (b,c) plane, sums[2*bc] = sum q[h](prd-tar)^2 and sums[2*bc+1] = sum q[h] tar^2.  swv2_loss_sums: one launch of
+ * BC * swv2_score_slices(BC, H, W) workgroups (the plan and slice bounds of swv2_score_sums) that store their slice's two sums at
+ * ws[(plane * slices + slice) * 2 ..], then one small launch that folds the slices of each plane in a fixed order into sums [BC][2].  No
+ * atomics, nothing to zero beforehand (sums and ws are written in full, never read first); two runs on the same inputs agree bit for bit,
+ * and with swv2_score_sums' S_dd and S_tt without a climatology.  A NaN in a plane reaches that plane's two sums only.  (113: ws, ws_bytes)
+ * The backward is dprd = coef[bc] * q[h] * (prd - tar) with coef from the chain rule of the chosen variant; the grid of swv2_l1_grad.
+ * Refused with SWV2_ERR_INVALID before any launch: a null pointer, W % 4 != 0, prd / tar / ws / dprd not 16-byte aligned, sums not 8-byte
+ * aligned, a workspace smaller than swv2_loss_ws_bytes, BC >= 2^20 (swv2_loss_grad: BC > 65535), H * W >= 2^30.  swv2_loss_ws_bytes is
+ * host-only (no HIP call) and returns 0 for a non-positive argument. */
+size_t swv2_loss_ws_bytes(int planes, int H, int W);      /* planes * swv2_score_slices(planes, H, W) * 8 */
+int swv2_loss_sums(const float* prd, const float* tar, const float* quad_w, float* sums, int BC, int H, int W, void* ws, size_t ws_bytes,
+                   void* stream);
 int swv2_loss_grad(const float* prd, const float* tar, const float* quad_w, const float* coef, float* dprd, int BC, int H,
                    int W, void* stream);
 /* The scalar on top of the sums (losses.py:200-232): loss = sum_{b,c} chw[c] f(S0 / S1) (S0 alone when absolute; f = sqrt

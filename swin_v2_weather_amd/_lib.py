@@ -13,9 +13,9 @@ import threading
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB_PATH = os.environ.get("SWV2_LIB") or os.path.join(HERE, "libswv2.so")     # SWV2_LIB: a privately built variant (tools/ab_macro.sh)
-SOURCES = ["capi.hip", "attn.hip", "attn2.hip", "attn_bwd_stream.hip", "attn_wide.hip", "attn_d256.hip", "gemm.hip", "gemm_tn.hip", "gemm_tn_slab.hip", "rowops.hip", "lamb.hip", "block.hip", "cpb.hip", "mlp.hip", "proj_ln.hip", "dataio.hip", "packed.hip", "score.hip", "stats.hip", "quantile.hip", "ensemble.hip", "loss_l1.hip", "sht.hip"]
+SOURCES = ["capi.hip", "attn.hip", "attn2.hip", "attn_bwd_stream.hip", "attn_wide.hip", "attn_d256.hip", "gemm.hip", "gemm_tn.hip", "gemm_tn_slab.hip", "rowops.hip", "lamb.hip", "block.hip", "cpb.hip", "mlp.hip", "proj_ln.hip", "dataio.hip", "packed.hip", "score.hip", "stats.hip", "quantile.hip", "ensemble.hip", "loss_l1.hip", "loss_l2.hip", "sht.hip"]
 
-ABI_VERSION = 112          # SWV2_VERSION of the include/swv2.h these ctypes mirrors were written against (checked in load())
+ABI_VERSION = 113         # SWV2_VERSION of the include/swv2.h these ctypes mirrors were written against (checked in load())
 
 _lib = None
 _lock = threading.Lock()
@@ -248,7 +248,8 @@ SYMBOLS = {
     "swv2_batch_sum": (_I, [_P, _P, _I, _L, _I, _P]),
     "swv2_merge_stats": (_I, [_P, _P, _P, _I, _I, _I, _I, _F, _P]),
     "swv2_merge_ln_bwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
-    "swv2_loss_sums": (_I, [_P, _P, _P, _P, _I, _I, _I, _P]),
+    "swv2_loss_ws_bytes": (C.c_size_t, [_I, _I, _I]),
+    "swv2_loss_sums": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, C.c_size_t, _P]),
     "swv2_loss_grad": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _P]),
     "swv2_loss_part_reduce": (_I, [_P, _I, _I, _I, _I, _I, _I, _P, _P]),
     "swv2_loss_resid_to_image": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),

@@ -3,7 +3,7 @@
 //
 //   launch 1  l1_sums_kernel       8 B/element   per (plane, slice) partial sums (S0, S1) -> workspace
 //   launch 2  l1_finalize_kernel   one workgroup: folds the slices, sums[B C][2]; with chw also the loss and coef[B C]
-//   backward  l1_grad_kernel       8 B/element read, 4 written: dprd = coef[bc] q[h] sign(prd - tar)
+//   backward  plane_grad_kernel<L1Grad>   8 B/element read, 4 written: dprd = coef[bc] q[h] sign(prd - tar)
 //
 //     S0 = sum q[h] |p - t|      S1 = sum q[h] |t|      norm = S0 (absolute) or S0 / S1      loss = sum_bc chw[c] norm[b, c]
 //     coef[bc] = d loss / d S0[bc] = chw[c] (absolute) or chw[c] / S1[bc]
@@ -31,33 +31,12 @@ __global__ __launch_bounds__(256) void l1_sums_kernel(const float* __restrict__ 
     const uint32_t plane = (uint32_t)H * W;                   // < 2^30 (checked by the host)
     uint32_t lo, hi;
     plane_slice_range(plane, sl, slices, lo, hi);
-    const float* p = prd + b * prd_bs + (long)c * plane;
-    const float* t = tar + b * tar_bs + (long)c * plane;
-    float s[2] = {0.f, 0.f};
-    // four independent 16-byte loads of each operand in flight per thread, as score_sums_kernel
-    uint32_t i = lo + threadIdx.x * 4;
-    for (; i + 3 * 1024 < hi; i += 4 * 1024) {
-        f32x4 a[4], bb[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            a[u] = *(const f32x4*)(p + i + u * 1024);
-            bb[u] = *(const f32x4*)(t + i + u * 1024);
-        }
-#pragma unroll
-        for (int u = 0; u < 4; ++u) l1_vec(a[u], bb[u], w[(i + u * 1024) / (uint32_t)W], s);
-    }
-    for (; i < hi; i += 1024) {
-        const f32x4 a = *(const f32x4*)(p + i), bb = *(const f32x4*)(t + i);
-        l1_vec(a, bb, w[i / (uint32_t)W], s);                  // W % 4 == 0: the 4 elements share a latitude row
-    }
+    const float* const op[2] = {prd + b * prd_bs + (long)c * plane, tar + b * tar_bs + (long)c * plane};
+    float s[2];
+    plane_stream_slice(op, lo, hi, W, w, s, [](const f32x4(&v)[2], float q, float(&a)[2]) { l1_vec(v[0], v[1], q, a); });
     __shared__ float r[2][4];
     plane_block_stage(s, r);
-    if (threadIdx.x == 0) {
-        float2 o;
-        o.x = plane_block_total(r[0]);
-        o.y = plane_block_total(r[1]);
-        *(float2*)(ws + ((size_t)pl * slices + sl) * 2) = o;
-    }
+    if (threadIdx.x == 0) *(float2*)(ws + ((size_t)pl * slices + sl) * 2) = make_float2(plane_block_total(r[0]), plane_block_total(r[1]));
 }
 
 // One workgroup of L1_FIN_WAVES waves: wave v folds the slice partials of the planes v, v + 16, ... in ascending order
@@ -100,42 +79,15 @@ __global__ __launch_bounds__(64 * L1_FIN_WAVES) void l1_finalize_kernel(const fl
     }
 }
 
-// grid = (plane / 4096, B * C), the index arithmetic of loss_grad_kernel (rowops.hip): a workgroup handles 4 x 256 float4 units of one
-// (b, c) plane, all eight loads in flight before the first store.  The sign comes from the two comparisons, never from the rounded
+// The element rule of plane_grad_kernel, c = coef[bc] q[h].  The sign comes from the two comparisons, never from the rounded
 // difference: exact whatever the denormal mode, 0 where p == t (as torch.abs differentiates) and where either is NaN.
-__global__ __launch_bounds__(256) void l1_grad_kernel(const float* __restrict__ prd, const float* __restrict__ tar,
-                                                      const float* __restrict__ qw, const float* __restrict__ coef,
-                                                      float* __restrict__ dprd, int H, int W) {
-    const int plane = H * W, bc = blockIdx.y;
-    const size_t base = (size_t)bc * plane;
-    const float cf = coef[bc];
-    f32x4 a[4], b[4];
-    int idx[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-        idx[u] = ((blockIdx.x * 4 + u) * 256 + threadIdx.x) * 4;
-        const int j = min(idx[u], plane - 4);                        // clamped: unconditional loads
-        a[u] = *(const f32x4*)(prd + base + j);
-        b[u] = *(const f32x4*)(tar + base + j);
-    }
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-        if (idx[u] < plane) {
-            const float c = cf * qw[idx[u] / W];
-            f32x4 o;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) o[e] = a[u][e] > b[u][e] ? c : (a[u][e] < b[u][e] ? -c : 0.f);
-            *(f32x4*)(dprd + base + idx[u]) = o;
-        }
-    }
-}
+struct L1Grad {
+    static __device__ __forceinline__ float grad(float c, float p, float t) { return p > t ? c : (p < t ? -c : 0.f); }
+};
 
 }  // namespace
 
-extern "C" size_t swv2_l1_ws_bytes(int planes, int H, int W) {
-    if (planes <= 0 || H <= 0 || W <= 0) return 0;
-    return (size_t)planes * plane_slices(planes) * 2 * sizeof(float);
-}
+extern "C" size_t swv2_l1_ws_bytes(int planes, int H, int W) { return plane_ws_bytes(planes, H, W, 2); }
 
 extern "C" int swv2_l1_sums(const float* prd, long prd_bstride, const float* tar, long tar_bstride, const float* w, int B, int C, int H, int W,
                             void* ws, size_t ws_bytes, void* stream) {
@@ -166,11 +118,5 @@ extern "C" int swv2_l1_finalize(const void* ws, size_t ws_bytes, int B, int C, i
 
 extern "C" int swv2_l1_grad(const float* prd, const float* tar, const float* quad_w, const float* coef, float* dprd, int BC, int H, int W,
                             void* stream) {
-    SWV2_CHECK_ARG(prd && tar && quad_w && coef && dprd && BC > 0 && H > 0 && W > 0 && W % 4 == 0, "l1_grad: bad argument (W % 4)");
-    SWV2_CHECK_ARG((long)H * W < (1L << 30) && BC <= 65535, "l1_grad: plane or B*C too large for the 32-bit index map");
-    SWV2_CHECK_ARG((((uintptr_t)prd | (uintptr_t)tar | (uintptr_t)dprd) & 15) == 0, "l1_grad: pointer not 16-byte aligned");
-    hipLaunchKernelGGL(l1_grad_kernel, dim3(cdiv((long)H * W, 4096), BC), dim3(256), 0, (hipStream_t)stream, prd, tar, quad_w, coef, dprd, H,
-                       W);
-    SWV2_CHECK_LAUNCH("swv2_l1_grad");
-    return SWV2_OK;
+    return plane_grad_launch<L1Grad>("l1_grad", prd, tar, quad_w, coef, dprd, BC, H, W, stream);
 }

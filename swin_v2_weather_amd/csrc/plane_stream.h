@@ -1,6 +1,5 @@
 // The plan of the plane-streaming kernels, stated once: forecast scores (score.hip), dataset statistics (stats.hip), order statistics
-// (quantile.hip), ensemble scores (ensemble.hip), the l1 loss (loss_l1.hip); swv2_loss_sums (rowops.hip) takes its slice count from here.  Each of them reads
-// `planes` planes of H x W fp32 values once (planes = B * C, or C for the statistics) and leaves a few numbers per plane.
+// (quantile.hip), ensemble scores (ensemble.hip), the l1 loss (loss_l1.hip), the l2 loss (loss_l2.hip).  Each of them reads `planes` planes of H x W fp32 values once (planes = B * C, or C for the statistics) and leaves a few numbers per plane.
 //
 // Slices.  A plane is cut into  slices = planes >= 2048 ? 1 : 2048 / planes  pieces, one workgroup of 256 threads each: at most 2048
 // workgroups, one round at 8 per CU (7 .. 56 slices at 146 planes all ran swv2_loss_sums at 4.5 TB/s: the read stream is the bound).
@@ -10,7 +9,8 @@
 //
 // Workgroup index.  (c * slices + sl) * B + b where a per-channel operand is shared (the climatology of score.hip, the row weights of
 // ensemble.hip): the B workgroups that read the same piece of it are neighbours in launch order, so it comes from HBM once and from
-// the memory-side cache afterwards.  plane * slices + sl where nothing is shared (stats.hip, quantile.hip) or the row weights only (loss_l1.hip).
+// the memory-side cache afterwards.  plane * slices + sl where nothing is shared (stats.hip, quantile.hip) or the row weights only (loss_l1.hip,
+// loss_l2.hip).  The sum kernels over prediction and truth walk their slice with plane_stream_slice; their gradients are plane_grad_kernel.
 //
 // Sums.  No float atomics and no pre-zeroed output: every partial sum has ONE owner, and the order of the additions is fixed by the
 // plan alone, so two runs on the same inputs agree bit for bit.  On its way into a plane's sum a term passes through
@@ -83,10 +83,79 @@ __device__ __forceinline__ void plane_fold_slices(const V* __restrict__ part, si
     for (int k = 0; k < N; ++k) a[k] = plane_wave_sum(a[k]);
 }
 
+// The walk of one thread over the slice [lo, hi) of a plane, for NOPS operands streamed side by side (op[k]: the plane's first element):
+// groups of four vectors 1024 elements apart, all 4 NOPS loads issued before the first use (one per iteration ran at 4.2 TB/s), then single vectors.  f(v, q, a) adds the
+// terms of one 16-byte vector position to the NS running sums a -- v[k] from operand k, q = w[row] (W % 4 == 0: the 4 elements share a
+// latitude row) -- and sees every position once, in ascending order: a sum grows by 4 ceil(vectors / 256) terms.  s: out, the thread's
+// sums from zero.  32-bit indices: hi <= plane < 2^30.  (The sums run in an array of this function's own and are handed over at the end:
+// summed straight into the caller's array, score_sums_kernel<false> came out with another schedule and ran 5 - 10 % slower.)
+template <int NOPS, int NS, class F>
+__device__ __forceinline__ void plane_stream_slice(const float* const (&op)[NOPS], uint32_t lo, uint32_t hi, int W, const float* __restrict__ w,
+                                                   float (&s)[NS], F&& f) {
+    float a[NS];
+#pragma unroll
+    for (int k = 0; k < NS; ++k) a[k] = 0.f;
+    uint32_t i = lo + threadIdx.x * 4;
+    for (; i + 3 * 1024 < hi; i += 4 * 1024) {
+        f32x4 v[4][NOPS];
+#pragma unroll
+        for (int u = 0; u < 4; ++u)
+#pragma unroll
+            for (int k = 0; k < NOPS; ++k) v[u][k] = *(const f32x4*)(op[k] + i + u * 1024);
+#pragma unroll
+        for (int u = 0; u < 4; ++u) f(v[u], w[(i + u * 1024) / (uint32_t)W], a);
+    }
+    for (; i < hi; i += 1024) {
+        f32x4 v[NOPS];
+#pragma unroll
+        for (int k = 0; k < NOPS; ++k) v[k] = *(const f32x4*)(op[k] + i);
+        f(v, w[i / (uint32_t)W], a);
+    }
+#pragma unroll
+    for (int k = 0; k < NS; ++k) s[k] = a[k];
+}
+
+// The gradient of a loss whose plane sums carry the row weights: dprd = Rule::grad(coef[bc] * qw[row], p, t) per element.  grid =
+// (ceil(plane / 4096), B * C): a workgroup handles 4 x 256 float4 units of one (b, c) plane, all eight loads in flight before the first
+// store; 32-bit index arithmetic (the first version did two 64-bit divisions per float4).
+template <class Rule>
+__global__ __launch_bounds__(256) void plane_grad_kernel(const float* __restrict__ prd, const float* __restrict__ tar,
+                                                         const float* __restrict__ qw, const float* __restrict__ coef,
+                                                         float* __restrict__ dprd, int H, int W) {
+    const int plane = H * W, bc = blockIdx.y;
+    const size_t base = (size_t)bc * plane;
+    const float cf = coef[bc];
+    f32x4 a[4], b[4];
+    int idx[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+        idx[u] = ((blockIdx.x * 4 + u) * 256 + threadIdx.x) * 4;
+        const int j = min(idx[u], plane - 4);                        // clamped: unconditional loads
+        a[u] = *(const f32x4*)(prd + base + j);
+        b[u] = *(const f32x4*)(tar + base + j);
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+        if (idx[u] < plane) {
+            const float c = cf * qw[idx[u] / W];
+            f32x4 o;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) o[e] = Rule::grad(c, a[u][e], b[u][e]);
+            *(f32x4*)(dprd + base + idx[u]) = o;
+        }
+    }
+}
+
 // ---- host side ----------------------------------------------------------------------------
 // planes * slices fits the 32-bit grid index, an element index fits 30 bits
 inline bool plane_shape_ok(long planes, int H, int W) {
     return planes > 0 && H > 0 && W > 0 && planes < (1L << 31) / PLANE_MAX_BLOCKS && (long)H * W < (1L << 30);
+}
+
+// bytes of a workspace of `floats` fp32 values per (plane, slice); 0 for a non-positive argument (host-only, no HIP call)
+inline size_t plane_ws_bytes(int planes, int H, int W, int floats) {
+    if (planes <= 0 || H <= 0 || W <= 0) return 0;
+    return (size_t)planes * plane_slices(planes) * floats * sizeof(float);
 }
 
 // The operands of an entry point that reads blocks of planes in place ([B, C, H, W] with contiguous planes, sample b at p + b * bstride):
@@ -102,4 +171,17 @@ inline bool plane_operands_ok(const char* who, std::initializer_list<const void*
         if (B != 1 && s < span) return swv2_set_error("%s: batch stride smaller than the C planes of a sample", who), false;
     if (ws_bytes < ws_need) return swv2_set_error("%s: workspace too small (%s)", who, ws_fn), false;
     return true;
+}
+
+// plane_grad_kernel<Rule> over contiguous [BC][H][W] operands, with every check its index map and 16-byte accesses need
+template <class Rule>
+int plane_grad_launch(const char* who, const float* prd, const float* tar, const float* qw, const float* coef, float* dprd, int BC, int H, int W,
+                      void* stream) {
+    SWV2_CHECK_ARG(prd && tar && qw && coef && dprd && BC > 0 && H > 0 && W > 0 && W % 4 == 0, "%s: bad argument (W %% 4)", who);
+    SWV2_CHECK_ARG((long)H * W < (1L << 30) && BC <= 65535, "%s: plane or B*C too large for the 32-bit index map", who);
+    SWV2_CHECK_ARG((((uintptr_t)prd | (uintptr_t)tar | (uintptr_t)dprd) & 15) == 0, "%s: pointer not 16-byte aligned", who);
+    hipLaunchKernelGGL(plane_grad_kernel<Rule>, dim3(cdiv((long)H * W, 4096), BC), dim3(256), 0, (hipStream_t)stream, prd, tar, qw, coef, dprd,
+                       H, W);
+    SWV2_CHECK_LAUNCH(who);
+    return SWV2_OK;
 }

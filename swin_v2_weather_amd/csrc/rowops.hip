@@ -1,8 +1,7 @@
 // Row-wise (HBM-bound) kernels of the SwinV2 hot path: fused LayerNorm + drop-path + residual (+ window reverse /
-// un-roll scatter), its backward, weight preparation, batch sums, the geometric l2 loss, fused Adam.
+// un-roll scatter), its backward, weight preparation, batch sums, fused Adam.
 // All of them stream rows with 16-byte accesses; G lanes cooperate on one row (G = 16/32/64 by channel count).
 #include "common.h"
-#include "plane_stream.h"
 
 namespace {
 
@@ -331,150 +330,6 @@ __global__ void merge_ln_bwd_kernel(const float* __restrict__ x, const uint16_t*
     }
 }
 
-// ------------------------------------------------------------------------------------------------
-// geometric l2 loss (losses.py:188-232, grids.py:115-117): per (b, c) quadrature sums in one pass
-//   sums[(b*C + c)*2 + 0] = sum_{h,w} q[h] (prd - tar)^2 ; [..+1] = sum_{h,w} q[h] tar^2
-// and the backward  dprd = coef[b][c] * q[h] * (prd - tar)   (coef from the host: chain rule of the chosen l2 variant)
-// ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void loss_sums_kernel(const float* __restrict__ prd, const float* __restrict__ tar,
-                                                        const float* __restrict__ qw, float* __restrict__ sums,
-                                                        int H, int W, int slices) {
-    const int bc = blockIdx.x / slices, sl = blockIdx.x - bc * slices;
-    const long plane = (long)H * W;
-    const long lo = plane * sl / slices / 4 * 4, hi = (sl + 1 == slices) ? plane : plane * (sl + 1) / slices / 4 * 4;
-    const float* p = prd + bc * plane;
-    const float* t = tar + bc * plane;
-    float s0 = 0.f, s1 = 0.f;
-    // four independent 16-byte loads of each operand in flight per thread (one pair per iteration ran at 4.2 TB/s)
-    long i = lo + threadIdx.x * 4;
-    for (; i + 3 * 1024 < hi; i += 4 * 1024) {
-        f32x4 a[4], b[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) { a[u] = *(const f32x4*)(p + i + u * 1024); b[u] = *(const f32x4*)(t + i + u * 1024); }
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const float q = qw[(i + u * 1024) / W];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const float d = a[u][e] - b[u][e];
-                s0 = fmaf(q * d, d, s0);
-                s1 = fmaf(q * b[u][e], b[u][e], s1);
-            }
-        }
-    }
-    for (; i < hi; i += 256 * 4) {
-        const f32x4 a = *(const f32x4*)(p + i), b = *(const f32x4*)(t + i);
-        const float q = qw[i / W];                 // W % 4 == 0: the 4 elements share a latitude row
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const float d = a[e] - b[e];
-            s0 = fmaf(q * d, d, s0);
-            s1 = fmaf(q * b[e], b[e], s1);
-        }
-    }
-    s0 = wave_sum(s0);
-    s1 = wave_sum(s1);
-    __shared__ float r0[4], r1[4];
-    if ((threadIdx.x & 63) == 0) { r0[threadIdx.x >> 6] = s0; r1[threadIdx.x >> 6] = s1; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        atomicAdd(sums + bc * 2, r0[0] + r0[1] + r0[2] + r0[3]);
-        atomicAdd(sums + bc * 2 + 1, r1[0] + r1[1] + r1[2] + r1[3]);
-    }
-}
-
-// loss = sum_{b,c} chw[c] f(S0 / S1)  (relative; S0 alone when absolute; f = sqrt unless squared) and the coefficient
-// the backward kernel multiplies in: coef[bc] = 2 d loss / d S0[bc].  One workgroup; replaces the half dozen elementwise /
-// reduction launches (and as many again in their autograd) that torch spent on this [B, C] tensor (losses.py:188-232).
-__global__ __launch_bounds__(256) void loss_finalize_kernel(const float* __restrict__ sums, int layers, const float* __restrict__ chw,
-                                                            int BC, int C, int absolute, int squared,
-                                                            float* __restrict__ loss, float* __restrict__ coef) {
-    float acc = 0.f;
-    for (int i = threadIdx.x; i < BC; i += 256) {
-        float s0 = 0.f, s1 = 0.f;
-        for (int l = 0; l < layers; ++l) { s0 += sums[((size_t)l * BC + i) * 2]; s1 += sums[((size_t)l * BC + i) * 2 + 1]; }
-        const float w = chw[i % C];
-        const float den = absolute ? 1.f : s1;
-        const float r = s0 / den;
-        float f, df;                                    // f(r), f'(r)
-        if (squared) { f = r; df = 1.f; } else { f = sqrtf(r); df = 0.5f / f; }
-        acc += w * f;
-        coef[i] = 2.f * w * df / den;
-    }
-    acc = wave_sum(acc);
-    __shared__ float red[4];
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) *loss = (red[0] + red[1]) + (red[2] + red[3]);
-}
-
-// per-group partial sums of the head epilogue (gemm.hip, Epi<E_UNPATCH_LOSS>: part[g][slot][Cout][2]) -> sums[j][b][..].  grid =
-// (B, SWV2_LOSS_PART_SLICES), 4 sub-slices of 256 threads; thread v < 2 Cout owns one (channel, sum) value and adds the groups
-// of its sample, slice and sub-slice in ascending order (coalesced: the 2 Cout values of a group slot are contiguous); the
-// sub-slices are combined through LDS in a fixed order.  Slot 1 of the group in front of the sample's first group holds the
-// rows of this sample that sit in a group starting in the previous one.
-__global__ __launch_bounds__(1024) void loss_part_reduce_kernel(const float* __restrict__ part, int M, int T, int Cout, int Ct,
-                                                                int coff, int B, float* __restrict__ sums) {
-    const int b = blockIdx.x, j = blockIdx.y, nv = 2 * Cout;
-    constexpr int GR = SWV2_LOSS_GROUP_ROWS;
-    const int ngroups = (M + GR - 1) / GR;
-    const int g_lo = (b * T + GR - 1) / GR, g_hi = min(((b + 1) * T + GR - 1) / GR, ngroups);     // groups whose first row lies in sample b
-    constexpr int S = SWV2_LOSS_PART_SLICES;
-    const int sub = threadIdx.x >> 8, t = threadIdx.x & 255;
-    __shared__ float red[3][256];
-    const int g0 = g_lo + ((j - g_lo) % S + S) % S + sub * S;          // first g >= g_lo with g % S == j, then the sub's offset
-    const size_t gs = (size_t)2 * nv;                                  // floats per group
-    for (int v0 = 0; v0 < nv; v0 += 256) {
-        const int v = v0 + t;
-        float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
-        if (v < nv) {
-            int g = g0;
-            for (; g + 12 * S < g_hi; g += 16 * S) {
-                a0 += part[(size_t)g * gs + v];
-                a1 += part[(size_t)(g + 4 * S) * gs + v];
-                a2 += part[(size_t)(g + 8 * S) * gs + v];
-                a3 += part[(size_t)(g + 12 * S) * gs + v];
-            }
-            for (; g < g_hi; g += 4 * S) a0 += part[(size_t)g * gs + v];
-            if (sub == 0 && b > 0 && g_lo > 0 && (g_lo - 1) % S == j) a1 += part[(size_t)(g_lo - 1) * gs + nv + v];
-        }
-        const float tot = (a0 + a1) + (a2 + a3);
-        if (sub) red[sub - 1][t] = tot;
-        __syncthreads();
-        if (!sub && v < nv) sums[(((size_t)j * B + b) * Ct + coff) * 2 + v] = ((tot + red[0][t]) + red[1][t]) + red[2][t];
-        __syncthreads();
-    }
-}
-
-// grid = (plane / 4096, B * C): a workgroup handles 4 x 256 float4 units of one (b, c) plane, all eight loads in flight
-// before the first store; 32-bit index arithmetic (the first version did two 64-bit divisions per float4)
-__global__ __launch_bounds__(256) void loss_grad_kernel(const float* __restrict__ prd, const float* __restrict__ tar,
-                                                        const float* __restrict__ qw, const float* __restrict__ coef,
-                                                        float* __restrict__ dprd, int H, int W) {
-    const int plane = H * W, bc = blockIdx.y;
-    const size_t base = (size_t)bc * plane;
-    const float cf = coef[bc];
-    f32x4 a[4], b[4];
-    int idx[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-        idx[u] = ((blockIdx.x * 4 + u) * 256 + threadIdx.x) * 4;
-        const int j = min(idx[u], plane - 4);                        // clamped: unconditional loads
-        a[u] = *(const f32x4*)(prd + base + j);
-        b[u] = *(const f32x4*)(tar + base + j);
-    }
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-        if (idx[u] < plane) {
-            const float c = cf * qw[idx[u] / W];
-            f32x4 o;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) o[e] = c * (a[u][e] - b[u][e]);
-            *(f32x4*)(dprd + base + idx[u]) = o;
-        }
-    }
-}
-
 // fused Adam over one flat fp32 buffer (torch.optim.Adam semantics, train.py:176: betas (0.9, 0.95), eps 1e-8,
 // no weight decay, bias correction).  step_size = lr / (1 - b1^t), bc2_sqrt = sqrt(1 - b2^t); inv_scale un-scales grads.
 // THE element update (adam_kernel, adam_multi_kernel's 16-byte walk); g is the un-scaled gradient.  adam_multi_kernel's scalar walk
@@ -694,98 +549,6 @@ extern "C" int swv2_merge_ln_bwd(const float* x, const void* dn_bf16, const floa
     hipLaunchKernelGGL(merge_ln_bwd_kernel, dim3(min(cdiv(M, 4), 4096)), dim3(256), 0, (hipStream_t)stream, x,
                        (const uint16_t*)dn_bf16, gamma, mean, rstd, dx, dgamma, dbeta, B, H, W, C);
     SWV2_CHECK_LAUNCH("swv2_merge_ln_bwd");
-    return SWV2_OK;
-}
-
-extern "C" int swv2_loss_sums(const float* prd, const float* tar, const float* quad_w, float* sums, int BC, int H, int W,
-                              void* stream) {
-    SWV2_CHECK_ARG(prd && tar && quad_w && sums && BC > 0 && H > 0 && W > 0 && W % 4 == 0, "loss_sums: bad argument (W % 4)");
-    const int slices = plane_slices(BC);                      // the slice count of plane_stream.h (loss_sums_kernel holds the same bounds in 64-bit form)
-    hipLaunchKernelGGL(loss_sums_kernel, dim3(BC * slices), dim3(256), 0, (hipStream_t)stream, prd, tar, quad_w, sums, H, W,
-                       slices);
-    SWV2_CHECK_LAUNCH("swv2_loss_sums");
-    return SWV2_OK;
-}
-
-extern "C" int swv2_loss_part_reduce(const float* part, int M, int T, int B, int Cout, int Ct, int coff, float* sums, void* stream) {
-    SWV2_CHECK_ARG(part && sums && M > 0 && T >= SWV2_LOSS_GROUP_ROWS && B > 0 && M == B * T && Cout > 0 && coff >= 0 && coff + Cout <= Ct,
-                   "loss_part_reduce: bad argument");
-    hipLaunchKernelGGL(loss_part_reduce_kernel, dim3(B, SWV2_LOSS_PART_SLICES), dim3(1024), 0, (hipStream_t)stream, part, M, T, Cout,
-                       Ct, coff, B, sums);
-    SWV2_CHECK_LAUNCH("swv2_loss_part_reduce");
-    return SWV2_OK;
-}
-
-extern "C" int swv2_loss_finalize(const float* sums, int layers, const float* chw, int BC, int C, int absolute, int squared, float* loss,
-                                  float* coef, void* stream) {
-    SWV2_CHECK_ARG(sums && chw && loss && coef && BC > 0 && C > 0 && BC % C == 0 && layers > 0, "loss_finalize: bad argument");
-    hipLaunchKernelGGL(loss_finalize_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, sums, layers, chw, BC, C, absolute, squared, loss,
-                       coef);
-    SWV2_CHECK_LAUNCH("swv2_loss_finalize");
-    return SWV2_OK;
-}
-
-extern "C" int swv2_loss_grad(const float* prd, const float* tar, const float* quad_w, const float* coef, float* dprd,
-                              int BC, int H, int W, void* stream) {
-    SWV2_CHECK_ARG(prd && tar && quad_w && coef && dprd && BC > 0 && W % 4 == 0, "loss_grad: bad argument (W % 4)");
-    SWV2_CHECK_ARG((long)H * W < (1L << 30) && BC <= 65535, "loss_grad: plane or B*C too large for the 32-bit index map");
-    hipLaunchKernelGGL(loss_grad_kernel, dim3(cdiv((long)H * W, 4096), BC), dim3(256), 0, (hipStream_t)stream, prd, tar, quad_w,
-                       coef, dprd, H, W);
-    SWV2_CHECK_LAUNCH("swv2_loss_grad");
-    return SWV2_OK;
-}
-
-// The loss epilogue's weighted residual back in IMAGE layout, scaled: out[b][c][4i+p][4j+q] = coef[b][c] * resid[(b,i,j)][c*16 + p*4 + q]
-// (+ add[b][c][..]) -- d loss / d prediction of a rollout step whose head carries a skip connection from an input that needs a
-// gradient (swinv2_global.py:799-801 inside helpers.py:26-41).  Workgroup = 16 consecutive patches of one patch row: their residual rows
-// (16 x N bf16, contiguous rows) go through LDS, then lane -> (patch, image row p) per channel so that a store instruction writes
-// 256 contiguous bytes.  Reads 2 N bytes per patch once; the two-pass loss_grad_kernel reads prediction and target (8 N bytes).
-template <int TOK>
-__global__ __launch_bounds__(256) void resid_to_image_kernel(const uint16_t* __restrict__ resid, const float* __restrict__ coef,
-                                                             const float* __restrict__ add, float* __restrict__ out, int Cout, int H,
-                                                             int W, int Cs, int Cadd, int gw) {
-    extern __shared__ __attribute__((aligned(16))) uint16_t rs[];
-    const int N = Cout * 16, P = N + 8;                    // LDS pitch
-    const int RP = SWV2_LOSS_RESID_PITCH(N);               // row pitch of the residual in memory
-    const int tid = threadIdx.x;
-    const int j0 = blockIdx.x * TOK, i = blockIdx.y, b = blockIdx.z;
-    const int gh = H >> 2;
-    const long m0 = ((long)b * gh + i) * gw + j0;
-    const int ntok = min(TOK, gw - j0);
-    const int cpr = N / 8;                                 // 16-byte chunks per row
-    for (int u = tid; u < ntok * cpr; u += 256) {
-        const int t = u / cpr, ch = u - t * cpr;
-        *(uint4*)(rs + t * P + 8 * ch) = *(const uint4*)(resid + (m0 + t) * RP + 8 * ch);
-    }
-    __syncthreads();
-    const int t = tid & (TOK - 1);
-    const long plane = (long)H * W;
-    for (int cp = tid / TOK; cp < Cout * 4; cp += 256 / TOK) {
-        const int c = cp >> 2, p = cp & 3;
-        if (t >= ntok) continue;
-        const uint2 r = *(const uint2*)(rs + t * P + c * 16 + p * 4);
-        const float cf = coef[b * Cout + c];
-        f32x4 v = {cf * __uint_as_float(r.x << 16), cf * __uint_as_float(r.x & 0xffff0000u), cf * __uint_as_float(r.y << 16),
-                   cf * __uint_as_float(r.y & 0xffff0000u)};
-        const long pix = (long)(4 * i + p) * W + 4 * (j0 + t);
-        if (add) v += *(const f32x4*)(add + ((long)b * Cadd + c) * plane + pix);
-        *(f32x4*)(out + ((long)b * Cs + c) * plane + pix) = v;
-    }
-}
-
-extern "C" int swv2_loss_resid_to_image(const void* resid, const float* coef, const float* add, float* out, int B, int Cout, int H, int W,
-                                        int Cs, int Cadd, void* stream) {
-    SWV2_CHECK_ARG(resid && coef && out && B > 0 && Cout > 0 && H > 0 && W > 0 && H % 4 == 0 && W % 4 == 0 && Cs >= Cout && (!add || Cadd >= Cout),
-                   "loss_resid_to_image: bad argument");
-    SWV2_CHECK_ARG(B <= 65535 && H / 4 <= 65535, "loss_resid_to_image: grid too large");
-    SWV2_CHECK_ARG((((uintptr_t)resid | (uintptr_t)out | (uintptr_t)add) & 15) == 0, "loss_resid_to_image: unaligned pointer");
-    constexpr int TOK = 16;
-    const int gw = W / 4, gh = H / 4;
-    const size_t lds = (size_t)TOK * (Cout * 16 + 8) * 2;
-    SWV2_CHECK_ARG(lds <= 64 * 1024, "loss_resid_to_image: Cout too large for the staging tile");
-    hipLaunchKernelGGL((resid_to_image_kernel<TOK>), dim3(cdiv(gw, TOK), gh, B), dim3(256), lds, (hipStream_t)stream, (const uint16_t*)resid,
-                       coef, add, out, Cout, H, W, Cs, Cadd, gw);
-    SWV2_CHECK_LAUNCH("swv2_loss_resid_to_image");
     return SWV2_OK;
 }
 

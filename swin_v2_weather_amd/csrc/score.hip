@@ -41,26 +41,13 @@ __global__ __launch_bounds__(256) void score_sums_kernel(const float* __restrict
     plane_slice_range(plane, sl, slices, lo, hi);
     const float* p = prd + b * prd_bs + (long)c * plane;
     const float* t = tar + b * tar_bs + (long)c * plane;
-    const float* m = CLIM ? clim + (long)c * plane : nullptr;
-    float s[4] = {0.f, 0.f, 0.f, 0.f};
-    const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
-    // four independent 16-byte loads of each operand in flight per thread (loss_sums_kernel: one per iteration ran at 4.2 TB/s)
-    uint32_t i = lo + threadIdx.x * 4;
-    for (; i + 3 * 1024 < hi; i += 4 * 1024) {
-        f32x4 a[4], bb[4], mm[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            a[u] = *(const f32x4*)(p + i + u * 1024);
-            bb[u] = *(const f32x4*)(t + i + u * 1024);
-            mm[u] = CLIM ? *(const f32x4*)(m + i + u * 1024) : zero;
-        }
-#pragma unroll
-        for (int u = 0; u < 4; ++u) score_vec<CLIM>(a[u], bb[u], mm[u], w[(i + u * 1024) / (uint32_t)W], s);
-    }
-    for (; i < hi; i += 1024) {
-        const f32x4 a = *(const f32x4*)(p + i), bb = *(const f32x4*)(t + i);
-        const f32x4 mm = CLIM ? *(const f32x4*)(m + i) : zero;
-        score_vec<CLIM>(a, bb, mm, w[i / (uint32_t)W], s);      // W % 4 == 0: the 4 elements share a latitude row
+    float s[4];
+    if constexpr (CLIM) {
+        const float* const op[3] = {p, t, clim + (long)c * plane};
+        plane_stream_slice(op, lo, hi, W, w, s, [](const f32x4(&v)[3], float q, float(&a)[4]) { score_vec<true>(v[0], v[1], v[2], q, a); });
+    } else {
+        const float* const op[2] = {p, t};
+        plane_stream_slice(op, lo, hi, W, w, s, [](const f32x4(&v)[2], float q, float(&a)[4]) { score_vec<false>(v[0], v[1], v[1], q, a); });      // (m is not read)
     }
     __shared__ float r[4][4];
     plane_block_stage(s, r);
@@ -106,10 +93,7 @@ extern "C" int swv2_score_slices(int planes, int H, int W) {
     return plane_slices(planes);
 }
 
-extern "C" size_t swv2_score_ws_bytes(int planes, int H, int W) {
-    if (planes <= 0 || H <= 0 || W <= 0) return 0;
-    return (size_t)planes * plane_slices(planes) * 4 * sizeof(float);
-}
+extern "C" size_t swv2_score_ws_bytes(int planes, int H, int W) { return plane_ws_bytes(planes, H, W, 4); }
 
 extern "C" int swv2_score_sums(const float* prd, long prd_bstride, const float* tar, long tar_bstride, const float* clim, const float* w,
                                int B, int C, int H, int W, void* ws, size_t ws_bytes, void* stream) {

@@ -369,9 +369,13 @@ def merge_ln_bwd(x, dn, gamma, mean, rstd, dx, dgamma, dbeta):
                                        B, H, W, Cc, _stream()), "swv2_merge_ln_bwd")
 
 
-def loss_sums(prd, tar, qw, sums):
+def loss_sums(prd, tar, qw, sums, ws=None):
+    """sums [B, C, 2] = (sum q (prd - tar)^2, sum q tar^2) per plane, written in full; prd, tar contiguous fp32 [B, C, H, W]; ws: a
+    loss_workspace to reuse (allocated here otherwise)"""
     B, Cc, H, W = prd.shape
-    L.check(L.load().swv2_loss_sums(_p(prd), _p(tar), _p(qw), _p(sums), B * Cc, H, W, _stream()), "swv2_loss_sums")
+    if ws is None:
+        ws = loss_workspace(B * Cc, H, W, prd.device)
+    L.check(L.load().swv2_loss_sums(_p(prd), _p(tar), _p(qw), _p(sums), B * Cc, H, W, _p(ws), ws.numel() * 4, _stream()), "swv2_loss_sums")
 
 
 def loss_finalize(sums, chw, absolute: bool, squared: bool, loss, coef):
@@ -482,6 +486,11 @@ def forecast_scores(prd, tar, w, clim=None, scale=None, ws=None):
 def l1_workspace(planes: int, H: int, W: int, device) -> torch.Tensor:
     """the caller's workspace of swv2_l1_sums / swv2_l1_finalize for `planes` = B * C planes: allocate once, reuse"""
     return torch.empty(int(L.load().swv2_l1_ws_bytes(planes, H, W)) // 4, dtype=torch.float32, device=device)
+
+
+def loss_workspace(planes: int, H: int, W: int, device) -> torch.Tensor:
+    """the caller's workspace of swv2_loss_sums for `planes` = B * C planes: allocate once, reuse"""
+    return torch.empty(int(L.load().swv2_loss_ws_bytes(planes, H, W)) // 4, dtype=torch.float32, device=device)
 
 
 def l1_sums(prd, tar, w, ws):

@@ -1,7 +1,7 @@
 """LossHandler with the reference's surface and semantics (utils/losses.py:30-232) on the fused quadrature kernels.
 
 The O(B*C*H*W) work -- the latitude-weighted sums of (prd - tar)^2 and tar^2 per (sample, channel) plane and the
-gradient d loss / d prd -- is two HIP kernels (swv2_loss_sums / swv2_loss_grad); the remaining arithmetic is on
+gradient d loss / d prd -- is two HIP entry points (swv2_loss_sums / swv2_loss_grad, csrc/loss_l2.hip); the remaining arithmetic is on
 [B, C] tensors.  Supported: the 'l2' family used by every entry of config/swin.yaml ('l2', 'squared geometric l2',
 'weighted absolute|relative temp-std squared geometric l2') and the 'l1' family (every string with the word l1 and
 without l2: losses.py:114-120 builds the same class with p = 1).
@@ -120,14 +120,15 @@ class _GeoL1(torch.autograd.Function):
 
 
 class _QuadSums(torch.autograd.Function):
-    """sums[b, c] = (sum_hw q[h] (prd - tar)^2, sum_hw q[h] tar^2); backward: dprd = 2 dS0[b,c] q[h] (prd - tar)"""
+    """sums[b, c] = (sum_hw q[h] (prd - tar)^2, sum_hw q[h] tar^2); backward: dprd = 2 dS0[b,c] q[h] (prd - tar).  `ws`: the
+    caller's workspace for this shape (ops.loss_workspace), or None"""
 
     @staticmethod
-    def forward(ctx, prd, tar, qw):
+    def forward(ctx, prd, tar, qw, ws=None):
         prd, tar = prd.contiguous().float(), tar.contiguous().float()
         B, C = prd.shape[:2]
-        sums = torch.zeros(B, C, 2, dtype=torch.float32, device=prd.device)
-        ops.loss_sums(prd, tar, qw, sums)
+        sums = torch.empty(B, C, 2, dtype=torch.float32, device=prd.device)
+        ops.loss_sums(prd, tar, qw, sums, ws)
         ctx.save_for_backward(prd, tar, qw)
         return sums
 
@@ -137,20 +138,21 @@ class _QuadSums(torch.autograd.Function):
         coef = (2.0 * dsums[..., 0]).contiguous().float()
         dprd = torch.empty_like(prd)
         ops.loss_grad(prd, tar, qw, coef, dprd)
-        return dprd, None, None
+        return dprd, None, None, None
 
 
 class _GeoL2(torch.autograd.Function):
     """The whole LossHandler value as one node: loss_sums (one pass over prd / tar), loss_finalize (the [B, C] arithmetic +
-    the backward coefficients), and in backward one loss_grad pass.  Same value and gradient as _QuadSums + torch ops."""
+    the backward coefficients), and in backward one loss_grad pass.  Same value and gradient as _QuadSums + torch ops.  `ws` as
+    for _QuadSums."""
 
     @staticmethod
-    def forward(ctx, prd, tar, qw, chw, absolute, squared):
+    def forward(ctx, prd, tar, qw, chw, absolute, squared, ws=None):
         prd, tar = prd.contiguous().float(), tar.contiguous().float()
         B, C = prd.shape[:2]
-        buf = torch.zeros(B * C * 3 + 1, dtype=torch.float32, device=prd.device)      # sums | coef | loss: one memset
+        buf = torch.empty(B * C * 3 + 1, dtype=torch.float32, device=prd.device)      # sums | coef | loss: one allocation, all written
         sums, coef, loss = buf[:B * C * 2].view(B, C, 2), buf[B * C * 2:B * C * 3], buf[B * C * 3:]
-        ops.loss_sums(prd, tar, qw, sums)
+        ops.loss_sums(prd, tar, qw, sums, ws)
         ops.loss_finalize(sums, chw, absolute, squared, loss, coef)
         ctx.save_for_backward(prd, tar, qw, coef)
         return loss.view(())
@@ -160,7 +162,7 @@ class _GeoL2(torch.autograd.Function):
         prd, tar, qw, coef = ctx.saved_tensors
         dprd = torch.empty_like(prd)
         ops.loss_grad(prd, tar, qw, (coef * gout).contiguous(), dprd)
-        return dprd, None, None, None, None, None
+        return dprd, None, None, None, None, None, None
 
 
 class _FusedGeoL2(torch.autograd.Function):
@@ -318,6 +320,7 @@ class LossHandler(nn.Module):
             rule = legendre_gauss_quadrature_weights
         self.register_buffer('quad_rows', rule(self.img_shape[0], self.img_shape[1], True).contiguous())
         self._l1_ws = {}                       # (device, B, C) -> the l1 kernels' workspace of that shape, made once and reused
+        self._l2_ws = {}                       # the same for swv2_loss_sums
         ms = torch.ones(self.n_future + 1, dtype=torch.float32) / float(self.n_future + 1)
         self.register_buffer('multistep_weight', ms.reshape(-1, 1, 1, 1))
 
@@ -362,11 +365,16 @@ class LossHandler(nn.Module):
                       chw.numel() == prd.shape[1] and prd.shape[0] * prd.shape[1] <= 65535 and prd.shape[2] * prd.shape[3] < 2 ** 30)
         if not on_kernels:
             return geometric_l1_torch(prd, tar, self.quad_rows, chw, self.absolute)
+        return _GeoL1.apply(prd, tar, self.quad_rows, chw.reshape(-1).contiguous().float(), self.absolute,
+                            self._workspace(self._l1_ws, ops.l1_workspace, prd))
+
+    @staticmethod
+    def _workspace(cache, make, prd):
         B, C, H, W = prd.shape
         key = (prd.device, B, C)
-        if key not in self._l1_ws:
-            self._l1_ws[key] = ops.l1_workspace(B * C, H, W, prd.device)
-        return _GeoL1.apply(prd, tar, self.quad_rows, chw.reshape(-1).contiguous().float(), self.absolute, self._l1_ws[key])
+        if key not in cache:
+            cache[key] = make(B * C, H, W, prd.device)
+        return cache[key]
 
     def forward(self, prd: torch.Tensor, tar: torch.Tensor, inp: torch.Tensor = None):
         lc, self._fused = self._fused, None
@@ -384,9 +392,10 @@ class LossHandler(nn.Module):
                 self._chw_key = key
             return _FusedGeoL2.apply(lc.sums if rsums is None else rsums, self._chw_flat, self.absolute, self.squared)
         chw = self._chw_now()
+        ws = self._workspace(self._l2_ws, ops.loss_workspace, prd)
         if prd.is_cuda and prd.requires_grad and not tar.requires_grad and os.environ.get("SWV2_LOSS_FUSED", "1") != "0":
-            return _GeoL2.apply(prd, tar, self.quad_rows, chw.reshape(-1).contiguous().float(), self.absolute, self.squared)
-        sums = _QuadSums.apply(prd, tar, self.quad_rows)
+            return _GeoL2.apply(prd, tar, self.quad_rows, chw.reshape(-1).contiguous().float(), self.absolute, self.squared, ws)
+        sums = _QuadSums.apply(prd, tar, self.quad_rows, ws)
         norms = sums[..., 0]
         if not self.absolute:
             norms = norms / sums[..., 1]

@@ -197,9 +197,9 @@ def test_lead_time_table_gains_the_ensemble_columns():
 
 # ---- the host half of the entry points ------------------------------------------------------------------------------------
 def test_abi_version_workspace_arithmetic_and_chain_lengths():
-    assert L.ABI_VERSION == 112 and "ensemble.hip" in L.SOURCES
+    assert L.ABI_VERSION == 113 and "ensemble.hip" in L.SOURCES
     lib = L.load()
-    assert lib.swv2_version() == 112
+    assert lib.swv2_version() == 113
     for (B, C, H, W) in ((1, 1, 1, 4), (2, 3, 5, 8), (1, 73, 720, 1440), (1, 2100, 2, 4), (3, 5, 16, 32)):
         slices = lib.swv2_score_slices(B * C, H, W)
         for m in (2, 8, 9, 16, 17, 50, 64):

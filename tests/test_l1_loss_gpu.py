@@ -212,15 +212,13 @@ def test_legendre_gauss_grid_for_l1_and_l2_against_fp64(dev, lib, tmp_path):
     ref, bound, _, _ = R.loss(S, R.sum_bounds(A, R.chain_length(H, W, slices)), lh.channel_weights.reshape(-1).cpu().numpy(), False)
     print(f"legendre_gauss 'geometric l1': {float(v.detach()):.7f}, fp64 {ref:.9f}, error / bound {abs(float(v.detach()) - ref) / bound:.3f}")
     assert abs(float(v.detach()) - ref) <= bound
-    # l2: sum_bc chw S_dd / S_tt.  swv2_loss_sums: the chain of score.hip's thread sum and butterfly, three additions for the four waves and
-    # the slices added by float atomics in arrival order (slices - 1 more); 4 roundings per term (tests/score_reference.py); swv2_loss_finalize:
-    # the division, the product with chw and ceil(B C / 256) + 6 + 3 additions
+    # l2: sum_bc chw S_dd / S_tt.  swv2_loss_sums: the chain of score.hip's sums (tests/score_reference.py::chain_length), 4 roundings per
+    # term; swv2_loss_finalize: the division, the product with chw and ceil(B C / 256) + 6 + 3 additions
     lh2 = handler("squared geometric l2", 0, tmp_path, aux, grid="legendre_gauss").to(dev).train()
     assert torch.equal(lh2.quad_rows.cpu(), q) and lh2.squared
     v2 = lh2(prd.to(dev).requires_grad_(True), tar.to(dev), None)
     S2, A2 = RS.sums(prd.numpy(), tar.numpy(), q.numpy())
-    vmax = max((hi - lo) // 4 for lo, hi in RS.slice_bounds(H * W, slices))
-    d2 = RS.gamma(4 * math.ceil(vmax / 256) + 6 + 3 + slices - 1 + RS.C_TERM) * A2
+    d2 = RS.sum_bounds(A2, RS.chain_length(H, W, slices))
     cw = lh2.channel_weights.reshape(1, -1).cpu().numpy().astype(np.float64)
     ratio = S2[..., 0] / S2[..., 3]
     dratio = (S2[..., 0] + d2[..., 0]) * (1 + R.U) / (S2[..., 3] - d2[..., 3]) - ratio

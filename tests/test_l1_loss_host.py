@@ -190,9 +190,9 @@ def test_legendre_gauss_rows_against_what_defines_the_rule(tmp_path):
 
 
 def test_abi_version_sources_and_workspace_arithmetic():
-    assert L.ABI_VERSION == 112 and "loss_l1.hip" in L.SOURCES
+    assert L.ABI_VERSION == 113 and "loss_l1.hip" in L.SOURCES
     lib = L.load()
-    assert lib.swv2_version() == 112
+    assert lib.swv2_version() == 113
     for (B, C, H, W) in ((1, 1, 1, 4), (2, 3, 5, 8), (1, 73, 720, 1440), (2, 73, 720, 1440), (1, 2100, 2, 4), (3, 5, 16, 32)):
         slices = lib.swv2_score_slices(B * C, H, W)
         assert lib.swv2_l1_ws_bytes(B * C, H, W) == B * C * slices * 8 and slices == R.plan_slices(B * C)

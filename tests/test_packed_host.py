@@ -256,7 +256,7 @@ def test_dataset_stats_on_a_packed_folder_equal_those_of_its_unpacked_folder(tmp
 # ---- the entry points, host half ---------------------------------------------------------------------------------------
 def test_workspace_arithmetic_and_abi_version():
     lib = L.load()
-    assert L.ABI_VERSION == 112 and lib.swv2_version() == 112
+    assert L.ABI_VERSION == 113 and lib.swv2_version() == 113
     for C, H, W, slices in ((73, 721, 1440, 28), (3, 9, 16, 682), (5, 33, 132, 409), (2048, 4, 4, 1), (4000, 4, 4, 1)):
         assert lib.swv2_pack_range_ws_bytes(C, H, W) == C * slices * 16 and lib.swv2_stats_slices(C, H, W) == slices
     for bad in ((0, 4, 4), (4, 0, 4), (4, 4, 0), (-1, 4, 4)):

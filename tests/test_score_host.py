@@ -138,9 +138,9 @@ def test_load_climatology_crops_selects_channels_and_normalises(tmp_path):
 
 
 def test_abi_version_plan_and_workspace_arithmetic():
-    assert L.ABI_VERSION == 112
+    assert L.ABI_VERSION == 113
     lib = L.load()
-    assert lib.swv2_version() == 112
+    assert lib.swv2_version() == 113
     for (B, C, H, W), slices in PLAN.items():
         assert lib.swv2_score_slices(B * C, H, W) == slices == R.plan_slices(B * C), (B, C, H, W)
         assert lib.swv2_score_ws_bytes(B * C, H, W) == B * C * slices * 16

@@ -225,9 +225,9 @@ def test_cli_flags():
 
 def test_abi_host_side():
     from swin_v2_weather_amd import _lib as L
-    assert "sht.hip" in L.SOURCES and L.ABI_VERSION == 112
+    assert "sht.hip" in L.SOURCES and L.ABI_VERSION == 113
     lib = L.load()
-    assert lib.swv2_version() == 112
+    assert lib.swv2_version() == 113
     for planes, lmax, mmax in ((1, 2, 3), (146, 720, 721), (5, 24, 9), (17, 19, 8), (3, 8, 17)):
         assert lib.swv2_sht_ws_bytes(planes, lmax, mmax) == -(-min(mmax, lmax) // L.SHT_MRUN) * planes * lmax * 4
     for bad in ((0, 8, 8), (4, 0, 8), (4, 8, 0), (-1, 8, 8), (4, -8, 8), (4, 8, -3)):

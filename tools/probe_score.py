@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Time swv2_score_sums against the unchanged swv2_loss_sums (the same read stream over prediction and truth).  GPU box.
+"""Time swv2_score_sums against swv2_loss_sums (the same read stream over prediction and truth; its two launches, sums and fold, timed as one).  GPU box.
 
 One process, device events around every launch, warm-up first, the kernels ALTERNATING launch by launch (loss_sums, score_sums without
 climatology, score_sums with climatology, swv2_score_finalize), --launches each per repeat, the whole measurement --repeats times for
@@ -30,10 +30,10 @@ prd, tar = torch.randn(B, C, H, W, device=dev, generator=g), torch.randn(B, C, H
 clim = torch.randn(C, H, W, device=dev, generator=g)
 from swin_v2_weather_amd.utils.weighted_acc_rmse import latitude_weights
 w = latitude_weights(H, dev)
-loss_out = torch.zeros(B, C, 2, device=dev)
-ws = ops.score_workspace(B * C, H, W, dev)
+loss_out = torch.empty(B, C, 2, device=dev)
+ws, loss_ws = ops.score_workspace(B * C, H, W, dev), ops.loss_workspace(B * C, H, W, dev)
 kernels = {
-    "loss_sums": lambda: ops.loss_sums(prd, tar, w, loss_out),
+    "loss_sums": lambda: ops.loss_sums(prd, tar, w, loss_out, loss_ws),
     "score_sums": lambda: ops.score_sums(prd, tar, w, ws),
     "score_sums_clim": lambda: ops.score_sums(prd, tar, w, ws, clim),
     "score_finalize": lambda: ops.score_finalize(ws, B, C, H, W),
