@@ -1169,8 +1169,9 @@ __global__ __launch_bounds__(WTH) void gemm_nt_wide_kernel(ALoad<AK> al, const u
 }
 
 // ------------------------------------------------------------------------------------------------
-// Resident-weight kernel for the two per-block row-streaming products at the benchmark width (qkv: N = 384, K = 128 and
-// d(qkv) -> dx: N = 128, K = 384).  gemm_nt_kernel above is latency-bound there (measured: ~20 us workgroup lifetime for
+// Resident-weight kernel for the qkv product of a block at the benchmark width (N = 384, K = 128; N = 256, K = 192 per q / k / v part at
+// C = 192).  The block's other row-streaming product, d(qkv) -> dx (N = 128, K = 384), started on this body and now runs the streaming
+// body of gemm_rw.hip (weight in registers, rows by LDS-DMA).  gemm_nt_kernel above is latency-bound there (measured: ~20 us workgroup lifetime for
 // 64 rows = one HBM round trip for the A panel + six dependent L2 round trips for the weight tiles + three epilogues, at
 // three workgroups per CU -> 3 TB/s).  Here ONE persistent 8-wave workgroup per CU keeps the whole bf16 weight (96 KB) in
 // LDS, walks row tiles t = blockIdx.x, + gridDim.x, ... and always has the NEXT tile's A rows in flight in registers while
@@ -1201,7 +1202,7 @@ __global__ __launch_bounds__(512) void gemm_rw_kernel(ALoad<AK> al, const uint16
     // The epilogue must not LOAD from global memory: such a load sits behind the next tile's A prefetch in the in-order
     // vmcnt queue, so waiting for it exposes the whole HBM round trip of the prefetch right there (measured with the
     // generic Epi::tile: 52 % / 40 % of the kernel inside the epilogue, 6 % in the explicit wait for A).  The bias lives
-    // in LDS; the scatter rows and the residual rows of the d(qkv) -> dx product are prefetched WITH the A rows.
+    // in LDS.
     __shared__ __attribute__((aligned(16))) float bs[N];
     uint16_t* As = (uint16_t*)as_raw;
     float* stage_all = (float*)as_raw;
@@ -1210,34 +1211,23 @@ __global__ __launch_bounds__(512) void gemm_rw_kernel(ALoad<AK> al, const uint16
     const int fr = lane & 15, g = lane >> 4;
     const int wr = wave >> 1, wc = wave & 1;
     const int ntiles = (M + BMT - 1) / BMT;
-    static_assert(EK != E_F32 || (RT == 1 && CT == 4), "the E_F32 prefetch below covers one 16 x 64 wave tile");
+    static_assert(AK == A_F32 && EK == E_QKV_HEADS, "instantiated for the qkv product only");
     for (int i = tid; i < N; i += NTH) bs[i] = ep.d.bias ? ep.d.bias[i] : 0.f;
-    // E_F32: this lane's epilogue row (lane >> 2 of the wave's 16) and its 16 columns
-    int erow_nxt = -1, erow_cur = -1;                       // destination row of the tile in flight / being computed
-    f32x4 aux_nxt[4], aux_cur[4];
-    const int ecol = wc * (N / 2) + (lane & 3) * 16;
 
     // ONE tile of A rows in flight per workgroup in registers.  (Two sets used alternately were measured SLOWER, 60.5 vs
     // 54.1 us for qkv: the kernel is not short of outstanding bytes.)  The gather rows of tile t + 2G are resolved while
     // tile t + G's data loads are issued, so the index load is never in front of a data load.
     typename ALoad<AK>::Raw ra[ACH];
     int arow[ACH];
-    int erow_res = -1;
-    // chunk c of a tile -> (row, 16-byte chunk column).  Row-major operands: consecutive threads walk a row.  Head-major
-    // operand ([Bw][h][S][Lp][16]: one (row, head) is 32 bytes, consecutive ROWS of a head are contiguous): consecutive
-    // threads take the two halves of a head for consecutive rows, so a wave reads 32 rows x 32 bytes = 1 KB contiguous
-    // (row-major order gave 32 separate 32-byte pieces per wave instruction).
-    auto crow = [&](int c) { return AK == A_HEADS ? ((c >> 1) & (BMT - 1)) : c / KC; };
-    auto ccol = [&](int c) { return AK == A_HEADS ? (((c / (2 * BMT)) << 1) | (c & 1)) : c % KC; };
-    static_assert(AK != A_HEADS || (BMT & (BMT - 1)) == 0, "head-major chunk map needs a power-of-two tile height");
+    // chunk c of a tile -> (row, 16-byte chunk column): consecutive threads walk a row
+    auto crow = [&](int c) { return c / KC; };
+    auto ccol = [&](int c) { return c % KC; };
     // Every load of the staging pipeline is UNCONDITIONAL (clamped address); validity travels in bit masks and invalid
     // chunks (rows past M, padded window rows) are zeroed when the tile is written to LDS.  Loads under `if` made the
     // compiler guard their destination registers with s_waitcnt vmcnt(0) right behind them, which turned the prefetch into
-    // a synchronous load (see gemm_tn.hip).  The launcher guarantees the tables this kernel reads unconditionally: a gather
-    // table for the fp32 operand, a scatter table + residual for the E_F32 epilogue.
+    // a synchronous load (see gemm_tn.hip).  The launcher guarantees the gather table this kernel reads unconditionally.
     uint32_t ain = 0;                 // bit i: chunk row i of the next issue lies inside [0, M)
     uint32_t aok = 0;                 // chunks in flight: bit i = valid
-    bool ein = false;                 // E_F32: this lane's epilogue row of the next tile lies inside [0, M)
     auto resolve = [&](int t) {
         ain = 0;
 #pragma unroll
@@ -1245,13 +1235,7 @@ __global__ __launch_bounds__(512) void gemm_rw_kernel(ALoad<AK> al, const uint16
             const int c = tid + i * NTH, m = t * BMT + crow(c);
             const bool in = (t < ntiles) && (m < M);
             ain |= (uint32_t)in << i;
-            if constexpr (AK == A_F32) arow[i] = al.d.rowidx[min(m, M - 1)];        // gather table entry (may be -1: padded row)
-            else arow[i] = min(m, M - 1);
-        }
-        if constexpr (EK == E_F32) {
-            const int m = t * BMT + wr * 16 + (lane >> 2);
-            ein = (t < ntiles) && (m < M);
-            erow_res = ein ? ep.d.rowidx[m] : -1;           // (conditional, like the A rows of this product: measured faster)
+            arow[i] = al.d.rowidx[min(m, M - 1)];           // gather table entry (may be -1: padded row)
         }
     };
     auto issue = [&]() {
@@ -1260,17 +1244,8 @@ __global__ __launch_bounds__(512) void gemm_rw_kernel(ALoad<AK> al, const uint16
         for (int i = 0; i < ACH; ++i) {
             const int c = tid + i * NTH;
             const int r = ((ain >> i) & 1) ? arow[i] : -1;
-            // (the head-major operand of the dx product keeps the conditional load: measured in situ on one box, unconditional
-            // 61.2 us vs conditional 55.7 us for that kernel, while the gathered fp32 operand of qkv gains, 47.9 -> 44.6 us)
-            if constexpr (AK == A_HEADS) ra[i] = al.raw_at(r, ccol(c) * 8);
-            else ra[i] = al.raw_unc(max(r, 0), ccol(c) * 8);
+            ra[i] = al.raw_unc(max(r, 0), ccol(c) * 8);     // (unconditional: 47.9 -> 44.6 us against the load under `if`)
             aok |= (uint32_t)(r >= 0) << i;
-        }
-        if constexpr (EK == E_F32) {
-            erow_nxt = ein ? erow_res : -1;
-            const float* ax = (const float*)ep.d.aux + (long)max(erow_nxt, 0) * ep.d.ld + ecol;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) aux_nxt[i] = *(const f32x4*)(ax + 4 * i);
         }
     };
     auto commit = [&]() {
@@ -1286,11 +1261,6 @@ __global__ __launch_bounds__(512) void gemm_rw_kernel(ALoad<AK> al, const uint16
         STAMP_WAITV();
         STAMP(0);
         commit();
-        if constexpr (EK == E_F32) {
-            erow_cur = erow_nxt;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) aux_cur[i] = aux_nxt[i];
-        }
         STAMP(1);
         __syncthreads();                                   // A tile (and, the first time, the weight) visible
         STAMP(2);
@@ -1328,7 +1298,7 @@ __global__ __launch_bounds__(512) void gemm_rw_kernel(ALoad<AK> al, const uint16
 #pragma unroll
                     for (int r = 0; r < 4; ++r) st[(4 * g + r) * EP + 16 * j + fr] = acc[i][j0 + j][r];
                 const int m0 = t * BMT + wr * 16 * RT + i * 16, n0 = wc * (N / 2) + j0 * 16;
-                if constexpr (EK == E_QKV_HEADS) {
+                {
                     // heads_item<HS, true> with the bias from LDS: lane = (row r, 16-column slot); HS = 32: a head is two slots
                     // (adjacent lane groups share the squared norm).  d.p1 = first q / k / v part of this launch's columns (a
                     // launch over one part of a split weight: BASELINE configs[4], see launch_nt2)
@@ -1366,17 +1336,6 @@ __global__ __launch_bounds__(512) void gemm_rw_kernel(ALoad<AK> al, const uint16
                         for (int e = 0; e < 8; ++e) w8[e] = v[8 + e] * rn;
                         *(uint4*)(o + 8) = pack8(w8);
                     }
-                } else if constexpr (EK == E_F32) {
-                    // Epi<E_F32>::tile with the scatter row and the residual prefetched (N == 128: no column tail)
-                    if (erow_cur >= 0) {
-                        float* o = (float*)ep.d.out + (long)erow_cur * ep.d.ld + ecol;
-                        const int r = lane >> 2, c0 = (lane & 3) * 16;
-#pragma unroll
-                        for (int q = 0; q < 4; ++q)
-                            *(f32x4*)(o + 4 * q) = *(const f32x4*)(st + r * EP + c0 + 4 * q) + *(const f32x4*)(bs + ecol + 4 * q) + aux_cur[q];
-                    }
-                } else {
-                    ep.tile(st, m0, n0, lane);
                 }
             }
         STAMP(6);
@@ -1432,7 +1391,9 @@ LinearKernel linear_kernel_for(int ak, int ek, const swv2_operand* a, const swv2
         // times, 3 x 108 MB, against the generic kernel's re-read of the weight per 64-row tile: 207 -> 3 x ~45 us)
         if (N == 768 && K == 192 && e->p[3] == 32 && e->p[0] == 8) return LinearKernel::RESIDENT_QKV192X3;
     }
-    if (dx_pair(ak, ek) && N == 128 && K == 384 && M >= 256 * 64 && e->rowidx && e->aux && !a->rowidx) return LinearKernel::RESIDENT_DX128;
+    // (its operand is fetched by LDS-DMA with 32-bit byte offsets: a larger one falls through to the tile kernels)
+    if (dx_pair(ak, ek) && N == 128 && K == 384 && M >= 256 * 64 && e->rowidx && e->aux && !a->rowidx && (double)M * K * 2 < 4.29e9)
+        return LinearKernel::RESIDENT_DX128;
     // wide products (K, N >= 512, N a multiple of 256): 256 x 256 tiles
     if (wide_pair(ak, ek)) {
         // BASELINE configs[4]'s d(qkv) -> dx product (N = 192, K = 768, head-major operand): one partial column tile of the DMA kernel --
@@ -1522,8 +1483,7 @@ int launch_nt2(const swv2_operand* a, const void* w, const swv2_epilogue* e, int
             }
             break;
         case LinearKernel::RESIDENT_DX128:
-            if constexpr (dx_pair(AK, EK))
-                hipLaunchKernelGGL((gemm_rw_kernel<AK, EK, 128, 384, 64>), dim3(256), dim3(512), 0, st, make_loader<AK>(a), wb, ep, M);
+            if constexpr (dx_pair(AK, EK)) swv2_rw_dx128_launch(a, w, e, M, st);      // gemm_rw.hip: the streaming body
             break;
         case LinearKernel::WIDE_DMA:
         case LinearKernel::WIDE:

@@ -7,6 +7,9 @@
 // gemm.hip: the wide weight-gradient kernel (partial matrices), launched by gemm_tn.hip
 int swv2_tn_wide_launch(const swv2_operand* y, const swv2_operand* x, float* part, float* dbpart, int M, int N, int K, int S, hipStream_t st);
 
+// gemm_rw.hip: the streaming body of the resident d(qkv) -> dx product at C = 128 (LinearKernel::RESIDENT_DX128, launched by gemm.hip)
+int swv2_rw_dx128_launch(const swv2_operand* a, const void* w, const swv2_epilogue* e, int M, hipStream_t st);
+
 // gemm_tn_slab.hip: the block's four weight gradients with every operand byte fetched once (LDS-DMA slabs).  swv2_tn_slab_covers: the
 // kernel runs these items with a workspace of ws_bytes on the current device (256 CUs assumed in a process without one); a covered
 // shape with too small a workspace is reported on stderr once per process.  swv2_block_wgrad asks it, then launches (0 or a negative error)
