@@ -651,6 +651,27 @@ int swv2_sht_repack(const float* src, float* dst, int planes, int nlat, int mmax
 int swv2_sht_synth(const float* table, const float* rweights, const float* coeffs, const float* response, int response_stride, float scale_m0,
                    float scale_m, float* S, int planes, int nlat, int lmax, int mmax, int nlon, void* stream);
 
+/* First-order conservative regridding to a coarser lat-lon grid (csrc/regrid.hip; utils/regrid.py states the operator and builds the
+ * tables; purely additive, the revision stays 113).  All tensors fp32, the tables int32 / fp32, all on the device.
+ *   x  C planes of [H][W] per sample, sample b at x + b * x_bstride (elements): a channel block of a wider tensor is read where it lies
+ *   y  C planes of [Hd][Wd] per sample, sample b at y + b * y_bstride: it may be a channel block of a wider output
+ *   lat_start, lat_count [Hd], lat_w [Hd][KH]: row J of the latitude operator has its weights at the source rows lat_start[J] + k, k < lat_count[J]
+ *   lon_start, lon_count [Wd], lon_w [Wd][KW]: row I of the longitude operator, at the source columns (lon_start[I] + k) mod W
+ *   r[J][i] = sum_{k < lat_count[J]} lat_w[J][k] x[lat_start[J] + k][i]
+ *   y[J][I] = sum_{k < lon_count[I]} lon_w[I][k] r[J][(lon_start[I] + k) mod W]
+ * both sums fp32 fma chains from zero with k ascending.  Table entries k >= count are never read, so a NaN or Inf in one source cell
+ * reaches exactly the target cells whose bands contain it.  One launch; every element of the C Hd Wd outputs of every sample is
+ * written by exactly one thread: no atomics, nothing to zero beforehand, two runs on the same inputs agree bit for bit.
+ * The host cannot see the device tables.  The kernel TRUSTS that 1 <= lat_count[J] <= KH, 0 <= lat_start[J], lat_start[J] + lat_count[J] <= H,
+ * 1 <= lon_count[I] <= min(KW, W) and 0 <= lon_start[I] < W: the caller guarantees it (utils/regrid.py::Regridder does).
+ * Refused with SWV2_ERR_INVALID before any launch: a null pointer, a non-positive size, W % 4 != 0, W > 16384 (the source row is kept in
+ * LDS), x not 16-byte aligned, a batch stride that is not a multiple of 4 or (B > 1) smaller than C H W / C Hd Wd, KH or KW outside
+ * 1 .. 32, B * C >= 2^20, H * W >= 2^30, Hd * Wd >= 2^30, B * C * ceil(Hd / R) >= 2^31 workgroups (R: the rows per workgroup, 4, 2 or 1).
+ * Wd is unrestricted and y needs no alignment beyond a float's. */
+int swv2_regrid(const float* x, long x_bstride, float* y, long y_bstride, int B, int C, int H, int W, int Hd, int Wd, const int* lat_start,
+                const int* lat_count, const float* lat_w, int KH, const int* lon_start, const int* lon_count, const float* lon_w, int KW,
+                void* stream);
+
 /* ------------------------------------------------------------------------------------------------------------
  * ERA5 input assembly (the step BEFORE the model): raw time slabs staged on the device by async H2D copies
  * -> the model's input / target buffers, one pass each.

@@ -22,6 +22,7 @@ ensemble-mean RMSE and the rank histogram per channel and lead time, one pass ov
 
     python -m swin_v2_weather_amd.inference --registry DIR --steps 8 [--init x0.npy] [--out forecast.npy]
                                             [--truth truth.npy [--climatology time_means.npy] [--scores-out scores.json] [--extremes]
+                                             [--score-grid DEG]
                                              [--spectrum] [--spectrum-out spectrum.npz]
                                              [--ensemble M --perturbation A [--seed S] [--member-batch K] [--perturbation-scale KM]]]
 """
@@ -38,7 +39,8 @@ import torch
 
 from .networks.helpers import get_model
 from .utils.YParams import load_yaml
-from .utils.weighted_acc_rmse import ForecastScorer, load_climatology, small_scale_power_ratio, spread_skill_ratio
+from .utils.regrid import Regridder, grid_for_degrees, model_grid
+from .utils.weighted_acc_rmse import ForecastScorer, RegriddedScorer, load_climatology, small_scale_power_ratio, spread_skill_ratio
 
 
 class _Params(dict):
@@ -150,12 +152,15 @@ def score_rollout(model, x0: torch.Tensor, truth, n_steps: int, coszen: torch.Te
     tqe [n_steps, B, Cout] | None).  extremes: every step's prediction also goes through scorer.quantile_error against that step's truth
     (the top-quantile error, tqe).  spectrum: every step's prediction and truth also go through scorer.power_spectrum ->
     spectrum = RolloutSpectrum(pred, truth [n_steps, Cout, lmax = H]: batch-mean degree power in the scorer's normalised units; ratio
-    [n_steps, B, Cout]: small_scale_power_ratio per sample), else None.  The predictions are `rollout`'s, bit for bit."""
+    [n_steps, B, Cout]: small_scale_power_ratio per sample), else None.  The predictions are `rollout`'s, bit for bit.
+    scorer may be a RegriddedScorer: truth stays on the model's grid and both are regridded before every score (no spectrum then)."""
     net = model.model if hasattr(model, "model") else model
     B, _, H, W = x0.shape
     Cout = net.out_chans
     if scorer is None:
         scorer = ForecastScorer(H, W, Cout, x0.device)
+    if spectrum and isinstance(scorer, RegriddedScorer):
+        raise ValueError("score_rollout: spectrum=True needs a ForecastScorer (degree spectra are taken on the model's own grid)")
     slots = n_steps if keep_forecast else 2
     out = torch.empty(B, slots * Cout, H, W, dtype=torch.float32, device=x0.device)
     coff_of = (lambda s: s * Cout) if keep_forecast else (lambda s: (s % 2) * Cout)
@@ -304,6 +309,15 @@ class _Parser(argparse.ArgumentParser):
         a = super().parse_args(args, namespace)
         if a.spectrum_out and not a.spectrum:
             self.error("--spectrum-out needs --spectrum")
+        if a.score_grid is not None:
+            if not a.truth:
+                self.error("--score-grid names the grid the scores are taken on: it needs --truth")
+            if a.spectrum:
+                self.error("--score-grid scores on a coarser grid; --spectrum is taken on the model's own grid: run them separately")
+            try:
+                grid_for_degrees(a.score_grid)
+            except ValueError as e:
+                self.error(f"--score-grid: {e}")
         if a.ensemble is None:
             for flag, v in (("--perturbation", a.perturbation), ("--seed", a.seed), ("--member-batch", a.member_batch),
                             ("--perturbation-scale", a.perturbation_scale)):
@@ -345,6 +359,11 @@ def build_parser() -> argparse.ArgumentParser:
                                                             "ssr_<name> columns (small-scale power ratio), \"ssr\" key")
     ap.add_argument("--spectrum-out", default=None, metavar="FILE.npz", help="with --spectrum: write the arrays degree [lmax], pred and truth "
                                                                              "[steps, Cout, lmax] (batch-mean degree power)")
+    ap.add_argument("--score-grid", type=float, default=None, metavar="DEG", help="with --truth: regrid forecast and analysis (first-order "
+                                                                                  "conservative) to the DEG-degree global grid and score there "
+                                                                                  "with cell-area weights (1.5: 121 x 240, the WeatherBench 2 "
+                                                                                  "scorecards' grid; 5.625: 32 x 64); the truth file stays on the "
+                                                                                  "model's grid")
     ap.add_argument("--ensemble", type=int, default=None, metavar="M", help="with --truth: roll out M members from perturbed initial conditions "
                                                                             "(member 0 is the control) and score CRPS, spread and ensemble-mean RMSE "
                                                                             "(crps_/spread_/ens_rmse_<name> columns, \"ensemble\" key)")
@@ -388,7 +407,13 @@ def _score_main(a, model, p, stats, x0, cz, n_invar):
     pc["time_means_path"] = a.climatology or (reg_tm if os.path.isfile(reg_tm) else p.get("time_means_path"))
     means, stds = stats if stats is not None else (None, None)
     clim = load_climatology(pc, means=means, stds=stds)
-    scorer = ForecastScorer(H, W, len(chans), x0.device, climatology=clim, stds=None if stds is None else stds[0, chans, 0, 0])
+    phys = None if stds is None else stds[0, chans, 0, 0]
+    grid = None
+    if a.score_grid is not None:
+        grid = grid_for_degrees(a.score_grid)
+        scorer = RegriddedScorer(Regridder(model_grid(H, W), grid, x0.device), len(chans), climatology=clim, stds=phys)
+    else:
+        scorer = ForecastScorer(H, W, len(chans), x0.device, climatology=clim, stds=phys)
     truth = np.load(a.truth, mmap_mode="r")              # read step by step: the whole array need not fit in host memory
     if truth.ndim != 5 or truth.shape[1] < a.steps:
         raise ValueError(f"--truth: expected [B, >= {a.steps}, Cout, H, W], got {truth.shape}")
@@ -407,10 +432,15 @@ def _score_main(a, model, p, stats, x0, cz, n_invar):
     else:
         names = [(v, i) for i, v in enumerate(("u10m", "v10m")) if i < len(chans)]
     print(f"scores in {'physical' if stds is not None else 'normalised'} units, {'with' if clim is not None else 'no climatology: without'} ACC")
+    if grid is not None:
+        print(f"scored on the {a.score_grid:g} degree grid ({grid.nlat} x {grid.nlon}, {'both poles' if grid.poles else 'no pole rows'}) after "
+              "first-order conservative regridding, cell-area weights")
     print(lead_time_table(sc, names, ensemble=ens))
     if a.scores_out:
         doc = {"lead_hours": [6.0 * (s + 1) for s in range(a.steps)], "rmse": sc.rmse.cpu().tolist(),
                "acc": None if sc.acc is None else sc.acc.cpu().tolist(), "tracked": dict(names)}
+        if grid is not None:
+            doc["grid"] = {"degrees": a.score_grid, "nlat": grid.nlat, "nlon": grid.nlon, "poles": grid.poles, "weights": "cell-area"}
         if sc.tqe is not None:
             doc["tqe"] = sc.tqe.mean(dim=1).cpu().tolist()
         if sc.spectrum is not None:

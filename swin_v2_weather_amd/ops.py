@@ -532,6 +532,38 @@ def l1_grad(prd, tar, qw, coef, dprd):
     L.check(L.load().swv2_l1_grad(_p(prd), _p(tar), _p(qw), _p(coef), _p(dprd), B * Cc, H, W, _stream()), "swv2_l1_grad")
 
 
+REGRID_MAX_BAND = 32          # the KH / KW cap of swv2_regrid
+
+
+def regrid_planes_ok(t: torch.Tensor, source: bool) -> bool:
+    """what swv2_regrid reads (source: 16-byte aligned, W % 4 == 0) or writes in place: a CUDA fp32 [B, C, H, W] tensor or channel block
+    of one with contiguous planes; the batch stride, unless B == 1, a multiple of 4 that steps over the C planes of a sample"""
+    if not (t.is_cuda and t.dtype == torch.float32 and t.dim() == 4 and t.numel() > 0):
+        return False
+    B, Cc, H, W = t.shape
+    if tuple(t.stride()[1:]) != (H * W, W, 1) or not (B == 1 or (t.stride(0) % 4 == 0 and t.stride(0) >= Cc * H * W)):
+        return False
+    return not source or (W % 4 == 0 and t.data_ptr() % 16 == 0)
+
+
+def regrid(x, y, lat_start, lat_count, lat_w, lon_start, lon_count, lon_w):
+    """y [B, C, Hd, Wd] = the banded operators applied to x [B, C, H, W] (each a tensor or channel block read / written in place):
+    swv2_regrid with the tables of utils/regrid.py::band_tables on the device (int32 start and count [n], fp32 weights [n, K]).  The
+    kernel trusts the tables' indices (include/swv2.h): build them with band_tables, as Regridder does."""
+    if not (regrid_planes_ok(x, True) and regrid_planes_ok(y, False)) or x.shape[:2] != y.shape[:2] or x.device != y.device:
+        raise L.Swv2Error(f"regrid: expected CUDA fp32 [B, C, H, W] -> [B, C, Hd, Wd] with contiguous planes and W % 4 == 0, got "
+                          f"{tuple(x.shape)} {x.dtype} strides {x.stride()} / {tuple(y.shape)} {y.dtype} strides {y.stride()}")
+    B, Cc, H, W = x.shape
+    Hd, Wd = y.shape[2:]
+    for t, dt, n, what in ((lat_start, torch.int32, Hd, "lat_start"), (lat_count, torch.int32, Hd, "lat_count"), (lat_w, torch.float32, Hd, "lat_w"),
+                           (lon_start, torch.int32, Wd, "lon_start"), (lon_count, torch.int32, Wd, "lon_count"), (lon_w, torch.float32, Wd, "lon_w")):
+        if _chk(t, dt, what).shape[0] != n or t.dim() != (2 if dt == torch.float32 else 1) or t.device != x.device:
+            raise L.Swv2Error(f"regrid: table {what} {tuple(t.shape)}, expected {n} rows on {x.device}")
+    L.check(L.load().swv2_regrid(_p(x), x.stride(0) if B > 1 else Cc * H * W, _p(y), y.stride(0) if B > 1 else Cc * Hd * Wd, B, Cc, H, W, Hd, Wd,
+                                 _p(lat_start), _p(lat_count), _p(lat_w), lat_w.shape[1], _p(lon_start), _p(lon_count), _p(lon_w), lon_w.shape[1],
+                                 _stream()), "swv2_regrid")
+
+
 def sht_power(table, X, keep_coeffs: bool = False, zero_coeffs: bool = False):
     """degree power [planes, lmax] of the spectral operand X [mmax, 2 planes, nlat] under table [mmax, lmax, nlat] (swv2_sht_power);
     with keep_coeffs also the coefficients [mmax, 2 planes, lmax] (l >= m written; the rest zeros with zero_coeffs, else whatever the

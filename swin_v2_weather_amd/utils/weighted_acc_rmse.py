@@ -219,11 +219,17 @@ def small_scale_power_ratio(pred: torch.Tensor, truth: torch.Tensor) -> torch.Te
 class ForecastScorer:
     """Latitude-weighted RMSE and ACC of [B, C, H, W] forecasts against the verifying analysis, both normalised as the model sees them.
     Owns the row weights, the normalised climatology [C, H, W] (None: no ACC) and the kernel workspace; `stds` [C] puts the batch-mean
-    RMSE into physical units.  One pass over prediction, truth and climatology per call on CUDA (csrc/score.hip), plain torch elsewhere."""
+    RMSE into physical units.  One pass over prediction, truth and climatology per call on CUDA (csrc/score.hip), plain torch elsewhere.
+    weights: an [H] row-weight vector in place of latitude_weights(H) (default None: the reference's cos(lat) weights, as ever)."""
 
-    def __init__(self, H, W, n_channels, device, climatology=None, stds=None):
+    def __init__(self, H, W, n_channels, device, climatology=None, stds=None, weights=None):
         self.H, self.W, self.C = int(H), int(W), int(n_channels)
-        self.w = latitude_weights(self.H, device)
+        if weights is None:
+            self.w = latitude_weights(self.H, device)
+        else:                                             # another convention's row weights [H] (RegriddedScorer: the target's cell areas)
+            self.w = torch.as_tensor(weights, dtype=torch.float32).reshape(-1).to(device).contiguous()
+            if self.w.numel() != self.H:
+                raise ValueError(f"{self.w.numel()} row weights for {self.H} rows")
         self.device = self.w.device                       # resolved: "cuda" names the current device, whose tensors say cuda:<index>
         self.clim = None
         if climatology is not None:
@@ -395,3 +401,64 @@ def ensemble_scores_torch(ens: torch.Tensor, tar: torch.Tensor, w=None, scale=No
         means = [m * sc for m in means[:3]] + means[3:]
     return EnsembleScores(torch.stack((s_mse, s_var, s_1, s_2), dim=-1), hist.to(torch.int32), ens_rmse, spread, crps, fair, *means)
 
+
+
+class RegriddedScorer:
+    """ForecastScorer on a coarser grid: every call regrids the named channel blocks of the wide tensors where they lie (utils/regrid.py::
+    Regridder: csrc/regrid.hip on CUDA fp32, the dense statement elsewhere) into coarse buffers kept per call shape, and hands those to an
+    inner ForecastScorer(Hd, Wd, C, weights = the target's cell areas, the climatology regridded once here).  The published tables of
+    this model family (WeatherBench 2 scorecards: 1.5 degrees, cell-area weights) are on such a grid.  score, mae, quantile_error and
+    ensemble_score keep ForecastScorer's signatures; .C, .H, .W and .clim are the SOURCE grid's (what score_rollout and
+    ensemble_rollout read), .grid is the target, .inner the coarse scorer.  power_spectrum raises: spectra are taken on the native grid."""
+
+    def __init__(self, regridder, n_channels, climatology=None, stds=None):
+        self.regridder, self.C = regridder, int(n_channels)
+        (self.H, self.W), self.grid, self.device = regridder.src.shape, regridder.dst, regridder.device
+        self.clim = None
+        if climatology is not None:
+            if isinstance(climatology, np.ndarray):
+                climatology = torch.from_numpy(np.array(climatology, dtype=np.float32))
+            self.clim = torch.as_tensor(climatology, dtype=torch.float32).to(self.device).contiguous()
+            if self.clim.shape != (self.C, self.H, self.W):
+                raise ValueError(f"climatology {tuple(self.clim.shape)}, expected {(self.C, self.H, self.W)}")
+        Hd, Wd = self.grid.shape
+        self.inner = ForecastScorer(Hd, Wd, self.C, self.device, climatology=None if self.clim is None else regridder(self.clim),
+                                    stds=stds, weights=regridder.area_weights)
+        self._buf = {}
+
+    def _coarse(self, name, x):
+        """x [..., C, H, W] (a view of the caller's tensor) regridded into this scorer's buffer of that name and shape"""
+        key = (name, tuple(x.shape[:-2]), x.dtype, x.device)
+        if key not in self._buf:
+            self._buf[key] = torch.empty(tuple(x.shape[:-2]) + self.grid.shape, dtype=x.dtype, device=x.device)
+        return self.regridder(x, out=self._buf[key])
+
+    def _blocks(self, who, prd, tar, coff_prd, coff_tar):
+        p, t = prd[:, coff_prd:coff_prd + self.C], tar[:, coff_tar:coff_tar + self.C]
+        if p.shape != t.shape or p.shape[1:] != (self.C, self.H, self.W):
+            raise ValueError(f"{who}: blocks {tuple(p.shape)} / {tuple(t.shape)}, expected [B, {self.C}, {self.H}, {self.W}]")
+        return self._coarse("prd", p), self._coarse("tar", t)
+
+    def score(self, prd, tar, coff_prd=0, coff_tar=0) -> Scores:
+        return self.inner.score(*self._blocks("score", prd, tar, coff_prd, coff_tar))
+
+    def mae(self, prd, tar, coff_prd=0, coff_tar=0) -> MaeScores:
+        return self.inner.mae(*self._blocks("mae", prd, tar, coff_prd, coff_tar))
+
+    def quantile_error(self, prd, tar, coff_prd=0, coff_tar=0) -> torch.Tensor:
+        return self.inner.quantile_error(*self._blocks("quantile_error", prd, tar, coff_prd, coff_tar))
+
+    def ensemble_score(self, ens, tar, n_members, coff_ens=0, coff_tar=0) -> EnsembleScores:
+        M = int(n_members)
+        if ens.dim() == 4:
+            if M < 1 or ens.shape[0] % M:
+                raise ValueError(f"ensemble_score: a batch of {ens.shape[0]} rows does not hold {M} members")
+            ens = ens.unflatten(0, (M, ens.shape[0] // M))
+        e, t = ens[:, :, coff_ens:coff_ens + self.C], tar[:, coff_tar:coff_tar + self.C]
+        if e.dim() != 5 or e.shape[0] != M or M < 2 or e.shape[1:] != t.shape or t.shape[1:] != (self.C, self.H, self.W):
+            raise ValueError(f"ensemble_score: members {tuple(e.shape)} / truth {tuple(t.shape)}, expected [{M} >= 2, B, {self.C}, {self.H}, {self.W}] "
+                             f"/ [B, {self.C}, {self.H}, {self.W}]")
+        return self.inner.ensemble_score(self._coarse("ens", e), self._coarse("tar", t), M)
+
+    def power_spectrum(self, *args, **kwargs):
+        raise ValueError("RegriddedScorer: degree spectra are taken on the model's own grid; use a ForecastScorer for power_spectrum")
