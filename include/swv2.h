@@ -591,6 +591,45 @@ int swv2_ens_sums(const float* ens, long ens_mstride, long ens_bstride, const fl
 int swv2_ens_finalize(const void* ws, size_t ws_bytes, int M, int B, int C, int H, int W, const float* scale, float* sums, int* hist,
                       float* ens_rmse, float* spread, float* crps, float* fair_crps, float* means, void* stream);
 
+/* Forecast events (csrc/events.hip; purely additive, the revision stays 113): the 2 x 2 contingency table of a forecast and the Brier sums
+ * and reliability counts of an ensemble for K <= 8 thresholds at once, per (sample, channel) plane, from ONE pass.  All fields fp32.
+ *   prd, tar  C planes of [H][W] per sample, sample b at ptr + b * bstride (elements), as swv2_score_sums takes them
+ *   ens       member m, sample b, channel c at ens + m * ens_mstride + b * ens_bstride + c * H * W, as swv2_ens_sums takes them; M = 2 .. 64
+ *   base      NULL or [C][H][W], shared by the samples (read like the climatology of swv2_score_sums)
+ *   thr       threshold k of plane (b, c) at thr[b * thr_bstride + c * K + k]; thr_bstride = 0: one [C][K] table for every sample
+ *   w         [H] row weights;  below: 0 or 1
+ *   theta = thr, or fl32(base + thr) with a base (one fp32 addition).  Event: x > theta, or x < theta with below; strict, in fp32: a value
+ *   equal to theta is no event.  A point is valid in its plane if prediction (every member), truth and base are not NaN there; +-inf are
+ *   valid.  Invalid points enter no sum and no count, and are counted in n_invalid[B][C].
+ *   deterministic, P / O = event in prediction / truth, over the valid points:
+ *     table[B][C][K][4] = (a, b, c, d) = (sum w [P and O], sum w [P and not O], sum w [not P and O], sum w [not P and not O]), four sums of their
+ *     own: with unit weights every cell is an exact integer for H W <= 2^24
+ *   ensemble, n = #{m : x_m event}, o = [truth event], over the valid points:
+ *     sums[B][C][K][3] = (S_e, S_f, S_o) = (sum w (n - M o)^2, sum w n (M - n), sum w o)      wv[B][C] = sum w
+ *     hist[B][C][K][2][M + 1]: [0][j] = #{points with n = j},  [1][j] = #{points with n = j and o = 1}  (int32 point counts, unweighted)
+ * swv2_event_sums / swv2_event_ens_sums: one launch of B * C * swv2_score_slices(B * C, H, W) workgroups (the plan and slice bounds of
+ * swv2_score_sums, workgroup index (c * slices + sl) * B + b); workgroup (plane, slice) stores its partial sums and counts in the workspace.
+ * No float atomics, nothing to zero beforehand; a slice without elements stores zeros.  The counts are integer adds in LDS; the bin
+ * (n = 0, o = 0), which holds nearly every point of a rare event, is not counted but formed by swv2_event_ens_finalize as the valid points
+ * minus the other bins (integers: exact).
+ * swv2_event_finalize / swv2_event_ens_finalize: one launch; folds the slices of each plane in a fixed order (two runs on the same inputs agree
+ * bit for bit, counts included) and writes the outputs above.
+ * Refused with SWV2_ERR_INVALID before any HIP call, the entry point's name in the message: a null pointer (base may be NULL), K outside
+ * 1 .. 8, M outside 2 .. 64, W % 4 != 0, prd / ens / tar / base / ws / table not 16-byte aligned, another pointer not 4-byte aligned, a member
+ * or batch stride that is not a multiple of 4 or (B > 1) a batch stride smaller than C H W, a thr_bstride that is neither 0 nor (B > 1) at
+ * least C K, B * C >= 2^20, H * W >= 2^30, a workspace smaller than the query.  The queries are host-only (no HIP call) and return 0 for a
+ * non-positive argument, K outside 1 .. 8 or M outside 2 .. 64. */
+size_t swv2_event_ws_bytes(int planes, int H, int W, int K);      /* planes * swv2_score_slices(planes, H, W) * (16 K + 4) */
+int swv2_event_sums(const float* prd, long prd_bstride, const float* tar, long tar_bstride, const float* base, const float* thr, long thr_bstride,
+                    const float* w, int K, int below, int B, int C, int H, int W, void* ws, size_t ws_bytes, void* stream);
+int swv2_event_finalize(const void* ws, size_t ws_bytes, int K, int B, int C, int H, int W, float* table, int* n_invalid, void* stream);
+size_t swv2_event_ens_ws_bytes(int planes, int H, int W, int M, int K);      /* planes * slices * (16 K + 4 + 8 K (M + 1)) */
+int swv2_event_ens_sums(const float* ens, long ens_mstride, long ens_bstride, const float* tar, long tar_bstride, const float* base,
+                        const float* thr, long thr_bstride, const float* w, int M, int K, int below, int B, int C, int H, int W, void* ws,
+                        size_t ws_bytes, void* stream);
+int swv2_event_ens_finalize(const void* ws, size_t ws_bytes, int M, int K, int B, int C, int H, int W, float* sums, float* wv, int* hist,
+                            int* n_invalid, void* stream);
+
 /* Geometric l1 loss (csrc/loss_l1.hip; reference utils/losses.py:114-120 with p = 1) and the latitude-weighted mean absolute error: per
  * (sample, channel) plane, from ONE pass over prediction and target.  All tensors fp32.
  *   prd, tar  C planes of [H][W] per sample, sample b at ptr + b * bstride (elements), as swv2_score_sums takes them;  w: [H] row weights

@@ -24,6 +24,7 @@ ensemble-mean RMSE and the rank histogram per channel and lead time, one pass ov
                                             [--truth truth.npy [--climatology time_means.npy] [--scores-out scores.json] [--extremes]
                                              [--score-grid DEG]
                                              [--spectrum] [--spectrum-out spectrum.npz]
+                                             [--event-anomaly S [S ...] | --event-quantile Q [Q ...]] [--event-below]
                                              [--ensemble M --perturbation A [--seed S] [--member-batch K] [--perturbation-scale KM]]]
 """
 from __future__ import annotations
@@ -40,7 +41,8 @@ import torch
 from .networks.helpers import get_model
 from .utils.YParams import load_yaml
 from .utils.regrid import Regridder, grid_for_degrees, model_grid
-from .utils.weighted_acc_rmse import ForecastScorer, RegriddedScorer, load_climatology, small_scale_power_ratio, spread_skill_ratio
+from .utils.weighted_acc_rmse import (EventSpec, ForecastScorer, RegriddedScorer, load_climatology, small_scale_power_ratio,  # noqa: F401
+                                      spread_skill_ratio)
 
 
 class _Params(dict):
@@ -128,12 +130,31 @@ def rollout(model, x0: torch.Tensor, n_steps: int, coszen: torch.Tensor | None =
 
 # degree power of forecast and analysis per lead time (batch means [n_steps, Cout, lmax]) and small_scale_power_ratio [n_steps, B, Cout]
 RolloutSpectrum = namedtuple("RolloutSpectrum", "pred truth ratio")
+# events=EventSpec(kind, levels, below) of score_rollout: per lead time the thresholds used ([K] for "anomaly", [B, C, K] for "quantile"), the
+# tables [n_steps, B, C, K, 4], n_invalid [n_steps, B, C] and `scores`: name -> [n_steps, C, K] fp64, from the tables summed over the batch
+RolloutEvents = namedtuple("RolloutEvents", "spec thresholds table n_invalid scores")
+# the same of ensemble_rollout: sums [n_steps, B, C, K, 3], wv [n_steps, B, C], hist [n_steps, B, C, K, 2, M + 1], n_invalid, and `scores`:
+# brier, fair_brier, brier_skill, reliability, resolution, uncertainty, roc_area -> [n_steps, C, K] fp64, pooled over the batch
+EnsembleRolloutEvents = namedtuple("EnsembleRolloutEvents", "spec thresholds sums wv hist n_invalid scores")
+
+
+def _stack_scores(per_step):
+    """[{name: [C, K]} per step] -> {name: [n_steps, C, K]}"""
+    return {k: torch.stack([d[k] for d in per_step], dim=0) for k in per_step[0]}
+
+
+def _events_of(per_step, spec):
+    """the EventScores of every step -> RolloutEvents"""
+    return RolloutEvents(spec, [t for t, _ in per_step], torch.stack([e.table for _, e in per_step], dim=0),
+                         torch.stack([e.n_invalid for _, e in per_step], dim=0), _stack_scores([e.pooled for _, e in per_step]))
 
 
 class RolloutScores(namedtuple("RolloutScores", "rmse acc rmse_samples acc_samples forecast tqe", defaults=(None,))):
     """score_rollout's answer.  The tuple keeps its six fields (callers unpack and build it positionally); `spectrum` rides along as an
-    attribute: None, or the RolloutSpectrum of score_rollout(..., spectrum=True).  (_replace builds a new tuple: carry it over by hand.)"""
+    attribute: None, or the RolloutSpectrum of score_rollout(..., spectrum=True); so does `events`: None, or the RolloutEvents of
+    score_rollout(..., events=spec).  (_replace builds a new tuple: carry them over by hand.)"""
     spectrum = None
+    events = None
 
     def with_spectrum(self, spectrum):
         self.spectrum = spectrum
@@ -143,7 +164,7 @@ class RolloutScores(namedtuple("RolloutScores", "rmse acc rmse_samples acc_sampl
 @torch.no_grad()
 def score_rollout(model, x0: torch.Tensor, truth, n_steps: int, coszen: torch.Tensor | None = None, n_invar: int = 0,
                   scorer: ForecastScorer | None = None, keep_forecast: bool = False, extremes: bool = False,
-                  spectrum: bool = False) -> RolloutScores:
+                  spectrum: bool = False, events: EventSpec | None = None) -> RolloutScores:
     """`rollout` with every step's prediction scored against truth[:, s] as soon as it is written.  truth: [B, n_steps, Cout, H, W]
     (normalised as the model's output) or a callable s -> [B, Cout, H, W].  scorer: a ForecastScorer (default: no climatology, so
     no ACC; normalised units).  Unless keep_forecast, the predictions live in a two-slot ring [B, 2 Cout, H, W]: memory does not grow
@@ -153,12 +174,18 @@ def score_rollout(model, x0: torch.Tensor, truth, n_steps: int, coszen: torch.Te
     (the top-quantile error, tqe).  spectrum: every step's prediction and truth also go through scorer.power_spectrum ->
     spectrum = RolloutSpectrum(pred, truth [n_steps, Cout, lmax = H]: batch-mean degree power in the scorer's normalised units; ratio
     [n_steps, B, Cout]: small_scale_power_ratio per sample), else None.  The predictions are `rollout`'s, bit for bit.
-    scorer may be a RegriddedScorer: truth stays on the model's grid and both are regridded before every score (no spectrum then)."""
+    scorer may be a RegriddedScorer: truth stays on the model's grid and both are regridded before every score (no spectrum then).
+    events: an EventSpec(kind "anomaly" | "quantile", levels, below): every step also goes through scorer.event_score with the thresholds
+    scorer.event_thresholds names (offsets from the climatology, or that step's spatial quantiles of the analysis) -> the attribute
+    `events`, a RolloutEvents; every other result is what the call without it returns, bit for bit."""
     net = model.model if hasattr(model, "model") else model
     B, _, H, W = x0.shape
     Cout = net.out_chans
     if scorer is None:
         scorer = ForecastScorer(H, W, Cout, x0.device)
+    if events is not None and events.kind == "anomaly" and scorer.clim is None:
+        raise ValueError("score_rollout: anomaly events need a scorer with a climatology")
+    ev = []
     if spectrum and isinstance(scorer, RegriddedScorer):
         raise ValueError("score_rollout: spectrum=True needs a ForecastScorer (degree spectra are taken on the model's own grid)")
     slots = n_steps if keep_forecast else 2
@@ -180,10 +207,16 @@ def score_rollout(model, x0: torch.Tensor, truth, n_steps: int, coszen: torch.Te
         if spectrum:
             ps = scorer.power_spectrum(out, tar, coff_prd=coff_of(s))
             spec.pred[s], spec.truth[s], spec.ratio[s] = ps.pred.mean(dim=0), ps.truth.mean(dim=0), small_scale_power_ratio(ps.pred, ps.truth)
+        if events is not None:
+            thr = scorer.event_thresholds(events, tar)
+            ev.append((thr, scorer.event_score(out, tar, thr, anomaly=events.kind == "anomaly", below=events.below, coff_prd=coff_of(s))))
         rmse[s], rmse_s[s] = r.rmse_mean, r.rmse
         if acc is not None:
             acc[s], acc_s[s] = r.acc_mean, r.acc
-    return RolloutScores(rmse, acc, rmse_s, acc_s, out.view(B, n_steps, Cout, H, W) if keep_forecast else None, tqe).with_spectrum(spec)
+    res = RolloutScores(rmse, acc, rmse_s, acc_s, out.view(B, n_steps, Cout, H, W) if keep_forecast else None, tqe).with_spectrum(spec)
+    if events is not None:
+        res.events = _events_of(ev, events)
+    return res
 
 
 def perturb_initial_condition(x0: torch.Tensor, n_members: int, amplitude: float, seed: int, n_fields: int, kind: str = "white",
@@ -218,8 +251,11 @@ def perturb_initial_condition(x0: torch.Tensor, n_members: int, amplitude: float
     return out
 
 
-EnsembleRolloutScores = namedtuple("EnsembleRolloutScores", "crps fair_crps spread ens_rmse crps_samples fair_crps_samples spread_samples "
-                                   "ens_rmse_samples hist forecast control", defaults=(None,))
+class EnsembleRolloutScores(namedtuple("EnsembleRolloutScores", "crps fair_crps spread ens_rmse crps_samples fair_crps_samples spread_samples "
+                                       "ens_rmse_samples hist forecast control", defaults=(None,))):
+    """ensemble_rollout's answer.  The tuple keeps its eleven fields; `events` rides along as an attribute: None, or the
+    EnsembleRolloutEvents of ensemble_rollout(..., events=spec)."""
+    events = None
 
 
 @torch.no_grad()
@@ -227,7 +263,7 @@ def ensemble_rollout(model, x0: torch.Tensor, truth, n_steps: int, n_members: in
                      coszen: torch.Tensor | None = None, n_invar: int = 0, scorer: ForecastScorer | None = None,
                      member_batch: int | None = None, keep_forecast: bool = False, n_fields: int | None = None,
                      score_control: bool = False, perturbation_kind: str = "white",
-                     length_scale_km: float | None = None) -> EnsembleRolloutScores:
+                     length_scale_km: float | None = None, events: EventSpec | None = None) -> EnsembleRolloutScores:
     """`score_rollout` for an ensemble: x0 [B, Cin, H, W] is perturbed into M = n_members initial conditions (perturb_initial_condition,
     which perturbation_kind and length_scale_km are handed to; n_fields defaults to Cin - n_invar - (1 if coszen is given)), all members are rolled out and every step is scored against truth[:, s]
     by scorer.ensemble_score as soon as all members have written it.  truth, scorer: as in score_rollout; coszen [B, n_steps - 1, H, W] is
@@ -236,10 +272,14 @@ def ensemble_rollout(model, x0: torch.Tensor, truth, n_steps: int, n_members: in
     the forecasts are rollout(model, perturb_initial_condition(...), n_steps, coszen.repeat(M, 1, 1, 1), n_invar)'s bit for bit.
     -> EnsembleRolloutScores(crps, fair_crps, spread, ens_rmse [n_steps, Cout]: batch means (the scorer's stds on crps, spread, ens_rmse);
     their _samples [n_steps, B, Cout]; hist [n_steps, B, Cout, M + 1] int32; forecast [M B, n_steps, Cout, H, W] | None;
-    control: with score_control, the RolloutScores of member 0 -- the deterministic forecast -- from scorer.score, else None)."""
+    control: with score_control, the RolloutScores of member 0 -- the deterministic forecast -- from scorer.score, else None).
+    events: an EventSpec, as in score_rollout: every step also goes through scorer.ensemble_event_score (Brier score, reliability, ROC area
+    of the exceedance probabilities) -> the attribute `events`, an EnsembleRolloutEvents; with score_control the control carries its own
+    RolloutEvents (the contingency tables of member 0).  Every other result is what the call without it returns, bit for bit."""
     net = model.model if hasattr(model, "model") else model
     B, Cin, H, W = x0.shape
     M, Cout = int(n_members), net.out_chans
+    ev, ev_ctl = [], []
     if M < 2:
         raise ValueError(f"ensemble_rollout: {M} members (an ensemble has at least 2)")
     K = M if member_batch is None else int(member_batch)
@@ -247,6 +287,8 @@ def ensemble_rollout(model, x0: torch.Tensor, truth, n_steps: int, n_members: in
         raise ValueError(f"ensemble_rollout: member_batch {member_batch}")
     if scorer is None:
         scorer = ForecastScorer(H, W, Cout, x0.device)
+    if events is not None and events.kind == "anomaly" and scorer.clim is None:
+        raise ValueError("ensemble_rollout: anomaly events need a scorer with a climatology")
     if n_fields is None:
         n_fields = Cin - n_invar - int(coszen is not None)
     xe = perturb_initial_condition(x0, M, amplitude, seed, n_fields, perturbation_kind, length_scale_km)
@@ -273,19 +315,33 @@ def ensemble_rollout(model, x0: torch.Tensor, truth, n_steps: int, n_members: in
         for k in mean:
             mean[k][s], samp[k][s] = getattr(r, k + "_mean"), getattr(r, k)
         hist[s] = r.hist
+        if events is not None:
+            thr = scorer.event_thresholds(events, tar)
+            kw = dict(anomaly=events.kind == "anomaly", below=events.below)
+            ev.append((thr, scorer.ensemble_event_score(out, tar, M, thr, coff_ens=coff_of(s), **kw)))
+            if score_control:
+                ev_ctl.append((thr, scorer.event_score(out[:B], tar, thr, coff_prd=coff_of(s), **kw)))
         if score_control:
             c = scorer.score(out[:B], tar, coff_prd=coff_of(s))
             ctl[0][s], ctl[1][s] = c.rmse_mean, c.rmse
             if ctl[2] is not None:
                 ctl[2][s], ctl[3][s] = c.acc_mean, c.acc
     control = None if ctl is None else RolloutScores(ctl[0], ctl[2], ctl[1], ctl[3], None)
-    return EnsembleRolloutScores(mean["crps"], mean["fair_crps"], mean["spread"], mean["ens_rmse"], samp["crps"], samp["fair_crps"], samp["spread"],
-                                 samp["ens_rmse"], hist, out.view(M * B, n_steps, Cout, H, W) if keep_forecast else None, control)
+    res = EnsembleRolloutScores(mean["crps"], mean["fair_crps"], mean["spread"], mean["ens_rmse"], samp["crps"], samp["fair_crps"], samp["spread"],
+                                samp["ens_rmse"], hist, out.view(M * B, n_steps, Cout, H, W) if keep_forecast else None, control)
+    if events is not None:
+        stack = lambda i: torch.stack([e[i] for _, e in ev], dim=0)      # noqa: E731
+        res.events = EnsembleRolloutEvents(events, [t for t, _ in ev], stack(0), stack(1), stack(2), stack(3),
+                                           _stack_scores([{**e.pooled, **e.reliability} for _, e in ev]))
+        if control is not None:
+            control.events = _events_of(ev_ctl, events)
+    return res
 
 
 def lead_time_table(scores: RolloutScores, names, hours_per_step: float = 6.0, ensemble: EnsembleRolloutScores | None = None) -> str:
     """one line per lead time: RMSE (and ACC, and the batch-mean top-quantile error and small-scale power ratio when scored) of the named channels;
-    names: [(column title, channel index)].  ensemble: the crps_, spread_ and ens_rmse_ columns of an ensemble_rollout follow."""
+    names: [(column title, channel index)].  ensemble: the crps_, spread_ and ens_rmse_ columns of an ensemble_rollout follow.  Scored
+    events add the equitable threat score of every threshold k, ets<k>_<name>, and -- for an ensemble -- its Brier score, bs<k>_<name>."""
     rm, ac = scores.rmse.cpu().numpy(), None if scores.acc is None else scores.acc.cpu().numpy()
     tq = None if scores.tqe is None else scores.tqe.mean(dim=1).cpu().numpy()
     sr = None if scores.spectrum is None else scores.spectrum.ratio.mean(dim=1).cpu().numpy()
@@ -293,11 +349,18 @@ def lead_time_table(scores: RolloutScores, names, hours_per_step: float = 6.0, e
         ([f"tqe_{n}" for n, _ in names] if tq is not None else []) + ([f"ssr_{n}" for n, _ in names] if sr is not None else [])
     ens = [] if ensemble is None else [(k, getattr(ensemble, k).cpu().numpy()) for k in ("crps", "spread", "ens_rmse")]
     cols += [f"{k}_{n}" for k, _ in ens for n, _ in names]
+    if scores.events is not None:
+        ens.append(("ets", scores.events.scores["ets"].cpu().numpy()))
+    if ensemble is not None and ensemble.events is not None:
+        ens.append(("bs", ensemble.events.scores["brier"].cpu().numpy()))
+    evs = [(k, v) for k, v in ens if v.ndim == 3]
+    ens = [(k, v) for k, v in ens if v.ndim == 2]
+    cols += [f"{k}{j}_{n}" for k, v in evs for j in range(v.shape[2]) for n, _ in names]
     lines = ["lead_h " + " ".join(f"{c:>12s}" for c in cols)]
     for s in range(rm.shape[0]):
         vals = [rm[s, i] for _, i in names] + ([ac[s, i] for _, i in names] if ac is not None else []) + \
             ([tq[s, i] for _, i in names] if tq is not None else []) + ([sr[s, i] for _, i in names] if sr is not None else []) + \
-            [v[s, i] for _, v in ens for _, i in names]
+            [v[s, i] for _, v in ens for _, i in names] + [v[s, i, j] for _, v in evs for j in range(v.shape[2]) for _, i in names]
         lines.append(f"{hours_per_step * (s + 1):6.0f} " + " ".join(f"{v:12.5f}" for v in vals))
     return "\n".join(lines)
 
@@ -318,6 +381,14 @@ class _Parser(argparse.ArgumentParser):
                 grid_for_degrees(a.score_grid)
             except ValueError as e:
                 self.error(f"--score-grid: {e}")
+        if a.event_anomaly is not None and a.event_quantile is not None:
+            self.error("--event-anomaly and --event-quantile name the thresholds in two ways: give one of them")
+        if a.event_below and a.event_anomaly is None and a.event_quantile is None:
+            self.error("--event-below turns the event of --event-anomaly / --event-quantile round: it needs one of them")
+        if (a.event_anomaly is not None or a.event_quantile is not None) and not a.truth:
+            self.error("--event-anomaly / --event-quantile score events against the verifying analysis: they need --truth")
+        if a.event_quantile is not None and not all(0.0 <= q <= 1.0 for q in a.event_quantile):
+            self.error("--event-quantile: levels within 0 .. 1")
         if a.ensemble is None:
             for flag, v in (("--perturbation", a.perturbation), ("--seed", a.seed), ("--member-batch", a.member_batch),
                             ("--perturbation-scale", a.perturbation_scale)):
@@ -364,6 +435,12 @@ def build_parser() -> argparse.ArgumentParser:
                                                                                   "with cell-area weights (1.5: 121 x 240, the WeatherBench 2 "
                                                                                   "scorecards' grid; 5.625: 32 x 64); the truth file stays on the "
                                                                                   "model's grid")
+    ap.add_argument("--event-anomaly", type=float, nargs="+", default=None, metavar="S", help="with --truth and a climatology: score the events "
+                    "\"more than S above the climatology\" (normalised units; one or more thresholds): ets<k>_<name> columns, with --ensemble "
+                    "also bs<k>_<name> (Brier score), \"events\" key")
+    ap.add_argument("--event-quantile", type=float, nargs="+", default=None, metavar="Q", help="with --truth: score the events \"above the Q "
+                    "quantile of the verifying analysis\" (its own spatial quantile per lead time, sample and channel); not with --event-anomaly")
+    ap.add_argument("--event-below", action="store_true", help="with --event-anomaly / --event-quantile: the event is \"below\" the threshold")
     ap.add_argument("--ensemble", type=int, default=None, metavar="M", help="with --truth: roll out M members from perturbed initial conditions "
                                                                             "(member 0 is the control) and score CRPS, spread and ensemble-mean RMSE "
                                                                             "(crps_/spread_/ens_rmse_<name> columns, \"ensemble\" key)")
@@ -418,15 +495,24 @@ def _score_main(a, model, p, stats, x0, cz, n_invar):
     if truth.ndim != 5 or truth.shape[1] < a.steps:
         raise ValueError(f"--truth: expected [B, >= {a.steps}, Cout, H, W], got {truth.shape}")
     truth_of = lambda s: torch.from_numpy(np.array(truth[:, s], dtype=np.float32)).to(x0.device)      # noqa: E731
+    spec = None
+    if a.event_anomaly is not None:
+        if clim is None:
+            raise ValueError("--event-anomaly: thresholds relative to the climatology need one (--climatology, or time_means.npy in the registry)")
+        spec = EventSpec("anomaly", tuple(a.event_anomaly), a.event_below)
+    elif a.event_quantile is not None:
+        spec = EventSpec("quantile", tuple(a.event_quantile), a.event_below)
     ens = None
     if a.ensemble is not None:
         # one rollout of all members: member 0 is the unperturbed forecast, scored as score_rollout scores it
         ens = ensemble_rollout(model, x0, truth_of, a.steps, a.ensemble, a.perturbation, a.seed or 0, cz, n_invar, scorer,
                                member_batch=a.member_batch, n_fields=len(p["in_channels"]), score_control=True,
-                               perturbation_kind="white" if a.perturbation_scale is None else "spherical", length_scale_km=a.perturbation_scale)
+                               perturbation_kind="white" if a.perturbation_scale is None else "spherical", length_scale_km=a.perturbation_scale,
+                               events=spec)
         sc = ens.control
     else:
-        sc = score_rollout(model, x0, truth_of, a.steps, cz, n_invar, scorer, keep_forecast=bool(a.out), extremes=a.extremes, spectrum=a.spectrum)
+        sc = score_rollout(model, x0, truth_of, a.steps, cz, n_invar, scorer, keep_forecast=bool(a.out), extremes=a.extremes, spectrum=a.spectrum,
+                           events=spec)
     if "track_channels" in p and "channel_names" in p:
         names = [(v, list(p["channel_names"]).index(v)) for v in p["track_channels"]]
     else:
@@ -449,6 +535,14 @@ def _score_main(a, model, p, stats, x0, cz, n_invar):
             doc["ensemble"] = {"members": a.ensemble, "crps": ens.crps.cpu().tolist(), "fair_crps": ens.fair_crps.cpu().tolist(),
                                "spread": ens.spread.cpu().tolist(), "ens_rmse": ens.ens_rmse.cpu().tolist(),
                                "spread_skill": spread_skill_ratio(ens.spread, ens.ens_rmse, a.ensemble).cpu().tolist()}
+        if sc.events is not None:
+            # pooled over the batch per lead time: the table [steps, C, K, 4] and its scores [steps, C, K]
+            doc["events"] = {"kind": spec.kind, "levels": list(spec.levels), "below": bool(spec.below),
+                             "table": sc.events.table.to(torch.float64).sum(dim=1).cpu().tolist(),
+                             **{k: v.cpu().tolist() for k, v in sc.events.scores.items()}}
+            if ens is not None:
+                doc["events"].update({k: ens.events.scores[k].cpu().tolist()
+                                      for k in ("brier", "fair_brier", "brier_skill", "reliability", "resolution", "roc_area")})
         with open(a.scores_out, "w") as f:
             json.dump(doc, f)
     if a.spectrum_out:

@@ -680,6 +680,91 @@ def ens_finalize(ws, M: int, B: int, Cc: int, H: int, W: int, scale=None):
     return sums, hist, er, sp, cr, fc, means
 
 
+EVENT_MAX_K = 8               # the threshold cap of swv2_event_sums / swv2_event_ens_sums
+
+
+def event_workspace(planes: int, H: int, W: int, K: int, device) -> torch.Tensor:
+    """the caller's workspace of swv2_event_sums / swv2_event_finalize for `planes` = B * C planes and K thresholds: allocate once, reuse"""
+    n = int(L.load().swv2_event_ws_bytes(planes, H, W, K))
+    if n == 0:
+        raise L.Swv2Error(f"event_workspace: planes {planes}, H {H}, W {W} must be positive and K = {K} within 1 .. {EVENT_MAX_K}")
+    return torch.empty(n // 4, dtype=torch.float32, device=device)
+
+
+def ens_event_workspace(planes: int, H: int, W: int, M: int, K: int, device) -> torch.Tensor:
+    """the caller's workspace of swv2_event_ens_sums / swv2_event_ens_finalize: allocate once, reuse"""
+    n = int(L.load().swv2_event_ens_ws_bytes(planes, H, W, M, K))
+    if n == 0:
+        raise L.Swv2Error(f"ens_event_workspace: planes {planes}, H {H}, W {W} must be positive, M = {M} within 2 .. {ENS_MAX_MEMBERS} and "
+                          f"K = {K} within 1 .. {EVENT_MAX_K}")
+    return torch.empty(n // 4, dtype=torch.float32, device=device)
+
+
+def _event_operands(who, x_shape, thr, w, base):
+    """checks of the operands both event kernels share -> (K, thr batch stride)"""
+    B, Cc, H, W = x_shape
+    _chk(w, torch.float32, "row weights"); _chk(thr, torch.float32, "thresholds")
+    if w.numel() != H:
+        raise L.Swv2Error(f"{who}: {w.numel()} row weights for {H} rows")
+    if thr.dim() != 3 or thr.shape[1] != Cc or thr.shape[0] not in (1, B) or not 1 <= thr.shape[2] <= EVENT_MAX_K:
+        raise L.Swv2Error(f"{who}: thresholds {tuple(thr.shape)}, expected [1 or {B}, {Cc}, K <= {EVENT_MAX_K}]")
+    if base is not None and (_chk(base, torch.float32, "base field").shape != (Cc, H, W)):
+        raise L.Swv2Error(f"{who}: base field {tuple(base.shape)}, expected {(Cc, H, W)}")
+    K = thr.shape[2]
+    return K, (Cc * K if thr.shape[0] == B and B > 1 else 0)
+
+
+def event_sums(prd, tar, thr, w, ws, base=None, below=False):
+    """the contingency-table partial sums of every (b, c) plane of prd / tar (each [B, C, H, W] or a channel block of a wider tensor, read
+    in place) into ws (event_workspace); thr [1 or B, C, K] contiguous, w [H] row weights, base [C, H, W] or None"""
+    if not (score_planes_ok(prd) and score_planes_ok(tar)) or prd.shape != tar.shape:
+        raise L.Swv2Error(f"event_sums: expected two CUDA fp32 [B, C, H, W] tensors of one shape with contiguous planes and W % 4 == 0, got "
+                          f"{tuple(prd.shape)} {prd.dtype} strides {prd.stride()} / {tuple(tar.shape)} {tar.dtype} strides {tar.stride()}")
+    B, Cc, H, W = prd.shape
+    K, tbs = _event_operands("event_sums", prd.shape, thr, w, base)
+    _chk(ws, torch.float32, "event workspace")
+    span = Cc * H * W
+    L.check(L.load().swv2_event_sums(_p(prd), prd.stride(0) if B > 1 else span, _p(tar), tar.stride(0) if B > 1 else span, _p(base), _p(thr), tbs,
+                                     _p(w), K, int(bool(below)), B, Cc, H, W, _p(ws), ws.numel() * 4, _stream()), "swv2_event_sums")
+
+
+def event_finalize(ws, K: int, B: int, Cc: int, H: int, W: int):
+    """slice partials -> (table [B, C, K, 4] fp32, n_invalid [B, C] int32), one launch"""
+    _chk(ws, torch.float32, "event workspace")
+    table = torch.empty(B, Cc, K, 4, dtype=torch.float32, device=ws.device)
+    ninv = torch.empty(B, Cc, dtype=torch.int32, device=ws.device)
+    L.check(L.load().swv2_event_finalize(_p(ws), ws.numel() * 4, K, B, Cc, H, W, _p(table), _p(ninv), _stream()), "swv2_event_finalize")
+    return table, ninv
+
+
+def ens_event_sums(ens, tar, thr, w, ws, base=None, below=False):
+    """the Brier partial sums and reliability counts of every (b, c) plane of the members ens [M, B, C, H, W] against tar [B, C, H, W] (both may
+    be channel blocks of wider tensors, read in place) into ws (ens_event_workspace)"""
+    if not (ens_members_ok(ens) and score_planes_ok(tar)) or ens.shape[1:] != tar.shape or ens.device != tar.device:
+        raise L.Swv2Error(f"ens_event_sums: expected CUDA fp32 members [M, B, C, H, W] (2 <= M <= {ENS_MAX_MEMBERS}) and truth [B, C, H, W] with "
+                          f"contiguous planes and W % 4 == 0, got {tuple(ens.shape)} {ens.dtype} strides {ens.stride()} / {tuple(tar.shape)} "
+                          f"{tar.dtype} strides {tar.stride()}")
+    M, B, Cc, H, W = ens.shape
+    K, tbs = _event_operands("ens_event_sums", tar.shape, thr, w, base)
+    _chk(ws, torch.float32, "ensemble event workspace")
+    span = Cc * H * W
+    L.check(L.load().swv2_event_ens_sums(_p(ens), ens.stride(0), ens.stride(1) if B > 1 else span, _p(tar), tar.stride(0) if B > 1 else span,
+                                         _p(base), _p(thr), tbs, _p(w), M, K, int(bool(below)), B, Cc, H, W, _p(ws), ws.numel() * 4, _stream()),
+            "swv2_event_ens_sums")
+
+
+def ens_event_finalize(ws, M: int, K: int, B: int, Cc: int, H: int, W: int):
+    """slice partials -> (sums [B, C, K, 3] = (S_e, S_f, S_o), wv [B, C], hist [B, C, K, 2, M + 1] int32, n_invalid [B, C] int32), one launch"""
+    _chk(ws, torch.float32, "ensemble event workspace")
+    sums = torch.empty(B, Cc, K, 3, dtype=torch.float32, device=ws.device)
+    wv = torch.empty(B, Cc, dtype=torch.float32, device=ws.device)
+    hist = torch.empty(B, Cc, K, 2, M + 1, dtype=torch.int32, device=ws.device)
+    ninv = torch.empty(B, Cc, dtype=torch.int32, device=ws.device)
+    L.check(L.load().swv2_event_ens_finalize(_p(ws), ws.numel() * 4, M, K, B, Cc, H, W, _p(sums), _p(wv), _p(hist), _p(ninv), _stream()),
+            "swv2_event_ens_finalize")
+    return sums, wv, hist, ninv
+
+
 QUANTILE_MAX_RANKS = 256      # the K cap of swv2_plane_order_stats
 
 

@@ -207,6 +207,10 @@ MaeScores = namedtuple("MaeScores", "mae mae_mean sums")
 EnsembleScores = namedtuple("EnsembleScores", "sums hist ens_rmse spread crps fair_crps ens_rmse_mean spread_mean crps_mean fair_crps_mean")
 PowerSpectrum = namedtuple("PowerSpectrum", "pred truth")
 
+# forecast events: contingency tables and Brier scores (the statements and the fp64 scores live in utils/events.py)
+from .events import (EVENT_MAX_K, EnsembleEventScores, EventScores, EventSpec, brier_scores, contingency_scores,  # noqa: E402,F401
+                     ensemble_event_sums_torch, event_table_torch, expand_thresholds, quantile_thresholds, reliability_scores)
+
 
 def small_scale_power_ratio(pred: torch.Tensor, truth: torch.Tensor) -> torch.Tensor:
     """degree power [..., lmax] x2 -> [...]: sum_{l >= lmax // 2} pred / sum_{l >= lmax // 2} truth, the share of the truth's power in the
@@ -352,6 +356,94 @@ class ForecastScorer:
             return EnsembleScores(sums, hist, er, sp, cr, fc, means[0], means[1], means[2], means[3])
         return ensemble_scores_torch(e, t, self.w, self.scale)
 
+    # ---- forecast events (utils/events.py, csrc/events.hip) ----
+    def _event_base(self, who, anomaly, base):
+        if anomaly:
+            if base is not None:
+                raise ValueError(f"{who}: anomaly=True takes the scorer's climatology as the base field; give one of the two")
+            if self.clim is None:
+                raise ValueError(f"{who}: anomaly=True needs a scorer with a climatology")
+            return self.clim
+        if base is None:
+            return None
+        base = torch.as_tensor(base, dtype=torch.float32).to(self.device).contiguous()
+        if base.shape != (self.C, self.H, self.W):
+            raise ValueError(f"{who}: base field {tuple(base.shape)}, expected {(self.C, self.H, self.W)}")
+        return base
+
+    def event_thresholds(self, spec, tar, coff_tar=0):
+        """the thresholds an EventSpec names for this truth: kind "anomaly" -> its levels [K] (offsets from the climatology, normalised
+        units; score with anomaly=True), kind "quantile" -> quantile_thresholds of channels coff_tar .. + C of tar [B, C, K]"""
+        if spec.kind == "anomaly":
+            return torch.as_tensor(spec.levels, dtype=torch.float32).reshape(-1)
+        if spec.kind == "quantile":
+            return quantile_thresholds(tar[:, coff_tar:coff_tar + self.C], spec.levels)
+        raise ValueError(f"EventSpec.kind {spec.kind!r}: \"anomaly\" or \"quantile\"")
+
+    def event_score(self, prd, tar, thresholds, anomaly=False, base=None, below=False, coff_prd=0, coff_tar=0) -> EventScores:
+        """The 2 x 2 contingency table of the event "x > theta" ("x < theta" with below) in channels coff_prd .. + C of prd against channels
+        coff_tar .. + C of tar (read in place), for thresholds [K], [C, K] or [B, C, K] in the scorer's normalised units; theta = threshold,
+        or base + threshold with a base field [C, H, W] (anomaly=True: the scorer's climatology) -> EventScores(table [B, C, K, 4] =
+        (a, b, c, d) with the scorer's row weights, n_invalid [B, C] int32: the points with a NaN, which enter no cell, scores: the dict of
+        contingency_scores per sample [B, C, K], pooled: the same from the tables summed over the batch [C, K], both fp64).  One pass of
+        swv2_event_sums per 8 thresholds on CUDA fp32, event_table_torch elsewhere."""
+        p, t = self._blocks("event_score", prd, tar, coff_prd, coff_tar)
+        base = self._event_base("event_score", anomaly, base)
+        B = p.shape[0]
+        thr = expand_thresholds(thresholds, B, self.C, p.device)
+        if _on_kernels(p, t) and p.device == self.device:
+            from .. import ops
+            tables = []
+            for k0 in range(0, thr.shape[2], EVENT_MAX_K):
+                tk = thr[:, :, k0:k0 + EVENT_MAX_K].contiguous()
+                K = tk.shape[2]
+                ws = self._workspace(("event", B, K), ops.event_workspace, B * self.C, self.H, self.W, K)
+                ops.event_sums(p, t, tk, self.w, ws, base, below)
+                tab, ninv = ops.event_finalize(ws, K, B, self.C, self.H, self.W)
+                tables.append(tab)
+            table = tables[0] if len(tables) == 1 else torch.cat(tables, dim=2)
+        else:
+            table, ninv = event_table_torch(p, t, thr, self.w, None if base is None else base.to(p.device), below)
+        return EventScores(table, ninv, contingency_scores(table), contingency_scores(table.to(torch.float64).sum(dim=0)))
+
+    def ensemble_event_score(self, ens, tar, n_members, thresholds, anomaly=False, base=None, below=False, coff_ens=0,
+                             coff_tar=0) -> EnsembleEventScores:
+        """The exceedance probabilities n / M of n_members forecasts (ens as ensemble_score takes it) against the event in the truth, for
+        thresholds as event_score takes them -> EnsembleEventScores(sums [B, C, K, 3] = (S_e, S_f, S_o), wv [B, C], hist
+        [B, C, K, 2, M + 1] int32 point counts ([0]: forecasts of n / M, [1]: those with the event observed), n_invalid [B, C], scores:
+        brier_scores per sample [B, C, K], pooled: the same from the sums added over the batch [C, K], reliability: reliability_scores of
+        the counts added over the batch [C, K]; all fp64).  The reliability table and the ROC area are point counts: they carry no area
+        weights.  One pass of swv2_event_ens_sums per 8 thresholds on CUDA fp32, ensemble_event_sums_torch elsewhere."""
+        M = int(n_members)
+        if ens.dim() == 4:
+            if M < 1 or ens.shape[0] % M:
+                raise ValueError(f"ensemble_event_score: a batch of {ens.shape[0]} rows does not hold {M} members")
+            ens = ens.unflatten(0, (M, ens.shape[0] // M))
+        e, t = ens[:, :, coff_ens:coff_ens + self.C], tar[:, coff_tar:coff_tar + self.C]
+        if e.dim() != 5 or e.shape[0] != M or M < 2 or e.shape[1:] != t.shape or t.shape[1:] != (self.C, self.H, self.W):
+            raise ValueError(f"ensemble_event_score: members {tuple(e.shape)} / truth {tuple(t.shape)}, expected [{M} >= 2, B, {self.C}, {self.H}, "
+                             f"{self.W}] / [B, {self.C}, {self.H}, {self.W}]")
+        base = self._event_base("ensemble_event_score", anomaly, base)
+        B = t.shape[0]
+        thr = expand_thresholds(thresholds, B, self.C, t.device)
+        from .. import ops
+        if e.is_cuda and t.is_cuda and e.device == self.device == t.device and ops.ens_members_ok(e) and ops.score_planes_ok(t):
+            parts = []
+            for k0 in range(0, thr.shape[2], EVENT_MAX_K):
+                tk = thr[:, :, k0:k0 + EVENT_MAX_K].contiguous()
+                K = tk.shape[2]
+                ws = self._workspace(("ens_event", M, B, K), ops.ens_event_workspace, B * self.C, self.H, self.W, M, K)
+                ops.ens_event_sums(e, t, tk, self.w, ws, base, below)
+                parts.append(ops.ens_event_finalize(ws, M, K, B, self.C, self.H, self.W))
+            sums, hist = (parts[0][i] if len(parts) == 1 else torch.cat([q[i] for q in parts], dim=2) for i in (0, 2))
+            wv, ninv = parts[0][1], parts[0][3]
+        else:
+            sums, wv, hist, ninv = ensemble_event_sums_torch(e, t, thr, self.w, None if base is None else base.to(t.device), below)
+        hp = hist.to(torch.int64).sum(dim=0)
+        return EnsembleEventScores(sums, wv, hist, ninv, brier_scores(sums, wv, M),
+                                   brier_scores(sums.to(torch.float64).sum(dim=0), wv.to(torch.float64).sum(dim=0), M),
+                                   reliability_scores(hp[..., 0, :], hp[..., 1, :]))
+
 
 # ---- ensemble scores: CRPS, spread, ensemble-mean RMSE, rank histogram (what Earth2MIP reports for perturbed-initial-condition runs) ----
 # M members x_m against the truth y, per grid point (every term from differences of inputs, so the rounding error of a sum is relative to
@@ -459,6 +551,31 @@ class RegriddedScorer:
             raise ValueError(f"ensemble_score: members {tuple(e.shape)} / truth {tuple(t.shape)}, expected [{M} >= 2, B, {self.C}, {self.H}, {self.W}] "
                              f"/ [B, {self.C}, {self.H}, {self.W}]")
         return self.inner.ensemble_score(self._coarse("ens", e), self._coarse("tar", t), M)
+
+    def event_thresholds(self, spec, tar, coff_tar=0):
+        """ForecastScorer.event_thresholds; the quantiles are those of the REGRIDDED truth"""
+        t = tar[:, coff_tar:coff_tar + self.C]
+        return self.inner.event_thresholds(spec, self._coarse("tar", t) if spec.kind == "quantile" else t)
+
+    def event_score(self, prd, tar, thresholds, anomaly=False, base=None, below=False, coff_prd=0, coff_tar=0) -> EventScores:
+        """ForecastScorer.event_score on the coarse grid: the FIELDS are regridded first and the events are then taken there, against the
+        regridded climatology (anomaly=True) or a base field given on the coarse grid, with the cell-area weights.  This is not the
+        regridding of the events: a cell's mean exceeds a threshold less often than its points do."""
+        return self.inner.event_score(*self._blocks("event_score", prd, tar, coff_prd, coff_tar), thresholds, anomaly=anomaly, base=base, below=below)
+
+    def ensemble_event_score(self, ens, tar, n_members, thresholds, anomaly=False, base=None, below=False, coff_ens=0,
+                             coff_tar=0) -> EnsembleEventScores:
+        """ForecastScorer.ensemble_event_score on the coarse grid; as event_score, the fields are regridded, not the events"""
+        M = int(n_members)
+        if ens.dim() == 4:
+            if M < 1 or ens.shape[0] % M:
+                raise ValueError(f"ensemble_event_score: a batch of {ens.shape[0]} rows does not hold {M} members")
+            ens = ens.unflatten(0, (M, ens.shape[0] // M))
+        e, t = ens[:, :, coff_ens:coff_ens + self.C], tar[:, coff_tar:coff_tar + self.C]
+        if e.dim() != 5 or e.shape[0] != M or M < 2 or e.shape[1:] != t.shape or t.shape[1:] != (self.C, self.H, self.W):
+            raise ValueError(f"ensemble_event_score: members {tuple(e.shape)} / truth {tuple(t.shape)}, expected [{M} >= 2, B, {self.C}, {self.H}, "
+                             f"{self.W}] / [B, {self.C}, {self.H}, {self.W}]")
+        return self.inner.ensemble_event_score(self._coarse("ens", e), self._coarse("tar", t), M, thresholds, anomaly=anomaly, base=base, below=below)
 
     def power_spectrum(self, *args, **kwargs):
         raise ValueError("RegriddedScorer: degree spectra are taken on the model's own grid; use a ForecastScorer for power_spectrum")
