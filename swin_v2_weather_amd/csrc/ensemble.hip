@@ -94,7 +94,7 @@ __global__ __launch_bounds__(256) void ens_sums_kernel(const ens_coef_t coef, co
     constexpr int CAP = MB <= 8 ? 8 : MB <= 16 ? 16 : MB <= 32 ? 32 : 64;
     constexpr int LO = FULL ? MB : MB == 8 ? 2 : MB - 7;      // MB - 8 < M <= MB (2 <= M <= 8 at MB = 8)
     const int M = FULL ? MB : Mrt;
-    const int b = blockIdx.x % B, cs = blockIdx.x / B, c = cs / slices, sl = cs - c * slices;
+    const auto [b, c, sl] = plane_shared_index(B, slices);
     const uint32_t plane = (uint32_t)H * W;                   // < 2^30 (checked by the host)
     uint32_t lo, hi;
     plane_slice_range(plane, sl, slices, lo, hi);
@@ -217,11 +217,21 @@ void ens_launch(dim3 grid, hipStream_t st, const float* ens, long ms, long bs, c
         hipLaunchKernelGGL((ens_sums_kernel<MB, PTS, false>), grid, dim3(256), 0, st, coef, ens, ms, bs, tar, tbs, w, part, cnt, M, B, C, H, W, slices);
 }
 
+// The workspace, carved here and nowhere else (offsets in 4-byte words): float part[slots][4], then int cnt[slots][M + 1].  swv2_ens_sums,
+// swv2_ens_finalize and swv2_ens_ws_bytes all go through it.
+struct ens_ws {
+    size_t cnt_at, words;
+    ens_ws(size_t slots, int M) : cnt_at(slots * 4), words(cnt_at + slots * (M + 1)) {}
+    size_t bytes() const { return words * 4; }
+    float* part(const void* ws) const { return (float*)ws; }
+    int* cnt(const void* ws) const { return (int*)ws + cnt_at; }
+};
+
 }  // namespace
 
 extern "C" size_t swv2_ens_ws_bytes(int planes, int H, int W, int M) {
     if (planes <= 0 || H <= 0 || W <= 0 || M < 2 || M > ENS_MAX_M) return 0;
-    return (size_t)planes * plane_slices(planes) * (4 * sizeof(float) + (size_t)(M + 1) * sizeof(int));
+    return ens_ws((size_t)planes * plane_slices(planes), M).bytes();
 }
 
 extern "C" int swv2_ens_sums(const float* ens, long ens_mstride, long ens_bstride, const float* tar, long tar_bstride, const float* w, int M, int B,
@@ -237,8 +247,9 @@ extern "C" int swv2_ens_sums(const float* ens, long ens_mstride, long ens_bstrid
     const int slices = plane_slices((long)B * C);
     const size_t slots = (size_t)B * C * slices;
     const dim3 grid((unsigned)slots);
-    float* part = (float*)ws;
-    int* cnt = (int*)(part + slots * 4);
+    const ens_ws lay(slots, M);
+    float* part = lay.part(ws);
+    int* cnt = lay.cnt(ws);
     hipStream_t st = (hipStream_t)stream;
 #define ENS_CASE(MB, PTS) \
     case MB: ens_launch<MB, PTS>(grid, st, ens, ens_mstride, ens_bstride, tar, tar_bstride, w, part, cnt, M, B, C, H, W, slices); break
@@ -265,8 +276,9 @@ extern "C" int swv2_ens_finalize(const void* ws, size_t ws_bytes, int M, int B, 
     if (!plane_operands_ok("ens_finalize", {ws, sums}, {}, 1, 0, ws_bytes, swv2_ens_ws_bytes(B * C, H, W, M), "swv2_ens_ws_bytes"))
         return SWV2_ERR_INVALID;
     const int slices = plane_slices((long)B * C);
-    const float* part = (const float*)ws;
-    const int* cnt = (const int*)(part + (size_t)B * C * slices * 4);
+    const ens_ws lay((size_t)B * C * slices, M);
+    const float* part = lay.part(ws);
+    const int* cnt = lay.cnt(ws);
     hipLaunchKernelGGL(ens_finalize_kernel, dim3(C), dim3(256), 0, (hipStream_t)stream, part, cnt, slices, M, B, C, (float)((long)H * W), scale, sums,
                        hist, ens_rmse, spread, crps, fair_crps, means);
     SWV2_CHECK_LAUNCH("swv2_ens_finalize");

@@ -40,12 +40,6 @@ constexpr int EVT_MBATCH = 8;
 template <bool BELOW>
 __device__ __forceinline__ bool evt_is(float x, float th) { return BELOW ? x < th : x > th; }
 
-__device__ __forceinline__ int evt_wave_sum_int(int v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
 // one 16-byte vector position of the deterministic table: a[4 k + (0 .. 3)] = the cells a, b, c, d of threshold k
 template <int K, bool BASE, bool BELOW>
 __device__ __forceinline__ void evt_vec(const f32x4 x, const f32x4 y, const f32x4 m, const float q, const float (&thr)[K], float (&a)[4 * K], int& ninv) {
@@ -72,7 +66,7 @@ __global__ __launch_bounds__(256) void event_sums_kernel(const float* __restrict
                                                          const float* __restrict__ base, const float* __restrict__ thr, long thr_bs,
                                                          const float* __restrict__ w, float* __restrict__ part, int* __restrict__ inv, int B, int C,
                                                          int H, int W, int slices) {
-    const int b = blockIdx.x % B, cs = blockIdx.x / B, c = cs / slices, sl = cs - c * slices;
+    const auto [b, c, sl] = plane_shared_index(B, slices);
     const uint32_t plane = (uint32_t)H * W;                   // < 2^30 (checked by the host)
     uint32_t lo, hi;
     plane_slice_range(plane, sl, slices, lo, hi);
@@ -94,7 +88,7 @@ __global__ __launch_bounds__(256) void event_sums_kernel(const float* __restrict
     }
     __shared__ float r[4 * K][4];
     __shared__ int ri[4];
-    ninv = evt_wave_sum_int(ninv);
+    ninv = plane_wave_sum(ninv);
     if ((threadIdx.x & 63) == 0) ri[threadIdx.x >> 6] = ninv;
     plane_block_stage(s, r);
     if (threadIdx.x == 0) {
@@ -106,15 +100,8 @@ __global__ __launch_bounds__(256) void event_sums_kernel(const float* __restrict
             for (int j = 0; j < 4; ++j) o[j] = plane_block_total(r[4 * k + j]);
             *(f32x4*)(part + (slot * K + k) * 4) = o;
         }
-        inv[slot] = (ri[0] + ri[1]) + (ri[2] + ri[3]);
+        inv[slot] = plane_block_total(ri);
     }
-}
-
-// the invalid count of plane pl, every lane of the wave ends with it
-__device__ __forceinline__ int evt_fold_inv(const int* __restrict__ inv, size_t pl, int slices, int lane) {
-    int n = 0;
-    for (int sl = lane; sl < slices; sl += 64) n += inv[pl * slices + sl];
-    return evt_wave_sum_int(n);
 }
 
 // One workgroup per channel: wave v folds the slice partials of the planes b = v, v + 4, ... (plane_fold_slices) and lane 0 writes them.
@@ -126,7 +113,8 @@ __global__ __launch_bounds__(256) void event_finalize_kernel(const float* __rest
         const size_t pl = (size_t)b * C + c;
         f32x4 a[K];
         plane_fold_slices<K>((const f32x4*)part, pl, slices, lane, a);
-        const int ni = evt_fold_inv(inv, pl, slices, lane);
+        int ni;
+        plane_fold_slices<1>(inv, pl, slices, lane, &ni);
         if (lane == 0) {
 #pragma unroll
             for (int k = 0; k < K; ++k) *(f32x4*)(table + (pl * K + k) * 4) = a[k];
@@ -141,7 +129,7 @@ __global__ __launch_bounds__(256) void ens_event_sums_kernel(const float* __rest
                                                              long tar_bs, const float* __restrict__ base, const float* __restrict__ thr, long thr_bs,
                                                              const float* __restrict__ w, float* __restrict__ part, int* __restrict__ inv,
                                                              int* __restrict__ cnt, int M, int B, int C, int H, int W, int slices) {
-    const int b = blockIdx.x % B, cs = blockIdx.x / B, c = cs / slices, sl = cs - c * slices;
+    const auto [b, c, sl] = plane_shared_index(B, slices);
     const uint32_t plane = (uint32_t)H * W;                   // < 2^30 (checked by the host)
     uint32_t lo, hi;
     plane_slice_range(plane, sl, slices, lo, hi);
@@ -213,7 +201,7 @@ __global__ __launch_bounds__(256) void ens_event_sums_kernel(const float* __rest
             }
         }
     }
-    ninv = evt_wave_sum_int(ninv);
+    ninv = plane_wave_sum(ninv);
     if ((threadIdx.x & 63) == 0) ri[threadIdx.x >> 6] = ninv;
     plane_block_stage(s, r);                                  // after its barrier the wave sums and every count of this workgroup are in LDS
     const size_t slot = (size_t)(b * C + c) * slices + sl;
@@ -227,7 +215,7 @@ __global__ __launch_bounds__(256) void ens_event_sums_kernel(const float* __rest
             o[3] = wv;
             *(f32x4*)(part + (slot * K + k) * 4) = o;
         }
-        inv[slot] = (ri[0] + ri[1]) + (ri[2] + ri[3]);
+        inv[slot] = plane_block_total(ri);
     }
     for (int i = threadIdx.x; i < nbins; i += 256) cnt[slot * (size_t)nbins + i] = hist[i];
 }
@@ -245,7 +233,8 @@ __global__ __launch_bounds__(256) void ens_event_finalize_kernel(const float* __
         const size_t pl = (size_t)b * C + c;
         f32x4 a[K];
         plane_fold_slices<K>((const f32x4*)part, pl, slices, lane, a);
-        const int ni = evt_fold_inv(inv, pl, slices, lane);
+        int ni;
+        plane_fold_slices<1>(inv, pl, slices, lane, &ni);
         if (lane == 0) {
 #pragma unroll
             for (int k = 0; k < K; ++k)
@@ -274,6 +263,17 @@ __global__ __launch_bounds__(256) void ens_event_finalize_kernel(const float* __
     }
 }
 
+// The workspace, carved here and nowhere else (offsets in 4-byte words): float part[slots][K][4], int inv[slots] and -- for the ensemble,
+// M > 0 -- int cnt[slots][K][2][M + 1].  The *_sums and *_finalize entry points and the *_ws_bytes queries all go through it.
+struct evt_ws {
+    size_t inv_at, cnt_at, words;
+    evt_ws(size_t slots, int K, int M) : inv_at(slots * K * 4), cnt_at(inv_at + slots), words(cnt_at + (M ? slots * K * 2 * (M + 1) : 0)) {}
+    size_t bytes() const { return words * 4; }
+    float* part(const void* ws) const { return (float*)ws; }
+    int* inv(const void* ws) const { return (int*)ws + inv_at; }
+    int* cnt(const void* ws) const { return (int*)ws + cnt_at; }
+};
+
 #define EVT_SWITCH_K(K, CALL) \
     switch (K) {              \
         case 1: CALL(1); break; case 2: CALL(2); break; case 3: CALL(3); break; case 4: CALL(4); break; \
@@ -284,12 +284,12 @@ __global__ __launch_bounds__(256) void ens_event_finalize_kernel(const float* __
 
 extern "C" size_t swv2_event_ws_bytes(int planes, int H, int W, int K) {
     if (planes <= 0 || H <= 0 || W <= 0 || K < 1 || K > EVT_MAX_K) return 0;
-    return (size_t)planes * plane_slices(planes) * (16 * (size_t)K + 4);
+    return evt_ws((size_t)planes * plane_slices(planes), K, 0).bytes();
 }
 
 extern "C" size_t swv2_event_ens_ws_bytes(int planes, int H, int W, int M, int K) {
     if (planes <= 0 || H <= 0 || W <= 0 || K < 1 || K > EVT_MAX_K || M < 2 || M > EVT_MAX_M) return 0;
-    return (size_t)planes * plane_slices(planes) * (16 * (size_t)K + 4 + 8 * (size_t)K * (M + 1));
+    return evt_ws((size_t)planes * plane_slices(planes), K, M).bytes();
 }
 
 extern "C" int swv2_event_sums(const float* prd, long prd_bstride, const float* tar, long tar_bstride, const float* base, const float* thr,
@@ -307,8 +307,9 @@ extern "C" int swv2_event_sums(const float* prd, long prd_bstride, const float* 
     const int slices = plane_slices((long)B * C);
     const size_t slots = (size_t)B * C * slices;
     const dim3 grid((unsigned)slots);
-    float* part = (float*)ws;
-    int* inv = (int*)(part + slots * K * 4);
+    const evt_ws lay(slots, K, 0);
+    float* part = lay.part(ws);
+    int* inv = lay.inv(ws);
     hipStream_t st = (hipStream_t)stream;
 #define EVT_LAUNCH(KK)                                                                                                                           \
     do {                                                                                                                                         \
@@ -332,8 +333,9 @@ extern "C" int swv2_event_finalize(const void* ws, size_t ws_bytes, int K, int B
     if (!plane_operands_ok("swv2_event_finalize", {ws, table}, {}, 1, 0, ws_bytes, swv2_event_ws_bytes(B * C, H, W, K), "swv2_event_ws_bytes"))
         return SWV2_ERR_INVALID;
     const int slices = plane_slices((long)B * C);
-    const float* part = (const float*)ws;
-    const int* inv = (const int*)(part + (size_t)B * C * slices * K * 4);
+    const evt_ws lay((size_t)B * C * slices, K, 0);
+    const float* part = lay.part(ws);
+    const int* inv = lay.inv(ws);
 #define EVT_LAUNCH(KK) hipLaunchKernelGGL(event_finalize_kernel<KK>, dim3(C), dim3(256), 0, (hipStream_t)stream, part, inv, slices, B, C, table, n_invalid)
     EVT_SWITCH_K(K, EVT_LAUNCH)
 #undef EVT_LAUNCH
@@ -358,9 +360,10 @@ extern "C" int swv2_event_ens_sums(const float* ens, long ens_mstride, long ens_
     const int slices = plane_slices((long)B * C);
     const size_t slots = (size_t)B * C * slices;
     const dim3 grid((unsigned)slots);
-    float* part = (float*)ws;
-    int* inv = (int*)(part + slots * K * 4);
-    int* cnt = inv + slots;
+    const evt_ws lay(slots, K, M);
+    float* part = lay.part(ws);
+    int* inv = lay.inv(ws);
+    int* cnt = lay.cnt(ws);
     hipStream_t st = (hipStream_t)stream;
 #define EVT_LAUNCH(KK)                                                                                                                           \
     do {                                                                                                                                         \
@@ -389,9 +392,10 @@ extern "C" int swv2_event_ens_finalize(const void* ws, size_t ws_bytes, int M, i
         return SWV2_ERR_INVALID;
     const int slices = plane_slices((long)B * C);
     const size_t slots = (size_t)B * C * slices;
-    const float* part = (const float*)ws;
-    const int* inv = (const int*)(part + slots * K * 4);
-    const int* cnt = inv + slots;
+    const evt_ws lay(slots, K, M);
+    const float* part = lay.part(ws);
+    const int* inv = lay.inv(ws);
+    const int* cnt = lay.cnt(ws);
 #define EVT_LAUNCH(KK)                                                                                                                      \
     hipLaunchKernelGGL(ens_event_finalize_kernel<KK>, dim3(C), dim3(256), 0, (hipStream_t)stream, part, inv, cnt, slices, M, B, C, H * W, sums, wv, hist, \
                        n_invalid)

@@ -1,5 +1,7 @@
 // The plan of the plane-streaming kernels, stated once: forecast scores (score.hip), dataset statistics (stats.hip), order statistics
-// (quantile.hip), ensemble scores (ensemble.hip), the l1 loss (loss_l1.hip), the l2 loss (loss_l2.hip).  Each of them reads `planes` planes of H x W fp32 values once (planes = B * C, or C for the statistics) and leaves a few numbers per plane.
+// (quantile.hip), ensemble scores (ensemble.hip), forecast events (events.hip), the l1 loss (loss_l1.hip), the l2 loss (loss_l2.hip), the
+// value range of the int16 packing (packed.hip).  Each of them reads `planes` planes of H x W fp32 values once (planes = B * C, or C for
+// the statistics and the packing) and leaves a few numbers per plane.
 //
 // Slices.  A plane is cut into  slices = planes >= 2048 ? 1 : 2048 / planes  pieces, one workgroup of 256 threads each: at most 2048
 // workgroups, one round at 8 per CU (7 .. 56 slices at 146 planes all ran swv2_loss_sums at 4.5 TB/s: the read stream is the bound).
@@ -7,9 +9,9 @@
 // one to the end: every bound is a multiple of 4 elements, so a thread's 16-byte vector never straddles one.  A slice without elements
 // is legal (a plane of fewer than 4 * slices elements has them) and stores zeros.  tests/plane_reference.py mirrors both rules.
 //
-// Workgroup index.  (c * slices + sl) * B + b where a per-channel operand is shared (the climatology of score.hip, the row weights of
-// ensemble.hip): the B workgroups that read the same piece of it are neighbours in launch order, so it comes from HBM once and from
-// the memory-side cache afterwards.  plane * slices + sl where nothing is shared (stats.hip, quantile.hip) or the row weights only (loss_l1.hip,
+// Workgroup index.  (c * slices + sl) * B + b where a per-channel operand is shared (the climatology of score.hip, the base field of
+// events.hip, the row weights of ensemble.hip): the B workgroups that read the same piece of it are neighbours in launch order, so it
+// comes from HBM once and from the memory-side cache afterwards; plane_shared_index decodes it.  plane * slices + sl where nothing is shared (stats.hip, quantile.hip) or the row weights only (loss_l1.hip,
 // loss_l2.hip).  The sum kernels over prediction and truth walk their slice with plane_stream_slice; their gradients are plane_grad_kernel.
 //
 // Sums.  No float atomics and no pre-zeroed output: every partial sum has ONE owner, and the order of the additions is fixed by the
@@ -20,7 +22,8 @@
 //     ceil(slices / 64)  the lane's running sum over the slice partials, sl = lane, lane + 64, ...   plane_fold_slices
 //     6                  wave64 butterfly
 // additions in the format of the sums (fp32; fp64 in stats.hip).  The chain_length of each tests/*_reference.py states the same count.
-// (quantile.hip counts with integer atomics, which no order can change, and uses the slices only.)
+// (quantile.hip counts with integer atomics, which no order can change, and uses the slices only.  The integer counts of ensemble.hip
+// and events.hip pass through the same stages -- plane_wave_sum(int), plane_block_total, plane_fold_slices -- in any order they like.)
 #pragma once
 #include <initializer_list>
 
@@ -36,6 +39,13 @@ __device__ __forceinline__ void plane_slice_range(uint32_t plane, int sl, int sl
     hi = (sl + 1 == slices) ? plane : (uint32_t)((uint64_t)plane * (sl + 1) / slices) / 4 * 4;
 }
 
+// (b, c, sl) of this workgroup under the shared-operand index (c * slices + sl) * B + b
+struct plane_bcs { int b, c, sl; };
+__device__ __forceinline__ plane_bcs plane_shared_index(int B, int slices) {
+    const int b = blockIdx.x % B, cs = blockIdx.x / B, c = cs / slices;
+    return {b, c, cs - c * slices};
+}
+
 // The fp64 butterfly.  Its own name on purpose: an overload wave_sum(double) declared inside a file's anonymous namespace would hide
 // wave_sum(float) there and turn every fp32 butterfly of that file into an fp64 one.
 __device__ __forceinline__ double wave_sum_f64(double v) {
@@ -44,8 +54,14 @@ __device__ __forceinline__ double wave_sum_f64(double v) {
     return v;
 }
 
-// the butterfly of one value of the kinds the partial sums are kept in: a float, a double, or four floats as one 16-byte vector
+// the butterfly of one value of the kinds the partial sums are kept in: a float, a double, four floats as one 16-byte vector, or an
+// integer count
 __device__ __forceinline__ float plane_wave_sum(float v) { return wave_sum(v); }
+__device__ __forceinline__ int plane_wave_sum(int v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    return v;
+}
 __device__ __forceinline__ double plane_wave_sum(double v) { return wave_sum_f64(v); }
 __device__ __forceinline__ f32x4 plane_wave_sum(f32x4 v) {
 #pragma unroll
@@ -69,7 +85,7 @@ template <class T>
 __device__ __forceinline__ T plane_block_total(const T (&r)[4]) { return (r[0] + r[1]) + (r[2] + r[3]); }
 
 // Slice fold by one wave: lane l adds the partials (N values of type V per slice) of the slices l, l + 64, ... of plane pl in ascending
-// order, then the butterfly; every lane ends with the plane's sums in a[0 .. N).
+// order, then the butterfly; every lane ends with the plane's sums in a[0 .. N).  V = int folds one count per slice the same way.
 template <int N, class V>
 __device__ __forceinline__ void plane_fold_slices(const V* __restrict__ part, size_t pl, int slices, int lane, V* a) {
 #pragma unroll

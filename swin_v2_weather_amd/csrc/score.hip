@@ -35,7 +35,7 @@ template <bool CLIM>
 __global__ __launch_bounds__(256) void score_sums_kernel(const float* __restrict__ prd, long prd_bs, const float* __restrict__ tar, long tar_bs,
                                                          const float* __restrict__ clim, const float* __restrict__ w, float* __restrict__ ws,
                                                          int B, int C, int H, int W, int slices) {
-    const int b = blockIdx.x % B, cs = blockIdx.x / B, c = cs / slices, sl = cs - c * slices;
+    const auto [b, c, sl] = plane_shared_index(B, slices);
     const uint32_t plane = (uint32_t)H * W;                   // < 2^30 (checked by the host)
     uint32_t lo, hi;
     plane_slice_range(plane, sl, slices, lo, hi);

@@ -115,17 +115,22 @@ def _rollout_steps(net, x0, n_steps, coszen, n_invar, out, coff_of):
         yield s
 
 
+def _ring(rows, n_steps, Cout, H, W, device, keep_forecast):
+    """-> (out [rows, slots Cout, H, W]: a slot per step if keep_forecast, else a ring of two; coff_of: s -> step s's first channel; forecast)"""
+    out = torch.empty(rows, (n_steps if keep_forecast else 2) * Cout, H, W, dtype=torch.float32, device=device)
+    return out, (lambda s: (s if keep_forecast else s % 2) * Cout), out.view(rows, n_steps, Cout, H, W) if keep_forecast else None
+
+
 @torch.no_grad()
 def rollout(model, x0: torch.Tensor, n_steps: int, coszen: torch.Tensor | None = None, n_invar: int = 0) -> torch.Tensor:
     """x0 [B, Cin, H, W] (fields | zenith(t0) | invariants) -> forecasts [B, n_steps, Cout, H, W].
     coszen [B, n_steps - 1, H, W]: cos-zenith of the steps 1 .. n_steps - 1 inputs (required iff the model takes one)."""
     net = model.model if hasattr(model, "model") else model
     B, _, H, W = x0.shape
-    Cout = net.out_chans
-    out = torch.empty(B, n_steps * Cout, H, W, dtype=torch.float32, device=x0.device)
-    for _ in _rollout_steps(net, x0, n_steps, coszen, n_invar, out, lambda s: s * Cout):
+    out, coff_of, forecast = _ring(B, n_steps, net.out_chans, H, W, x0.device, True)
+    for _ in _rollout_steps(net, x0, n_steps, coszen, n_invar, out, coff_of):
         pass
-    return out.view(B, n_steps, Cout, H, W)
+    return forecast
 
 
 # degree power of forecast and analysis per lead time (batch means [n_steps, Cout, lmax]) and small_scale_power_ratio [n_steps, B, Cout]
@@ -143,12 +148,6 @@ def _stack_scores(per_step):
     return {k: torch.stack([d[k] for d in per_step], dim=0) for k in per_step[0]}
 
 
-def _events_of(per_step, spec):
-    """the EventScores of every step -> RolloutEvents"""
-    return RolloutEvents(spec, [t for t, _ in per_step], torch.stack([e.table for _, e in per_step], dim=0),
-                         torch.stack([e.n_invalid for _, e in per_step], dim=0), _stack_scores([e.pooled for _, e in per_step]))
-
-
 class RolloutScores(namedtuple("RolloutScores", "rmse acc rmse_samples acc_samples forecast tqe", defaults=(None,))):
     """score_rollout's answer.  The tuple keeps its six fields (callers unpack and build it positionally); `spectrum` rides along as an
     attribute: None, or the RolloutSpectrum of score_rollout(..., spectrum=True); so does `events`: None, or the RolloutEvents of
@@ -159,6 +158,50 @@ class RolloutScores(namedtuple("RolloutScores", "rmse acc rmse_samples acc_sampl
     def with_spectrum(self, spectrum):
         self.spectrum = spectrum
         return self
+
+
+def _truth_at(truth, s, device):
+    return (truth(s) if callable(truth) else truth[:, s]).to(device)
+
+
+def _check_events(who, events, scorer):
+    if events is not None and events.kind == "anomaly" and scorer.clim is None:
+        raise ValueError(f"{who}: anomaly events need a scorer with a climatology")
+
+
+class _StepScores:
+    """the per-step results of ONE deterministic forecast: score_rollout's, and the control (member 0) of ensemble_rollout"""
+
+    def __init__(self, scorer, n_steps, B, Cout, H, device, events=None, extremes=False, spectrum=False):
+        new = lambda *shape: torch.empty(n_steps, *shape, dtype=torch.float32, device=device)      # noqa: E731
+        self.rmse, self.rmse_s = new(Cout), new(B, Cout)
+        self.acc, self.acc_s = (new(Cout), new(B, Cout)) if scorer.clim is not None else (None, None)
+        self.tqe = new(B, Cout) if extremes else None
+        self.spec = RolloutSpectrum(new(Cout, H), new(Cout, H), new(B, Cout)) if spectrum else None
+        self.events, self.ev = events, []
+
+    def add(self, s, scorer, out, tar, coff):
+        r = scorer.score(out, tar, coff_prd=coff)
+        if self.tqe is not None:
+            self.tqe[s] = scorer.quantile_error(out, tar, coff_prd=coff)
+        if self.spec is not None:
+            ps = scorer.power_spectrum(out, tar, coff_prd=coff)
+            self.spec.pred[s], self.spec.truth[s], self.spec.ratio[s] = ps.pred.mean(dim=0), ps.truth.mean(dim=0), small_scale_power_ratio(ps.pred, ps.truth)
+        self.rmse[s], self.rmse_s[s] = r.rmse_mean, r.rmse
+        if self.acc is not None:
+            self.acc[s], self.acc_s[s] = r.acc_mean, r.acc
+
+    def add_events(self, s, scorer, out, tar, coff, thr=None):      # (a call of its own: the control scores its events first, on the ensemble's thr)
+        if self.events is not None:
+            thr = scorer.event_thresholds(self.events, tar) if thr is None else thr
+            self.ev.append((thr, scorer.event_score(out, tar, thr, anomaly=self.events.kind == "anomaly", below=self.events.below, coff_prd=coff)))
+
+    def result(self, forecast) -> RolloutScores:
+        res = RolloutScores(self.rmse, self.acc, self.rmse_s, self.acc_s, forecast, self.tqe).with_spectrum(self.spec)
+        if self.events is not None:           # the EventScores of every step -> RolloutEvents
+            res.events = RolloutEvents(self.events, [t for t, _ in self.ev], torch.stack([e.table for _, e in self.ev], dim=0),
+                                       torch.stack([e.n_invalid for _, e in self.ev], dim=0), _stack_scores([e.pooled for _, e in self.ev]))
+        return res
 
 
 @torch.no_grad()
@@ -183,40 +226,16 @@ def score_rollout(model, x0: torch.Tensor, truth, n_steps: int, coszen: torch.Te
     Cout = net.out_chans
     if scorer is None:
         scorer = ForecastScorer(H, W, Cout, x0.device)
-    if events is not None and events.kind == "anomaly" and scorer.clim is None:
-        raise ValueError("score_rollout: anomaly events need a scorer with a climatology")
-    ev = []
+    _check_events("score_rollout", events, scorer)
     if spectrum and isinstance(scorer, RegriddedScorer):
         raise ValueError("score_rollout: spectrum=True needs a ForecastScorer (degree spectra are taken on the model's own grid)")
-    slots = n_steps if keep_forecast else 2
-    out = torch.empty(B, slots * Cout, H, W, dtype=torch.float32, device=x0.device)
-    coff_of = (lambda s: s * Cout) if keep_forecast else (lambda s: (s % 2) * Cout)
-    rmse = torch.empty(n_steps, Cout, dtype=torch.float32, device=x0.device)
-    rmse_s = torch.empty(n_steps, B, Cout, dtype=torch.float32, device=x0.device)
-    acc, acc_s = (torch.empty_like(rmse), torch.empty_like(rmse_s)) if scorer.clim is not None else (None, None)
-    tqe = torch.empty_like(rmse_s) if extremes else None
-    spec = None
-    if spectrum:
-        spec = RolloutSpectrum(torch.empty(n_steps, Cout, H, dtype=torch.float32, device=x0.device),
-                               torch.empty(n_steps, Cout, H, dtype=torch.float32, device=x0.device), torch.empty_like(rmse_s))
+    out, coff_of, forecast = _ring(B, n_steps, Cout, H, W, x0.device, keep_forecast)
+    steps = _StepScores(scorer, n_steps, B, Cout, H, x0.device, events, extremes, spectrum)
     for s in _rollout_steps(net, x0, n_steps, coszen, n_invar, out, coff_of):
-        tar = (truth(s) if callable(truth) else truth[:, s]).to(x0.device)
-        r = scorer.score(out, tar, coff_prd=coff_of(s))
-        if extremes:
-            tqe[s] = scorer.quantile_error(out, tar, coff_prd=coff_of(s))
-        if spectrum:
-            ps = scorer.power_spectrum(out, tar, coff_prd=coff_of(s))
-            spec.pred[s], spec.truth[s], spec.ratio[s] = ps.pred.mean(dim=0), ps.truth.mean(dim=0), small_scale_power_ratio(ps.pred, ps.truth)
-        if events is not None:
-            thr = scorer.event_thresholds(events, tar)
-            ev.append((thr, scorer.event_score(out, tar, thr, anomaly=events.kind == "anomaly", below=events.below, coff_prd=coff_of(s))))
-        rmse[s], rmse_s[s] = r.rmse_mean, r.rmse
-        if acc is not None:
-            acc[s], acc_s[s] = r.acc_mean, r.acc
-    res = RolloutScores(rmse, acc, rmse_s, acc_s, out.view(B, n_steps, Cout, H, W) if keep_forecast else None, tqe).with_spectrum(spec)
-    if events is not None:
-        res.events = _events_of(ev, events)
-    return res
+        tar = _truth_at(truth, s, x0.device)
+        steps.add(s, scorer, out, tar, coff_of(s))
+        steps.add_events(s, scorer, out, tar, coff_of(s))
+    return steps.result(forecast)
 
 
 def perturb_initial_condition(x0: torch.Tensor, n_members: int, amplitude: float, seed: int, n_fields: int, kind: str = "white",
@@ -279,7 +298,6 @@ def ensemble_rollout(model, x0: torch.Tensor, truth, n_steps: int, n_members: in
     net = model.model if hasattr(model, "model") else model
     B, Cin, H, W = x0.shape
     M, Cout = int(n_members), net.out_chans
-    ev, ev_ctl = [], []
     if M < 2:
         raise ValueError(f"ensemble_rollout: {M} members (an ensemble has at least 2)")
     K = M if member_batch is None else int(member_batch)
@@ -287,14 +305,11 @@ def ensemble_rollout(model, x0: torch.Tensor, truth, n_steps: int, n_members: in
         raise ValueError(f"ensemble_rollout: member_batch {member_batch}")
     if scorer is None:
         scorer = ForecastScorer(H, W, Cout, x0.device)
-    if events is not None and events.kind == "anomaly" and scorer.clim is None:
-        raise ValueError("ensemble_rollout: anomaly events need a scorer with a climatology")
+    _check_events("ensemble_rollout", events, scorer)
     if n_fields is None:
         n_fields = Cin - n_invar - int(coszen is not None)
     xe = perturb_initial_condition(x0, M, amplitude, seed, n_fields, perturbation_kind, length_scale_km)
-    slots = n_steps if keep_forecast else 2
-    out = torch.empty(M * B, slots * Cout, H, W, dtype=torch.float32, device=x0.device)
-    coff_of = (lambda s: s * Cout) if keep_forecast else (lambda s: (s % 2) * Cout)
+    out, coff_of, forecast = _ring(M * B, n_steps, Cout, H, W, x0.device, keep_forecast)
     chunks = []
     for m0 in range(0, M, K):
         r0, r1 = m0 * B, min(m0 + K, M) * B
@@ -302,39 +317,27 @@ def ensemble_rollout(model, x0: torch.Tensor, truth, n_steps: int, n_members: in
         chunks.append(_rollout_steps(net, xe[r0:r1], n_steps, cz, n_invar, out[r0:r1], coff_of))
     mean = {k: torch.empty(n_steps, Cout, dtype=torch.float32, device=x0.device) for k in ("crps", "fair_crps", "spread", "ens_rmse")}
     samp = {k: torch.empty(n_steps, B, Cout, dtype=torch.float32, device=x0.device) for k in mean}
-    hist = torch.empty(n_steps, B, Cout, M + 1, dtype=torch.int32, device=x0.device)
-    ctl = None
-    if score_control:
-        ctl = [torch.empty(n_steps, Cout, dtype=torch.float32, device=x0.device), torch.empty(n_steps, B, Cout, dtype=torch.float32, device=x0.device)]
-        ctl += [torch.empty_like(t) for t in ctl] if scorer.clim is not None else [None, None]
+    hist, ev = torch.empty(n_steps, B, Cout, M + 1, dtype=torch.int32, device=x0.device), []
+    ctl = _StepScores(scorer, n_steps, B, Cout, H, x0.device, events) if score_control else None      # member 0: the deterministic forecast
     for s in range(n_steps):
         for ch in chunks:
             next(ch)
-        tar = (truth(s) if callable(truth) else truth[:, s]).to(x0.device)
+        tar = _truth_at(truth, s, x0.device)
         r = scorer.ensemble_score(out, tar, M, coff_ens=coff_of(s))
         for k in mean:
             mean[k][s], samp[k][s] = getattr(r, k + "_mean"), getattr(r, k)
         hist[s] = r.hist
+        thr = None if events is None else scorer.event_thresholds(events, tar)
         if events is not None:
-            thr = scorer.event_thresholds(events, tar)
-            kw = dict(anomaly=events.kind == "anomaly", below=events.below)
-            ev.append((thr, scorer.ensemble_event_score(out, tar, M, thr, coff_ens=coff_of(s), **kw)))
-            if score_control:
-                ev_ctl.append((thr, scorer.event_score(out[:B], tar, thr, coff_prd=coff_of(s), **kw)))
-        if score_control:
-            c = scorer.score(out[:B], tar, coff_prd=coff_of(s))
-            ctl[0][s], ctl[1][s] = c.rmse_mean, c.rmse
-            if ctl[2] is not None:
-                ctl[2][s], ctl[3][s] = c.acc_mean, c.acc
-    control = None if ctl is None else RolloutScores(ctl[0], ctl[2], ctl[1], ctl[3], None)
-    res = EnsembleRolloutScores(mean["crps"], mean["fair_crps"], mean["spread"], mean["ens_rmse"], samp["crps"], samp["fair_crps"], samp["spread"],
-                                samp["ens_rmse"], hist, out.view(M * B, n_steps, Cout, H, W) if keep_forecast else None, control)
+            ev.append((thr, scorer.ensemble_event_score(out, tar, M, thr, anomaly=events.kind == "anomaly", below=events.below, coff_ens=coff_of(s))))
+        if ctl is not None:
+            ctl.add_events(s, scorer, out[:B], tar, coff_of(s), thr)
+            ctl.add(s, scorer, out[:B], tar, coff_of(s))
+    res = EnsembleRolloutScores(*mean.values(), *samp.values(), hist, forecast, None if ctl is None else ctl.result(None))      # (the fields' order)
     if events is not None:
         stack = lambda i: torch.stack([e[i] for _, e in ev], dim=0)      # noqa: E731
         res.events = EnsembleRolloutEvents(events, [t for t, _ in ev], stack(0), stack(1), stack(2), stack(3),
                                            _stack_scores([{**e.pooled, **e.reliability} for _, e in ev]))
-        if control is not None:
-            control.events = _events_of(ev_ctl, events)
     return res
 
 

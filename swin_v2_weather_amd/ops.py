@@ -7,6 +7,7 @@ from __future__ import annotations
 
 import ctypes as C
 import functools
+import math
 from typing import Optional
 
 import torch
@@ -423,40 +424,84 @@ def score_slices(planes: int, H: int, W: int) -> int:
     return int(L.load().swv2_score_slices(planes, H, W))
 
 
-def score_workspace(planes: int, H: int, W: int, device) -> torch.Tensor:
-    """the caller's workspace of swv2_score_sums / swv2_score_finalize for `planes` = B * C planes: allocate once, reuse"""
-    return torch.empty(int(L.load().swv2_score_ws_bytes(planes, H, W)) // 4, dtype=torch.float32, device=device)
+# ---- blocks of planes read in place (DESIGN "Blocks of planes read in place"): the operand contract of every score family ----------------
+ENS_MAX_MEMBERS = 64          # the M cap of swv2_ens_sums
+EVENT_MAX_K = 8               # the threshold cap of swv2_event_sums / swv2_event_ens_sums
+QUANTILE_MAX_RANKS = 256      # the K cap of swv2_plane_order_stats
+REGRID_MAX_BAND = 32          # the KH / KW cap of swv2_regrid
 
 
-def _planes_in_place(t: torch.Tensor, lead: int) -> bool:
-    """a CUDA fp32 block of planes a plane-streaming kernel (csrc/plane_stream.h) reads in place: `lead` leading dimensions ([B] or
-    [M, B]), then [C, H, W] with contiguous planes, 16-byte aligned; the batch stride, unless B == 1, a multiple of 4 that steps over the
-    C planes of a sample"""
+def _planes_in_place(t: torch.Tensor, lead: int = 1, vec=True) -> bool:
+    """THE rule.  A CUDA fp32 block of planes a kernel takes where it lies: `lead` leading dimensions ([B], or [M, B] for the member view
+    with 2 <= M <= ENS_MAX_MEMBERS and a member stride that is a multiple of 4), then [C, H, W] with contiguous planes; the batch
+    stride, unless B == 1 (where nobody uses it), a multiple of 4 that steps over the C planes of a sample.  vec: how the kernel touches
+    the planes -- True: 16-byte vectors that never straddle a row (aligned, W % 4 == 0); "plane": 16-byte vectors through the
+    flattened plane (aligned, H * W % 4 == 0, H * W < 2^30); False: single elements (no further rule)."""
     if not (t.is_cuda and t.dtype == torch.float32 and t.dim() == lead + 3 and t.numel() > 0):
         return False
     B, (Cc, H, W), bs = t.shape[lead - 1], t.shape[lead:], t.stride(lead - 1)
-    return tuple(t.stride()[lead:]) == (H * W, W, 1) and t.data_ptr() % 16 == 0 and (B == 1 or (bs % 4 == 0 and bs >= Cc * H * W))
+    if tuple(t.stride()[lead:]) != (H * W, W, 1) or not (B == 1 or (bs % 4 == 0 and bs >= Cc * H * W)):
+        return False
+    if lead == 2 and not (2 <= t.shape[0] <= ENS_MAX_MEMBERS and t.stride(0) % 4 == 0):
+        return False
+    whole = {True: W % 4 == 0, "plane": (H * W) % 4 == 0 and H * W < 2 ** 30, False: None}[vec]
+    return whole is None or (whole and t.data_ptr() % 16 == 0)
+
+
+def _plane_block(who: str, t: torch.Tensor, lead: int = 1, vec=True):
+    """t under _planes_in_place, or Swv2Error -> what the C call takes of it: (pointer, batch stride), for the member view (pointer,
+    member stride, batch stride).  The batch stride handed on is the tensor's, or the span of one sample where B == 1."""
+    if not _planes_in_place(t, lead, vec):
+        dims = "[M, B, C, H, W] members, 2 <= M <= %d," % ENS_MAX_MEMBERS if lead == 2 else "[B, C, H, W]"
+        rule = {True: ", 16-byte aligned, W % 4 == 0", "plane": ", 16-byte aligned, H * W % 4 == 0", False: ""}[vec]
+        raise L.Swv2Error(f"{who}: expected a CUDA fp32 {dims} block of planes to take in place (contiguous planes{rule}; strides above the "
+                          f"planes multiples of 4 that step over a sample, unless B == 1), got {tuple(t.shape)} {t.dtype} strides {t.stride()} "
+                          f"on {t.device}, address % 16 = {t.data_ptr() % 16 if t.numel() else 0}")
+    bs = t.stride(lead - 1) if t.shape[lead - 1] > 1 else math.prod(t.shape[lead:])
+    return (t.data_ptr(), bs) if lead == 1 else (t.data_ptr(), t.stride(0), bs)
+
+
+def _plane_blocks(who: str, x: torch.Tensor, tar: torch.Tensor, lead: int = 1):
+    """the operand pair of the sum kernels: x ([B, ...], or the member view with lead = 2) and the truth [B, C, H, W] of the same planes on
+    the same device -> _plane_block of each"""
+    px, pt = _plane_block(who, x, lead), _plane_block(who, tar)
+    if x.shape[lead - 1:] != tar.shape or x.device != tar.device:
+        raise L.Swv2Error(f"{who}: blocks {tuple(x.shape)} on {x.device} / {tuple(tar.shape)} on {tar.device} do not name the same planes")
+    return px, pt
+
+
+def _row_weights(who: str, w: torch.Tensor, H: int):
+    if _chk(w, torch.float32, "row weights").numel() != H:
+        raise L.Swv2Error(f"{who}: {w.numel()} row weights for {H} rows")
+
+
+def _plane_workspace(who: str, nbytes: int, dtype, device, limits: str = "") -> torch.Tensor:
+    """nbytes (the answer of the family's swv2_*_ws_bytes) as a fresh tensor of dtype; a family that answers 0 for arguments outside its
+    limits names them, and 0 is refused with that text"""
+    if limits and not nbytes:
+        raise L.Swv2Error(f"{who}: {limits}")
+    return torch.empty(int(nbytes) // dtype.itemsize, dtype=dtype, device=device)
+
+
+def score_workspace(planes: int, H: int, W: int, device) -> torch.Tensor:
+    """the caller's workspace of swv2_score_sums / swv2_score_finalize for `planes` = B * C planes: allocate once, reuse"""
+    return _plane_workspace("score_workspace", L.load().swv2_score_ws_bytes(planes, H, W), torch.float32, device)
 
 
 def score_planes_ok(t: torch.Tensor) -> bool:
     """what swv2_score_sums takes in place: a CUDA fp32 [B, C, H, W] tensor or channel block of one (contiguous planes, W % 4 == 0)"""
-    return _planes_in_place(t, 1) and t.shape[3] % 4 == 0
+    return _planes_in_place(t)
 
 
 def score_sums(prd, tar, w, ws, clim=None):
     """the four weighted sums of every (b, c) plane of prd / tar (each [B, C, H, W] or a channel block `x[:, a:b]` of a wider contiguous
     tensor, scored in place) as slice partials in ws (score_workspace); w [H] row weights, clim [C, H, W] or None"""
-    if not (score_planes_ok(prd) and score_planes_ok(tar)) or prd.shape != tar.shape:
-        raise L.Swv2Error(f"score_sums: expected two CUDA fp32 [B, C, H, W] tensors of one shape with contiguous planes and W % 4 == 0, got "
-                          f"{tuple(prd.shape)} {prd.dtype} strides {prd.stride()} / {tuple(tar.shape)} {tar.dtype} strides {tar.stride()}")
+    (pp, pbs), (tp, tbs) = _plane_blocks("score_sums", prd, tar)
     B, Cc, H, W = prd.shape
-    _chk(w, torch.float32, "row weights"); _chk(ws, torch.float32, "score workspace")
-    if w.numel() != H:
-        raise L.Swv2Error(f"score_sums: {w.numel()} row weights for {H} rows")
+    _row_weights("score_sums", w, H); _chk(ws, torch.float32, "score workspace")
     if clim is not None and (_chk(clim, torch.float32, "climatology").shape != (Cc, H, W)):
         raise L.Swv2Error(f"score_sums: climatology {tuple(clim.shape)}, expected {(Cc, H, W)}")
-    L.check(L.load().swv2_score_sums(_p(prd), prd.stride(0) if B > 1 else Cc * H * W, _p(tar), tar.stride(0) if B > 1 else Cc * H * W,
-                                     _p(clim), _p(w), B, Cc, H, W, _p(ws), ws.numel() * 4, _stream()), "swv2_score_sums")
+    L.check(L.load().swv2_score_sums(pp, pbs, tp, tbs, _p(clim), _p(w), B, Cc, H, W, _p(ws), ws.numel() * 4, _stream()), "swv2_score_sums")
 
 
 def score_finalize(ws, B: int, Cc: int, H: int, W: int, scale=None):
@@ -485,26 +530,21 @@ def forecast_scores(prd, tar, w, clim=None, scale=None, ws=None):
 
 def l1_workspace(planes: int, H: int, W: int, device) -> torch.Tensor:
     """the caller's workspace of swv2_l1_sums / swv2_l1_finalize for `planes` = B * C planes: allocate once, reuse"""
-    return torch.empty(int(L.load().swv2_l1_ws_bytes(planes, H, W)) // 4, dtype=torch.float32, device=device)
+    return _plane_workspace("l1_workspace", L.load().swv2_l1_ws_bytes(planes, H, W), torch.float32, device)
 
 
 def loss_workspace(planes: int, H: int, W: int, device) -> torch.Tensor:
     """the caller's workspace of swv2_loss_sums for `planes` = B * C planes: allocate once, reuse"""
-    return torch.empty(int(L.load().swv2_loss_ws_bytes(planes, H, W)) // 4, dtype=torch.float32, device=device)
+    return _plane_workspace("loss_workspace", L.load().swv2_loss_ws_bytes(planes, H, W), torch.float32, device)
 
 
 def l1_sums(prd, tar, w, ws):
     """S0 = sum w |prd - tar| and S1 = sum w |tar| of every (b, c) plane (prd / tar as score_sums takes them: [B, C, H, W] or a channel
     block of a wider contiguous tensor, read in place) as slice partials in ws (l1_workspace); w [H] row weights"""
-    if not (score_planes_ok(prd) and score_planes_ok(tar)) or prd.shape != tar.shape:
-        raise L.Swv2Error(f"l1_sums: expected two CUDA fp32 [B, C, H, W] tensors of one shape with contiguous planes and W % 4 == 0, got "
-                          f"{tuple(prd.shape)} {prd.dtype} strides {prd.stride()} / {tuple(tar.shape)} {tar.dtype} strides {tar.stride()}")
+    (pp, pbs), (tp, tbs) = _plane_blocks("l1_sums", prd, tar)
     B, Cc, H, W = prd.shape
-    _chk(w, torch.float32, "row weights"); _chk(ws, torch.float32, "l1 workspace")
-    if w.numel() != H:
-        raise L.Swv2Error(f"l1_sums: {w.numel()} row weights for {H} rows")
-    L.check(L.load().swv2_l1_sums(_p(prd), prd.stride(0) if B > 1 else Cc * H * W, _p(tar), tar.stride(0) if B > 1 else Cc * H * W, _p(w),
-                                  B, Cc, H, W, _p(ws), ws.numel() * 4, _stream()), "swv2_l1_sums")
+    _row_weights("l1_sums", w, H); _chk(ws, torch.float32, "l1 workspace")
+    L.check(L.load().swv2_l1_sums(pp, pbs, tp, tbs, _p(w), B, Cc, H, W, _p(ws), ws.numel() * 4, _stream()), "swv2_l1_sums")
 
 
 def l1_finalize(ws, B: int, Cc: int, H: int, W: int, chw=None, absolute: bool = False):
@@ -532,34 +572,26 @@ def l1_grad(prd, tar, qw, coef, dprd):
     L.check(L.load().swv2_l1_grad(_p(prd), _p(tar), _p(qw), _p(coef), _p(dprd), B * Cc, H, W, _stream()), "swv2_l1_grad")
 
 
-REGRID_MAX_BAND = 32          # the KH / KW cap of swv2_regrid
-
-
 def regrid_planes_ok(t: torch.Tensor, source: bool) -> bool:
-    """what swv2_regrid reads (source: 16-byte aligned, W % 4 == 0) or writes in place: a CUDA fp32 [B, C, H, W] tensor or channel block
-    of one with contiguous planes; the batch stride, unless B == 1, a multiple of 4 that steps over the C planes of a sample"""
-    if not (t.is_cuda and t.dtype == torch.float32 and t.dim() == 4 and t.numel() > 0):
-        return False
-    B, Cc, H, W = t.shape
-    if tuple(t.stride()[1:]) != (H * W, W, 1) or not (B == 1 or (t.stride(0) % 4 == 0 and t.stride(0) >= Cc * H * W)):
-        return False
-    return not source or (W % 4 == 0 and t.data_ptr() % 16 == 0)
+    """what swv2_regrid reads (source: 16-byte vectors along the rows) or writes (element by element: any address, any width) in place: a
+    CUDA fp32 [B, C, H, W] tensor or channel block of one"""
+    return _planes_in_place(t, vec=bool(source))
 
 
 def regrid(x, y, lat_start, lat_count, lat_w, lon_start, lon_count, lon_w):
     """y [B, C, Hd, Wd] = the banded operators applied to x [B, C, H, W] (each a tensor or channel block read / written in place):
     swv2_regrid with the tables of utils/regrid.py::band_tables on the device (int32 start and count [n], fp32 weights [n, K]).  The
     kernel trusts the tables' indices (include/swv2.h): build them with band_tables, as Regridder does."""
-    if not (regrid_planes_ok(x, True) and regrid_planes_ok(y, False)) or x.shape[:2] != y.shape[:2] or x.device != y.device:
-        raise L.Swv2Error(f"regrid: expected CUDA fp32 [B, C, H, W] -> [B, C, Hd, Wd] with contiguous planes and W % 4 == 0, got "
-                          f"{tuple(x.shape)} {x.dtype} strides {x.stride()} / {tuple(y.shape)} {y.dtype} strides {y.stride()}")
+    (xp, xbs), (yp, ybs) = _plane_block("regrid", x), _plane_block("regrid", y, vec=False)
+    if x.shape[:2] != y.shape[:2] or x.device != y.device:
+        raise L.Swv2Error(f"regrid: source {tuple(x.shape)} on {x.device} / destination {tuple(y.shape)} on {y.device}: expected one B, C and device")
     B, Cc, H, W = x.shape
     Hd, Wd = y.shape[2:]
     for t, dt, n, what in ((lat_start, torch.int32, Hd, "lat_start"), (lat_count, torch.int32, Hd, "lat_count"), (lat_w, torch.float32, Hd, "lat_w"),
                            (lon_start, torch.int32, Wd, "lon_start"), (lon_count, torch.int32, Wd, "lon_count"), (lon_w, torch.float32, Wd, "lon_w")):
         if _chk(t, dt, what).shape[0] != n or t.dim() != (2 if dt == torch.float32 else 1) or t.device != x.device:
             raise L.Swv2Error(f"regrid: table {what} {tuple(t.shape)}, expected {n} rows on {x.device}")
-    L.check(L.load().swv2_regrid(_p(x), x.stride(0) if B > 1 else Cc * H * W, _p(y), y.stride(0) if B > 1 else Cc * Hd * Wd, B, Cc, H, W, Hd, Wd,
+    L.check(L.load().swv2_regrid(xp, xbs, yp, ybs, B, Cc, H, W, Hd, Wd,
                                  _p(lat_start), _p(lat_count), _p(lat_w), lat_w.shape[1], _p(lon_start), _p(lon_count), _p(lon_w), lon_w.shape[1],
                                  _stream()), "swv2_regrid")
 
@@ -630,37 +662,25 @@ def sht_synth(table, rweights, coef, response=None, scales=(1.0, 1.0), *, nlon: 
     return S
 
 
-ENS_MAX_MEMBERS = 64          # the M cap of swv2_ens_sums
-
-
 def ens_workspace(planes: int, H: int, W: int, M: int, device) -> torch.Tensor:
     """the caller's workspace of swv2_ens_sums / swv2_ens_finalize for `planes` = B * C planes and M members: allocate once, reuse"""
-    n = int(L.load().swv2_ens_ws_bytes(planes, H, W, M))
-    if n == 0:
-        raise L.Swv2Error(f"ens_workspace: planes {planes}, H {H}, W {W} must be positive and M = {M} within 2 .. {ENS_MAX_MEMBERS}")
-    return torch.empty(n // 4, dtype=torch.float32, device=device)
+    return _plane_workspace("ens_workspace", L.load().swv2_ens_ws_bytes(planes, H, W, M), torch.float32, device,
+                            f"planes {planes}, H {H}, W {W} must be positive and M = {M} within 2 .. {ENS_MAX_MEMBERS}")
 
 
 def ens_members_ok(t: torch.Tensor) -> bool:
     """what swv2_ens_sums reads in place as the members: a CUDA fp32 [M, B, C, H, W] view (contiguous planes, W % 4 == 0, 2 <= M <= 64,
     member and batch strides multiples of 4) -- a channel block of a member-major [M * B, channels, H, W] tensor viewed that way"""
-    return _planes_in_place(t, 2) and 2 <= t.shape[0] <= ENS_MAX_MEMBERS and t.shape[4] % 4 == 0 and t.stride(0) % 4 == 0
+    return _planes_in_place(t, lead=2)
 
 
 def ens_sums(ens, tar, w, ws):
     """the partial sums and rank counts of every (b, c) plane of the members ens [M, B, C, H, W] against tar [B, C, H, W] (both may be
     channel blocks of wider tensors, read in place) into ws (ens_workspace); w [H] row weights"""
-    if not (ens_members_ok(ens) and score_planes_ok(tar)) or ens.shape[1:] != tar.shape or ens.device != tar.device:
-        raise L.Swv2Error(f"ens_sums: expected CUDA fp32 members [M, B, C, H, W] (2 <= M <= {ENS_MAX_MEMBERS}) and truth [B, C, H, W] with contiguous "
-                          f"planes and W % 4 == 0, got {tuple(ens.shape)} {ens.dtype} strides {ens.stride()} / {tuple(tar.shape)} {tar.dtype} "
-                          f"strides {tar.stride()}")
+    (ep, ems, ebs), (tp, tbs) = _plane_blocks("ens_sums", ens, tar, lead=2)
     M, B, Cc, H, W = ens.shape
-    _chk(w, torch.float32, "row weights"); _chk(ws, torch.float32, "ensemble workspace")
-    if w.numel() != H:
-        raise L.Swv2Error(f"ens_sums: {w.numel()} row weights for {H} rows")
-    span = Cc * H * W
-    L.check(L.load().swv2_ens_sums(_p(ens), ens.stride(0), ens.stride(1) if B > 1 else span, _p(tar), tar.stride(0) if B > 1 else span, _p(w),
-                                   M, B, Cc, H, W, _p(ws), ws.numel() * 4, _stream()), "swv2_ens_sums")
+    _row_weights("ens_sums", w, H); _chk(ws, torch.float32, "ensemble workspace")
+    L.check(L.load().swv2_ens_sums(ep, ems, ebs, tp, tbs, _p(w), M, B, Cc, H, W, _p(ws), ws.numel() * 4, _stream()), "swv2_ens_sums")
 
 
 def ens_finalize(ws, M: int, B: int, Cc: int, H: int, W: int, scale=None):
@@ -680,32 +700,23 @@ def ens_finalize(ws, M: int, B: int, Cc: int, H: int, W: int, scale=None):
     return sums, hist, er, sp, cr, fc, means
 
 
-EVENT_MAX_K = 8               # the threshold cap of swv2_event_sums / swv2_event_ens_sums
-
-
 def event_workspace(planes: int, H: int, W: int, K: int, device) -> torch.Tensor:
     """the caller's workspace of swv2_event_sums / swv2_event_finalize for `planes` = B * C planes and K thresholds: allocate once, reuse"""
-    n = int(L.load().swv2_event_ws_bytes(planes, H, W, K))
-    if n == 0:
-        raise L.Swv2Error(f"event_workspace: planes {planes}, H {H}, W {W} must be positive and K = {K} within 1 .. {EVENT_MAX_K}")
-    return torch.empty(n // 4, dtype=torch.float32, device=device)
+    return _plane_workspace("event_workspace", L.load().swv2_event_ws_bytes(planes, H, W, K), torch.float32, device,
+                            f"planes {planes}, H {H}, W {W} must be positive and K = {K} within 1 .. {EVENT_MAX_K}")
 
 
 def ens_event_workspace(planes: int, H: int, W: int, M: int, K: int, device) -> torch.Tensor:
     """the caller's workspace of swv2_event_ens_sums / swv2_event_ens_finalize: allocate once, reuse"""
-    n = int(L.load().swv2_event_ens_ws_bytes(planes, H, W, M, K))
-    if n == 0:
-        raise L.Swv2Error(f"ens_event_workspace: planes {planes}, H {H}, W {W} must be positive, M = {M} within 2 .. {ENS_MAX_MEMBERS} and "
-                          f"K = {K} within 1 .. {EVENT_MAX_K}")
-    return torch.empty(n // 4, dtype=torch.float32, device=device)
+    return _plane_workspace("ens_event_workspace", L.load().swv2_event_ens_ws_bytes(planes, H, W, M, K), torch.float32, device,
+                            f"planes {planes}, H {H}, W {W} must be positive, M = {M} within 2 .. {ENS_MAX_MEMBERS} and K = {K} within 1 .. "
+                            f"{EVENT_MAX_K}")
 
 
 def _event_operands(who, x_shape, thr, w, base):
     """checks of the operands both event kernels share -> (K, thr batch stride)"""
     B, Cc, H, W = x_shape
-    _chk(w, torch.float32, "row weights"); _chk(thr, torch.float32, "thresholds")
-    if w.numel() != H:
-        raise L.Swv2Error(f"{who}: {w.numel()} row weights for {H} rows")
+    _row_weights(who, w, H); _chk(thr, torch.float32, "thresholds")
     if thr.dim() != 3 or thr.shape[1] != Cc or thr.shape[0] not in (1, B) or not 1 <= thr.shape[2] <= EVENT_MAX_K:
         raise L.Swv2Error(f"{who}: thresholds {tuple(thr.shape)}, expected [1 or {B}, {Cc}, K <= {EVENT_MAX_K}]")
     if base is not None and (_chk(base, torch.float32, "base field").shape != (Cc, H, W)):
@@ -717,15 +728,12 @@ def _event_operands(who, x_shape, thr, w, base):
 def event_sums(prd, tar, thr, w, ws, base=None, below=False):
     """the contingency-table partial sums of every (b, c) plane of prd / tar (each [B, C, H, W] or a channel block of a wider tensor, read
     in place) into ws (event_workspace); thr [1 or B, C, K] contiguous, w [H] row weights, base [C, H, W] or None"""
-    if not (score_planes_ok(prd) and score_planes_ok(tar)) or prd.shape != tar.shape:
-        raise L.Swv2Error(f"event_sums: expected two CUDA fp32 [B, C, H, W] tensors of one shape with contiguous planes and W % 4 == 0, got "
-                          f"{tuple(prd.shape)} {prd.dtype} strides {prd.stride()} / {tuple(tar.shape)} {tar.dtype} strides {tar.stride()}")
+    (pp, pbs), (tp, tbs) = _plane_blocks("event_sums", prd, tar)
     B, Cc, H, W = prd.shape
-    K, tbs = _event_operands("event_sums", prd.shape, thr, w, base)
+    K, thr_bs = _event_operands("event_sums", prd.shape, thr, w, base)
     _chk(ws, torch.float32, "event workspace")
-    span = Cc * H * W
-    L.check(L.load().swv2_event_sums(_p(prd), prd.stride(0) if B > 1 else span, _p(tar), tar.stride(0) if B > 1 else span, _p(base), _p(thr), tbs,
-                                     _p(w), K, int(bool(below)), B, Cc, H, W, _p(ws), ws.numel() * 4, _stream()), "swv2_event_sums")
+    L.check(L.load().swv2_event_sums(pp, pbs, tp, tbs, _p(base), _p(thr), thr_bs, _p(w), K, int(bool(below)), B, Cc, H, W, _p(ws), ws.numel() * 4,
+                                     _stream()), "swv2_event_sums")
 
 
 def event_finalize(ws, K: int, B: int, Cc: int, H: int, W: int):
@@ -740,17 +748,12 @@ def event_finalize(ws, K: int, B: int, Cc: int, H: int, W: int):
 def ens_event_sums(ens, tar, thr, w, ws, base=None, below=False):
     """the Brier partial sums and reliability counts of every (b, c) plane of the members ens [M, B, C, H, W] against tar [B, C, H, W] (both may
     be channel blocks of wider tensors, read in place) into ws (ens_event_workspace)"""
-    if not (ens_members_ok(ens) and score_planes_ok(tar)) or ens.shape[1:] != tar.shape or ens.device != tar.device:
-        raise L.Swv2Error(f"ens_event_sums: expected CUDA fp32 members [M, B, C, H, W] (2 <= M <= {ENS_MAX_MEMBERS}) and truth [B, C, H, W] with "
-                          f"contiguous planes and W % 4 == 0, got {tuple(ens.shape)} {ens.dtype} strides {ens.stride()} / {tuple(tar.shape)} "
-                          f"{tar.dtype} strides {tar.stride()}")
+    (ep, ems, ebs), (tp, tbs) = _plane_blocks("ens_event_sums", ens, tar, lead=2)
     M, B, Cc, H, W = ens.shape
-    K, tbs = _event_operands("ens_event_sums", tar.shape, thr, w, base)
+    K, thr_bs = _event_operands("ens_event_sums", tar.shape, thr, w, base)
     _chk(ws, torch.float32, "ensemble event workspace")
-    span = Cc * H * W
-    L.check(L.load().swv2_event_ens_sums(_p(ens), ens.stride(0), ens.stride(1) if B > 1 else span, _p(tar), tar.stride(0) if B > 1 else span,
-                                         _p(base), _p(thr), tbs, _p(w), M, K, int(bool(below)), B, Cc, H, W, _p(ws), ws.numel() * 4, _stream()),
-            "swv2_event_ens_sums")
+    L.check(L.load().swv2_event_ens_sums(ep, ems, ebs, tp, tbs, _p(base), _p(thr), thr_bs, _p(w), M, K, int(bool(below)), B, Cc, H, W, _p(ws),
+                                         ws.numel() * 4, _stream()), "swv2_event_ens_sums")
 
 
 def ens_event_finalize(ws, M: int, K: int, B: int, Cc: int, H: int, W: int):
@@ -765,18 +768,15 @@ def ens_event_finalize(ws, M: int, K: int, B: int, Cc: int, H: int, W: int):
     return sums, wv, hist, ninv
 
 
-QUANTILE_MAX_RANKS = 256      # the K cap of swv2_plane_order_stats
-
-
 def quantile_workspace(planes: int, H: int, W: int, K: int, device) -> torch.Tensor:
     """the caller's workspace of swv2_plane_order_stats for `planes` = B * C planes and K ranks: allocate once, reuse; never zeroed"""
-    return torch.empty(int(L.load().swv2_quantile_ws_bytes(planes, H, W, K)) // 4, dtype=torch.int32, device=device)
+    return _plane_workspace("quantile_workspace", L.load().swv2_quantile_ws_bytes(planes, H, W, K), torch.int32, device)
 
 
 def quantile_planes_ok(t: torch.Tensor) -> bool:
     """what swv2_plane_order_stats reads in place: a CUDA fp32 [B, C, H, W] tensor or channel block of one (contiguous planes,
     H * W % 4 == 0)"""
-    return _planes_in_place(t, 1) and (t.shape[2] * t.shape[3]) % 4 == 0 and t.shape[2] * t.shape[3] < 2 ** 30
+    return _planes_in_place(t, vec="plane")
 
 
 def plane_order_stats(x, ranks, ws=None):
@@ -784,9 +784,7 @@ def plane_order_stats(x, ranks, ws=None):
     x: [B, C, H, W] or a channel block of a wider tensor, read in place; ranks: [K] int32 on x's device, distinct, ascending, in
     [0, H * W), K <= QUANTILE_MAX_RANKS (the caller's promise: utils/weighted_acc_rmse.quantile_ranks builds them); ws: a
     quantile_workspace to reuse (allocated here otherwise)."""
-    if not quantile_planes_ok(x):
-        raise L.Swv2Error(f"plane_order_stats: expected a CUDA fp32 [B, C, H, W] tensor with contiguous planes and H * W % 4 == 0, got "
-                          f"{tuple(x.shape)} {x.dtype} strides {x.stride()}")
+    xp, xbs = _plane_block("plane_order_stats", x, vec="plane")
     B, Cc, H, W = x.shape
     _chk(ranks, torch.int32, "ranks")
     K = ranks.numel()
@@ -797,7 +795,7 @@ def plane_order_stats(x, ranks, ws=None):
     _chk(ws, torch.int32, "quantile workspace")
     out = torch.empty(K, B, Cc, dtype=torch.float32, device=x.device)
     nan_count = torch.empty(B, Cc, dtype=torch.int32, device=x.device)
-    L.check(L.load().swv2_plane_order_stats(_p(x), x.stride(0) if B > 1 else Cc * H * W, B, Cc, H, W, _p(ranks), K, _p(out), _p(nan_count),
+    L.check(L.load().swv2_plane_order_stats(xp, xbs, B, Cc, H, W, _p(ranks), K, _p(out), _p(nan_count),
                                             _p(ws), ws.numel() * 4, _stream()), "swv2_plane_order_stats")
     return out, nan_count
 
@@ -890,7 +888,7 @@ def era5_pack_i16(slab, out, offset, scale, stream=None):
 
 def pack_range_workspace(Cc: int, H: int, W: int, device) -> torch.Tensor:
     """the slice partials of swv2_pack_range (bytes; not zeroed: every launch stores all of them)"""
-    return torch.empty(int(L.load().swv2_pack_range_ws_bytes(Cc, H, W)), dtype=torch.uint8, device=device)
+    return _plane_workspace("pack_range_workspace", L.load().swv2_pack_range_ws_bytes(Cc, H, W), torch.uint8, device)
 
 
 def pack_range(slab, rng, missing, ws, first: bool, stream=None):

@@ -1,5 +1,10 @@
-"""Validation metric used by the trainer (reference utils/weighted_acc_rmse.py:50-86): cos-latitude weighted RMSE.
-Validation only -- not on the timed training path -- so this is plain torch."""
+"""Forecast verification: the reference's metric functions under their names (utils/weighted_acc_rmse.py there), ForecastScorer (RMSE /
+ACC, MAE, top-quantile error, degree spectra, ensemble scores and events of channel blocks of wide tensors, read where they lie) and
+RegriddedScorer (the same on a coarser grid: cut the blocks, regrid them, hand them to an inner ForecastScorer).
+
+Blocks that ops.py's operand contract accepts (CUDA fp32, DESIGN "Blocks of planes read in place") go through the HIP kernels, one
+streaming pass per score family; anything else -- CPU tensors (the host tests, the gloo trainer), odd widths, other dtypes -- runs the
+plain-torch statement of the same sums.  Each view of the operands is cut and checked once: _channel_blocks and _member_blocks."""
 import os
 from collections import namedtuple
 
@@ -18,8 +23,7 @@ def weighted_rmse_torch(pred: torch.Tensor, target: torch.Tensor) -> torch.Tenso
 
 
 # ---- forecast scoring: RMSE and anomaly correlation per channel (reference utils/weighted_acc_rmse.py:50-115) ----------------
-# On CUDA fp32 inputs with contiguous planes and W % 4 == 0 the sums come from ONE pass of swv2_score_sums (csrc/score.hip) instead of
-# torch's ten; anything else (CPU tensors -- the host tests, the gloo trainer --, odd widths, other dtypes) runs plain torch.
+# On the kernel path the sums come from ONE pass of swv2_score_sums (csrc/score.hip) instead of torch's ten.
 _WEIGHTS = {}
 
 
@@ -52,6 +56,48 @@ def _on_kernels(pred: torch.Tensor, target: torch.Tensor) -> bool:
         return False
     from .. import ops
     return ops.score_planes_ok(pred) and ops.score_planes_ok(target)
+
+
+def _ensemble_on_kernels(ens: torch.Tensor, target: torch.Tensor, device) -> bool:
+    """members [M, B, C, H, W] and truth [B, C, H, W] that swv2_ens_sums / swv2_event_ens_sums take in place, on the scorer's device"""
+    if not (ens.is_cuda and target.is_cuda and ens.device == device == target.device):
+        return False
+    from .. import ops
+    return ops.ens_members_ok(ens) and ops.score_planes_ok(target)
+
+
+def _channel_blocks(who, C, H, W, prd, tar, coff_prd, coff_tar):
+    """the [B, C, H, W] channel blocks of prd and tar at their offsets, as views"""
+    p, t = prd[:, coff_prd:coff_prd + C], tar[:, coff_tar:coff_tar + C]
+    if p.shape != t.shape or p.shape[1:] != (C, H, W):
+        raise ValueError(f"{who}: blocks {tuple(p.shape)} / {tuple(t.shape)}, expected [B, {C}, {H}, {W}]")
+    return p, t
+
+
+def _member_blocks(who, C, H, W, ens, tar, n_members, coff_ens, coff_tar):
+    """the member view: ens [M B, Cany, H, W] with a member-major batch (row m B + b) or [M, B, Cany, H, W] -> (channels coff_ens .. + C of
+    it as [M, B, C, H, W], channels coff_tar .. + C of tar as [B, C, H, W]), both views"""
+    M = int(n_members)
+    if ens.dim() == 4:
+        if M < 1 or ens.shape[0] % M:
+            raise ValueError(f"{who}: a batch of {ens.shape[0]} rows does not hold {M} members")
+        ens = ens.unflatten(0, (M, ens.shape[0] // M))                    # always a view: row m B + b -> [m, b]
+    e, t = ens[:, :, coff_ens:coff_ens + C], tar[:, coff_tar:coff_tar + C]
+    if e.dim() != 5 or e.shape[0] != M or M < 2 or e.shape[1:] != t.shape or t.shape[1:] != (C, H, W):
+        raise ValueError(f"{who}: members {tuple(e.shape)} / truth {tuple(t.shape)}, expected [{M} >= 2, B, {C}, {H}, {W}] / [B, {C}, {H}, {W}]")
+    return e, t
+
+
+def _as_climatology(x, C, H, W, device):
+    """a climatology given as an array or tensor -> contiguous fp32 [C, H, W] on device, or None"""
+    if x is None:
+        return None
+    if isinstance(x, np.ndarray):
+        x = torch.from_numpy(np.array(x, dtype=np.float32))          # (a copy: the array may be read-only)
+    x = torch.as_tensor(x, dtype=torch.float32).to(device).contiguous()
+    if x.shape != (C, H, W):
+        raise ValueError(f"climatology {tuple(x.shape)}, expected {(C, H, W)}")
+    return x
 
 
 def _torch_sums(pred, target, w, clim=None):
@@ -235,13 +281,7 @@ class ForecastScorer:
             if self.w.numel() != self.H:
                 raise ValueError(f"{self.w.numel()} row weights for {self.H} rows")
         self.device = self.w.device                       # resolved: "cuda" names the current device, whose tensors say cuda:<index>
-        self.clim = None
-        if climatology is not None:
-            if isinstance(climatology, np.ndarray):
-                climatology = torch.from_numpy(np.array(climatology, dtype=np.float32))          # (a copy: the array may be read-only)
-            self.clim = torch.as_tensor(climatology, dtype=torch.float32).to(self.device).contiguous()
-            if self.clim.shape != (self.C, self.H, self.W):
-                raise ValueError(f"climatology {tuple(self.clim.shape)}, expected {(self.C, self.H, self.W)}")
+        self.clim = _as_climatology(climatology, self.C, self.H, self.W, self.device)
         self.scale = None if stds is None else torch.as_tensor(stds, dtype=torch.float32).reshape(-1).to(self.device).contiguous()
         if self.scale is not None and self.scale.numel() != self.C:
             raise ValueError(f"{self.scale.numel()} stds for {self.C} channels")
@@ -253,17 +293,17 @@ class ForecastScorer:
             self._ws[key] = make(*args, self.device)
         return self._ws[key]
 
-    def _blocks(self, who, prd, tar, coff_prd, coff_tar):
-        """the [B, C, H, W] channel blocks of prd and tar at their offsets, as views"""
-        p, t = prd[:, coff_prd:coff_prd + self.C], tar[:, coff_tar:coff_tar + self.C]
-        if p.shape != t.shape or p.shape[1:] != (self.C, self.H, self.W):
-            raise ValueError(f"{who}: blocks {tuple(p.shape)} / {tuple(t.shape)}, expected [B, {self.C}, {self.H}, {self.W}]")
-        return p, t
+    def _threshold_chunks(self, thr, key, make, *args):
+        """thr [1 or B, C, K] in chunks of EVENT_MAX_K thresholds -> (the chunk, contiguous; its K; the workspace of that call shape)"""
+        for k0 in range(0, thr.shape[2], EVENT_MAX_K):
+            tk = thr[:, :, k0:k0 + EVENT_MAX_K].contiguous()
+            K = tk.shape[2]
+            yield tk, K, self._workspace(key + (K,), make, *args, K)
 
     def score(self, prd, tar, coff_prd=0, coff_tar=0) -> Scores:
         """channels coff_prd .. + C of prd against channels coff_tar .. + C of tar (scored in place, no copy) ->
         Scores(rmse [B, C], acc [B, C] | None, rmse_mean [C] (x stds), acc_mean [C] | None, sums [B, C, 4])"""
-        p, t = self._blocks("score", prd, tar, coff_prd, coff_tar)
+        p, t = _channel_blocks("score", self.C, self.H, self.W, prd, tar, coff_prd, coff_tar)
         if _on_kernels(p, t) and p.device == self.device:
             from .. import ops
             B = p.shape[0]
@@ -288,7 +328,7 @@ class ForecastScorer:
         """latitude-weighted mean absolute error of channels coff_prd .. + C of prd against channels coff_tar .. + C of tar (read in
         place) -> MaeScores(mae [B, C] = S0 / (H W), mae_mean [C] = mean_b mae (x stds), sums [B, C, 2] = (S0, S1)) with
         S0 = sum w[h] |prd - tar|, S1 = sum w[h] |tar|.  One pass of swv2_l1_sums (csrc/loss_l1.hip) on CUDA, plain torch elsewhere."""
-        p, t = self._blocks("mae", prd, tar, coff_prd, coff_tar)
+        p, t = _channel_blocks("mae", self.C, self.H, self.W, prd, tar, coff_prd, coff_tar)
         n = float(self.H * self.W)
         if _on_kernels(p, t) and p.device == self.device:
             from .. import ops
@@ -315,13 +355,13 @@ class ForecastScorer:
             raise ValueError(f"power_spectrum: block {tuple(p.shape)}, expected [B, {self.C}, {self.H}, {self.W}]")
         if tar is None:
             return PowerSpectrum(degree_power(p), None)
-        p, t = self._blocks("power_spectrum", prd, tar, coff_prd, coff_tar)
+        p, t = _channel_blocks("power_spectrum", self.C, self.H, self.W, prd, tar, coff_prd, coff_tar)
         return PowerSpectrum(degree_power(p), degree_power(t))
 
     def quantile_error(self, prd, tar, coff_prd=0, coff_tar=0) -> torch.Tensor:
         """top_quantiles_error_torch of channels coff_prd .. + C of prd against channels coff_tar .. + C of tar (read in place) -> [B, C].
         The rank tensor and the workspace (one per B) are made once and reused."""
-        p, t = self._blocks("quantile_error", prd, tar, coff_prd, coff_tar)
+        p, t = _channel_blocks("quantile_error", self.C, self.H, self.W, prd, tar, coff_prd, coff_tar)
         q = quantile_levels()
         if not (_quantiles_on_kernels(p) and _quantiles_on_kernels(t) and p.device == self.device == t.device):
             return torch.mean(plane_quantiles(p, q) - plane_quantiles(t, q), dim=0)
@@ -338,18 +378,10 @@ class ForecastScorer:
         inference.ensemble_rollout) -> EnsembleScores(sums [B, C, 4] = (S_mse, S_var, S_1, S_2), hist [B, C, M + 1] int32, ens_rmse, spread,
         crps, fair_crps [B, C], and their batch means [C]; the scorer's stds multiply ens_rmse_mean, spread_mean and crps_mean).  One
         workspace per (M, B) is kept and reused."""
-        M = int(n_members)
-        if ens.dim() == 4:
-            if M < 1 or ens.shape[0] % M:
-                raise ValueError(f"ensemble_score: a batch of {ens.shape[0]} rows does not hold {M} members")
-            ens = ens.unflatten(0, (M, ens.shape[0] // M))                    # always a view: row m B + b -> [m, b]
-        e, t = ens[:, :, coff_ens:coff_ens + self.C], tar[:, coff_tar:coff_tar + self.C]
-        if e.dim() != 5 or e.shape[0] != M or M < 2 or e.shape[1:] != t.shape or t.shape[1:] != (self.C, self.H, self.W):
-            raise ValueError(f"ensemble_score: members {tuple(e.shape)} / truth {tuple(t.shape)}, expected [{M} >= 2, B, {self.C}, {self.H}, {self.W}] "
-                             f"/ [B, {self.C}, {self.H}, {self.W}]")
-        from .. import ops
-        if e.is_cuda and t.is_cuda and e.device == self.device == t.device and ops.ens_members_ok(e) and ops.score_planes_ok(t):
-            B = t.shape[0]
+        e, t = _member_blocks("ensemble_score", self.C, self.H, self.W, ens, tar, n_members, coff_ens, coff_tar)
+        if _ensemble_on_kernels(e, t, self.device):
+            from .. import ops
+            M, B = e.shape[:2]
             ws = self._workspace(("ensemble", M, B), ops.ens_workspace, B * self.C, self.H, self.W, M)
             ops.ens_sums(e, t, self.w, ws)
             sums, hist, er, sp, cr, fc, means = ops.ens_finalize(ws, M, B, self.C, self.H, self.W, self.scale)
@@ -387,17 +419,14 @@ class ForecastScorer:
         (a, b, c, d) with the scorer's row weights, n_invalid [B, C] int32: the points with a NaN, which enter no cell, scores: the dict of
         contingency_scores per sample [B, C, K], pooled: the same from the tables summed over the batch [C, K], both fp64).  One pass of
         swv2_event_sums per 8 thresholds on CUDA fp32, event_table_torch elsewhere."""
-        p, t = self._blocks("event_score", prd, tar, coff_prd, coff_tar)
+        p, t = _channel_blocks("event_score", self.C, self.H, self.W, prd, tar, coff_prd, coff_tar)
         base = self._event_base("event_score", anomaly, base)
         B = p.shape[0]
         thr = expand_thresholds(thresholds, B, self.C, p.device)
         if _on_kernels(p, t) and p.device == self.device:
             from .. import ops
             tables = []
-            for k0 in range(0, thr.shape[2], EVENT_MAX_K):
-                tk = thr[:, :, k0:k0 + EVENT_MAX_K].contiguous()
-                K = tk.shape[2]
-                ws = self._workspace(("event", B, K), ops.event_workspace, B * self.C, self.H, self.W, K)
+            for tk, K, ws in self._threshold_chunks(thr, ("event", B), ops.event_workspace, B * self.C, self.H, self.W):
                 ops.event_sums(p, t, tk, self.w, ws, base, below)
                 tab, ninv = ops.event_finalize(ws, K, B, self.C, self.H, self.W)
                 tables.append(tab)
@@ -414,25 +443,14 @@ class ForecastScorer:
         brier_scores per sample [B, C, K], pooled: the same from the sums added over the batch [C, K], reliability: reliability_scores of
         the counts added over the batch [C, K]; all fp64).  The reliability table and the ROC area are point counts: they carry no area
         weights.  One pass of swv2_event_ens_sums per 8 thresholds on CUDA fp32, ensemble_event_sums_torch elsewhere."""
-        M = int(n_members)
-        if ens.dim() == 4:
-            if M < 1 or ens.shape[0] % M:
-                raise ValueError(f"ensemble_event_score: a batch of {ens.shape[0]} rows does not hold {M} members")
-            ens = ens.unflatten(0, (M, ens.shape[0] // M))
-        e, t = ens[:, :, coff_ens:coff_ens + self.C], tar[:, coff_tar:coff_tar + self.C]
-        if e.dim() != 5 or e.shape[0] != M or M < 2 or e.shape[1:] != t.shape or t.shape[1:] != (self.C, self.H, self.W):
-            raise ValueError(f"ensemble_event_score: members {tuple(e.shape)} / truth {tuple(t.shape)}, expected [{M} >= 2, B, {self.C}, {self.H}, "
-                             f"{self.W}] / [B, {self.C}, {self.H}, {self.W}]")
+        e, t = _member_blocks("ensemble_event_score", self.C, self.H, self.W, ens, tar, n_members, coff_ens, coff_tar)
         base = self._event_base("ensemble_event_score", anomaly, base)
-        B = t.shape[0]
+        M, B = e.shape[:2]
         thr = expand_thresholds(thresholds, B, self.C, t.device)
-        from .. import ops
-        if e.is_cuda and t.is_cuda and e.device == self.device == t.device and ops.ens_members_ok(e) and ops.score_planes_ok(t):
+        if _ensemble_on_kernels(e, t, self.device):
+            from .. import ops
             parts = []
-            for k0 in range(0, thr.shape[2], EVENT_MAX_K):
-                tk = thr[:, :, k0:k0 + EVENT_MAX_K].contiguous()
-                K = tk.shape[2]
-                ws = self._workspace(("ens_event", M, B, K), ops.ens_event_workspace, B * self.C, self.H, self.W, M, K)
+            for tk, K, ws in self._threshold_chunks(thr, ("ens_event", M, B), ops.ens_event_workspace, B * self.C, self.H, self.W, M):
                 ops.ens_event_sums(e, t, tk, self.w, ws, base, below)
                 parts.append(ops.ens_event_finalize(ws, M, K, B, self.C, self.H, self.W))
             sums, hist = (parts[0][i] if len(parts) == 1 else torch.cat([q[i] for q in parts], dim=2) for i in (0, 2))
@@ -452,8 +470,8 @@ class ForecastScorer:
 # per plane, with row weights w[h] and N = H W:
 #     S_mse = sum w (xbar - y)^2    S_var = sum w s2    S_1 = sum w e1    S_2 = sum w e2    hist[r] = #{points of rank r}
 #     ens_rmse = sqrt(S_mse / N)    spread = sqrt(S_var / N)    crps = (S_1 / M - S_2 / M^2) / N    fair_crps = (S_1 / M - S_2 / (M (M - 1))) / N
-# On CUDA fp32 members with contiguous planes and W % 4 == 0 the sums come from ONE pass of swv2_ens_sums (csrc/ensemble.hip: the M
-# values of a grid point in registers); anything else runs ensemble_scores_torch.
+# On the kernel path the sums come from ONE pass of swv2_ens_sums (csrc/ensemble.hip: the M values of a grid point in registers);
+# anything else runs ensemble_scores_torch.
 
 
 def spread_skill_ratio(spread: torch.Tensor, ens_rmse: torch.Tensor, n_members: int) -> torch.Tensor:
@@ -494,7 +512,6 @@ def ensemble_scores_torch(ens: torch.Tensor, tar: torch.Tensor, w=None, scale=No
     return EnsembleScores(torch.stack((s_mse, s_var, s_1, s_2), dim=-1), hist.to(torch.int32), ens_rmse, spread, crps, fair, *means)
 
 
-
 class RegriddedScorer:
     """ForecastScorer on a coarser grid: every call regrids the named channel blocks of the wide tensors where they lie (utils/regrid.py::
     Regridder: csrc/regrid.hip on CUDA fp32, the dense statement elsewhere) into coarse buffers kept per call shape, and hands those to an
@@ -506,13 +523,7 @@ class RegriddedScorer:
     def __init__(self, regridder, n_channels, climatology=None, stds=None):
         self.regridder, self.C = regridder, int(n_channels)
         (self.H, self.W), self.grid, self.device = regridder.src.shape, regridder.dst, regridder.device
-        self.clim = None
-        if climatology is not None:
-            if isinstance(climatology, np.ndarray):
-                climatology = torch.from_numpy(np.array(climatology, dtype=np.float32))
-            self.clim = torch.as_tensor(climatology, dtype=torch.float32).to(self.device).contiguous()
-            if self.clim.shape != (self.C, self.H, self.W):
-                raise ValueError(f"climatology {tuple(self.clim.shape)}, expected {(self.C, self.H, self.W)}")
+        self.clim = _as_climatology(climatology, self.C, self.H, self.W, self.device)
         Hd, Wd = self.grid.shape
         self.inner = ForecastScorer(Hd, Wd, self.C, self.device, climatology=None if self.clim is None else regridder(self.clim),
                                     stds=stds, weights=regridder.area_weights)
@@ -525,32 +536,25 @@ class RegriddedScorer:
             self._buf[key] = torch.empty(tuple(x.shape[:-2]) + self.grid.shape, dtype=x.dtype, device=x.device)
         return self.regridder(x, out=self._buf[key])
 
-    def _blocks(self, who, prd, tar, coff_prd, coff_tar):
-        p, t = prd[:, coff_prd:coff_prd + self.C], tar[:, coff_tar:coff_tar + self.C]
-        if p.shape != t.shape or p.shape[1:] != (self.C, self.H, self.W):
-            raise ValueError(f"{who}: blocks {tuple(p.shape)} / {tuple(t.shape)}, expected [B, {self.C}, {self.H}, {self.W}]")
+    def _pair(self, who, prd, tar, coff_prd, coff_tar):
+        p, t = _channel_blocks(who, self.C, self.H, self.W, prd, tar, coff_prd, coff_tar)
         return self._coarse("prd", p), self._coarse("tar", t)
 
+    def _members(self, who, ens, tar, n_members, coff_ens, coff_tar):
+        e, t = _member_blocks(who, self.C, self.H, self.W, ens, tar, n_members, coff_ens, coff_tar)
+        return self._coarse("ens", e), self._coarse("tar", t), e.shape[0]
+
     def score(self, prd, tar, coff_prd=0, coff_tar=0) -> Scores:
-        return self.inner.score(*self._blocks("score", prd, tar, coff_prd, coff_tar))
+        return self.inner.score(*self._pair("score", prd, tar, coff_prd, coff_tar))
 
     def mae(self, prd, tar, coff_prd=0, coff_tar=0) -> MaeScores:
-        return self.inner.mae(*self._blocks("mae", prd, tar, coff_prd, coff_tar))
+        return self.inner.mae(*self._pair("mae", prd, tar, coff_prd, coff_tar))
 
     def quantile_error(self, prd, tar, coff_prd=0, coff_tar=0) -> torch.Tensor:
-        return self.inner.quantile_error(*self._blocks("quantile_error", prd, tar, coff_prd, coff_tar))
+        return self.inner.quantile_error(*self._pair("quantile_error", prd, tar, coff_prd, coff_tar))
 
     def ensemble_score(self, ens, tar, n_members, coff_ens=0, coff_tar=0) -> EnsembleScores:
-        M = int(n_members)
-        if ens.dim() == 4:
-            if M < 1 or ens.shape[0] % M:
-                raise ValueError(f"ensemble_score: a batch of {ens.shape[0]} rows does not hold {M} members")
-            ens = ens.unflatten(0, (M, ens.shape[0] // M))
-        e, t = ens[:, :, coff_ens:coff_ens + self.C], tar[:, coff_tar:coff_tar + self.C]
-        if e.dim() != 5 or e.shape[0] != M or M < 2 or e.shape[1:] != t.shape or t.shape[1:] != (self.C, self.H, self.W):
-            raise ValueError(f"ensemble_score: members {tuple(e.shape)} / truth {tuple(t.shape)}, expected [{M} >= 2, B, {self.C}, {self.H}, {self.W}] "
-                             f"/ [B, {self.C}, {self.H}, {self.W}]")
-        return self.inner.ensemble_score(self._coarse("ens", e), self._coarse("tar", t), M)
+        return self.inner.ensemble_score(*self._members("ensemble_score", ens, tar, n_members, coff_ens, coff_tar))
 
     def event_thresholds(self, spec, tar, coff_tar=0):
         """ForecastScorer.event_thresholds; the quantiles are those of the REGRIDDED truth"""
@@ -561,21 +565,13 @@ class RegriddedScorer:
         """ForecastScorer.event_score on the coarse grid: the FIELDS are regridded first and the events are then taken there, against the
         regridded climatology (anomaly=True) or a base field given on the coarse grid, with the cell-area weights.  This is not the
         regridding of the events: a cell's mean exceeds a threshold less often than its points do."""
-        return self.inner.event_score(*self._blocks("event_score", prd, tar, coff_prd, coff_tar), thresholds, anomaly=anomaly, base=base, below=below)
+        return self.inner.event_score(*self._pair("event_score", prd, tar, coff_prd, coff_tar), thresholds, anomaly=anomaly, base=base, below=below)
 
     def ensemble_event_score(self, ens, tar, n_members, thresholds, anomaly=False, base=None, below=False, coff_ens=0,
                              coff_tar=0) -> EnsembleEventScores:
         """ForecastScorer.ensemble_event_score on the coarse grid; as event_score, the fields are regridded, not the events"""
-        M = int(n_members)
-        if ens.dim() == 4:
-            if M < 1 or ens.shape[0] % M:
-                raise ValueError(f"ensemble_event_score: a batch of {ens.shape[0]} rows does not hold {M} members")
-            ens = ens.unflatten(0, (M, ens.shape[0] // M))
-        e, t = ens[:, :, coff_ens:coff_ens + self.C], tar[:, coff_tar:coff_tar + self.C]
-        if e.dim() != 5 or e.shape[0] != M or M < 2 or e.shape[1:] != t.shape or t.shape[1:] != (self.C, self.H, self.W):
-            raise ValueError(f"ensemble_event_score: members {tuple(e.shape)} / truth {tuple(t.shape)}, expected [{M} >= 2, B, {self.C}, {self.H}, "
-                             f"{self.W}] / [B, {self.C}, {self.H}, {self.W}]")
-        return self.inner.ensemble_event_score(self._coarse("ens", e), self._coarse("tar", t), M, thresholds, anomaly=anomaly, base=base, below=below)
+        return self.inner.ensemble_event_score(*self._members("ensemble_event_score", ens, tar, n_members, coff_ens, coff_tar), thresholds,
+                                               anomaly=anomaly, base=base, below=below)
 
     def power_spectrum(self, *args, **kwargs):
         raise ValueError("RegriddedScorer: degree spectra are taken on the model's own grid; use a ForecastScorer for power_spectrum")
