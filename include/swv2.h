@@ -630,6 +630,42 @@ int swv2_event_ens_sums(const float* ens, long ens_mstride, long ens_bstride, co
 int swv2_event_ens_finalize(const void* ws, size_t ws_bytes, int M, int K, int B, int C, int H, int W, float* sums, float* wv, int* hist,
                             int* n_invalid, void* stream);
 
+/* Neighbourhood verification (csrc/fss.hip; purely additive, the revision stays 113): the integer sums behind the fractions skill score
+ * (Roberts and Lean 2008) of a forecast against the analysis, for K <= 8 thresholds and S <= 8 box sizes at once, per (sample, channel) plane.
+ *   prd, tar, base, thr, thr_bstride, below: the operands of swv2_event_sums, with its event, theta = thr or fl32(base + thr), strictness, fp32
+ *   comparison and validity.  An invalid point (a NaN in prediction, truth or base) is NO EVENT IN EITHER FIELD and is counted per plane in
+ *   n_invalid[B][C]; it stays in every denominator.
+ *   scales    int[S] on the HOST: half-widths r in grid points, strictly ascending, 0 <= r <= 32, 2 r + 1 <= W
+ *   The neighbourhood of (h, w) at scale r is rows max(0, h - r) .. min(H - 1, h + r) and columns w - r .. w + r MODULO W: the longitude is
+ *   periodic, the poles clip the box; it holds N_h = (rows in the clipped box) * (2 r + 1) points.  n_f(h, w) / n_o(h, w) = the number of
+ *   forecast / analysis events in it, integers.
+ *     rows[B][C][K][S][H][3] = (sum_w (n_f - n_o)^2, sum_w n_f^2, sum_w n_o^2)      int64, exact
+ *   The area weighting is the caller's, in fp64, a dot product over H (utils/events.py::fss_scores): with q[h] = w[h] / N_h^2,
+ *     FBS = sum_h q[h] rows[.., h, 0]    SF, SO likewise from [.., 1], [.., 2]    FSS = 1 - FBS / (SF + SO)   (0 / 0 = NaN in that entry only)
+ *   At r = 0, (FBS, SF, SO) = (b + c, a + b, a + c) of the contingency table of swv2_event_sums.  Scores over a batch or over lead times are
+ *   the scores of the SUMMED rows.  The kernels do no floating-point arithmetic on an output: there is no tolerance, and two runs agree bit
+ *   for bit by construction.
+ * Integer types: a box count is at most 65 * 65 = 4225 (int); a squared difference at most 4225^2 = 1.8e7, of which a thread adds at most 4
+ * and 16 lanes at most 64 in 32 bits (1.15e9 < 2^32); everything beyond is 64-bit: a row sum at W = 16384 is at most 2.9e11.
+ * swv2_fss_rows is ONE entry point over two launches on `stream`, no host synchronisation: the masks (one streaming pass on the slices and
+ * workgroup index of swv2_event_sums, each input read once: 2 K event bits per point as bit rows in the workspace, and the invalid points per
+ * slice), then the boxes (one workgroup per (plane, threshold, band of rows): planes * K * ceil(H / band) workgroups with
+ * band = swv2_fss_band_rows(planes, H, K, r_max = scales[S - 1]); each slides the box counts of its columns down the band from an LDS image
+ * of the bit rows, for every scale, and stores its band of `rows`; the first of a plane also folds n_invalid).  No float atomics, nothing to
+ * zero beforehand, every slot of rows and n_invalid is written, nothing outside them and the workspace is written.
+ * swv2_fss_band_rows: the plan, host-only.  Bands are at least max(2 r_max + 1, 32) rows tall and at most 80 -- except that a call of fewer
+ * than 8 workgroups (one per XCD) is cut further, down to bands of 8 rows, until it has 8.  0 for a non-positive or out-of-range argument.
+ * Refused with SWV2_ERR_INVALID before any HIP call, the entry point's name in the message: a null pointer (base may be NULL), K or S outside
+ * 1 .. 8, scales not strictly ascending, outside 0 .. 32 or with 2 r + 1 > W, W % 4 != 0, prd / tar / base / ws not 16-byte aligned, rows not
+ * 8-byte aligned, thr / n_invalid not 4-byte aligned, a batch stride that is not a multiple of 4 or (B > 1) smaller than C H W, a thr_bstride
+ * that is neither 0 nor (B > 1) at least C K, B * C >= 2^20, H * W >= 2^30, a workspace smaller than swv2_fss_ws_bytes.  The queries are
+ * host-only (no HIP call) and return 0 for a non-positive argument or K, S outside 1 .. 8. */
+int swv2_fss_band_rows(int planes, int H, int K, int r_max);
+size_t swv2_fss_ws_bytes(int planes, int H, int W, int K, int S);     /* 4 * planes * (2 K H ceil(W / 32) + swv2_score_slices(planes, H, W)) */
+int swv2_fss_rows(const float* prd, long prd_bstride, const float* tar, long tar_bstride, const float* base, const float* thr, long thr_bstride,
+                  const int* scales, int K, int S, int below, int B, int C, int H, int W, void* ws, size_t ws_bytes, long long* rows,
+                  int* n_invalid, void* stream);
+
 /* Geometric l1 loss (csrc/loss_l1.hip; reference utils/losses.py:114-120 with p = 1) and the latitude-weighted mean absolute error: per
  * (sample, channel) plane, from ONE pass over prediction and target.  All tensors fp32.
  *   prd, tar  C planes of [H][W] per sample, sample b at ptr + b * bstride (elements), as swv2_score_sums takes them;  w: [H] row weights

@@ -24,7 +24,7 @@ ensemble-mean RMSE and the rank histogram per channel and lead time, one pass ov
                                             [--truth truth.npy [--climatology time_means.npy] [--scores-out scores.json] [--extremes]
                                              [--score-grid DEG]
                                              [--spectrum] [--spectrum-out spectrum.npz]
-                                             [--event-anomaly S [S ...] | --event-quantile Q [Q ...]] [--event-below]
+                                             [--event-anomaly S [S ...] | --event-quantile Q [Q ...]] [--event-below] [--event-scales R [R ...]]
                                              [--ensemble M --perturbation A [--seed S] [--member-batch K] [--perturbation-scale KM]]]
 """
 from __future__ import annotations
@@ -141,6 +141,10 @@ RolloutEvents = namedtuple("RolloutEvents", "spec thresholds table n_invalid sco
 # the same of ensemble_rollout: sums [n_steps, B, C, K, 3], wv [n_steps, B, C], hist [n_steps, B, C, K, 2, M + 1], n_invalid, and `scores`:
 # brier, fair_brier, brier_skill, reliability, resolution, uncertainty, roc_area -> [n_steps, C, K] fp64, pooled over the batch
 EnsembleRolloutEvents = namedtuple("EnsembleRolloutEvents", "spec thresholds sums wv hist n_invalid scores")
+# neighbourhoods=(r, ...) of score_rollout, beside events=: the scales as given, rows [n_steps, B, C, K, S, H, 3] int64, n_invalid
+# [n_steps, B, C] and `scores`: fss, fbs [n_steps, C, K, S], fss_uniform, base_rate, useful_scale [n_steps, C, K], from the rows summed over
+# the batch (utils/events.py::fss_scores)
+RolloutNeighbourhoods = namedtuple("RolloutNeighbourhoods", "scales rows n_invalid scores")
 
 
 def _stack_scores(per_step):
@@ -151,9 +155,11 @@ def _stack_scores(per_step):
 class RolloutScores(namedtuple("RolloutScores", "rmse acc rmse_samples acc_samples forecast tqe", defaults=(None,))):
     """score_rollout's answer.  The tuple keeps its six fields (callers unpack and build it positionally); `spectrum` rides along as an
     attribute: None, or the RolloutSpectrum of score_rollout(..., spectrum=True); so does `events`: None, or the RolloutEvents of
-    score_rollout(..., events=spec).  (_replace builds a new tuple: carry them over by hand.)"""
+    score_rollout(..., events=spec), and `neighbourhoods`: None, or the RolloutNeighbourhoods of score_rollout(..., events=spec,
+    neighbourhoods=scales).  (_replace builds a new tuple: carry them over by hand.)"""
     spectrum = None
     events = None
+    neighbourhoods = None
 
     def with_spectrum(self, spectrum):
         self.spectrum = spectrum
@@ -164,21 +170,24 @@ def _truth_at(truth, s, device):
     return (truth(s) if callable(truth) else truth[:, s]).to(device)
 
 
-def _check_events(who, events, scorer):
+def _check_events(who, events, scorer, neighbourhoods=None):
     if events is not None and events.kind == "anomaly" and scorer.clim is None:
         raise ValueError(f"{who}: anomaly events need a scorer with a climatology")
+    if neighbourhoods is not None and events is None:
+        raise ValueError(f"{who}: neighbourhoods= are taken around the events of events=: give an EventSpec")
 
 
 class _StepScores:
     """the per-step results of ONE deterministic forecast: score_rollout's, and the control (member 0) of ensemble_rollout"""
 
-    def __init__(self, scorer, n_steps, B, Cout, H, device, events=None, extremes=False, spectrum=False):
+    def __init__(self, scorer, n_steps, B, Cout, H, device, events=None, extremes=False, spectrum=False, neighbourhoods=None):
         new = lambda *shape: torch.empty(n_steps, *shape, dtype=torch.float32, device=device)      # noqa: E731
         self.rmse, self.rmse_s = new(Cout), new(B, Cout)
         self.acc, self.acc_s = (new(Cout), new(B, Cout)) if scorer.clim is not None else (None, None)
         self.tqe = new(B, Cout) if extremes else None
         self.spec = RolloutSpectrum(new(Cout, H), new(Cout, H), new(B, Cout)) if spectrum else None
         self.events, self.ev = events, []
+        self.scales, self.nb = (None if neighbourhoods is None else tuple(neighbourhoods)), []
 
     def add(self, s, scorer, out, tar, coff):
         r = scorer.score(out, tar, coff_prd=coff)
@@ -195,19 +204,25 @@ class _StepScores:
         if self.events is not None:
             thr = scorer.event_thresholds(self.events, tar) if thr is None else thr
             self.ev.append((thr, scorer.event_score(out, tar, thr, anomaly=self.events.kind == "anomaly", below=self.events.below, coff_prd=coff)))
+            if self.scales is not None:
+                self.nb.append(scorer.neighbourhood_score(out, tar, thr, self.scales, anomaly=self.events.kind == "anomaly", below=self.events.below,
+                                                          coff_prd=coff))
 
     def result(self, forecast) -> RolloutScores:
         res = RolloutScores(self.rmse, self.acc, self.rmse_s, self.acc_s, forecast, self.tqe).with_spectrum(self.spec)
         if self.events is not None:           # the EventScores of every step -> RolloutEvents
             res.events = RolloutEvents(self.events, [t for t, _ in self.ev], torch.stack([e.table for _, e in self.ev], dim=0),
                                        torch.stack([e.n_invalid for _, e in self.ev], dim=0), _stack_scores([e.pooled for _, e in self.ev]))
+        if self.scales is not None:
+            res.neighbourhoods = RolloutNeighbourhoods(self.scales, torch.stack([n.rows for n in self.nb], dim=0),
+                                                       torch.stack([n.n_invalid for n in self.nb], dim=0), _stack_scores([n.pooled for n in self.nb]))
         return res
 
 
 @torch.no_grad()
 def score_rollout(model, x0: torch.Tensor, truth, n_steps: int, coszen: torch.Tensor | None = None, n_invar: int = 0,
                   scorer: ForecastScorer | None = None, keep_forecast: bool = False, extremes: bool = False,
-                  spectrum: bool = False, events: EventSpec | None = None) -> RolloutScores:
+                  spectrum: bool = False, events: EventSpec | None = None, neighbourhoods=None) -> RolloutScores:
     """`rollout` with every step's prediction scored against truth[:, s] as soon as it is written.  truth: [B, n_steps, Cout, H, W]
     (normalised as the model's output) or a callable s -> [B, Cout, H, W].  scorer: a ForecastScorer (default: no climatology, so
     no ACC; normalised units).  Unless keep_forecast, the predictions live in a two-slot ring [B, 2 Cout, H, W]: memory does not grow
@@ -220,17 +235,19 @@ def score_rollout(model, x0: torch.Tensor, truth, n_steps: int, coszen: torch.Te
     scorer may be a RegriddedScorer: truth stays on the model's grid and both are regridded before every score (no spectrum then).
     events: an EventSpec(kind "anomaly" | "quantile", levels, below): every step also goes through scorer.event_score with the thresholds
     scorer.event_thresholds names (offsets from the climatology, or that step's spatial quantiles of the analysis) -> the attribute
-    `events`, a RolloutEvents; every other result is what the call without it returns, bit for bit."""
+    `events`, a RolloutEvents; every other result is what the call without it returns, bit for bit.
+    neighbourhoods: with events, half-widths (r, ...) in grid points: every step also goes through scorer.neighbourhood_score with the
+    same thresholds (the fractions skill score per scale) -> the attribute `neighbourhoods`, a RolloutNeighbourhoods."""
     net = model.model if hasattr(model, "model") else model
     B, _, H, W = x0.shape
     Cout = net.out_chans
     if scorer is None:
         scorer = ForecastScorer(H, W, Cout, x0.device)
-    _check_events("score_rollout", events, scorer)
+    _check_events("score_rollout", events, scorer, neighbourhoods)
     if spectrum and isinstance(scorer, RegriddedScorer):
         raise ValueError("score_rollout: spectrum=True needs a ForecastScorer (degree spectra are taken on the model's own grid)")
     out, coff_of, forecast = _ring(B, n_steps, Cout, H, W, x0.device, keep_forecast)
-    steps = _StepScores(scorer, n_steps, B, Cout, H, x0.device, events, extremes, spectrum)
+    steps = _StepScores(scorer, n_steps, B, Cout, H, x0.device, events, extremes, spectrum, neighbourhoods)
     for s in _rollout_steps(net, x0, n_steps, coszen, n_invar, out, coff_of):
         tar = _truth_at(truth, s, x0.device)
         steps.add(s, scorer, out, tar, coff_of(s))
@@ -282,7 +299,7 @@ def ensemble_rollout(model, x0: torch.Tensor, truth, n_steps: int, n_members: in
                      coszen: torch.Tensor | None = None, n_invar: int = 0, scorer: ForecastScorer | None = None,
                      member_batch: int | None = None, keep_forecast: bool = False, n_fields: int | None = None,
                      score_control: bool = False, perturbation_kind: str = "white",
-                     length_scale_km: float | None = None, events: EventSpec | None = None) -> EnsembleRolloutScores:
+                     length_scale_km: float | None = None, events: EventSpec | None = None, neighbourhoods=None) -> EnsembleRolloutScores:
     """`score_rollout` for an ensemble: x0 [B, Cin, H, W] is perturbed into M = n_members initial conditions (perturb_initial_condition,
     which perturbation_kind and length_scale_km are handed to; n_fields defaults to Cin - n_invar - (1 if coszen is given)), all members are rolled out and every step is scored against truth[:, s]
     by scorer.ensemble_score as soon as all members have written it.  truth, scorer: as in score_rollout; coszen [B, n_steps - 1, H, W] is
@@ -294,7 +311,11 @@ def ensemble_rollout(model, x0: torch.Tensor, truth, n_steps: int, n_members: in
     control: with score_control, the RolloutScores of member 0 -- the deterministic forecast -- from scorer.score, else None).
     events: an EventSpec, as in score_rollout: every step also goes through scorer.ensemble_event_score (Brier score, reliability, ROC area
     of the exceedance probabilities) -> the attribute `events`, an EnsembleRolloutEvents; with score_control the control carries its own
-    RolloutEvents (the contingency tables of member 0).  Every other result is what the call without it returns, bit for bit."""
+    RolloutEvents (the contingency tables of member 0).  Every other result is what the call without it returns, bit for bit.
+    neighbourhoods: refused.  The fractions skill score here is that of ONE forecast (score_rollout); a probabilistic one is not built."""
+    if neighbourhoods is not None:
+        raise ValueError("ensemble_rollout: neighbourhoods= is not supported: there is no ensemble (probabilistic) fractions skill score; "
+                         "score the deterministic forecast with score_rollout(..., events=, neighbourhoods=)")
     net = model.model if hasattr(model, "model") else model
     B, Cin, H, W = x0.shape
     M, Cout = int(n_members), net.out_chans
@@ -344,7 +365,8 @@ def ensemble_rollout(model, x0: torch.Tensor, truth, n_steps: int, n_members: in
 def lead_time_table(scores: RolloutScores, names, hours_per_step: float = 6.0, ensemble: EnsembleRolloutScores | None = None) -> str:
     """one line per lead time: RMSE (and ACC, and the batch-mean top-quantile error and small-scale power ratio when scored) of the named channels;
     names: [(column title, channel index)].  ensemble: the crps_, spread_ and ens_rmse_ columns of an ensemble_rollout follow.  Scored
-    events add the equitable threat score of every threshold k, ets<k>_<name>, and -- for an ensemble -- its Brier score, bs<k>_<name>."""
+    events add the equitable threat score of every threshold k, ets<k>_<name>, and -- for an ensemble -- its Brier score, bs<k>_<name>;
+    scored neighbourhoods add the fractions skill score of every threshold k and scale r, fss<k>_r<r>_<name>, behind them."""
     rm, ac = scores.rmse.cpu().numpy(), None if scores.acc is None else scores.acc.cpu().numpy()
     tq = None if scores.tqe is None else scores.tqe.mean(dim=1).cpu().numpy()
     sr = None if scores.spectrum is None else scores.spectrum.ratio.mean(dim=1).cpu().numpy()
@@ -359,11 +381,17 @@ def lead_time_table(scores: RolloutScores, names, hours_per_step: float = 6.0, e
     evs = [(k, v) for k, v in ens if v.ndim == 3]
     ens = [(k, v) for k, v in ens if v.ndim == 2]
     cols += [f"{k}{j}_{n}" for k, v in evs for j in range(v.shape[2]) for n, _ in names]
+    nbh = scores.neighbourhoods
+    fss = None if nbh is None else nbh.scores["fss"].cpu().numpy()             # [n_steps, C, K, S]
+    if fss is not None:
+        cols += [f"fss{j}_r{r}_{n}" for j in range(fss.shape[2]) for r in nbh.scales for n, _ in names]
     lines = ["lead_h " + " ".join(f"{c:>12s}" for c in cols)]
     for s in range(rm.shape[0]):
         vals = [rm[s, i] for _, i in names] + ([ac[s, i] for _, i in names] if ac is not None else []) + \
             ([tq[s, i] for _, i in names] if tq is not None else []) + ([sr[s, i] for _, i in names] if sr is not None else []) + \
             [v[s, i] for _, v in ens for _, i in names] + [v[s, i, j] for _, v in evs for j in range(v.shape[2]) for _, i in names]
+        if fss is not None:
+            vals += [fss[s, i, j, q] for j in range(fss.shape[2]) for q in range(fss.shape[3]) for _, i in names]
         lines.append(f"{hours_per_step * (s + 1):6.0f} " + " ".join(f"{v:12.5f}" for v in vals))
     return "\n".join(lines)
 
@@ -392,6 +420,14 @@ class _Parser(argparse.ArgumentParser):
             self.error("--event-anomaly / --event-quantile score events against the verifying analysis: they need --truth")
         if a.event_quantile is not None and not all(0.0 <= q <= 1.0 for q in a.event_quantile):
             self.error("--event-quantile: levels within 0 .. 1")
+        if a.event_scales is not None:
+            if a.event_anomaly is None and a.event_quantile is None:
+                self.error("--event-scales takes neighbourhoods around the events of --event-anomaly / --event-quantile: it needs one of them")
+            if a.ensemble is not None:
+                self.error("--event-scales (the fractions skill score) is scored for a single forecast: run it without --ensemble")
+            r = a.event_scales
+            if any(y <= x for x, y in zip(r, r[1:])) or r[0] < 0 or r[-1] > 32:
+                self.error("--event-scales: strictly ascending half-widths in grid points, within 0 .. 32")
         if a.ensemble is None:
             for flag, v in (("--perturbation", a.perturbation), ("--seed", a.seed), ("--member-batch", a.member_batch),
                             ("--perturbation-scale", a.perturbation_scale)):
@@ -444,6 +480,9 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--event-quantile", type=float, nargs="+", default=None, metavar="Q", help="with --truth: score the events \"above the Q "
                     "quantile of the verifying analysis\" (its own spatial quantile per lead time, sample and channel); not with --event-anomaly")
     ap.add_argument("--event-below", action="store_true", help="with --event-anomaly / --event-quantile: the event is \"below\" the threshold")
+    ap.add_argument("--event-scales", type=int, nargs="+", default=None, metavar="R", help="with --event-anomaly / --event-quantile: also the "
+                    "fractions skill score of those events over boxes of 2 R + 1 grid points (ascending half-widths within 0 .. 32, on the "
+                    "--score-grid if given): fss<k>_r<R>_<name> columns, \"fss\" key")
     ap.add_argument("--ensemble", type=int, default=None, metavar="M", help="with --truth: roll out M members from perturbed initial conditions "
                                                                             "(member 0 is the control) and score CRPS, spread and ensemble-mean RMSE "
                                                                             "(crps_/spread_/ens_rmse_<name> columns, \"ensemble\" key)")
@@ -515,7 +554,7 @@ def _score_main(a, model, p, stats, x0, cz, n_invar):
         sc = ens.control
     else:
         sc = score_rollout(model, x0, truth_of, a.steps, cz, n_invar, scorer, keep_forecast=bool(a.out), extremes=a.extremes, spectrum=a.spectrum,
-                           events=spec)
+                           events=spec, neighbourhoods=None if a.event_scales is None else tuple(a.event_scales))
     if "track_channels" in p and "channel_names" in p:
         names = [(v, list(p["channel_names"]).index(v)) for v in p["track_channels"]]
     else:
@@ -546,6 +585,10 @@ def _score_main(a, model, p, stats, x0, cz, n_invar):
             if ens is not None:
                 doc["events"].update({k: ens.events.scores[k].cpu().tolist()
                                       for k in ("brier", "fair_brier", "brier_skill", "reliability", "resolution", "roc_area")})
+        if sc.neighbourhoods is not None:
+            # pooled over the batch per lead time: fss [steps, C, K, S], fss_uniform and useful_scale (a half-width, or -1) [steps, C, K]
+            doc["fss"] = {"scales": list(sc.neighbourhoods.scales),
+                          **{k: sc.neighbourhoods.scores[k].cpu().tolist() for k in ("fss", "fss_uniform", "useful_scale")}}
         with open(a.scores_out, "w") as f:
             json.dump(doc, f)
     if a.spectrum_out:

@@ -427,6 +427,7 @@ def score_slices(planes: int, H: int, W: int) -> int:
 # ---- blocks of planes read in place (DESIGN "Blocks of planes read in place"): the operand contract of every score family ----------------
 ENS_MAX_MEMBERS = 64          # the M cap of swv2_ens_sums
 EVENT_MAX_K = 8               # the threshold cap of swv2_event_sums / swv2_event_ens_sums
+FSS_MAX_S = 8                 # the scale cap of swv2_fss_rows (its threshold cap is EVENT_MAX_K, its largest half-width 32)
 QUANTILE_MAX_RANKS = 256      # the K cap of swv2_plane_order_stats
 REGRID_MAX_BAND = 32          # the KH / KW cap of swv2_regrid
 
@@ -766,6 +767,39 @@ def ens_event_finalize(ws, M: int, K: int, B: int, Cc: int, H: int, W: int):
     L.check(L.load().swv2_event_ens_finalize(_p(ws), ws.numel() * 4, M, K, B, Cc, H, W, _p(sums), _p(wv), _p(hist), _p(ninv), _stream()),
             "swv2_event_ens_finalize")
     return sums, wv, hist, ninv
+
+
+def fss_band_rows(planes: int, H: int, K: int, r_max: int) -> int:
+    """rows per band of swv2_fss_rows' box launch (host-only): one workgroup per (plane, threshold, band)"""
+    return int(L.load().swv2_fss_band_rows(planes, H, K, r_max))
+
+
+def fss_workspace(planes: int, H: int, W: int, K: int, S: int, device) -> torch.Tensor:
+    """the caller's workspace of swv2_fss_rows for `planes` = B * C planes, K thresholds and S scales: allocate once, reuse; never zeroed"""
+    return _plane_workspace("fss_workspace", L.load().swv2_fss_ws_bytes(planes, H, W, K, S), torch.int32, device,
+                            f"planes {planes}, H {H}, W {W} must be positive and K = {K}, S = {S} within 1 .. {FSS_MAX_S}")
+
+
+def fss_rows(prd, tar, thr, scales, ws, base=None, below=False):
+    """the neighbourhood sums of every (b, c) plane of prd / tar (each [B, C, H, W] or a channel block of a wider tensor, read in place)
+    -> (rows [B, C, K, S, H, 3] int64 = (sum_w (n_f - n_o)^2, sum_w n_f^2, sum_w n_o^2), n_invalid [B, C] int32); thr [1 or B, C, K]
+    contiguous, scales: S strictly ascending half-widths in 0 .. 32 (host integers), ws: fss_workspace, base [C, H, W] or None"""
+    (pp, pbs), (tp, tbs) = _plane_blocks("fss_rows", prd, tar)
+    B, Cc, H, W = prd.shape
+    _chk(thr, torch.float32, "thresholds")
+    if thr.dim() != 3 or thr.shape[1] != Cc or thr.shape[0] not in (1, B) or not 1 <= thr.shape[2] <= EVENT_MAX_K:
+        raise L.Swv2Error(f"fss_rows: thresholds {tuple(thr.shape)}, expected [1 or {B}, {Cc}, K <= {EVENT_MAX_K}]")
+    if base is not None and (_chk(base, torch.float32, "base field").shape != (Cc, H, W)):
+        raise L.Swv2Error(f"fss_rows: base field {tuple(base.shape)}, expected {(Cc, H, W)}")
+    K, S = thr.shape[2], len(scales)
+    thr_bs = Cc * K if thr.shape[0] == B and B > 1 else 0
+    _chk(ws, torch.int32, "fss workspace")
+    rows = torch.empty(B, Cc, K, S, H, 3, dtype=torch.int64, device=prd.device)
+    ninv = torch.empty(B, Cc, dtype=torch.int32, device=prd.device)
+    sc = (C.c_int * max(S, 1))(*[int(r) for r in scales])
+    L.check(L.load().swv2_fss_rows(pp, pbs, tp, tbs, _p(base), _p(thr), thr_bs, sc, K, S, int(bool(below)), B, Cc, H, W, _p(ws), ws.numel() * 4,
+                                   _p(rows), _p(ninv), _stream()), "swv2_fss_rows")
+    return rows, ninv
 
 
 def quantile_workspace(planes: int, H: int, W: int, K: int, device) -> torch.Tensor:

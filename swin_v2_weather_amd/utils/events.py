@@ -10,7 +10,8 @@ kernels of csrc/events.hip; the statements here are the same definitions in plai
                     hist[0][j] = #{valid points with n = j}   hist[1][j] = #{... and o = 1}     (point counts, unweighted)
 
 The scores are formed in fp64 from the tables, by the functions below alone; scores over a batch or over lead times are the scores of the
-SUMMED tables, never means of scores.  None of this is compared with a verification package: the identities of tests/test_events_host.py
+SUMMED tables, never means of scores.  The neighbourhood sums of the fractions skill score (csrc/fss.hip) are stated further down, beside
+their functions.  None of this is compared with a verification package: the identities of tests/test_events_host.py
 pin it.
 """
 from collections import namedtuple
@@ -22,6 +23,9 @@ EVENT_MAX_K = 8               # thresholds per kernel call (more run in chunks)
 EventSpec = namedtuple("EventSpec", "kind levels below", defaults=(False,))          # kind: "anomaly" | "quantile"
 EventScores = namedtuple("EventScores", "table n_invalid scores pooled")
 EnsembleEventScores = namedtuple("EnsembleEventScores", "sums wv hist n_invalid scores pooled reliability")
+FSS_MAX_S = 8                 # scales per kernel call (more run in chunks)
+FSS_MAX_R = 32                # the largest half-width of a neighbourhood, in grid points
+NeighbourhoodScores = namedtuple("NeighbourhoodScores", "rows n_invalid scores pooled")
 CONTINGENCY_NAMES = ("base_rate", "freq_bias", "pod", "far", "csi", "ets", "sedi")
 BRIER_NAMES = ("brier", "fair_brier", "brier_skill")
 RELIABILITY_NAMES = ("reliability", "resolution", "uncertainty", "roc_area")
@@ -148,6 +152,93 @@ def reliability_scores(hist_fc, hist_ob) -> dict:
     Hr, Fr = hits / hits[..., -1:], fals / fals[..., -1:]
     roc = ((Fr[..., 1:] - Fr[..., :-1]) * (Hr[..., 1:] + Hr[..., :-1]) * 0.5).sum(dim=-1)
     return dict(reliability=rel.squeeze(-1), resolution=res.squeeze(-1), uncertainty=unc.squeeze(-1), roc_area=roc)
+
+
+# ---- neighbourhood verification: the fractions skill score (Roberts and Lean 2008) --------------------------------------------------
+# include/swv2.h states this for csrc/fss.hip; the same in plain torch.  The event, theta, below, strictness, the fp32 comparison and
+# validity are those above, except that an invalid point is NO EVENT IN EITHER FIELD (and stays in every denominator); it is counted in
+# n_invalid.  A scale is a half-width r in grid points, 0 <= r <= 32, 2 r + 1 <= W.  The neighbourhood of (h, w): rows max(0, h - r) ..
+# min(H - 1, h + r), columns w - r .. w + r modulo W (periodic longitude, the poles clip the box), N_h = rows of the clipped box * (2 r + 1)
+# points; n_f / n_o = forecast / analysis events in it.
+#     rows[B, C, K, S, H, 3] = (sum_w (n_f - n_o)^2, sum_w n_f^2, sum_w n_o^2)          int64, exact
+#     q[h] = w[h] / N_h^2     FBS = sum_h q[h] rows[..., h, 0]     SF, SO likewise     FSS = 1 - FBS / (SF + SO)     (0 / 0 -> NaN there only)
+# At r = 0 with the same weights (FBS, SF, SO) = (b + c, a + b, a + c) of the contingency table: the base rate f_o = SO_0 / (W sum w) comes
+# from scale 0, and fss_uniform = 0.5 + f_o / 2 is the level from which a forecast counts as useful.  Scores over a batch or over lead
+# times are the scores of the SUMMED rows.
+def check_scales(scales, W: int) -> tuple:
+    """the scales as a tuple of ints, or ValueError: strictly ascending, within 0 .. FSS_MAX_R, 2 r + 1 <= W"""
+    sc = tuple(int(r) for r in scales)
+    if not sc or any(float(r) != float(s) for r, s in zip(sc, scales)):
+        raise ValueError(f"scales {tuple(scales)}: expected at least one integer half-width")
+    if any(b <= a for a, b in zip(sc, sc[1:])) or sc[0] < 0 or sc[-1] > FSS_MAX_R:
+        raise ValueError(f"scales {sc}: expected strictly ascending half-widths within 0 .. {FSS_MAX_R}")
+    if 2 * sc[-1] + 1 > W:
+        raise ValueError(f"scales {sc}: a box of 2 * {sc[-1]} + 1 columns is wider than the grid's {W}")
+    return sc
+
+
+def _box_count(e, r: int):
+    """e [..., H, W] int64 -> the number of ones in the box of half-width r around every point (columns modulo W, rows clipped)"""
+    H, W = e.shape[-2:]
+    if r == 0:
+        return e
+    F = torch.nn.functional
+    c = F.pad(torch.cat((e[..., W - r:], e, e[..., :r]), dim=-1).cumsum(dim=-1), (1, 0))
+    row = c[..., 2 * r + 1:] - c[..., :W]                                    # [..., H, W]: the window sums of every row
+    c = F.pad(F.pad(row, (0, 0, r, r)).cumsum(dim=-2), (0, 0, 1, 0))
+    return c[..., 2 * r + 1:, :] - c[..., :H, :]
+
+
+def fss_rows_torch(prd, tar, thresholds, scales, base=None, below=False):
+    """prd, tar [B, C, H, W] (any float dtype; compared in fp32), thresholds [K] | [C, K] | [B, C, K], scales: half-widths (check_scales),
+    base [C, H, W] | None -> (rows [B, C, K, S, H, 3] int64, n_invalid [B, C] int32); counted in int64 with cumulative sums: exact"""
+    B, Cc, H, W = prd.shape
+    if tar.shape != prd.shape:
+        raise ValueError(f"fss_rows_torch: prediction {tuple(prd.shape)} / truth {tuple(tar.shape)}")
+    sc = check_scales(scales, W)
+    thr = expand_thresholds(thresholds, B, Cc, prd.device)
+    valid = ~(torch.isnan(prd) | torch.isnan(tar))
+    if base is not None:
+        valid = valid & ~torch.isnan(base.to(prd.device)).unsqueeze(0)
+    th = _theta(thr, base, prd)
+    v5 = valid.unsqueeze(2)
+    P = (_event(prd.to(torch.float32).unsqueeze(2), th, below) & v5).to(torch.int64)
+    O = (_event(tar.to(torch.float32).unsqueeze(2), th, below) & v5).to(torch.int64)
+    rows = []
+    for r in sc:
+        nf, no = _box_count(P, r), _box_count(O, r)
+        rows.append(torch.stack((((nf - no) ** 2).sum(dim=-1), (nf * nf).sum(dim=-1), (no * no).sum(dim=-1)), dim=-1))       # [B, C, K, H, 3]
+    return torch.stack(rows, dim=3), (~valid).sum(dim=(-1, -2)).to(torch.int32)
+
+
+def box_sizes(H: int, scales) -> torch.Tensor:
+    """N_h [S, H] int64: the points of the box around a point of row h (the poles clip its rows, the longitude wraps)"""
+    h = torch.arange(H, dtype=torch.int64)
+    return torch.stack([((h + int(r)).clamp(max=H - 1) - (h - int(r)).clamp(min=0) + 1) * (2 * int(r) + 1) for r in scales], dim=0)
+
+
+def fss_scores(rows, w, scales, W: int, fields: int = 1) -> dict:
+    """rows [..., S, H, 3] int64 (summed over the `fields` samples or lead times that are pooled), row weights w [H], the scales of axis S
+    (scales[0] = 0: the base rate is read there) and the grid's width -> {fss [..., S], fbs [..., S] (= FBS), fss_uniform [...],
+    base_rate [...] = SO_0 / (fields W sum w)} in fp64"""
+    r = torch.as_tensor(rows)
+    sc = tuple(int(s) for s in scales)
+    if r.dim() < 3 or r.shape[-1] != 3 or r.shape[-3] != len(sc) or sc[0] != 0:
+        raise ValueError(f"fss_scores: rows {tuple(r.shape)} for scales {sc}: expected [..., {len(sc)}, H, 3] and scales[0] = 0")
+    w64 = torch.as_tensor(w).to(device=r.device, dtype=torch.float64).reshape(-1)
+    q = w64 / box_sizes(r.shape[-2], sc).to(device=r.device, dtype=torch.float64) ** 2          # [S, H]
+    fbs, sf, so = ((r[..., j].to(torch.float64) * q).sum(dim=-1) for j in range(3))            # the dot products over H
+    base_rate = so[..., 0] / (w64.sum() * float(W) * float(fields))
+    return dict(fss=1.0 - fbs / (sf + so), fbs=fbs, fss_uniform=0.5 + 0.5 * base_rate, base_rate=base_rate)
+
+
+def useful_scale(fss, fss_uniform, scales) -> torch.Tensor:
+    """fss [..., S], fss_uniform [...] -> int64 [...]: the smallest scale with fss >= fss_uniform, or -1 (a NaN score is never useful)"""
+    f = torch.as_tensor(fss)
+    ok = f >= torch.as_tensor(fss_uniform).to(f.device).unsqueeze(-1)
+    sc = torch.as_tensor([int(s) for s in scales], dtype=torch.int64, device=f.device)
+    first = ok.to(torch.int64).argmax(dim=-1)                               # the first True where there is one
+    return torch.where(ok.any(dim=-1), sc[first], torch.full_like(first, -1))
 
 
 def quantile_thresholds(truth, q) -> torch.Tensor:

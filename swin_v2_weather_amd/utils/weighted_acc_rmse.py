@@ -256,6 +256,7 @@ PowerSpectrum = namedtuple("PowerSpectrum", "pred truth")
 # forecast events: contingency tables and Brier scores (the statements and the fp64 scores live in utils/events.py)
 from .events import (EVENT_MAX_K, EnsembleEventScores, EventScores, EventSpec, brier_scores, contingency_scores,  # noqa: E402,F401
                      ensemble_event_sums_torch, event_table_torch, expand_thresholds, quantile_thresholds, reliability_scores)
+from .events import (FSS_MAX_S, NeighbourhoodScores, box_sizes, check_scales, fss_rows_torch, fss_scores, useful_scale)  # noqa: E402,F401
 
 
 def small_scale_power_ratio(pred: torch.Tensor, truth: torch.Tensor) -> torch.Tensor:
@@ -435,6 +436,46 @@ class ForecastScorer:
             table, ninv = event_table_torch(p, t, thr, self.w, None if base is None else base.to(p.device), below)
         return EventScores(table, ninv, contingency_scores(table), contingency_scores(table.to(torch.float64).sum(dim=0)))
 
+    def neighbourhood_score(self, prd, tar, thresholds, scales, anomaly=False, base=None, below=False, coff_prd=0,
+                            coff_tar=0) -> NeighbourhoodScores:
+        """The fractions skill score of the event of event_score (same blocks, thresholds, base field and direction) over boxes of
+        half-width r grid points for every r of `scales` (strictly ascending, 0 .. 32, 2 r + 1 <= W; periodic in longitude, clipped at the
+        poles) -> NeighbourhoodScores(rows [B, C, K, S, H, 3] int64 = (sum_w (n_f - n_o)^2, sum_w n_f^2, sum_w n_o^2), n_invalid [B, C]
+        int32: the points with a NaN, which are events in neither field, scores: the dict of fss_scores per sample (fss, fbs [B, C, K, S],
+        fss_uniform, base_rate [B, C, K]) plus useful_scale [B, C, K], pooled: the same from the rows summed over the batch; fp64, with
+        the scorer's row weights).  Scale 0 carries the base rate: it is always computed, and stays out of rows and scores where `scales`
+        does not name it.  swv2_fss_rows per 8 thresholds and 8 scales on CUDA fp32, fss_rows_torch elsewhere."""
+        p, t = _channel_blocks("neighbourhood_score", self.C, self.H, self.W, prd, tar, coff_prd, coff_tar)
+        base = self._event_base("neighbourhood_score", anomaly, base)
+        asked = check_scales(scales, self.W)
+        sc = asked if asked[0] == 0 else (0,) + asked
+        B = p.shape[0]
+        thr = expand_thresholds(thresholds, B, self.C, p.device)
+        if _on_kernels(p, t) and p.device == self.device:
+            from .. import ops
+            per_s = []
+
+            def make(planes, H, W, S, K, device):             # (_threshold_chunks appends K and the device)
+                return ops.fss_workspace(planes, H, W, K, S, device)
+            for s0 in range(0, len(sc), FSS_MAX_S):
+                sk = sc[s0:s0 + FSS_MAX_S]
+                per_k = []
+                for tk, K, ws in self._threshold_chunks(thr, ("fss", B, len(sk)), make, B * self.C, self.H, self.W, len(sk)):
+                    r, ninv = ops.fss_rows(p, t, tk, sk, ws, base, below)
+                    per_k.append(r)
+                per_s.append(per_k[0] if len(per_k) == 1 else torch.cat(per_k, dim=2))
+            rows = per_s[0] if len(per_s) == 1 else torch.cat(per_s, dim=3)
+        else:
+            rows, ninv = fss_rows_torch(p, t, thr, sc, None if base is None else base.to(p.device), below)
+
+        def scores(r, fields=1):
+            s = fss_scores(r, self.w, sc, self.W, fields)
+            if sc is not asked:
+                s["fss"], s["fbs"] = s["fss"][..., 1:], s["fbs"][..., 1:]
+            s["useful_scale"] = useful_scale(s["fss"], s["fss_uniform"], asked)
+            return s
+        return NeighbourhoodScores(rows if sc is asked else rows[:, :, :, 1:], ninv, scores(rows), scores(rows.sum(dim=0), B))
+
     def ensemble_event_score(self, ens, tar, n_members, thresholds, anomaly=False, base=None, below=False, coff_ens=0,
                              coff_tar=0) -> EnsembleEventScores:
         """The exceedance probabilities n / M of n_members forecasts (ens as ensemble_score takes it) against the event in the truth, for
@@ -566,6 +607,13 @@ class RegriddedScorer:
         regridded climatology (anomaly=True) or a base field given on the coarse grid, with the cell-area weights.  This is not the
         regridding of the events: a cell's mean exceeds a threshold less often than its points do."""
         return self.inner.event_score(*self._pair("event_score", prd, tar, coff_prd, coff_tar), thresholds, anomaly=anomaly, base=base, below=below)
+
+    def neighbourhood_score(self, prd, tar, thresholds, scales, anomaly=False, base=None, below=False, coff_prd=0,
+                            coff_tar=0) -> NeighbourhoodScores:
+        """ForecastScorer.neighbourhood_score on the coarse grid: regrid first, then take the neighbourhoods there (the scales count
+        grid points of the COARSE grid)"""
+        return self.inner.neighbourhood_score(*self._pair("neighbourhood_score", prd, tar, coff_prd, coff_tar), thresholds, scales, anomaly=anomaly,
+                                              base=base, below=below)
 
     def ensemble_event_score(self, ens, tar, n_members, thresholds, anomaly=False, base=None, below=False, coff_ens=0,
                              coff_tar=0) -> EnsembleEventScores:
