@@ -13,7 +13,7 @@ import threading
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB_PATH = os.environ.get("SWV2_LIB") or os.path.join(HERE, "libswv2.so")     # SWV2_LIB: a privately built variant (tools/ab_macro.sh)
-SOURCES = ["capi.hip", "attn.hip", "attn2.hip", "attn_bwd_stream.hip", "attn_wide.hip", "attn_d256.hip", "gemm.hip", "gemm_rw.hip", "gemm_tn.hip", "gemm_tn_slab.hip", "rowops.hip", "lamb.hip", "block.hip", "cpb.hip", "mlp.hip", "proj_ln.hip", "dataio.hip", "packed.hip", "score.hip", "stats.hip", "quantile.hip", "ensemble.hip", "loss_l1.hip", "loss_l2.hip", "sht.hip", "regrid.hip", "events.hip", "fss.hip"]
+SOURCES = ["capi.hip", "attn.hip", "attn2.hip", "attn_bwd_stream.hip", "attn_wide.hip", "attn_d256.hip", "gemm.hip", "gemm_wide.hip", "gemm_rw.hip", "gemm_tn.hip", "gemm_tn_slab.hip", "rowops.hip", "lamb.hip", "block.hip", "cpb.hip", "mlp.hip", "proj_ln.hip", "dataio.hip", "packed.hip", "score.hip", "stats.hip", "quantile.hip", "ensemble.hip", "loss_l1.hip", "loss_l2.hip", "sht.hip", "regrid.hip", "events.hip", "fss.hip"]
 
 ABI_VERSION = 113         # SWV2_VERSION of the include/swv2.h these ctypes mirrors were written against (checked in load())
 

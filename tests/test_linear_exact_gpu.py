@@ -1,4 +1,4 @@
-"""GPU (-m gpu): the forward GEMM engine behind swv2_linear (csrc/gemm.hip, csrc/gemm_common.h) element by element against fp64:
+"""GPU (-m gpu): the forward GEMM engine behind swv2_linear (csrc/gemm.hip, csrc/gemm_wide.hip, csrc/gemm_rw.hip, csrc/gemm_epilogue.h, csrc/gemm_common.h) element by element against fp64:
 every loader and epilogue that the earlier exact suites leave to a relative l2 norm, on every kernel linear_kernel_for can choose.
 
 The case builders, the references, the bounds and their derivations are in tests/linear_reference.py (checked without a GPU by

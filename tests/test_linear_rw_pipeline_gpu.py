@@ -1,7 +1,7 @@
 """GPU (-m gpu): the two resident row GEMMs of a block at C = 128 (swv2_linear: RESIDENT_QKV128 and RESIDENT_DX128) at the real window
 geometry (Lp 176, L 162, 8 heads of 12 in 16-wide slots), at the row counts where a staged row pipeline can go wrong.  The d(qkv) -> dx
 product runs csrc/gemm_rw.hip: rows by LDS-DMA in stages of 32, three stage slots, two stages in flight, counted waits.  The qkv product
-runs the first body (csrc/gemm.hip); its two cases are kept so that a later move of qkv to the streaming body finds its tests here.
+runs the weight-in-LDS body of the same file; its two cases are kept so that a later move of qkv to the streaming body finds its tests here.
 
 Every case goes through the machinery of tests/test_linear_exact_gpu.py (run_case: swv2_linear_kernel names the resident kernel, every
 element against fp64 within the bounds of tests/linear_reference.py, guard rows, untouched elements still NaN, two runs bit-equal), once

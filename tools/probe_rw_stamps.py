@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""In-kernel phase timing of the two bodies of the resident-weight GEMM (gemm_rw_kernel): the weight-in-LDS body of csrc/gemm.hip (qkv)
-and the streaming body of csrc/gemm_rw.hip (d(qkv) -> dx).  Private build with -DSWV2_RW_STAMPS; wave 0 of every workgroup sums s_memtime
+"""In-kernel phase timing of the two bodies of the resident-weight GEMM (gemm_rw_kernel): the weight-in-LDS body (qkv)
+and the streaming body (d(qkv) -> dx), both in csrc/gemm_rw.hip.  Private build with -DSWV2_RW_STAMPS; wave 0 of every workgroup sums s_memtime
 deltas per phase -- GPU box, diagnostics only."""
 import ctypes, os, subprocess, sys, torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__))); sys.path.insert(0, ROOT)
