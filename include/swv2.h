@@ -315,6 +315,19 @@ int swv2_block_wgrad(const swv2_wgrad_item* items4, int slices, void* ws, size_t
 #define SWV2_BLOCK_WGRAD_SLAB 0         /* gemm_tn_slab.hip: slices = 0 at its two block shapes with a workspace that holds its plan */
 #define SWV2_BLOCK_WGRAD_GROUPED 1      /* the grouped 128 x 128 tile kernel                                                          */
 int swv2_block_wgrad_kernel(const swv2_wgrad_item* items4, int slices, size_t ws_bytes);
+/* The plan behind that answer, from the function swv2_block_wgrad itself switches on.  cus = 0: the calling thread's current device
+ * (as swv2_block_wgrad_kernel); cus > 0: plan the slab kernel for that many CUs -- host arithmetic only, so a process without a GPU
+ * can sweep it.  Per product (0 fc2, 1 fc1, 2 proj, 3 qkv): S row slices, SR rows per stage (slab: slice s owns the stages s, s + S,
+ * ...; grouped: the 128-row steps of the tile kernel), the workgroups launched for it; bytes: the workspace the plan needs
+ * (<= swv2_block_wgrad_ws_bytes).  Additive to revision 113 (a new entry point and its struct, no member of another struct moves). */
+typedef struct swv2_block_wgrad_plan_t {
+    int kernel;            /* SWV2_BLOCK_WGRAD_* */
+    int S[4];
+    int SR[4];
+    int wgs[4];
+    size_t bytes;
+} swv2_block_wgrad_plan_t;
+int swv2_block_wgrad_plan(const swv2_wgrad_item* items4, int slices, size_t ws_bytes, int cus, swv2_block_wgrad_plan_t* out);
 
 /* Head dims 65 .. 128 (DP = 96 up to 96 channels, else 128): SWV2_EPI_QKV_HEADS then leaves the squared norms of q, k in rnorm (which the
  * caller zeroes first) and un-normalised values in qkvh; this pass finishes F.normalize (swinv2_global.py:300-304):

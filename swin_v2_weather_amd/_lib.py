@@ -13,7 +13,7 @@ import threading
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB_PATH = os.environ.get("SWV2_LIB") or os.path.join(HERE, "libswv2.so")     # SWV2_LIB: a privately built variant (tools/ab_macro.sh)
-SOURCES = ["capi.hip", "attn.hip", "attn2.hip", "attn_bwd_stream.hip", "attn_wide.hip", "attn_d256.hip", "gemm.hip", "gemm_wide.hip", "gemm_rw.hip", "gemm_tn.hip", "gemm_tn_slab.hip", "rowops.hip", "lamb.hip", "block.hip", "cpb.hip", "mlp.hip", "proj_ln.hip", "dataio.hip", "packed.hip", "score.hip", "stats.hip", "quantile.hip", "ensemble.hip", "loss_l1.hip", "loss_l2.hip", "sht.hip", "regrid.hip", "events.hip", "fss.hip"]
+SOURCES = ["capi.hip", "attn.hip", "attn2.hip", "attn_bwd_stream.hip", "attn_wide.hip", "attn_d256.hip", "gemm.hip", "gemm_wide.hip", "gemm_rw.hip", "gemm_tn.hip", "gemm_tn_wide.hip", "gemm_tn_slab.hip", "rowops.hip", "lamb.hip", "block.hip", "cpb.hip", "mlp.hip", "proj_ln.hip", "dataio.hip", "packed.hip", "score.hip", "stats.hip", "quantile.hip", "ensemble.hip", "loss_l1.hip", "loss_l2.hip", "sht.hip", "regrid.hip", "events.hip", "fss.hip"]
 
 ABI_VERSION = 113         # SWV2_VERSION of the include/swv2.h these ctypes mirrors were written against (checked in load())
 
@@ -108,6 +108,12 @@ class LambItem(C.Structure):         # swv2_lamb_item
 class WgradItem(C.Structure):
     _fields_ = [("dy", Operand), ("x", Operand), ("dW", C.c_void_p), ("db", C.c_void_p), ("nmap", C.c_void_p),
                 ("kmap", C.c_void_p), ("ldw", C.c_int)]
+
+
+class BlockWgradPlan(C.Structure):
+    """swv2_block_wgrad_plan's answer: the kernel swv2_block_wgrad runs (BLOCK_WGRAD_*) and, per product, its row slices S, stage rows
+    SR and workgroups; bytes = the workspace that plan needs"""
+    _fields_ = [("kernel", C.c_int), ("S", C.c_int * 4), ("SR", C.c_int * 4), ("wgs", C.c_int * 4), ("bytes", C.c_size_t)]
 
 
 class Epilogue(C.Structure):
@@ -236,6 +242,7 @@ SYMBOLS = {
     "swv2_linear_kernel": (_I, [C.POINTER(Operand), C.POINTER(Epilogue), _I]),
     "swv2_linear_wgrad_kernel": (_I, [C.POINTER(Operand), C.POINTER(Operand), _I, C.c_size_t]),
     "swv2_block_wgrad_kernel": (_I, [C.POINTER(WgradItem), _I, C.c_size_t]),
+    "swv2_block_wgrad_plan": (_I, [C.POINTER(WgradItem), _I, C.c_size_t, _I, C.POINTER(BlockWgradPlan)]),
     "swv2_linear_wgrad": (_I, [C.POINTER(Operand), C.POINTER(Operand), _P, _P, _P, _P, _I, _I, _P]),
     "swv2_linear_wgrad_ws_bytes": (C.c_size_t, [_I, _I, _I, _I]),
     "swv2_qk_normalize": (_I, [_P, _P, _I, _I, _I, _I, _I, _P]),

@@ -266,7 +266,7 @@ extern "C" int swv2_block_bwd(const swv2_block_desc* d, void* st) {
     case SWV2_STEP_WGRAD_FC2: case SWV2_STEP_WGRAD_FC1: case SWV2_STEP_WGRAD_PROJ: case SWV2_STEP_WGRAD_QKV: {
         // one product as a launch of its own (sp row slices, the block's workspace): da2^T GELU(h), dh^T x1, da1^T merge(oh), dqkv^T gather(x)
         const swv2_wgrad_item& w = it[s == SWV2_STEP_WGRAD_FC2 ? 0 : s == SWV2_STEP_WGRAD_FC1 ? 1 : s == SWV2_STEP_WGRAD_PROJ ? 2 : 3];
-        LAUNCH(s, swv2_linear_wgrad_ws(&w.dy, &w.x, w.dW, w.db, w.nmap, w.kmap, w.ldw, sp, d->wgrad_ws, d->wgrad_ws_bytes, st));
+        LAUNCH(s, swv2_wgrad_launch(w, sp, d->wgrad_ws, d->wgrad_ws_bytes, st));
     } break;
     case SWV2_STEP_DH: {           // dh = (da2 W2) * GELU'(h)
         swv2_epilogue e = epi(SWV2_EPI_GELU_GRAD, d->dh, hid, nullptr, d->hpre);

@@ -169,5 +169,7 @@ int swv2_proj_ln_bwd_impl(const swv2_proj_ln_bwd_args* a, void* stream, int* def
 // swv2_launch_ln_partials_reduce2 itself).  ln == nullptr: plain swv2_block_wgrad.
 struct swv2_ln_partials { const float* ws[2]; float* dgamma[2]; float* dbeta[2]; int n[2]; int C; };
 int swv2_block_wgrad_ln(const swv2_wgrad_item* items4, int slices, void* ws, size_t ws_bytes, const swv2_ln_partials* ln, void* stream);
+// swv2_linear_wgrad_ws for a product that is already an item (block.hip -> gemm_tn.hip): the same checks, the same launches
+int swv2_wgrad_launch(const swv2_wgrad_item& item, int splits, void* ws, size_t ws_bytes, void* stream);
 
 static inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }

@@ -1,6 +1,6 @@
 // Shared pieces of the GEMM engine: tile constants, LDS swizzle, GELU, the head-major window layout, operand loaders, host checks.
 // Included by every engine source: gemm.hip (the 128-row NT tile kernel, kernel selection, swv2_linear), gemm_wide.hip (256 x 256 NT
-// kernels), gemm_rw.hip (the resident-weight row GEMMs of a block), gemm_tn.hip / gemm_tn_slab.hip (weight gradients), and by the fused
+// kernels), gemm_rw.hip (the resident-weight row GEMMs of a block), gemm_tn.hip / gemm_tn_wide.hip / gemm_tn_slab.hip (weight gradients), and by the fused
 // kernels (mlp.hip, proj_ln.hip).  The epilogues of the NT products are in gemm_epilogue.h.
 #pragma once
 #include <cstdlib>
@@ -14,11 +14,17 @@ int swv2_rw_dx128_launch(const swv2_operand* a, const void* w, const swv2_epilog
 // gemm_wide.hip: the 256 x 256 kernels (LinearKernel::WIDE_DMA: dma = true, WIDE) for the internal kinds (ak, ek) of a wide_pair
 int swv2_nt_wide_launch(int ak, int ek, bool dma, const swv2_operand* a, const void* w, const swv2_epilogue* e, int M, int N, int K, hipStream_t st);
 
+// gemm_tn_wide.hip: one weight gradient on 256 x 256 tiles (WgradKernel::WIDE).  gemm_tn.hip's selector needs only the bytes of workspace
+// the wide plan wants for (M, N, K), 0 = shape not covered; the launch is for an item and a workspace the selector accepted
+size_t swv2_tn_wide_ws_bytes(int M, int N, int K);
+int swv2_tn_wide_launch(const swv2_wgrad_item& it, void* ws, hipStream_t st);
+
 // gemm_tn_slab.hip: the block's four weight gradients with every operand byte fetched once (LDS-DMA slabs).  swv2_tn_slab_covers: the
-// kernel runs these items with a workspace of ws_bytes on the current device (256 CUs assumed in a process without one); a covered
-// shape with too small a workspace is reported on stderr once per process.  swv2_block_wgrad asks it, then launches (0 or a negative error)
+// kernel runs these items with a workspace of ws_bytes on `cus` CUs (0: the current device's, 256 assumed in a process without one),
+// and, where it does, *plan (optional) receives the slices, stage rows, workgroups and bytes; a covered shape with too small a workspace
+// is reported on stderr once per process.  swv2_block_wgrad asks it, then launches (0 or a negative error)
 size_t swv2_tn_slab_ws_bytes(int C, int hidden, int heads_dp);
-bool swv2_tn_slab_covers(const swv2_wgrad_item* it, size_t ws_bytes);
+bool swv2_tn_slab_covers(const swv2_wgrad_item* it, size_t ws_bytes, int cus, swv2_block_wgrad_plan_t* plan);
 int swv2_tn_slab_launch(const swv2_wgrad_item* it, void* ws, size_t ws_bytes, const swv2_ln_partials* ln, hipStream_t st);
 
 // The two run-time switches of the GEMM engine, each parsed here and nowhere else; read per call (the tests toggle them in-process).
@@ -33,7 +39,7 @@ namespace {
 constexpr int BM = 128, BN = 128, BK = 64;
 constexpr int KCH = BK / 8;                 // 16-byte chunks per tile row
 constexpr int NTHREADS = 256;
-// the 256 x 256 tile kernels (gemm_wide.hip; the wide weight-gradient kernel of gemm_tn.hip): 8 waves, four LDS-DMA stage slots of
+// the 256 x 256 tile kernels (gemm_wide.hip; the wide weight-gradient kernel of gemm_tn_wide.hip): 8 waves, four LDS-DMA stage slots of
 // (256 + 256) rows x 32 k (32 KB each) + a 2 KB pad behind the last (the epilogue's staging = slot 3 + pad)
 constexpr int WBM = 256, WBN = 256, WTH = 512;
 constexpr int WSTG = (WBM + WBN) * 32;                 // elements per stage slot
@@ -365,6 +371,17 @@ template <> struct ALoad<A_MERGE_LN> : ALoadBase<ALoad<A_MERGE_LN>, uint4> {
     }
     __device__ __forceinline__ uint4 cvt(const Raw& r) const { return r; }
 };
+
+// ------------------------------------------------------------------------------------------------
+// The destination rule of every weight gradient, stated once (swv2.h, swv2_linear_wgrad): output row n goes to nmap[n], column k to
+// kmap[k] (no map: itself); a negative entry drops the element; what is kept accumulates onto dW[n][k] (row pitch ldw) / db[n].
+// wg_index: one index through its optional map; the caller keeps the element where every mapped index is >= 0.  Used by the epilogue
+// of tn_tile (dW and db), by tn_reduce_kernel and by the bias part of tn_wide_reduce_kernel.  The dW part of tn_wide_reduce_kernel and
+// both parts of tn_slab_reduce_kernel keep the same expression open-coded: through this helper they compile to another branch
+// structure, and so does every site through a helper that returns the address or a "keep" flag (LABNOTES "Weight-gradient engine by
+// role").
+// ------------------------------------------------------------------------------------------------
+__device__ __forceinline__ int wg_index(const int32_t* map, int i) { return map ? map[i] : i; }
 
 template <int AK>
 ALoad<AK> make_loader(const swv2_operand* o) {

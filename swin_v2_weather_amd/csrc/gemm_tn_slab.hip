@@ -44,6 +44,32 @@ constexpr int SL_SMEM = 160 * 1024;           // the whole LDS of a CU: one work
 constexpr int SL_IDX_CAP = 4096;              // gather index table in LDS: a ring of two halves (2 x 2048 rows), refilled while the other half is in use
 enum { F_ROW = 0, F_ROWG = 1, F_F32 = 2, F_F32G = 3, F_HEAD = 4 };
 
+// The shape table: one configuration per (shape set, product).  slab_job<SET, I> is instantiated from it, and the host's plan, the
+// workspace bound and the reduction's chunk map read the same objects -- a shape set is one entry here and one kernel in SL_KERNELS.
+//   FY, FX: operand forms of dY and X; TN x TK: output tile of a workgroup; WGN x WGK: its 8 waves; SR: rows per stage; NS: stage slots;
+//   INPLACE: the bf16 copy of an fp32 stage overwrites the head of its own slab (LDS budget)
+struct SlCfg {
+    int FY, FX, TN, TK, WGN, WGK, SR, NS;
+    bool INPLACE;
+    constexpr int IA() const { return TN / (16 * WGN); }       // 16 x 16 accumulator fragments of a wave along n, along k
+    constexpr int JB() const { return TK / (16 * WGK); }
+};
+struct SlSet { int C, hidden, heads, hcols; SlCfg p[4]; };      // the block shape (hcols: padded head columns) and fc2, fc1, proj, qkv
+constexpr SlSet SL_SETS[] = {
+    // C = 128, hidden = 512, 8 heads x 16 columns (the BASELINE cfg 2 / 3 / 5 block)
+    {128, 512, 8, 16, {{F_ROW, F_ROWG, 128, 512, 1, 8, 32, 3, false},      // fc2: d(a2)^T GELU(hpre)
+                       {F_ROW, F_F32, 512, 128, 8, 1, 32, 3, false},       // fc1: d(h)^T x1
+                       {F_ROW, F_HEAD, 128, 128, 2, 4, 64, 4, false},      // proj: d(a1)^T merge(oh)
+                       {F_HEAD, F_F32G, 384, 128, 8, 1, 32, 3, false}}},   // qkv: d(qkv)^T gather(x)
+    // C = 192, hidden = 768, 8 heads x 32 columns (head dim 24 padded: the BASELINE cfg 4 block).  The outputs of fc2 / fc1 / qkv
+    // (192 x 768) do not fit one workgroup's registers: two column tiles each (the narrow operand is read twice)
+    {192, 768, 8, 32, {{F_ROW, F_ROWG, 192, 384, 1, 8, 32, 3, false},
+                       {F_ROW, F_F32, 384, 192, 8, 1, 32, 3, false},
+                       {F_ROW, F_HEAD, 192, 256, 2, 4, 32, 4, false},
+                       {F_HEAD, F_F32G, 384, 192, 8, 1, 32, 3, true}}},
+};
+constexpr int SL_NSETS = sizeof(SL_SETS) / sizeof(SL_SETS[0]);
+
 // In-kernel phase timing (diagnostic builds only, -DSWV2_SLAB_STAMPS, tools/probe_wgrad_slab.py stamps): wave 0 of every workgroup
 // sums s_memtime deltas per phase and overwrites the head of its partial tile with them (the results are garbage then).
 #ifdef SWV2_SLAB_STAMPS
@@ -101,10 +127,13 @@ __device__ __forceinline__ int sl_swz(int r, int u) {
     else { static_assert((W * 2) % 128 == 0, "slab width"); return u ^ ((r >> 1) & 3); }
 }
 
-template <int FY, int FX, int TN, int TK, int WGN, int WGK, int SR, int NS, bool INPLACE = false>
+template <int SET, int I>
 __device__ __forceinline__ void slab_job(const SlProd& P, const int j, unsigned char* __restrict__ smem, [[maybe_unused]] unsigned long long* stamps) {
+    constexpr SlCfg CF = SL_SETS[SET].p[I];
+    constexpr int FY = CF.FY, FX = CF.FX, TN = CF.TN, TK = CF.TK, WGN = CF.WGN, WGK = CF.WGK, SR = CF.SR, NS = CF.NS;
+    constexpr bool INPLACE = CF.INPLACE;
     static_assert(WGN * WGK == 8, "8 waves");
-    constexpr int IA = TN / (16 * WGN), JB = TK / (16 * WGK);
+    constexpr int IA = CF.IA(), JB = CF.JB();
     static_assert(IA * 16 * WGN == TN && JB * 16 * WGK == TK, "wave tiles");
     constexpr bool XF32 = FX == F_F32 || FX == F_F32G;
     constexpr int YP = TN * 2, XP = TK * 2;                       // bf16 row pitches (row-major slabs)
@@ -159,6 +188,9 @@ __device__ __forceinline__ void slab_job(const SlProd& P, const int j, unsigned 
     if constexpr (FX == F_ROWG || FX == F_F32G) __syncthreads();
 
     // ---- DMA geometry.  Instruction q of this wave is instruction ii = 8 q + wave of the stage: LDS bytes ii * 1024 .. + 1023 of (dY | X)
+    // (written out per operand, dY then X, with the head-major split in place: one source description per operand form -- through
+    // HeadLayout, or the same arithmetic in one shared function -- moves the instruction stream of both kernels, LABNOTES
+    // "Weight-gradient engine by role")
     int orow[NIW];                            // row inside the stage
     uint32_t ocol[NIW];                       // row-major: element column (incl. n0 / k0); head-major: element offset of the column part
 #pragma unroll
@@ -327,7 +359,7 @@ __device__ __forceinline__ void slab_job(const SlProd& P, const int j, unsigned 
                 // Fragments in chunks of at most four along the longer side of the wave tile (the other side, <= 4 fragments, stays in
                 // registers for the k-step): with all IA + JB fragments live beside 144 accumulator registers the C = 192 shapes spilled,
                 // and a scratch access is a VMEM operation that would break the counted vmcnt waits of the DMA pipeline.
-                auto read_a = [&](int i) -> bf16x8 {
+                auto read_a = [&](int i) -> bf16x8 {          // (the K = 32 fragment is open-coded: see gemm_tn_wide_kernel)
                     bf16x4 a0, a1;
                     if constexpr (FY == F_ROW) {
                         a0 = tr_row(Ys, std::integral_constant<int, TN>{}, 32 * kk, n_w + 16 * i);
@@ -446,25 +478,26 @@ __device__ __forceinline__ void slab_job(const SlProd& P, const int j, unsigned 
     }
 }
 
-// shape set 0: C = 128, hidden = 512, 8 heads x 16 columns (the BASELINE cfg 2 / 3 / 5 block)
+// a workgroup of shape set SET: the product whose range of workgroups holds it
+template <int SET>
+__device__ __forceinline__ void slab_set(const SlArgs& a, unsigned char* smem) {
+    const int b = blockIdx.x;
+    if (b < a.p[1].first) slab_job<SET, 0>(a.p[0], b - a.p[0].first, smem, a.stamps);
+    else if (b < a.p[2].first) slab_job<SET, 1>(a.p[1], b - a.p[1].first, smem, a.stamps);
+    else if (b < a.p[3].first) slab_job<SET, 2>(a.p[2], b - a.p[2].first, smem, a.stamps);
+    else slab_job<SET, 3>(a.p[3], b - a.p[3].first, smem, a.stamps);
+}
+// one kernel per shape set, in the order of SL_SETS (the names are what the profiles and the kernel timings match on)
 __global__ __launch_bounds__(SL_TH) void gemm_tn_slab_c128_kernel(SlArgs a) {
     __shared__ __attribute__((aligned(1024))) unsigned char smem[SL_SMEM];
-    const int b = blockIdx.x;
-    if (b < a.p[1].first) slab_job<F_ROW, F_ROWG, 128, 512, 1, 8, 32, 3>(a.p[0], b - a.p[0].first, smem, a.stamps);          // fc2: d(a2)^T GELU(hpre)
-    else if (b < a.p[2].first) slab_job<F_ROW, F_F32, 512, 128, 8, 1, 32, 3>(a.p[1], b - a.p[1].first, smem, a.stamps);      // fc1: d(h)^T x1
-    else if (b < a.p[3].first) slab_job<F_ROW, F_HEAD, 128, 128, 2, 4, 64, 4>(a.p[2], b - a.p[2].first, smem, a.stamps); // proj: d(a1)^T merge(oh)
-    else slab_job<F_HEAD, F_F32G, 384, 128, 8, 1, 32, 3>(a.p[3], b - a.p[3].first, smem, a.stamps);                          // qkv: d(qkv)^T gather(x)
+    slab_set<0>(a, smem);
 }
-// shape set 1: C = 192, hidden = 768, 8 heads x 32 columns (head dim 24 padded: the BASELINE cfg 4 block).  The outputs of fc2 / fc1 /
-// qkv (192 x 768) do not fit one workgroup's registers: two column tiles each (the narrow operand is read twice).
 __global__ __launch_bounds__(SL_TH) void gemm_tn_slab_c192_kernel(SlArgs a) {
     __shared__ __attribute__((aligned(1024))) unsigned char smem[SL_SMEM];
-    const int b = blockIdx.x;
-    if (b < a.p[1].first) slab_job<F_ROW, F_ROWG, 192, 384, 1, 8, 32, 3>(a.p[0], b - a.p[0].first, smem, a.stamps);
-    else if (b < a.p[2].first) slab_job<F_ROW, F_F32, 384, 192, 8, 1, 32, 3>(a.p[1], b - a.p[1].first, smem, a.stamps);
-    else if (b < a.p[3].first) slab_job<F_ROW, F_HEAD, 192, 256, 2, 4, 32, 4>(a.p[2], b - a.p[2].first, smem, a.stamps);
-    else slab_job<F_HEAD, F_F32G, 384, 192, 8, 1, 32, 3, true>(a.p[3], b - a.p[3].first, smem, a.stamps);
+    slab_set<1>(a, smem);
 }
+void (*const SL_KERNELS[])(SlArgs) = {gemm_tn_slab_c128_kernel, gemm_tn_slab_c192_kernel};
+static_assert(sizeof(SL_KERNELS) / sizeof(SL_KERNELS[0]) == SL_NSETS, "one kernel per shape set");
 
 // dW[nmap(n)][kmap(k)] += sum over the slices of a product's partial chunks; db[nmap(n)] += sum of the partial rows (fixed order).
 // One workgroup per 1 KB chunk (64 lanes x 4 floats in accumulator layout): its S slices are S contiguous KB; the eight 64-thread groups
@@ -519,7 +552,7 @@ __global__ __launch_bounds__(512) void tn_slab_reduce_kernel(SlRedArgs a) {
         redf[sg * 64 + lane] = a0 + a1;
         __syncthreads();
         if (sg == 0 && p.db && p.dbpart && n < p.N) {
-            const int nn = p.nmap ? p.nmap[n] : n;
+            const int nn = p.nmap ? p.nmap[n] : n;          // (wg_index open-coded here and below: through the helper this kernel is class D)
             float t = 0.f;
 #pragma unroll
             for (int e = 0; e < 8; ++e) t += redf[e * 64 + lane];
@@ -579,14 +612,9 @@ __global__ __launch_bounds__(512) void tn_slab_reduce_kernel(SlRedArgs a) {
     }
 }
 
-struct SlShape { int TN[4], TK[4], SR[4], WGN[4], WGK[4]; };       // (the template arguments of the kernel's four instantiations)
-const SlShape SL_SETS[2] = {{{128, 512, 128, 384}, {512, 128, 128, 128}, {32, 32, 64, 32}, {1, 8, 2, 8}, {8, 1, 4, 1}},
-                            {{192, 384, 192, 384}, {384, 192, 256, 192}, {32, 32, 32, 32}, {1, 8, 2, 8}, {8, 1, 4, 1}}};
-// block shapes: {C, hidden, heads, head columns}
-const int SL_BLOCKS[2][4] = {{128, 512, 8, 16}, {192, 768, 8, 32}};
 int sl_set(int C, int hidden, int heads_dp) {
-    for (int i = 0; i < 2; ++i)
-        if (C == SL_BLOCKS[i][0] && hidden == SL_BLOCKS[i][1] && heads_dp == SL_BLOCKS[i][2] * SL_BLOCKS[i][3]) return i;
+    for (int i = 0; i < SL_NSETS; ++i)
+        if (C == SL_SETS[i].C && hidden == SL_SETS[i].hidden && heads_dp == SL_SETS[i].heads * SL_SETS[i].hcols) return i;
     return -1;
 }
 
@@ -616,10 +644,10 @@ SlPlan sl_plan(const swv2_wgrad_item* it, int cus) {
     const int C = N[0], hid = K[0];
     p.set = sl_set(C, hid, K[2]);
     if (p.set < 0) return p;
-    const SlShape& sh = SL_SETS[p.set];
+    const SlSet& set = SL_SETS[p.set];
+    const SlCfg* sh = set.p;
     if (!(N[1] == hid && K[1] == C && N[2] == C && N[3] == 3 * K[2] && K[3] == C)) return p;
-    if (!(it[2].x.p[3] == SL_BLOCKS[p.set][3] && it[3].dy.p[3] == SL_BLOCKS[p.set][3] && it[2].x.p[0] == SL_BLOCKS[p.set][2] &&
-          it[3].dy.p[0] == SL_BLOCKS[p.set][2])) return p;
+    if (!(it[2].x.p[3] == set.hcols && it[3].dy.p[3] == set.hcols && it[2].x.p[0] == set.heads && it[3].dy.p[0] == set.heads)) return p;
     if (!(it[0].dy.ld == C && it[0].x.ld == hid && it[1].dy.ld == hid && it[1].x.ld == C && it[2].dy.ld == C && it[3].x.ld == C)) return p;
     if (cus < 16 || cus > 1024) return p;
     // bytes per row of each product; rows in proportion so that every workgroup streams about the same number of bytes
@@ -629,13 +657,13 @@ SlPlan sl_plan(const swv2_wgrad_item* it, int cus) {
     const double wgt[4] = {1.55, 1.0, 1.0, 1.1};
     for (int i = 0; i < 4; ++i) {
         const double xb = it[i].x.kind == SWV2_OP_F32 ? 4.0 : 2.0;
-        p.ntile[i] = (N[i] / sh.TN[i]) * (K[i] / sh.TK[i]);
-        cost[i] = wgt[i] * (double)it[i].dy.rows * (2.0 * N[i] * (K[i] / sh.TK[i]) + xb * K[i] * (N[i] / sh.TN[i]));
+        p.ntile[i] = (N[i] / sh[i].TN) * (K[i] / sh[i].TK);
+        cost[i] = wgt[i] * (double)it[i].dy.rows * (2.0 * N[i] * (K[i] / sh[i].TK) + xb * K[i] * (N[i] / sh[i].TN));
         tot += cost[i];
     }
     int used = 0;
     for (int i = 0; i < 4; ++i) {
-        const int T = cdiv(it[i].dy.rows, sh.SR[i]);
+        const int T = cdiv(it[i].dy.rows, sh[i].SR);
         int sl = (int)(cus * cost[i] / tot / p.ntile[i] + 0.5);          // row slices; every slice runs ntile workgroups
         sl = std::max(1, std::min(sl, T));
         p.S[i] = sl;
@@ -647,7 +675,7 @@ SlPlan sl_plan(const swv2_wgrad_item* it, int cus) {
         int best = -1;
         double br = 0;
         for (int i = 0; i < 4; ++i) {
-            const int T = cdiv(it[i].dy.rows, sh.SR[i]);
+            const int T = cdiv(it[i].dy.rows, sh[i].SR);
             if (used < cus ? (p.S[i] >= T || used + p.ntile[i] > cus) : p.S[i] <= 1) continue;
             const double r = cost[i] / p.S[i];
             if (best < 0 || (used < cus ? r > br : r < br)) { best = i; br = r; }
@@ -658,10 +686,10 @@ SlPlan sl_plan(const swv2_wgrad_item* it, int cus) {
     }
     size_t off = 0;
     for (int i = 0; i < 4; ++i) {
-        const int T = cdiv(it[i].dy.rows, sh.SR[i]);
+        const int T = cdiv(it[i].dy.rows, sh[i].SR);
         if ((double)it[i].dy.rows * std::max(N[i], K[i]) * 4.0 >= 4.29e9) return p;         // 32-bit byte offsets
         p.part_off[i] = off;
-        off += (size_t)p.wgs[i] * sh.TN[i] * sh.TK[i] * sizeof(float);
+        off += (size_t)p.wgs[i] * sh[i].TN * sh[i].TK * sizeof(float);
         p.db_off[i] = off;
         off += (size_t)p.S[i] * N[i] * sizeof(float);
         off = (off + 255) / 256 * 256;
@@ -689,28 +717,33 @@ size_t swv2_tn_slab_ws_bytes(int C, int hidden, int heads_dp) {
     const int set = sl_set(C, hidden, heads_dp);
     if (set < 0) return 0;
     const int cus = SL_CU_BOUND;
-    const SlShape& sh = SL_SETS[set];
+    const SlCfg* sh = SL_SETS[set].p;
     size_t tile = 0;
-    for (int i = 0; i < 4; ++i) tile = std::max(tile, (size_t)sh.TN[i] * sh.TK[i] * 4);
+    for (int i = 0; i < 4; ++i) tile = std::max(tile, (size_t)sh[i].TN * sh[i].TK * 4);
     return (size_t)cus * tile + (size_t)cus * std::max(hidden, 3 * heads_dp) * 4 + 4 * 256;
 }
 
-// the slab kernel runs these items with this workspace on the current device (see gemm_common.h)
-bool swv2_tn_slab_covers(const swv2_wgrad_item* it, size_t ws_bytes) {
-    const SlPlan pl = sl_plan(it, sl_cus());
+// the slab kernel runs these items with this workspace on `cus` CUs (0: the current device's); *plan: its numbers (see gemm_common.h)
+bool swv2_tn_slab_covers(const swv2_wgrad_item* it, size_t ws_bytes, int cus, swv2_block_wgrad_plan_t* plan) {
+    const SlPlan pl = sl_plan(it, cus > 0 ? cus : sl_cus());
     if (pl.ok && ws_bytes < pl.total) {
         static int once = 0;
         if (!once++) fprintf(stderr, "swv2: grouped weight gradient declined (workspace %zu bytes, %zu needed): size it with swv2_block_wgrad_ws_bytes; "
                                      "running the 128 x 128 tile kernels\n", ws_bytes, pl.total);
     }
-    return pl.ok && ws_bytes >= pl.total;
+    if (!(pl.ok && ws_bytes >= pl.total)) return false;
+    if (plan) {
+        for (int i = 0; i < 4; ++i) { plan->S[i] = pl.S[i]; plan->SR[i] = SL_SETS[pl.set].p[i].SR; plan->wgs[i] = pl.wgs[i]; }
+        plan->bytes = pl.total;
+    }
+    return true;
 }
 
 // for items swv2_tn_slab_covers accepts; 0 or a negative error code
 int swv2_tn_slab_launch(const swv2_wgrad_item* it, void* ws, size_t ws_bytes, const swv2_ln_partials* ln, hipStream_t st) {
     const SlPlan pl = sl_plan(it, sl_cus());
     SWV2_CHECK_ARG(pl.ok && ws_bytes >= pl.total, "swv2_block_wgrad(slab): items or workspace not covered (swv2_tn_slab_covers)");
-    const SlShape& sh = SL_SETS[pl.set];
+    const SlCfg* sh = SL_SETS[pl.set].p;
     SlArgs a = {};
     SlRedArgs r = {};
     int first = 0, rfirst = 0, dbfirst = 0;
@@ -729,8 +762,8 @@ int swv2_tn_slab_launch(const swv2_wgrad_item* it, void* ws, size_t ws_bytes, co
         first += pl.wgs[i];
         SlRed& q = r.p[i];
         q.dW = it[i].dW; q.db = it[i].db; q.nmap = it[i].nmap; q.kmap = it[i].kmap; q.part = p.part; q.dbpart = p.dbpart;
-        q.ldw = it[i].ldw; q.N = p.N; q.K = p.K; q.TN = sh.TN[i]; q.TK = sh.TK[i]; q.WGK = sh.WGK[i];
-        q.IA = sh.TN[i] / (16 * sh.WGN[i]); q.JB = sh.TK[i] / (16 * sh.WGK[i]); q.ntk = p.K / sh.TK[i]; q.S = pl.S[i]; q.first = rfirst;
+        q.ldw = it[i].ldw; q.N = p.N; q.K = p.K; q.TN = sh[i].TN; q.TK = sh[i].TK; q.WGK = sh[i].WGK;
+        q.IA = sh[i].IA(); q.JB = sh[i].JB(); q.ntk = p.K / sh[i].TK; q.S = pl.S[i]; q.first = rfirst;
         rfirst += p.N * p.K / 256 / cpw;
         q.dbfirst = dbfirst;
         dbfirst += cdiv(p.N, 64);
@@ -747,8 +780,7 @@ int swv2_tn_slab_launch(const swv2_wgrad_item* it, void* ws, size_t ws_bytes, co
     if (ws_bytes >= pl.total + (size_t)first * 64) a.stamps = (unsigned long long*)((char*)ws + ws_bytes - (size_t)first * 64);
     { static int once = 0; if (!once++) fprintf(stderr, "slab plan: workgroups %d %d %d %d\n", pl.wgs[0], pl.wgs[1], pl.wgs[2], pl.wgs[3]); }
 #endif
-    if (pl.set == 0) hipLaunchKernelGGL(gemm_tn_slab_c128_kernel, dim3(first), dim3(SL_TH), 0, st, a);
-    else hipLaunchKernelGGL(gemm_tn_slab_c192_kernel, dim3(first), dim3(SL_TH), 0, st, a);
+    hipLaunchKernelGGL(SL_KERNELS[pl.set], dim3(first), dim3(SL_TH), 0, st, a);
     hipLaunchKernelGGL(tn_slab_reduce_kernel, dim3(rfirst + dbfirst + lnblocks), dim3(512), 0, st, r);
     SWV2_CHECK_LAUNCH("swv2_block_wgrad(slab)");
     return 0;

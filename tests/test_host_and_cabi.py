@@ -62,7 +62,8 @@ def test_ctypes_structs_follow_the_header_field_order():
     pairs = {"swv2_attn_args": L.AttnArgs, "swv2_operand": L.Operand, "swv2_epilogue": L.Epilogue, "swv2_block_desc": L.BlockDesc,
              "swv2_mlp_args": L.MlpArgs, "swv2_mlp_bwd_args": L.MlpBwdArgs, "swv2_proj_ln_args": L.ProjLnArgs,
              "swv2_proj_ln_bwd_args": L.ProjLnBwdArgs, "swv2_ln_args": L.LnArgs,
-             "swv2_wgrad_item": L.WgradItem, "swv2_block_plan_t": L.BlockPlan, "swv2_attn_kernel_t": L.AttnKernelInfo}
+             "swv2_wgrad_item": L.WgradItem, "swv2_block_plan_t": L.BlockPlan, "swv2_attn_kernel_t": L.AttnKernelInfo,
+             "swv2_block_wgrad_plan_t": L.BlockWgradPlan}
     pairs["swv2_adam_item"] = L.AdamItem
     for cname, cls in pairs.items():
         assert [f[0] for f in cls._fields_] == header_struct_fields(cname), cname
@@ -698,14 +699,13 @@ def test_ddp_bucket_plan_overlaps_backward_and_isolates_pos_embed():
     assert "DDP_BUCKET_CAP_MB" in inspect.getsource(T.Trainer.__init__) or "DDP_BUCKET_CAP_MB" in inspect.getsource(T)
 
 
-def test_dma_kernels_with_hand_counted_waits_use_no_scratch(tmp_path):
-    """csrc/gemm_tn_slab.hip retires its LDS-DMA loads with hand-counted `s_waitcnt vmcnt(N)`: a register spill is a VMEM operation
-    the count does not know about (a reload would be waited for too early or too late).  The compiler's own resource report must
-    show 0 bytes of scratch and 0 spilled VGPRs for both slab kernels (cross-compiled for gfx950, no GPU needed)."""
+def _kernel_resources(source, tmp_path):
+    """{kernel symbol: {"ScratchSize [bytes/lane]": n, "VGPRs Spill": n}} from the compiler's own resource report of one csrc file
+    (cross-compiled for gfx950, no GPU needed)"""
     import subprocess
-    src = os.path.join(L.CSRC, "gemm_tn_slab.hip")
+    src = os.path.join(L.CSRC, source)
     r = subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Rpass-analysis=kernel-resource-usage",
-                        "-c", src, "-o", str(tmp_path / "slab.o")], capture_output=True, text=True, timeout=900)
+                        "-c", src, "-o", str(tmp_path / (source + ".o"))], capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     seen = {}
     name = None
@@ -717,9 +717,27 @@ def test_dma_kernels_with_hand_counted_waits_use_no_scratch(tmp_path):
         m = re.search(r"(ScratchSize \[bytes/lane\]|VGPRs Spill): (\d+)", line)
         if m and name:
             seen.setdefault(name, {})[m.group(1)] = int(m.group(2))
+    return seen
+
+
+def test_dma_kernels_with_hand_counted_waits_use_no_scratch(tmp_path):
+    """csrc/gemm_tn_slab.hip retires its LDS-DMA loads with hand-counted `s_waitcnt vmcnt(N)`: a register spill is a VMEM operation
+    the count does not know about (a reload would be waited for too early or too late).  The compiler's own resource report must
+    show 0 bytes of scratch and 0 spilled VGPRs for both slab kernels (cross-compiled for gfx950, no GPU needed)."""
+    seen = _kernel_resources("gemm_tn_slab.hip", tmp_path)
     slab = {k: v for k, v in seen.items() if "gemm_tn_slab_c" in k}
     assert len(slab) == 2, sorted(seen)
     for k, v in slab.items():
+        assert v.get("ScratchSize [bytes/lane]") == 0 and v.get("VGPRs Spill") == 0, (k, v)
+
+
+def test_wide_weight_gradient_kernels_use_no_scratch(tmp_path):
+    """the same for csrc/gemm_tn_wide.hip: the three gemm_tn_wide_kernel instantiations (bf16 x bf16, bf16 x head-major, head-major x
+    bf16) keep three stages of LDS-DMA in flight and wait on `s_waitcnt vmcnt(8)` by hand"""
+    seen = _kernel_resources("gemm_tn_wide.hip", tmp_path)
+    wide = {k: v for k, v in seen.items() if "gemm_tn_wide_kernel" in k}
+    assert len(wide) == 3, sorted(seen)
+    for k, v in wide.items():
         assert v.get("ScratchSize [bytes/lane]") == 0 and v.get("VGPRs Spill") == 0, (k, v)
 
 

@@ -1,11 +1,11 @@
 """GPU (-m gpu): every weight-gradient path, element by element, against fp64.
 
 A block's four weight gradients (fc2, fc1, proj, qkv and their bias gradients) run on one of four kernel families:
-  * slab        -- gemm_tn_slab.hip, swv2_block_wgrad(items, 0, ...) for the block shapes of SL_BLOCKS (C 128 / 192);
+  * slab        -- gemm_tn_slab.hip, swv2_block_wgrad(items, 0, ...) for the block shapes of SL_SETS (C 128 / 192);
                    per-workgroup partial tiles in bf16, folded in fp32
   * grouped     -- gemm_tn_group_kernel, swv2_block_wgrad(items, 8 / 16, ...) (and slices 0 at every other width)
   * single      -- gemm_tn_kernel, swv2_linear_wgrad_ws per product, fp32 atomics (no workspace) or per-slice partials
-  * wide        -- gemm_tn_wide_kernel, swv2_linear_wgrad_ws with SWV2_GEMM_WIDE=1 when N, K >= 512 (multiples of 256),
+  * wide        -- gemm_tn_wide_kernel (gemm_tn_wide.hip), swv2_linear_wgrad_ws with SWV2_GEMM_WIDE=1 when N, K >= 512 (multiples of 256),
                    M >= 8192 and a multiple of 32
 The items use the block's operand kinds: 0 fc2 (BF16, BF16_GELU), 1 fc1 (BF16, F32), 2 proj (BF16, HEADS with kmap),
 3 qkv (HEADS with nmap, F32 gathered through rowidx with -1 rows).
@@ -27,6 +27,8 @@ library's own bf16(GELU(pre)), read from the library by the gelu_lut fixture).  
 Every result is filed under a path name, and the error bar follows from the name (_family); before each launch the library is asked
 which kernel it will run for exactly these arguments (swv2_block_wgrad_kernel / swv2_linear_wgrad_kernel), and the answer must be
 the one the name claims: a slab that declines (workspace, shape, CU count) fails the test instead of borrowing the looser bar.
+The slab's row slices come from the library too (swv2_block_wgrad_plan, the function the launch switches on): the slice-aligned
+cancellation test builds its data on them, and one case checks that planning for "the current device" is planning for its CU count.
 
 Conventions of the product the operands follow (swv2_block_bwd): the padded rows t >= L of a window are zero in the
 head-major operands and in the proj product's dY (their bias gradient counts every row); the padded head columns
@@ -55,7 +57,7 @@ C32 = 2.0 ** -20
 # data, 1.5e-3 A when every slice's partial is coherent and the total cancels (test_slab_on_cancelling_data)
 C_SLAB = 2.0 ** -8
 
-# block shapes: the two slab shape sets (gemm_tn_slab.hip SL_BLOCKS) and one width at which the wide kernel takes the
+# block shapes: the two slab shape sets (gemm_tn_slab.hip SL_SETS) and one width at which the wide kernel takes the
 # fp32-X, head-major and gathered products (no slab set: swv2_block_wgrad(items, 0) runs the grouped tile kernel)
 SETS = {
     "c128": dict(C=128, hid=512, h=8, hd=16, DP=16, slab=True),
@@ -66,7 +68,8 @@ SETS = {
 # Row counts (M = token rows of items 0 / 1; Bw = windows of items 2 / 3, which have Bw * 176 head-major rows).  The slab's
 # planner (sl_plan) splits sl_cus() workgroups over the four products in proportion to their bytes, S = min(sl, T) row slices
 # of T = ceil(rows / SR) stages (SR = 32; 64 for proj at C 128), then hands the rounding remainder out one slice at a time.
-# Branches reached at 256 CUs (an MI355X), per shape set [c128 | c192]; S = slices of items 0..3:
+# Branches reached at 256 CUs (an MI355X), per shape set [c128 | c192]; S = slices of items 0..3 (swv2_block_wgrad_plan reports them;
+# tests/test_wgrad_plan_host.py pins four of these rows and sweeps every CU count):
 #   (162, 1)      one window of one sample: all four clamped to S = T = [6 6 3 6 | 6 6 6 6], remainder loop finds no product to grow
 #   (324, 2)      two windows: all clamped, S = T = [11 11 6 11 | 11 11 11 11]
 #   (31, 1)       SR - 1: items 0 / 1 a SINGLE ragged stage (T = 1, S = 1); all clamped
@@ -486,34 +489,47 @@ def test_random_operands_per_element_bound(dev, K, monkeypatch, gelu_lut, tag, M
 # ---------------------------------------------------------------------------------------------------------------
 # The slab on cancelling data
 # ---------------------------------------------------------------------------------------------------------------
-def sl_plan_slices(sd, M, Bw, cus):
-    """gemm_tn_slab.hip sl_plan: the row slices S of the four products (for the slice-aligned cancellation below)"""
-    C, hid, hdp = sd["C"], sd["hid"], sd["h"] * sd["DP"]
-    st = {128: dict(TN=[128, 512, 128, 384], TK=[512, 128, 128, 128], SR=[32, 32, 64, 32]),
-          192: dict(TN=[192, 384, 192, 384], TK=[384, 192, 256, 192], SR=[32, 32, 32, 32])}[C]
-    N, Kk, rows = [C, hid, C, 3 * hdp], [hid, C, hdp, C], [M, M, Bw * LP, Bw * LP]
-    xb, wgt = [2.0, 4.0, 2.0, 4.0], [1.55, 1.0, 1.0, 1.1]
-    ntile = [(N[i] // st["TN"][i]) * (Kk[i] // st["TK"][i]) for i in range(4)]
-    cost = [wgt[i] * rows[i] * (2.0 * N[i] * (Kk[i] // st["TK"][i]) + xb[i] * Kk[i] * (N[i] // st["TN"][i])) for i in range(4)]
-    T = [-(-rows[i] // st["SR"][i]) for i in range(4)]
-    S = [max(1, min(int(cus * cost[i] / sum(cost) / ntile[i] + 0.5), T[i])) for i in range(4)]
-    used = sum(S[i] * ntile[i] for i in range(4))
-    for _ in range(64):
-        if used == cus:
-            break
-        best, br = -1, 0.0
-        for i in range(4):
-            if (S[i] >= T[i] or used + ntile[i] > cus) if used < cus else S[i] <= 1:
-                continue
-            r = cost[i] / S[i]
-            if best < 0 or (r > br if used < cus else r < br):
-                best, br = i, r
-        if best < 0:
-            break
-        d = 1 if used < cus else -1
-        S[best] += d
-        used += d * ntile[best]
-    return S, st["SR"]
+def shape_items(L, sd, M, Bw):
+    """the four items of swv2_block_wgrad for a block shape at M token rows and Bw windows, shapes only: every pointer is a stand-in
+    (the kernel and plan queries dereference none), so this needs no GPU"""
+    C, hid, h, DP = sd["C"], sd["hid"], sd["h"], sd["DP"]
+    fake = 0x10000
+
+    def op(kind, rows, cols, ld, gather=False, p=(0, 0, 0, 0)):
+        o = L.Operand()
+        o.kind, o.ptr, o.rowidx, o.ld, o.rows, o.cols = kind, fake, fake if gather else None, ld, rows, cols
+        o.p = (ctypes.c_int * 4)(*p)
+        return o
+
+    def heads(parts):
+        return op(L.OP_HEADS, Bw * LP, parts * h * DP, parts, p=(h, 0, LP, DP))
+
+    pairs = [(op(L.OP_BF16, M, C, C), op(L.OP_BF16_GELU, M, hid, hid)), (op(L.OP_BF16, M, hid, hid), op(L.OP_F32, M, C, C)),
+             (op(L.OP_BF16, Bw * LP, C, C), heads(1)), (heads(3), op(L.OP_F32, Bw * LP, C, C, gather=True))]
+    items = (L.WgradItem * 4)()
+    for i, (dy, x) in enumerate(pairs):
+        items[i].dy, items[i].x, items[i].dW, items[i].ldw = dy, x, fake, x.cols
+    return items
+
+
+def slab_plan(L, sd, M, Bw, cus):
+    """the library's plan of swv2_block_wgrad(items, 0, ...) for this shape with a workspace of swv2_block_wgrad_ws_bytes on `cus` CUs
+    (0: the current device's): swv2_block_wgrad_plan, the function the launch itself switches on.  Returns (plan, workspace bytes)"""
+    lib = L.load()
+    nb = lib.swv2_block_wgrad_ws_bytes(sd["C"], sd["hid"], sd["h"] * sd["DP"], 0)
+    plan = L.BlockWgradPlan()
+    L.check(lib.swv2_block_wgrad_plan(shape_items(L, sd, M, Bw), 0, nb, cus, ctypes.byref(plan)), "swv2_block_wgrad_plan")
+    return plan, nb
+
+
+@pytest.mark.parametrize("tag,M,Bw", [("c128", 162, 1), ("c192", 4374, 27)])
+def test_plan_query_for_the_current_device(K, tag, M, Bw):
+    """cus = 0 plans for the current device as the launch sees it: its CU count, at most 320"""
+    L = K["L"]
+    here, _ = slab_plan(L, SETS[tag], M, Bw, 0)
+    want, _ = slab_plan(L, SETS[tag], M, Bw, min(torch.cuda.get_device_properties(0).multi_processor_count, 320))
+    assert here.kernel == want.kernel == L.BLOCK_WGRAD_SLAB
+    assert (list(here.S), list(here.SR), list(here.wgs), here.bytes) == (list(want.S), list(want.SR), list(want.wgs), want.bytes)
 
 
 @pytest.mark.parametrize("tag", ["c128", "c192"])
@@ -530,7 +546,9 @@ def test_slab_on_cancelling_data(dev, K, monkeypatch, gelu_lut, tag, how):
     if how == "halves":
         signs = [torch.where(torch.arange(R, device=dev) < R // 2, 1.0, -1.0).double() for R in rows]
     else:
-        S, SR = sl_plan_slices(sd, M, Bw, min(torch.cuda.get_device_properties(0).multi_processor_count, 320))
+        plan, _ = slab_plan(K["L"], sd, M, Bw, 0)          # the slices of the launch below (the current device's CUs)
+        assert plan.kernel == K["L"].BLOCK_WGRAD_SLAB
+        S, SR = list(plan.S), list(plan.SR)
         signs = [torch.where(((torch.arange(R, device=dev) // SR[i]) % S[i]) < S[i] // 2, 1.0, -1.0).double() for i, R in enumerate(rows)]
     prods = make_block(K, sd, M, Bw, "random", 77, gelu_lut, dev, signs=signs)
     bases = _bases(prods, "random", 77, dev)

@@ -1,6 +1,9 @@
 #!/usr/bin/env python3
-"""Did a source change alter what the compiler emits?  Builds one csrc file from two trees and compares every kernel's instruction stream.
-usage: tools/isa_diff.py OLD_TREE NEW_TREE FILE.hip [-v] [-- extra hipcc flags]          (needs hipcc, no GPU)
+"""Did a source change alter what the compiler emits?  Builds csrc files from two trees and compares every kernel's instruction stream.
+usage: tools/isa_diff.py OLD_TREE NEW_TREE FILE.hip [NEW_FILE.hip ...] [-v] [-- extra hipcc flags]          (needs hipcc, no GPU)
+FILE.hip is built from the old tree; from the new tree the NEW_FILEs (FILE.hip itself where none is given).  Kernels are matched by name
+(for an anonymous-namespace kernel the name does not depend on the file), so kernels that moved to another source file compare as
+usual: `isa_diff.py old new gemm_tn.hip gemm_tn.hip gemm_tn_wide.hip`.
 
 Both builds: hipcc --offload-arch=gfx950 -O3 -std=c++17 -S --cuda-device-only.  Comment lines, directives and the per-build __hip_cuid_*
 symbol are dropped; what is left of a kernel (labels + instructions) is its stream.  One line per kernel:
@@ -91,11 +94,18 @@ def main():
         args, flags = args[:i], args[i + 1:]
     verbose = "-v" in args
     args = [a for a in args if a != "-v"]
-    if len(args) != 3:
+    if len(args) < 3:
         sys.exit(__doc__)
+    new_files = args[3:] or [args[2]]
     with tempfile.TemporaryDirectory() as tmp:
         old = kernels(build(args[0], args[2], flags, os.path.join(tmp, "old.s")))
-        new = kernels(build(args[1], args[2], flags, os.path.join(tmp, "new.s")))
+        new = {}
+        for i, f in enumerate(new_files):
+            ks = kernels(build(args[1], f, flags, os.path.join(tmp, "new%d.s" % i)))
+            twice = sorted(set(ks) & set(new))
+            if twice:
+                sys.exit("kernel(s) in more than one new file: %s" % " ".join(twice))
+            new.update(ks)
     names = list(old) + [n for n in new if n not in old]
     try:
         pretty = subprocess.run(["c++filt"] + names, stdout=subprocess.PIPE, check=True).stdout.decode().splitlines()
@@ -103,7 +113,7 @@ def main():
         pretty = names
     worst = "A"
     fmt = lambda m: " / ".join(str(m.get(k, "?")) for k, _ in META)
-    print("%s %s: class  kernel  %s (old -> new where different)" % (args[2], " ".join(flags), " / ".join(t for _, t in META)))
+    print("%s %s: class  kernel  %s (old -> new where different)" % (args[2] if new_files == [args[2]] else "%s -> %s" % (args[2], " + ".join(new_files)), " ".join(flags), " / ".join(t for _, t in META)))
     for n, p in zip(names, pretty):
         p = re.sub(r"\((anonymous namespace)::\w+\)$|\(.*\)$", "", p.replace("(anonymous namespace)::", "")).replace("void ", "")
         if n not in old or n not in new:
