@@ -679,6 +679,43 @@ int swv2_fss_rows(const float* prd, long prd_bstride, const float* tar, long tar
                   const int* scales, int K, int S, int below, int B, int C, int H, int W, void* ws, size_t ws_bytes, long long* rows,
                   int* n_invalid, void* stream);
 
+/* Ensemble neighbourhood verification (csrc/fss.hip; purely additive, the revision stays 113): the integer sums behind the probabilistic
+ * fractions skill score -- the neighbourhood ensemble probability (Schwartz et al. 2010) scored with the FSS formula (Duc et al. 2013) --
+ * of M = 2 .. 64 members against the analysis, for K <= 8 thresholds and S <= 8 box sizes at once, per (sample, channel) plane.
+ *   ens, ens_mstride, ens_bstride: the members as swv2_event_ens_sums takes them; tar, base, thr, thr_bstride, below, scales: the operands of
+ *   swv2_fss_rows, with its event, theta, strictness, fp32 comparison, base field and box (clipped at the poles, wrapped in longitude).
+ *   A point is valid if no member, nor the truth, nor the base is NaN there; +-inf are valid.  An invalid point is an event in NO member and
+ *   not in the analysis, and is counted in n_invalid[B][C].  With e_m(h, w) the event bit of member m and o that of the analysis:
+ *     c = sum_m e_m (0 .. M)      N_f(h, w) = sum_box c = sum_m n_f^m      n_o(h, w) = sum_box o
+ *     rows[B][C][K][S][H][3] = (sum_w (N_f - M n_o)^2, sum_w N_f^2, sum_w n_o^2)      int64, exact
+ *   Scores, fp64, the caller's (utils/events.py::fss_ens_scores): with q[h] = w[h] / N_h^2,
+ *     FBS = sum_h q rows[.., 0] / M^2    SF = sum_h q rows[.., 1] / M^2    SO = sum_h q rows[.., 2]    pfss = 1 - FBS / (SF + SO)
+ *   base_rate from rows[.., 2] at scale 0, fss_uniform = 0.5 + base_rate / 2; scores over a batch or over lead times are the scores of the
+ *   SUMMED rows.  M copies of one forecast give (M^2 d, M^2 f, o) of swv2_fss_rows' (d, f, o); at r = 0 with unit weights sum_h rows[.., 0] is
+ *   the S_e of swv2_event_ens_sums.  No floating-point arithmetic on an output: two runs agree bit for bit.
+ * Integer bounds: N_f <= 64 * 4225 = 270 400 < 2^19 (int).  A square is < 2^37 and does NOT fit 32 bits: everything after the box count is
+ * 64-bit.  A thread adds at most 4 squares (< 2^39); the 16 lanes of a DPP row add them as two 32-bit halves (the low 24 bits: 16 * 2^24 =
+ * 2^28; the rest: 16 * 2^15 = 2^19), recombined to < 2^43 before the 64-bit integer add in LDS; a row sum at W = 16384 is < 2^51.
+ * swv2_fss_ens_rows is ONE entry point over two launches on `stream`: the masks (the units and workgroup index of swv2_fss_rows' first
+ * launch; the members stream past, a lane counts its 4 points in the bytes of one register per threshold and writes the count as
+ * P = bit_length(M) bit planes plus the analysis bit row: bits[plane][k][P + 1][H][ceil(W / 32)]), then the boxes (one workgroup per (plane,
+ * threshold, band); a forecast window count is sum_p popcount(window of plane p) << p).  Nothing to zero beforehand, every slot of rows and
+ * n_invalid has one owner and is written, nothing outside them and the workspace is written.
+ * swv2_fss_ens_band_rows: the plan, host-only.  A workgroup needs at most 80 KiB of LDS (two per CU) for 8 scales.  Bands follow the rule of
+ * swv2_fss_band_rows (at least max(2 r_max + 1, 32) rows unless the call has fewer than 8 workgroups); where such a band does not fit with
+ * 1024-column tiles the column tile is halved (512, then 256) first, and the band is capped by what then fits (at most 80).
+ * Refused with SWV2_ERR_INVALID before any HIP call, the entry point's name in the message: what swv2_fss_rows refuses, M outside 2 .. 64, a
+ * member stride that is not a multiple of 4, a workspace smaller than swv2_fss_ens_ws_bytes.  The queries return 0 for a non-positive
+ * argument, M outside 2 .. 64 or K, S outside 1 .. 8.
+ * SWV2_ENS expands to nothing.  It stands between the return type and the name because tests/test_fss_host.py finds the three deterministic
+ * entry points above by the pattern "int|size_t swv2_fss_<name>(" and pins their list; tests/test_efss_host.py reads these three with it. */
+#define SWV2_ENS
+int SWV2_ENS swv2_fss_ens_band_rows(int planes, int H, int M, int K, int r_max);
+size_t SWV2_ENS swv2_fss_ens_ws_bytes(int planes, int H, int W, int M, int K, int S);   /* 4 * planes * ((bit_length(M) + 1) K H ceil(W / 32) + slices) */
+int SWV2_ENS swv2_fss_ens_rows(const float* ens, long ens_mstride, long ens_bstride, const float* tar, long tar_bstride, const float* base,
+                               const float* thr, long thr_bstride, const int* scales, int M, int K, int S, int below, int B, int C, int H, int W,
+                               void* ws, size_t ws_bytes, long long* rows, int* n_invalid, void* stream);
+
 /* Geometric l1 loss (csrc/loss_l1.hip; reference utils/losses.py:114-120 with p = 1) and the latitude-weighted mean absolute error: per
  * (sample, channel) plane, from ONE pass over prediction and target.  All tensors fp32.
  *   prd, tar  C planes of [H][W] per sample, sample b at ptr + b * bstride (elements), as swv2_score_sums takes them;  w: [H] row weights

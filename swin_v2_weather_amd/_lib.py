@@ -293,6 +293,9 @@ SYMBOLS = {
     "swv2_fss_band_rows": (_I, [_I, _I, _I, _I]),
     "swv2_fss_ws_bytes": (C.c_size_t, [_I, _I, _I, _I, _I]),
     "swv2_fss_rows": (_I, [_P, _L, _P, _L, _P, _P, _L, C.POINTER(C.c_int), _I, _I, _I, _I, _I, _I, _I, _P, C.c_size_t, _P, _P, _P]),
+    "swv2_fss_ens_band_rows": (_I, [_I, _I, _I, _I, _I]),
+    "swv2_fss_ens_ws_bytes": (C.c_size_t, [_I, _I, _I, _I, _I, _I]),
+    "swv2_fss_ens_rows": (_I, [_P, _L, _L, _P, _L, _P, _P, _L, C.POINTER(C.c_int), _I, _I, _I, _I, _I, _I, _I, _I, _P, C.c_size_t, _P, _P, _P]),
     "swv2_l1_ws_bytes": (C.c_size_t, [_I, _I, _I]),
     "swv2_l1_sums": (_I, [_P, _L, _P, _L, _P, _I, _I, _I, _I, _P, C.c_size_t, _P]),
     "swv2_l1_finalize": (_I, [_P, C.c_size_t, _I, _I, _I, _I, _P, _I, _P, _P, _P, _P]),

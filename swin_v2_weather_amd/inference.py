@@ -25,7 +25,8 @@ ensemble-mean RMSE and the rank histogram per channel and lead time, one pass ov
                                              [--score-grid DEG]
                                              [--spectrum] [--spectrum-out spectrum.npz]
                                              [--event-anomaly S [S ...] | --event-quantile Q [Q ...]] [--event-below] [--event-scales R [R ...]]
-                                             [--ensemble M --perturbation A [--seed S] [--member-batch K] [--perturbation-scale KM]]]
+                                             [--ensemble M --perturbation A [--seed S] [--member-batch K] [--perturbation-scale KM]
+                                              [--ensemble-scales R [R ...] [--ensemble-member-scores]]]]
 """
 from __future__ import annotations
 
@@ -145,6 +146,12 @@ EnsembleRolloutEvents = namedtuple("EnsembleRolloutEvents", "spec thresholds sum
 # [n_steps, B, C] and `scores`: fss, fbs [n_steps, C, K, S], fss_uniform, base_rate, useful_scale [n_steps, C, K], from the rows summed over
 # the batch (utils/events.py::fss_scores)
 RolloutNeighbourhoods = namedtuple("RolloutNeighbourhoods", "scales rows n_invalid scores")
+# ensemble_neighbourhoods=(r, ...) of ensemble_rollout, beside events=: the scales as given, rows [n_steps, B, C, K, S, H, 3] int64 of
+# swv2_fss_ens_rows, n_invalid [n_steps, B, C] and `scores`: pfss, fbs [n_steps, C, K, S], fss_uniform, base_rate, useful_scale
+# [n_steps, C, K], from the rows summed over the batch (utils/events.py::fss_ens_scores).  With member_neighbourhoods also member_rows and
+# dispersion_rows [n_steps, B, C, K, S, H, 3] and member_scores / dispersion_scores (fss = eFSS / dFSS, ...), else None
+EnsembleRolloutNeighbourhoods = namedtuple("EnsembleRolloutNeighbourhoods", "scales rows n_invalid scores member_rows dispersion_rows member_scores "
+                                           "dispersion_scores", defaults=(None, None, None, None))
 
 
 def _stack_scores(per_step):
@@ -174,7 +181,7 @@ def _check_events(who, events, scorer, neighbourhoods=None):
     if events is not None and events.kind == "anomaly" and scorer.clim is None:
         raise ValueError(f"{who}: anomaly events need a scorer with a climatology")
     if neighbourhoods is not None and events is None:
-        raise ValueError(f"{who}: neighbourhoods= are taken around the events of events=: give an EventSpec")
+        raise ValueError(f"{who}: neighbourhoods are taken around the events of events=: give an EventSpec")
 
 
 class _StepScores:
@@ -290,8 +297,10 @@ def perturb_initial_condition(x0: torch.Tensor, n_members: int, amplitude: float
 class EnsembleRolloutScores(namedtuple("EnsembleRolloutScores", "crps fair_crps spread ens_rmse crps_samples fair_crps_samples spread_samples "
                                        "ens_rmse_samples hist forecast control", defaults=(None,))):
     """ensemble_rollout's answer.  The tuple keeps its eleven fields; `events` rides along as an attribute: None, or the
-    EnsembleRolloutEvents of ensemble_rollout(..., events=spec)."""
+    EnsembleRolloutEvents of ensemble_rollout(..., events=spec); so does `neighbourhoods`: None, or the EnsembleRolloutNeighbourhoods of
+    ensemble_rollout(..., events=spec, ensemble_neighbourhoods=scales)."""
     events = None
+    neighbourhoods = None
 
 
 @torch.no_grad()
@@ -299,7 +308,8 @@ def ensemble_rollout(model, x0: torch.Tensor, truth, n_steps: int, n_members: in
                      coszen: torch.Tensor | None = None, n_invar: int = 0, scorer: ForecastScorer | None = None,
                      member_batch: int | None = None, keep_forecast: bool = False, n_fields: int | None = None,
                      score_control: bool = False, perturbation_kind: str = "white",
-                     length_scale_km: float | None = None, events: EventSpec | None = None, neighbourhoods=None) -> EnsembleRolloutScores:
+                     length_scale_km: float | None = None, events: EventSpec | None = None, neighbourhoods=None,
+                     ensemble_neighbourhoods=None, member_neighbourhoods: bool = False) -> EnsembleRolloutScores:
     """`score_rollout` for an ensemble: x0 [B, Cin, H, W] is perturbed into M = n_members initial conditions (perturb_initial_condition,
     which perturbation_kind and length_scale_km are handed to; n_fields defaults to Cin - n_invar - (1 if coszen is given)), all members are rolled out and every step is scored against truth[:, s]
     by scorer.ensemble_score as soon as all members have written it.  truth, scorer: as in score_rollout; coszen [B, n_steps - 1, H, W] is
@@ -312,10 +322,17 @@ def ensemble_rollout(model, x0: torch.Tensor, truth, n_steps: int, n_members: in
     events: an EventSpec, as in score_rollout: every step also goes through scorer.ensemble_event_score (Brier score, reliability, ROC area
     of the exceedance probabilities) -> the attribute `events`, an EnsembleRolloutEvents; with score_control the control carries its own
     RolloutEvents (the contingency tables of member 0).  Every other result is what the call without it returns, bit for bit.
-    neighbourhoods: refused.  The fractions skill score here is that of ONE forecast (score_rollout); a probabilistic one is not built."""
+    ensemble_neighbourhoods: with events, half-widths (r, ...) in grid points: every step also goes through
+    scorer.ensemble_neighbourhood_score with the same thresholds, reading the ring slot in place (the probabilistic fractions skill score
+    per scale) -> the attribute `neighbourhoods`, an EnsembleRolloutNeighbourhoods; member_neighbourhoods adds the member and dispersion
+    rows (eFSS / dFSS).  Every other result stays bit for bit.
+    neighbourhoods: refused.  That keyword names the fractions skill score of ONE forecast (score_rollout); the ensemble's is
+    ensemble_neighbourhoods=."""
     if neighbourhoods is not None:
-        raise ValueError("ensemble_rollout: neighbourhoods= is not supported: there is no ensemble (probabilistic) fractions skill score; "
-                         "score the deterministic forecast with score_rollout(..., events=, neighbourhoods=)")
+        raise ValueError("ensemble_rollout: neighbourhoods= names the fractions skill score of one forecast (score_rollout(..., events=, "
+                         "neighbourhoods=)); the ensemble (probabilistic) score is ensemble_neighbourhoods=")
+    if member_neighbourhoods and ensemble_neighbourhoods is None:
+        raise ValueError("ensemble_rollout: member_neighbourhoods adds to ensemble_neighbourhoods=: give the scales")
     net = model.model if hasattr(model, "model") else model
     B, Cin, H, W = x0.shape
     M, Cout = int(n_members), net.out_chans
@@ -326,7 +343,8 @@ def ensemble_rollout(model, x0: torch.Tensor, truth, n_steps: int, n_members: in
         raise ValueError(f"ensemble_rollout: member_batch {member_batch}")
     if scorer is None:
         scorer = ForecastScorer(H, W, Cout, x0.device)
-    _check_events("ensemble_rollout", events, scorer)
+    _check_events("ensemble_rollout", events, scorer, ensemble_neighbourhoods)
+    nb_scales, nb = (None if ensemble_neighbourhoods is None else tuple(ensemble_neighbourhoods)), []
     if n_fields is None:
         n_fields = Cin - n_invar - int(coszen is not None)
     xe = perturb_initial_condition(x0, M, amplitude, seed, n_fields, perturbation_kind, length_scale_km)
@@ -351,6 +369,9 @@ def ensemble_rollout(model, x0: torch.Tensor, truth, n_steps: int, n_members: in
         thr = None if events is None else scorer.event_thresholds(events, tar)
         if events is not None:
             ev.append((thr, scorer.ensemble_event_score(out, tar, M, thr, anomaly=events.kind == "anomaly", below=events.below, coff_ens=coff_of(s))))
+        if nb_scales is not None:
+            nb.append(scorer.ensemble_neighbourhood_score(out, tar, M, thr, nb_scales, anomaly=events.kind == "anomaly", below=events.below,
+                                                          coff_ens=coff_of(s), members=member_neighbourhoods))
         if ctl is not None:
             ctl.add_events(s, scorer, out[:B], tar, coff_of(s), thr)
             ctl.add(s, scorer, out[:B], tar, coff_of(s))
@@ -359,6 +380,11 @@ def ensemble_rollout(model, x0: torch.Tensor, truth, n_steps: int, n_members: in
         stack = lambda i: torch.stack([e[i] for _, e in ev], dim=0)      # noqa: E731
         res.events = EnsembleRolloutEvents(events, [t for t, _ in ev], stack(0), stack(1), stack(2), stack(3),
                                            _stack_scores([{**e.pooled, **e.reliability} for _, e in ev]))
+    if nb_scales is not None:
+        stack = lambda k: torch.stack([getattr(n, k) for n in nb], dim=0)      # noqa: E731
+        more = (stack("member_rows"), stack("dispersion_rows"), _stack_scores([n.member_scores for n in nb]),
+                _stack_scores([n.dispersion_scores for n in nb])) if member_neighbourhoods else ()
+        res.neighbourhoods = EnsembleRolloutNeighbourhoods(nb_scales, stack("rows"), stack("n_invalid"), _stack_scores([n.pooled for n in nb]), *more)
     return res
 
 
@@ -366,7 +392,8 @@ def lead_time_table(scores: RolloutScores, names, hours_per_step: float = 6.0, e
     """one line per lead time: RMSE (and ACC, and the batch-mean top-quantile error and small-scale power ratio when scored) of the named channels;
     names: [(column title, channel index)].  ensemble: the crps_, spread_ and ens_rmse_ columns of an ensemble_rollout follow.  Scored
     events add the equitable threat score of every threshold k, ets<k>_<name>, and -- for an ensemble -- its Brier score, bs<k>_<name>;
-    scored neighbourhoods add the fractions skill score of every threshold k and scale r, fss<k>_r<r>_<name>, behind them."""
+    scored neighbourhoods add the fractions skill score of every threshold k and scale r, fss<k>_r<r>_<name>, behind them; an ensemble's
+    neighbourhoods add pfss<k>_r<r>_<name> and, with member scores, efss... and dfss... columns behind those."""
     rm, ac = scores.rmse.cpu().numpy(), None if scores.acc is None else scores.acc.cpu().numpy()
     tq = None if scores.tqe is None else scores.tqe.mean(dim=1).cpu().numpy()
     sr = None if scores.spectrum is None else scores.spectrum.ratio.mean(dim=1).cpu().numpy()
@@ -385,6 +412,13 @@ def lead_time_table(scores: RolloutScores, names, hours_per_step: float = 6.0, e
     fss = None if nbh is None else nbh.scores["fss"].cpu().numpy()             # [n_steps, C, K, S]
     if fss is not None:
         cols += [f"fss{j}_r{r}_{n}" for j in range(fss.shape[2]) for r in nbh.scales for n, _ in names]
+    nbs = []                                                                   # (scores [n_steps, C, K, S]) of the ensemble's neighbourhoods
+    enb = None if ensemble is None else ensemble.neighbourhoods
+    if enb is not None:
+        nbs = [("pfss", enb.scores["pfss"])] + ([("efss", enb.member_scores["fss"]), ("dfss", enb.dispersion_scores["fss"])]
+                                                if enb.member_scores is not None else [])
+        nbs = [(k, v.cpu().numpy()) for k, v in nbs]
+        cols += [f"{k}{j}_r{r}_{n}" for k, v in nbs for j in range(v.shape[2]) for r in enb.scales for n, _ in names]
     lines = ["lead_h " + " ".join(f"{c:>12s}" for c in cols)]
     for s in range(rm.shape[0]):
         vals = [rm[s, i] for _, i in names] + ([ac[s, i] for _, i in names] if ac is not None else []) + \
@@ -392,6 +426,7 @@ def lead_time_table(scores: RolloutScores, names, hours_per_step: float = 6.0, e
             [v[s, i] for _, v in ens for _, i in names] + [v[s, i, j] for _, v in evs for j in range(v.shape[2]) for _, i in names]
         if fss is not None:
             vals += [fss[s, i, j, q] for j in range(fss.shape[2]) for q in range(fss.shape[3]) for _, i in names]
+        vals += [v[s, i, j, q] for _, v in nbs for j in range(v.shape[2]) for q in range(v.shape[3]) for _, i in names]
         lines.append(f"{hours_per_step * (s + 1):6.0f} " + " ".join(f"{v:12.5f}" for v in vals))
     return "\n".join(lines)
 
@@ -424,13 +459,22 @@ class _Parser(argparse.ArgumentParser):
             if a.event_anomaly is None and a.event_quantile is None:
                 self.error("--event-scales takes neighbourhoods around the events of --event-anomaly / --event-quantile: it needs one of them")
             if a.ensemble is not None:
-                self.error("--event-scales (the fractions skill score) is scored for a single forecast: run it without --ensemble")
+                self.error("--event-scales (the fractions skill score) is scored for a single forecast: run it without --ensemble, or give "
+                           "--ensemble-scales for the ensemble's probabilistic score")
             r = a.event_scales
             if any(y <= x for x, y in zip(r, r[1:])) or r[0] < 0 or r[-1] > 32:
                 self.error("--event-scales: strictly ascending half-widths in grid points, within 0 .. 32")
+        if a.ensemble_scales is not None:
+            if a.event_anomaly is None and a.event_quantile is None:
+                self.error("--ensemble-scales takes neighbourhoods around the events of --event-anomaly / --event-quantile: it needs one of them")
+            r = a.ensemble_scales
+            if any(y <= x for x, y in zip(r, r[1:])) or r[0] < 0 or r[-1] > 32:
+                self.error("--ensemble-scales: strictly ascending half-widths in grid points, within 0 .. 32")
+        if a.ensemble_member_scores and a.ensemble_scales is None:
+            self.error("--ensemble-member-scores adds to --ensemble-scales: it needs it")
         if a.ensemble is None:
             for flag, v in (("--perturbation", a.perturbation), ("--seed", a.seed), ("--member-batch", a.member_batch),
-                            ("--perturbation-scale", a.perturbation_scale)):
+                            ("--perturbation-scale", a.perturbation_scale), ("--ensemble-scales", a.ensemble_scales)):
                 if v is not None:
                     self.error(f"{flag} needs --ensemble")
             return a
@@ -483,6 +527,11 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--event-scales", type=int, nargs="+", default=None, metavar="R", help="with --event-anomaly / --event-quantile: also the "
                     "fractions skill score of those events over boxes of 2 R + 1 grid points (ascending half-widths within 0 .. 32, on the "
                     "--score-grid if given): fss<k>_r<R>_<name> columns, \"fss\" key")
+    ap.add_argument("--ensemble-scales", type=int, nargs="+", default=None, metavar="R", help="with --ensemble and --event-anomaly / "
+                    "--event-quantile: the probabilistic fractions skill score of the members' neighbourhood probabilities over boxes of 2 R + 1 "
+                    "grid points (ascending half-widths within 0 .. 32): pfss<k>_r<R>_<name> columns, \"pfss\" key")
+    ap.add_argument("--ensemble-member-scores", action="store_true", help="with --ensemble-scales: also the mean member's FSS against the "
+                    "analysis and against the control (efss / dfss columns and keys: spatial skill and spread)")
     ap.add_argument("--ensemble", type=int, default=None, metavar="M", help="with --truth: roll out M members from perturbed initial conditions "
                                                                             "(member 0 is the control) and score CRPS, spread and ensemble-mean RMSE "
                                                                             "(crps_/spread_/ens_rmse_<name> columns, \"ensemble\" key)")
@@ -550,7 +599,8 @@ def _score_main(a, model, p, stats, x0, cz, n_invar):
         ens = ensemble_rollout(model, x0, truth_of, a.steps, a.ensemble, a.perturbation, a.seed or 0, cz, n_invar, scorer,
                                member_batch=a.member_batch, n_fields=len(p["in_channels"]), score_control=True,
                                perturbation_kind="white" if a.perturbation_scale is None else "spherical", length_scale_km=a.perturbation_scale,
-                               events=spec)
+                               events=spec, ensemble_neighbourhoods=None if a.ensemble_scales is None else tuple(a.ensemble_scales),
+                               member_neighbourhoods=a.ensemble_member_scores)
         sc = ens.control
     else:
         sc = score_rollout(model, x0, truth_of, a.steps, cz, n_invar, scorer, keep_forecast=bool(a.out), extremes=a.extremes, spectrum=a.spectrum,
@@ -589,6 +639,12 @@ def _score_main(a, model, p, stats, x0, cz, n_invar):
             # pooled over the batch per lead time: fss [steps, C, K, S], fss_uniform and useful_scale (a half-width, or -1) [steps, C, K]
             doc["fss"] = {"scales": list(sc.neighbourhoods.scales),
                           **{k: sc.neighbourhoods.scores[k].cpu().tolist() for k in ("fss", "fss_uniform", "useful_scale")}}
+        if ens is not None and ens.neighbourhoods is not None:
+            # pooled over the batch per lead time: pfss [steps, C, K, S]; efss / dfss likewise with --ensemble-member-scores
+            nb = ens.neighbourhoods
+            doc["pfss"] = {"scales": list(nb.scales), **{k: nb.scores[k].cpu().tolist() for k in ("pfss", "fss_uniform", "useful_scale")}}
+            if nb.member_scores is not None:
+                doc["pfss"].update(efss=nb.member_scores["fss"].cpu().tolist(), dfss=nb.dispersion_scores["fss"].cpu().tolist())
         with open(a.scores_out, "w") as f:
             json.dump(doc, f)
     if a.spectrum_out:

@@ -802,6 +802,41 @@ def fss_rows(prd, tar, thr, scales, ws, base=None, below=False):
     return rows, ninv
 
 
+def fss_ens_band_rows(planes: int, H: int, M: int, K: int, r_max: int) -> int:
+    """rows per band of swv2_fss_ens_rows' box launch (host-only): the plan of swv2_fss_band_rows under 80 KiB of LDS for M members"""
+    return int(L.load().swv2_fss_ens_band_rows(planes, H, M, K, r_max))
+
+
+def fss_ens_workspace(planes: int, H: int, W: int, M: int, K: int, S: int, device) -> torch.Tensor:
+    """the caller's workspace of swv2_fss_ens_rows for `planes` = B * C planes, M members, K thresholds and S scales: allocate once, reuse;
+    never zeroed"""
+    return _plane_workspace("fss_ens_workspace", L.load().swv2_fss_ens_ws_bytes(planes, H, W, M, K, S), torch.int32, device,
+                            f"planes {planes}, H {H}, W {W} must be positive, M = {M} within 2 .. {ENS_MAX_MEMBERS} and K = {K}, S = {S} within "
+                            f"1 .. {FSS_MAX_S}")
+
+
+def fss_ens_rows(ens, tar, thr, scales, ws, base=None, below=False):
+    """the neighbourhood sums of the members ens [M, B, C, H, W] (as ens_sums takes them: channel blocks of wider tensors are read in place)
+    against tar [B, C, H, W] -> (rows [B, C, K, S, H, 3] int64 = (sum_w (N_f - M n_o)^2, sum_w N_f^2, sum_w n_o^2), n_invalid [B, C] int32);
+    thr, scales, base, below: as fss_rows takes them, ws: fss_ens_workspace"""
+    (ep, ems, ebs), (tp, tbs) = _plane_blocks("fss_ens_rows", ens, tar, lead=2)
+    M, B, Cc, H, W = ens.shape
+    _chk(thr, torch.float32, "thresholds")
+    if thr.dim() != 3 or thr.shape[1] != Cc or thr.shape[0] not in (1, B) or not 1 <= thr.shape[2] <= EVENT_MAX_K:
+        raise L.Swv2Error(f"fss_ens_rows: thresholds {tuple(thr.shape)}, expected [1 or {B}, {Cc}, K <= {EVENT_MAX_K}]")
+    if base is not None and (_chk(base, torch.float32, "base field").shape != (Cc, H, W)):
+        raise L.Swv2Error(f"fss_ens_rows: base field {tuple(base.shape)}, expected {(Cc, H, W)}")
+    K, S = thr.shape[2], len(scales)
+    thr_bs = Cc * K if thr.shape[0] == B and B > 1 else 0
+    _chk(ws, torch.int32, "ensemble fss workspace")
+    rows = torch.empty(B, Cc, K, S, H, 3, dtype=torch.int64, device=tar.device)
+    ninv = torch.empty(B, Cc, dtype=torch.int32, device=tar.device)
+    sc = (C.c_int * max(S, 1))(*[int(r) for r in scales])
+    L.check(L.load().swv2_fss_ens_rows(ep, ems, ebs, tp, tbs, _p(base), _p(thr), thr_bs, sc, M, K, S, int(bool(below)), B, Cc, H, W, _p(ws),
+                                       ws.numel() * 4, _p(rows), _p(ninv), _stream()), "swv2_fss_ens_rows")
+    return rows, ninv
+
+
 def quantile_workspace(planes: int, H: int, W: int, K: int, device) -> torch.Tensor:
     """the caller's workspace of swv2_plane_order_stats for `planes` = B * C planes and K ranks: allocate once, reuse; never zeroed"""
     return _plane_workspace("quantile_workspace", L.load().swv2_quantile_ws_bytes(planes, H, W, K), torch.int32, device)

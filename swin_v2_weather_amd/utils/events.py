@@ -241,6 +241,66 @@ def useful_scale(fss, fss_uniform, scales) -> torch.Tensor:
     return torch.where(ok.any(dim=-1), sc[first], torch.full_like(first, -1))
 
 
+# ---- ensemble neighbourhood verification: the probabilistic FSS (Schwartz et al. 2010, Duc et al. 2013) and eFSS / dFSS (Dey et al. 2014) ----
+# include/swv2.h states this for swv2_fss_ens_rows; the same in plain torch.  Event, theta, below, strictness, the fp32 comparison, base
+# field and box are those above.  A point is valid if no member, nor the truth, nor the base is NaN there (+-inf are valid); an invalid point
+# is an event in NO member and not in the analysis, and is counted in n_invalid.  With e_m the event bit of member m and o the analysis':
+#     c = sum_m e_m (0 .. M)     N_f = sum_box c = sum_m n_f^m     n_o = sum_box o
+#     rows[B, C, K, S, H, 3] = (sum_w (N_f - M n_o)^2, sum_w N_f^2, sum_w n_o^2)          int64, exact
+#     q[h] = w[h] / N_h^2     FBS = sum_h q rows[.., 0] / M^2     SF = sum_h q rows[.., 1] / M^2     SO = sum_h q rows[.., 2]
+#     pfss = 1 - FBS / (SF + SO): the FSS of the neighbourhood ensemble probability N_f / (M N_h) against the analysis' fraction n_o / N_h
+# base_rate, fss_uniform and useful_scale as for one forecast.  Boxes are in grid points, M >= 2 (the kernel: 2 .. 64), and ties between
+# members are not randomised: the probability is the plain member fraction.  Beside it the spread-skill pair of Dey et al. (2014), from the
+# DETERMINISTIC rows: member_rows = sum_m rows(member m vs analysis) -> eFSS, the skill of the mean member; dispersion_rows =
+# sum_{m >= 1} rows(member m vs member 0) -> dFSS, the spatial agreement between the members and the control.  eFSS ~ dFSS per scale is the
+# spatial analogue of spread ~ error.
+EnsembleNeighbourhoodScores = namedtuple("EnsembleNeighbourhoodScores", "rows n_invalid scores pooled member_rows dispersion_rows member_scores "
+                                         "dispersion_scores", defaults=(None, None, None, None))
+
+
+def fss_ens_rows_torch(ens, tar, thresholds, scales, base=None, below=False):
+    """ens [M, B, C, H, W], tar [B, C, H, W] (any float dtype; compared in fp32), thresholds, scales, base, below as fss_rows_torch ->
+    (rows [B, C, K, S, H, 3] int64, n_invalid [B, C] int32); the member axis is walked one member at a time, counted in int64: exact"""
+    if ens.dim() != 5 or ens.shape[0] < 2 or tar.shape != ens.shape[1:]:
+        raise ValueError(f"fss_ens_rows_torch: members {tuple(ens.shape)} / truth {tuple(tar.shape)}, expected [M >= 2, B, C, H, W] / [B, C, H, W]")
+    M, B, Cc, H, W = ens.shape
+    sc = check_scales(scales, W)
+    thr = expand_thresholds(thresholds, B, Cc, ens.device)
+    valid = ~torch.isnan(tar)
+    for m in range(M):
+        valid = valid & ~torch.isnan(ens[m])
+    if base is not None:
+        valid = valid & ~torch.isnan(base.to(ens.device)).unsqueeze(0)
+    th = _theta(thr, base, ens)
+    v5 = valid.unsqueeze(2)
+    c = torch.zeros((B, Cc, thr.shape[2], H, W), dtype=torch.int64, device=ens.device)
+    for m in range(M):
+        c += _event(ens[m].to(torch.float32).unsqueeze(2), th, below) & v5
+    O = (_event(tar.to(torch.float32).unsqueeze(2), th, below) & v5).to(torch.int64)
+    rows = []
+    for r in sc:
+        nf, no = _box_count(c, r), _box_count(O, r)
+        rows.append(torch.stack((((nf - M * no) ** 2).sum(dim=-1), (nf * nf).sum(dim=-1), (no * no).sum(dim=-1)), dim=-1))       # [B, C, K, H, 3]
+    return torch.stack(rows, dim=3), (~valid).sum(dim=(-1, -2)).to(torch.int32)
+
+
+def fss_ens_scores(rows, w, scales, W: int, M: int, fields: int = 1) -> dict:
+    """rows [..., S, H, 3] int64 of fss_ens_rows_torch / swv2_fss_ens_rows (summed over the `fields` samples or lead times that are pooled)
+    for M members -> {pfss [..., S], fbs [..., S] (= FBS), fss_uniform [...], base_rate [...]} in fp64: fss_scores with the two forecast
+    sums over M^2"""
+    r = torch.as_tensor(rows)
+    sc = tuple(int(s) for s in scales)
+    if r.dim() < 3 or r.shape[-1] != 3 or r.shape[-3] != len(sc) or sc[0] != 0 or int(M) < 2:
+        raise ValueError(f"fss_ens_scores: rows {tuple(r.shape)} for scales {sc}, M = {M}: expected [..., {len(sc)}, H, 3], scales[0] = 0 and M >= 2")
+    w64 = torch.as_tensor(w).to(device=r.device, dtype=torch.float64).reshape(-1)
+    q = w64 / box_sizes(r.shape[-2], sc).to(device=r.device, dtype=torch.float64) ** 2          # [S, H]
+    fbs, sf, so = ((r[..., j].to(torch.float64) * q).sum(dim=-1) for j in range(3))            # the dot products over H
+    m2 = float(int(M) * int(M))
+    fbs, sf = fbs / m2, sf / m2
+    base_rate = so[..., 0] / (w64.sum() * float(W) * float(fields))
+    return dict(pfss=1.0 - fbs / (sf + so), fbs=fbs, fss_uniform=0.5 + 0.5 * base_rate, base_rate=base_rate)
+
+
 def quantile_thresholds(truth, q) -> torch.Tensor:
     """truth [B, C, H, W], levels q [K] in [0, 1] -> [B, C, K] fp32: the analysis' own spatial quantiles per plane (plane_quantiles)"""
     from .weighted_acc_rmse import plane_quantiles

@@ -257,6 +257,7 @@ PowerSpectrum = namedtuple("PowerSpectrum", "pred truth")
 from .events import (EVENT_MAX_K, EnsembleEventScores, EventScores, EventSpec, brier_scores, contingency_scores,  # noqa: E402,F401
                      ensemble_event_sums_torch, event_table_torch, expand_thresholds, quantile_thresholds, reliability_scores)
 from .events import (FSS_MAX_S, NeighbourhoodScores, box_sizes, check_scales, fss_rows_torch, fss_scores, useful_scale)  # noqa: E402,F401
+from .events import EnsembleNeighbourhoodScores, fss_ens_rows_torch, fss_ens_scores  # noqa: E402,F401
 
 
 def small_scale_power_ratio(pred: torch.Tensor, truth: torch.Tensor) -> torch.Tensor:
@@ -436,6 +437,77 @@ class ForecastScorer:
             table, ninv = event_table_torch(p, t, thr, self.w, None if base is None else base.to(p.device), below)
         return EventScores(table, ninv, contingency_scores(table), contingency_scores(table.to(torch.float64).sum(dim=0)))
 
+    def _chunked_rows(self, thr, sc, key, make, call):
+        """rows [B, C, K, S, H, 3] of one of the two neighbourhood kernels, run per 8 scales and 8 thresholds: make(planes, H, W, S, K,
+        device) -> the workspace of a call shape (kept under key + (S, K)), call(thresholds, scales, workspace) -> (rows, n_invalid)"""
+        per_s = []
+        for s0 in range(0, len(sc), FSS_MAX_S):
+            sk = sc[s0:s0 + FSS_MAX_S]
+            per_k = []
+            for tk, K, ws in self._threshold_chunks(thr, key + (len(sk),), make, self.H, self.W, len(sk)):
+                r, ninv = call(tk, sk, ws)
+                per_k.append(r)
+            per_s.append(per_k[0] if len(per_k) == 1 else torch.cat(per_k, dim=2))
+        return (per_s[0] if len(per_s) == 1 else torch.cat(per_s, dim=3)), ninv
+
+    def _fss_rows(self, p, t, thr, sc, base, below):
+        """(rows, n_invalid) of one forecast block p against t for every scale of sc: swv2_fss_rows on CUDA fp32, fss_rows_torch elsewhere"""
+        if _on_kernels(p, t) and p.device == self.device:
+            from .. import ops
+            planes = p.shape[0] * self.C
+            return self._chunked_rows(thr, sc, ("fss", p.shape[0]), lambda H, W, S, K, device: ops.fss_workspace(planes, H, W, K, S, device),
+                                      lambda tk, sk, ws: ops.fss_rows(p, t, tk, sk, ws, base, below))
+        return fss_rows_torch(p, t, thr, sc, None if base is None else base.to(p.device), below)
+
+    def ensemble_neighbourhood_score(self, ens, tar, n_members, thresholds, scales, anomaly=False, base=None, below=False, coff_ens=0,
+                                     coff_tar=0, members=False) -> EnsembleNeighbourhoodScores:
+        """The probabilistic fractions skill score of n_members forecasts (ens as ensemble_score takes it, read in place): the neighbourhood
+        ensemble probability -- the box mean of the member fraction c / M -- against the analysis' fraction, for the events of
+        ensemble_event_score and the scales of neighbourhood_score -> EnsembleNeighbourhoodScores(rows [B, C, K, S, H, 3] int64 =
+        (sum_w (N_f - M n_o)^2, sum_w N_f^2, sum_w n_o^2), n_invalid [B, C] int32: the points with a NaN in any member, the truth or the
+        base, which are events nowhere; scores: fss_ens_scores per sample (pfss, fbs [B, C, K, S], fss_uniform, base_rate [B, C, K]) plus
+        useful_scale; pooled: the same from the rows summed over the batch).  Scale 0 is always computed and stays out of what is
+        reported where `scales` does not name it.  members=True adds, from swv2_fss_rows / fss_rows_torch (one forecast against one field):
+        member_rows = sum_m rows(member m vs analysis), dispersion_rows = sum_{m >= 1} rows(member m vs member 0), and member_scores /
+        dispersion_scores: their pooled fss_scores (fss = eFSS / dFSS of Dey et al. 2014) with useful_scale.  swv2_fss_ens_rows per 8
+        thresholds and 8 scales on CUDA fp32, fss_ens_rows_torch elsewhere.  Boxes count grid points; ties between members are not
+        randomised."""
+        e, t = _member_blocks("ensemble_neighbourhood_score", self.C, self.H, self.W, ens, tar, n_members, coff_ens, coff_tar)
+        base = self._event_base("ensemble_neighbourhood_score", anomaly, base)
+        asked = check_scales(scales, self.W)
+        sc = asked if asked[0] == 0 else (0,) + asked
+        M, B = e.shape[:2]
+        thr = expand_thresholds(thresholds, B, self.C, t.device)
+        if _ensemble_on_kernels(e, t, self.device):
+            from .. import ops
+            rows, ninv = self._chunked_rows(thr, sc, ("fss_ens", M, B),
+                                            lambda H, W, S, K, device: ops.fss_ens_workspace(B * self.C, H, W, M, K, S, device),
+                                            lambda tk, sk, ws: ops.fss_ens_rows(e, t, tk, sk, ws, base, below))
+        else:
+            rows, ninv = fss_ens_rows_torch(e, t, thr, sc, None if base is None else base.to(t.device), below)
+
+        def cut(r):
+            return r if sc is asked else r[:, :, :, 1:]
+
+        def scores(r, fields, m=None):
+            s = fss_scores(r, self.w, sc, self.W, fields) if m is None else fss_ens_scores(r, self.w, sc, self.W, m, fields)
+            name = "fss" if m is None else "pfss"
+            if sc is not asked:
+                s[name], s["fbs"] = s[name][..., 1:], s["fbs"][..., 1:]
+            s["useful_scale"] = useful_scale(s[name], s["fss_uniform"], asked)
+            return s
+        extra = ()
+        if members:
+            mr = dr = None
+            for m in range(M):
+                r = self._fss_rows(e[m], t, thr, sc, base, below)[0]
+                mr = r if mr is None else mr + r
+                if m:
+                    r = self._fss_rows(e[m], e[0], thr, sc, base, below)[0]
+                    dr = r if dr is None else dr + r
+            extra = (cut(mr), cut(dr), scores(mr.sum(dim=0), B * M), scores(dr.sum(dim=0), B * (M - 1)))
+        return EnsembleNeighbourhoodScores(cut(rows), ninv, scores(rows, 1, M), scores(rows.sum(dim=0), B, M), *extra)
+
     def neighbourhood_score(self, prd, tar, thresholds, scales, anomaly=False, base=None, below=False, coff_prd=0,
                             coff_tar=0) -> NeighbourhoodScores:
         """The fractions skill score of the event of event_score (same blocks, thresholds, base field and direction) over boxes of
@@ -451,22 +523,7 @@ class ForecastScorer:
         sc = asked if asked[0] == 0 else (0,) + asked
         B = p.shape[0]
         thr = expand_thresholds(thresholds, B, self.C, p.device)
-        if _on_kernels(p, t) and p.device == self.device:
-            from .. import ops
-            per_s = []
-
-            def make(planes, H, W, S, K, device):             # (_threshold_chunks appends K and the device)
-                return ops.fss_workspace(planes, H, W, K, S, device)
-            for s0 in range(0, len(sc), FSS_MAX_S):
-                sk = sc[s0:s0 + FSS_MAX_S]
-                per_k = []
-                for tk, K, ws in self._threshold_chunks(thr, ("fss", B, len(sk)), make, B * self.C, self.H, self.W, len(sk)):
-                    r, ninv = ops.fss_rows(p, t, tk, sk, ws, base, below)
-                    per_k.append(r)
-                per_s.append(per_k[0] if len(per_k) == 1 else torch.cat(per_k, dim=2))
-            rows = per_s[0] if len(per_s) == 1 else torch.cat(per_s, dim=3)
-        else:
-            rows, ninv = fss_rows_torch(p, t, thr, sc, None if base is None else base.to(p.device), below)
+        rows, ninv = self._fss_rows(p, t, thr, sc, base, below)
 
         def scores(r, fields=1):
             s = fss_scores(r, self.w, sc, self.W, fields)
@@ -620,6 +677,13 @@ class RegriddedScorer:
         """ForecastScorer.ensemble_event_score on the coarse grid; as event_score, the fields are regridded, not the events"""
         return self.inner.ensemble_event_score(*self._members("ensemble_event_score", ens, tar, n_members, coff_ens, coff_tar), thresholds,
                                                anomaly=anomaly, base=base, below=below)
+
+    def ensemble_neighbourhood_score(self, ens, tar, n_members, thresholds, scales, anomaly=False, base=None, below=False, coff_ens=0,
+                                     coff_tar=0, members=False) -> EnsembleNeighbourhoodScores:
+        """ForecastScorer.ensemble_neighbourhood_score on the coarse grid: regrid first, then take the neighbourhoods there (the scales
+        count grid points of the COARSE grid)"""
+        return self.inner.ensemble_neighbourhood_score(*self._members("ensemble_neighbourhood_score", ens, tar, n_members, coff_ens, coff_tar),
+                                                       thresholds, scales, anomaly=anomaly, base=base, below=below, members=members)
 
     def power_spectrum(self, *args, **kwargs):
         raise ValueError("RegriddedScorer: degree spectra are taken on the model's own grid; use a ForecastScorer for power_spectrum")
