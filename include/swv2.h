@@ -776,6 +776,25 @@ int swv2_sht_repack(const float* src, float* dst, int planes, int nlat, int mmax
 int swv2_sht_synth(const float* table, const float* rweights, const float* coeffs, const float* response, int response_stride, float scale_m0,
                    float scale_m, float* S, int planes, int nlat, int lmax, int mmax, int nlon, void* stream);
 
+/* Cross spectra of plane pairs (csrc/sht.hip; utils/sht.py: cross_power; purely additive, the revision stays 113).  The operand holds
+ * planes = 2 pairs planes in the order a_0, b_0, a_1, b_1, ... (what swv2_sht_repack leaves for fields stacked [pairs][2][nlat][nlon]), so
+ * column 4 p + {0, 1, 2, 3} of X[m] is {re a_p, im a_p, re b_p, im b_p}.
+ *   spectra  [3][pairs][lmax]   P_aa[p][l] = sum_m w_m |c_a|^2,  P_bb likewise,  C_ab[p][l] = sum_m w_m (re_a re_b + im_a im_b)
+ *   gspectra [3][pairs][lmax]   the gradients g_aa, g_bb, g_ab with respect to them
+ * swv2_sht_cross_power is swv2_sht_power on the 2 pairs planes with the cross term formed beside the auto terms in the same epilogue: P_aa
+ * and P_bb carry the bits swv2_sht_power gives for planes 2 p and 2 p + 1, the coefficients (or NULL) are the same, the partials and the
+ * ascending fold work the same way (no atomics, two runs agree bit for bit).
+ * swv2_sht_cross_adjoint: dX[m][n][k] = sum_{l >= m} table[m][l][k] ((2 w_m g_self[p][l]) c[m][n][l] + (w_m g_ab[p][l]) c[m][n ^ 2][l]),
+ * p = n / 4, g_self = g_aa for n % 4 < 2, else g_bb; per operand element the scales are exact, the partner's product is rounded once and
+ * one fma joins the two.  Every element of dX is written (zeros for m >= lmax); coefficients with l < m are never read.
+ * Refused with SWV2_ERR_INVALID before any launch: a null pointer (coeffs of the forward excepted), pairs outside 1 .. 32767, the shape
+ * limits of swv2_sht_power for 2 pairs planes, a workspace smaller than swv2_sht_cross_ws_bytes (host-only; 0 for a non-positive argument). */
+size_t swv2_sht_cross_ws_bytes(int pairs, int lmax, int mmax);   /* ceil(min(mmax, lmax) / 8) * 3 * pairs * lmax * 4 */
+int swv2_sht_cross_power(const float* table, const float* X, float* spectra, float* coeffs, int pairs, int nlat, int lmax, int mmax, void* ws,
+                         size_t ws_bytes, void* stream);
+int swv2_sht_cross_adjoint(const float* table, const float* coeffs, const float* gspectra, float* dX, int pairs, int nlat, int lmax, int mmax,
+                           void* stream);
+
 /* First-order conservative regridding to a coarser lat-lon grid (csrc/regrid.hip; utils/regrid.py states the operator and builds the
  * tables; purely additive, the revision stays 113).  All tensors fp32, the tables int32 / fp32, all on the device.
  *   x  C planes of [H][W] per sample, sample b at x + b * x_bstride (elements): a channel block of a wider tensor is read where it lies

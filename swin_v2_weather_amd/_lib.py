@@ -303,6 +303,9 @@ SYMBOLS = {
     "swv2_sht_ws_bytes": (C.c_size_t, [_I, _I, _I]),
     "swv2_sht_power": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P, C.c_size_t, _P]),
     "swv2_sht_adjoint": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P]),
+    "swv2_sht_cross_ws_bytes": (C.c_size_t, [_I, _I, _I]),
+    "swv2_sht_cross_power": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P, C.c_size_t, _P]),
+    "swv2_sht_cross_adjoint": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P]),
     "swv2_sht_repack": (_I, [_P, _P, _I, _I, _I, _F, _I, _P]),
     "swv2_sht_synth": (_I, [_P, _P, _P, _P, _I, _F, _F, _P, _I, _I, _I, _I, _I, _P]),
     "swv2_regrid": (_I, [_P, _L, _P, _L] + [_I] * 6 + [_P, _P, _P, _I, _P, _P, _P, _I, _P]),

@@ -7,6 +7,9 @@
 //   backward  sht_adjoint_kernel   dX[m][n][k] = sum_{l >= m} T[m][l][k] (2 w_m g[plane][l]) c[m][n][l]
 //   inverse   sht_synth_kernel     S[m][n][k] = (1 / w_k) sum_{l >= m} T[m][l][k] (f_m h[plane][l]) c[m][n][l]: the adjoint's product with
 //                                  another operand scale and the row weight taken out again in the epilogue (utils/sht.py: filter, noise)
+//   pairs     sht_power_kernel<true>   the forward on planes interleaved as pairs (a_p, b_p): besides the two auto spectra the cross
+//                                  spectrum  partial[run][2 pairs + p][l] = sum_{m in run} w_m (re_a re_b + im_a im_b)  (utils/sht.py: cross_power)
+//             sht_cross_adjoint_kernel   dX[m][n][k] = sum_{l >= m} T[m][l][k] ((2 w_m g_self[p][l]) c[m][n][l] + (w_m g_ab[p][l]) c[m][n ^ 2][l])
 //   both      sht_repack_kernel    rfft's layout [plane][k][m][re, im] <-> the operand layout [m][n][k], times 2 pi
 //
 // Layouts.  T [mmax][lmax][nlat] dense (entries l < m are zero and never read); X and dX [mmax][2 planes][nlat]; the coefficients
@@ -63,6 +66,23 @@ struct SynthScale {
     __device__ __forceinline__ float operator()(float v, int n, int l) const {
         const float s = H ? f * h[(size_t)(n >> 1) * hs + l] : f;          // (loaded under the caller's predicate only: the select comes last)
         return real && (n & 1) ? 0.f : s * v;
+    }
+};
+
+// the cross adjoint's A operand.  Column n = 4 p + (0: re a, 1: im a, 2: re b, 3: im b) of pair p has its partner (the same part of the
+// other plane) at n ^ 2, and  d/dc[n] of  g_aa P_aa + g_bb P_bb + g_ab C_ab  is  2 w_m g_self c[n] + w_m g_ab c[n ^ 2],  g_self = g_aa for the
+// a columns (n & 2 == 0), g_bb for the b columns.  Roundings, in this order: s = w2 g_self and t = w1 g_ab are exact (w2 = 2 w_m and
+// w1 = w_m are powers of two); t c[n ^ 2] is rounded once; fmaf(s, c[n], that) once.  The partner is read here, under the caller's predicate
+// (n < N implies n ^ 2 < N because N is a multiple of 4; l is in [m, lmax), the rows that were written).
+struct CrossScale {
+    const float* g;          // [3][pairs][lmax]: g_aa, g_bb, g_ab
+    const float* cm;         // this m's coefficients [4 pairs][lmax]
+    int lmax, pairs;
+    float w2, w1;
+    __device__ __forceinline__ float operator()(float v, int n, int l) const {
+        const int p = n >> 2;
+        const float s = w2 * g[((size_t)((n >> 1) & 1) * pairs + p) * lmax + l], t = w1 * g[((size_t)2 * pairs + p) * lmax + l];
+        return fmaf(s, v, t * cm[(size_t)(n ^ 2) * lmax + l]);
     }
 };
 
@@ -137,7 +157,11 @@ __device__ __forceinline__ void tile_product(f32x16 (&acc)[2], const bool (&use)
     }
 }
 
-// grid (l tiles of 128, n tiles of 64, runs of SHT_MRUN m)
+// grid (l tiles of 128, n tiles of 64, runs of SHT_MRUN m).  CROSS: the planes are pairs (a_p, b_p) = planes (2 p, 2 p + 1); an accumulator's
+// registers 4 g .. 4 g + 3 of a lane are re a, im a, re b, im b of one pair at one (m, l), so the cross term needs no lane movement.  The auto
+// terms are formed exactly as without CROSS (the same bits as the plain forward on the same planes); the partials then lie as
+// ws[run][3 pairs][lmax]: rows p of P_aa, pairs + p of P_bb, 2 pairs + p of C_ab -- sht_fold_kernel with 3 pairs "planes" leaves [3][pairs][lmax].
+template <bool CROSS>
 __global__ __launch_bounds__(256, 2) void sht_power_kernel(const float* __restrict__ T, const float* __restrict__ X, float* __restrict__ ws,
                                                         float* __restrict__ coef, int planes, int nlat, int lmax, int mmax) {
     __shared__ float As[SHT_RT * SHT_PA], Bs[SHT_RT * SHT_PB];
@@ -146,11 +170,14 @@ __global__ __launch_bounds__(256, 2) void sht_power_kernel(const float* __restri
     if (m0 >= m_end) return;                                                           // (uniform) nothing of this run reaches these rows
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int lw = l0 + (wave >> 1) * 64, nw = n0 + (wave & 1) * 32 + 4 * (lane >> 5);
-    float pw[2][8];
+    float pw[2][8], cx[2][CROSS ? 4 : 1];
 #pragma unroll
-    for (int j = 0; j < 2; ++j)
+    for (int j = 0; j < 2; ++j) {
 #pragma unroll
         for (int q = 0; q < 8; ++q) pw[j][q] = 0.f;
+#pragma unroll
+        for (int q = 0; q < (CROSS ? 4 : 1); ++q) cx[j][q] = 0.f;
+    }
     for (int m = m0; m < m_end; ++m) {
         f32x16 acc[2];
         bool use[2];
@@ -172,6 +199,11 @@ __global__ __launch_bounds__(256, 2) void sht_power_kernel(const float* __restri
                 const float re = acc[j][2 * q], im = acc[j][2 * q + 1];
                 pw[j][q] = fmaf(wm, fmaf(im, im, re * re), pw[j][q]);
             }
+            if (CROSS) {
+#pragma unroll
+                for (int q = 0; q < 4; ++q)
+                    cx[j][q] = fmaf(wm, fmaf(acc[j][4 * q + 1], acc[j][4 * q + 3], acc[j][4 * q] * acc[j][4 * q + 2]), cx[j][q]);
+            }
             if (coef && l >= m && l < lmax) {
 #pragma unroll
                 for (int q = 0; q < 16; ++q) {
@@ -188,7 +220,16 @@ __global__ __launch_bounds__(256, 2) void sht_power_kernel(const float* __restri
 #pragma unroll
         for (int q = 0; q < 8; ++q) {
             const int n = nw + 2 * (q & 1) + 8 * (q >> 1);                             // the even (re) row of the pair
-            if (n < N) ws[((size_t)blockIdx.z * planes + (n >> 1)) * lmax + l] = pw[j][q];
+            if (!CROSS) {
+                if (n < N) ws[((size_t)blockIdx.z * planes + (n >> 1)) * lmax + l] = pw[j][q];
+            } else if (n < N) ws[((size_t)blockIdx.z * 3 * (planes >> 1) + (size_t)(q & 1) * (planes >> 1) + (n >> 2)) * lmax + l] = pw[j][q];      // q & 1: a or b
+        }
+        if (CROSS) {
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int n = nw + 8 * q;
+                if (n < N) ws[((size_t)blockIdx.z * 3 * (planes >> 1) + (size_t)2 * (planes >> 1) + (n >> 2)) * lmax + l] = cx[j][q];
+            }
         }
     }
 }
@@ -238,6 +279,14 @@ __global__ __launch_bounds__(256, 2) void sht_adjoint_kernel(const float* __rest
                                                           float* __restrict__ dX, int planes, int nlat, int lmax) {
     __shared__ float As[SHT_RT * SHT_PA], Bs[SHT_RT * SHT_PB];
     back_tile<false>(T, coef, GradScale{g, lmax, blockIdx.z == 0 ? 2.f : 4.f}, nullptr, dX, planes, nlat, lmax, As, Bs);
+}
+
+__global__ __launch_bounds__(256, 2) void sht_cross_adjoint_kernel(const float* __restrict__ T, const float* __restrict__ coef,
+                                                                const float* __restrict__ g, float* __restrict__ dX, int pairs, int nlat, int lmax) {
+    __shared__ float As[SHT_RT * SHT_PA], Bs[SHT_RT * SHT_PB];
+    const bool m0 = blockIdx.z == 0;
+    back_tile<false>(T, coef, CrossScale{g, coef + (size_t)blockIdx.z * 4 * pairs * lmax, lmax, pairs, m0 ? 2.f : 4.f, m0 ? 1.f : 2.f}, nullptr, dX,
+                     2 * pairs, nlat, lmax, As, Bs);
 }
 
 // S[m][n][k] = rw[k] sum_{l >= m} T[m][l][k] (f_m h[plane][l]) c[m][n][l]; the imaginary rows of m = 0 and of m = m_nyq (nlon / 2 for an even
@@ -312,12 +361,44 @@ extern "C" int swv2_sht_power(const float* table, const float* X, float* power, 
     SWV2_CHECK_ARG(cdiv(2L * planes, SHT_TN) <= 65535, "sht_power: too many planes for one launch");
     SWV2_CHECK_ARG(ws_bytes >= swv2_sht_ws_bytes(planes, lmax, mmax), "sht_power: workspace too small (swv2_sht_ws_bytes)");
     const int mtop = mmax < lmax ? mmax : lmax;
-    hipLaunchKernelGGL(sht_power_kernel, dim3(cdiv(lmax, SHT_TO), cdiv(2L * planes, SHT_TN), cdiv(mtop, SHT_MRUN)), dim3(256), 0, (hipStream_t)stream,
+    hipLaunchKernelGGL(sht_power_kernel<false>, dim3(cdiv(lmax, SHT_TO), cdiv(2L * planes, SHT_TN), cdiv(mtop, SHT_MRUN)), dim3(256), 0, (hipStream_t)stream,
                        table, X, (float*)ws, coeffs, planes, nlat, lmax, mmax);
     SWV2_CHECK_LAUNCH("swv2_sht_power");
     hipLaunchKernelGGL(sht_fold_kernel, dim3(cdiv((long)planes * lmax, 256)), dim3(256), 0, (hipStream_t)stream, (const float*)ws, power, planes,
                        lmax, mtop);
     SWV2_CHECK_LAUNCH("swv2_sht_power (fold)");
+    return SWV2_OK;
+}
+
+extern "C" size_t swv2_sht_cross_ws_bytes(int pairs, int lmax, int mmax) {
+    if (pairs <= 0 || lmax <= 0 || mmax <= 0) return 0;
+    return (size_t)cdiv(mmax < lmax ? mmax : lmax, SHT_MRUN) * 3 * pairs * lmax * sizeof(float);
+}
+
+extern "C" int swv2_sht_cross_power(const float* table, const float* X, float* spectra, float* coeffs, int pairs, int nlat, int lmax, int mmax,
+                                    void* ws, size_t ws_bytes, void* stream) {
+    SWV2_CHECK_ARG(table && X && spectra && ws, "sht_cross_power: null pointer");
+    SWV2_CHECK_ARG(pairs > 0 && pairs <= 32767, "sht_cross_power: pairs outside 1 .. 32767");
+    SWV2_CHECK_ARG(sht_shape_ok(2 * pairs, nlat, lmax, mmax), "sht_cross_power: bad shape (nlat, lmax, mmax > 0; nlat, lmax <= 2^15, mmax < 2^16; one m's slice < 2^31 elements)");
+    SWV2_CHECK_ARG(ws_bytes >= swv2_sht_cross_ws_bytes(pairs, lmax, mmax), "sht_cross_power: workspace too small (swv2_sht_cross_ws_bytes)");
+    const int mtop = mmax < lmax ? mmax : lmax;
+    hipLaunchKernelGGL(sht_power_kernel<true>, dim3(cdiv(lmax, SHT_TO), cdiv(4L * pairs, SHT_TN), cdiv(mtop, SHT_MRUN)), dim3(256), 0, (hipStream_t)stream,
+                       table, X, (float*)ws, coeffs, 2 * pairs, nlat, lmax, mmax);
+    SWV2_CHECK_LAUNCH("swv2_sht_cross_power");
+    hipLaunchKernelGGL(sht_fold_kernel, dim3(cdiv(3L * pairs * lmax, 256)), dim3(256), 0, (hipStream_t)stream, (const float*)ws, spectra, 3 * pairs,
+                       lmax, mtop);
+    SWV2_CHECK_LAUNCH("swv2_sht_cross_power (fold)");
+    return SWV2_OK;
+}
+
+extern "C" int swv2_sht_cross_adjoint(const float* table, const float* coeffs, const float* gspectra, float* dX, int pairs, int nlat, int lmax, int mmax,
+                                      void* stream) {
+    SWV2_CHECK_ARG(table && coeffs && gspectra && dX, "sht_cross_adjoint: null pointer");
+    SWV2_CHECK_ARG(pairs > 0 && pairs <= 32767, "sht_cross_adjoint: pairs outside 1 .. 32767");
+    SWV2_CHECK_ARG(sht_shape_ok(2 * pairs, nlat, lmax, mmax), "sht_cross_adjoint: bad shape (nlat, lmax, mmax > 0; nlat, lmax <= 2^15, mmax < 2^16; one m's slice < 2^31 elements)");
+    hipLaunchKernelGGL(sht_cross_adjoint_kernel, dim3(cdiv(nlat, SHT_TO), cdiv(4L * pairs, SHT_TN), mmax), dim3(256), 0, (hipStream_t)stream, table, coeffs,
+                       gspectra, dX, pairs, nlat, lmax);
+    SWV2_CHECK_LAUNCH("swv2_sht_cross_adjoint");
     return SWV2_OK;
 }
 

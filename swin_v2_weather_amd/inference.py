@@ -23,7 +23,7 @@ ensemble-mean RMSE and the rank histogram per channel and lead time, one pass ov
     python -m swin_v2_weather_amd.inference --registry DIR --steps 8 [--init x0.npy] [--out forecast.npy]
                                             [--truth truth.npy [--climatology time_means.npy] [--scores-out scores.json] [--extremes]
                                              [--score-grid DEG]
-                                             [--spectrum] [--spectrum-out spectrum.npz]
+                                             [--spectrum] [--spectrum-out spectrum.npz] [--coherence]
                                              [--event-anomaly S [S ...] | --event-quantile Q [Q ...]] [--event-below] [--event-scales R [R ...]]
                                              [--ensemble M --perturbation A [--seed S] [--member-batch K] [--perturbation-scale KM]
                                               [--ensemble-scales R [R ...] [--ensemble-member-scores]]]]
@@ -42,6 +42,7 @@ import torch
 from .networks.helpers import get_model
 from .utils.YParams import load_yaml
 from .utils.regrid import Regridder, grid_for_degrees, model_grid
+from .utils.sht import coherence_scale
 from .utils.weighted_acc_rmse import (EventSpec, ForecastScorer, RegriddedScorer, load_climatology, small_scale_power_ratio,  # noqa: F401
                                       spread_skill_ratio)
 
@@ -136,6 +137,10 @@ def rollout(model, x0: torch.Tensor, n_steps: int, coszen: torch.Tensor | None =
 
 # degree power of forecast and analysis per lead time (batch means [n_steps, Cout, lmax]) and small_scale_power_ratio [n_steps, B, Cout]
 RolloutSpectrum = namedtuple("RolloutSpectrum", "pred truth ratio")
+# spectral coherence of forecast against analysis per lead time: the batch mean [n_steps, Cout, lmax] (fp64; NaN where a power is zero), the
+# effective resolution coherence_scale(., level) per sample [n_steps, B, Cout] (int64) and the level it was taken at
+RolloutCoherence = namedtuple("RolloutCoherence", "coherence scale level")
+COHERENCE_LEVEL = 0.5
 # events=EventSpec(kind, levels, below) of score_rollout: per lead time the thresholds used ([K] for "anomaly", [B, C, K] for "quantile"), the
 # tables [n_steps, B, C, K, 4], n_invalid [n_steps, B, C] and `scores`: name -> [n_steps, C, K] fp64, from the tables summed over the batch
 RolloutEvents = namedtuple("RolloutEvents", "spec thresholds table n_invalid scores")
@@ -163,8 +168,10 @@ class RolloutScores(namedtuple("RolloutScores", "rmse acc rmse_samples acc_sampl
     """score_rollout's answer.  The tuple keeps its six fields (callers unpack and build it positionally); `spectrum` rides along as an
     attribute: None, or the RolloutSpectrum of score_rollout(..., spectrum=True); so does `events`: None, or the RolloutEvents of
     score_rollout(..., events=spec), and `neighbourhoods`: None, or the RolloutNeighbourhoods of score_rollout(..., events=spec,
-    neighbourhoods=scales).  (_replace builds a new tuple: carry them over by hand.)"""
+    neighbourhoods=scales), and `coherence`: None, or the RolloutCoherence of score_rollout(..., coherence=True).  (_replace builds a new
+    tuple: carry them over by hand.)"""
     spectrum = None
+    coherence = None
     events = None
     neighbourhoods = None
 
@@ -187,12 +194,14 @@ def _check_events(who, events, scorer, neighbourhoods=None):
 class _StepScores:
     """the per-step results of ONE deterministic forecast: score_rollout's, and the control (member 0) of ensemble_rollout"""
 
-    def __init__(self, scorer, n_steps, B, Cout, H, device, events=None, extremes=False, spectrum=False, neighbourhoods=None):
+    def __init__(self, scorer, n_steps, B, Cout, H, device, events=None, extremes=False, spectrum=False, neighbourhoods=None, coherence=False):
         new = lambda *shape: torch.empty(n_steps, *shape, dtype=torch.float32, device=device)      # noqa: E731
         self.rmse, self.rmse_s = new(Cout), new(B, Cout)
         self.acc, self.acc_s = (new(Cout), new(B, Cout)) if scorer.clim is not None else (None, None)
         self.tqe = new(B, Cout) if extremes else None
         self.spec = RolloutSpectrum(new(Cout, H), new(Cout, H), new(B, Cout)) if spectrum else None
+        self.coh = RolloutCoherence(torch.empty(n_steps, Cout, H, dtype=torch.float64, device=device),
+                                    torch.empty(n_steps, B, Cout, dtype=torch.int64, device=device), COHERENCE_LEVEL) if coherence else None
         self.events, self.ev = events, []
         self.scales, self.nb = (None if neighbourhoods is None else tuple(neighbourhoods)), []
 
@@ -203,6 +212,9 @@ class _StepScores:
         if self.spec is not None:
             ps = scorer.power_spectrum(out, tar, coff_prd=coff)
             self.spec.pred[s], self.spec.truth[s], self.spec.ratio[s] = ps.pred.mean(dim=0), ps.truth.mean(dim=0), small_scale_power_ratio(ps.pred, ps.truth)
+        if self.coh is not None:
+            coh = scorer.spectral_coherence(out, tar, coff_prd=coff)
+            self.coh.coherence[s], self.coh.scale[s] = coh.mean(dim=0), coherence_scale(coh, self.coh.level)
         self.rmse[s], self.rmse_s[s] = r.rmse_mean, r.rmse
         if self.acc is not None:
             self.acc[s], self.acc_s[s] = r.acc_mean, r.acc
@@ -217,6 +229,7 @@ class _StepScores:
 
     def result(self, forecast) -> RolloutScores:
         res = RolloutScores(self.rmse, self.acc, self.rmse_s, self.acc_s, forecast, self.tqe).with_spectrum(self.spec)
+        res.coherence = self.coh
         if self.events is not None:           # the EventScores of every step -> RolloutEvents
             res.events = RolloutEvents(self.events, [t for t, _ in self.ev], torch.stack([e.table for _, e in self.ev], dim=0),
                                        torch.stack([e.n_invalid for _, e in self.ev], dim=0), _stack_scores([e.pooled for _, e in self.ev]))
@@ -229,7 +242,7 @@ class _StepScores:
 @torch.no_grad()
 def score_rollout(model, x0: torch.Tensor, truth, n_steps: int, coszen: torch.Tensor | None = None, n_invar: int = 0,
                   scorer: ForecastScorer | None = None, keep_forecast: bool = False, extremes: bool = False,
-                  spectrum: bool = False, events: EventSpec | None = None, neighbourhoods=None) -> RolloutScores:
+                  spectrum: bool = False, events: EventSpec | None = None, neighbourhoods=None, coherence: bool = False) -> RolloutScores:
     """`rollout` with every step's prediction scored against truth[:, s] as soon as it is written.  truth: [B, n_steps, Cout, H, W]
     (normalised as the model's output) or a callable s -> [B, Cout, H, W].  scorer: a ForecastScorer (default: no climatology, so
     no ACC; normalised units).  Unless keep_forecast, the predictions live in a two-slot ring [B, 2 Cout, H, W]: memory does not grow
@@ -244,17 +257,22 @@ def score_rollout(model, x0: torch.Tensor, truth, n_steps: int, coszen: torch.Te
     scorer.event_thresholds names (offsets from the climatology, or that step's spatial quantiles of the analysis) -> the attribute
     `events`, a RolloutEvents; every other result is what the call without it returns, bit for bit.
     neighbourhoods: with events, half-widths (r, ...) in grid points: every step also goes through scorer.neighbourhood_score with the
-    same thresholds (the fractions skill score per scale) -> the attribute `neighbourhoods`, a RolloutNeighbourhoods."""
+    same thresholds (the fractions skill score per scale) -> the attribute `neighbourhoods`, a RolloutNeighbourhoods.
+    coherence: every step's prediction and truth also go through scorer.spectral_coherence -> the attribute `coherence`, a
+    RolloutCoherence(coherence [n_steps, Cout, lmax = H] fp64: the batch mean of C / sqrt(P_pred P_truth) per degree; scale [n_steps, B, Cout]:
+    utils/sht.py::coherence_scale per sample, the degree down to which the forecast is in the right place; level), else None."""
     net = model.model if hasattr(model, "model") else model
     B, _, H, W = x0.shape
     Cout = net.out_chans
     if scorer is None:
         scorer = ForecastScorer(H, W, Cout, x0.device)
     _check_events("score_rollout", events, scorer, neighbourhoods)
+    if coherence and isinstance(scorer, RegriddedScorer):
+        raise ValueError("score_rollout: coherence=True needs a ForecastScorer (degree spectra are taken on the model's own grid)")
     if spectrum and isinstance(scorer, RegriddedScorer):
         raise ValueError("score_rollout: spectrum=True needs a ForecastScorer (degree spectra are taken on the model's own grid)")
     out, coff_of, forecast = _ring(B, n_steps, Cout, H, W, x0.device, keep_forecast)
-    steps = _StepScores(scorer, n_steps, B, Cout, H, x0.device, events, extremes, spectrum, neighbourhoods)
+    steps = _StepScores(scorer, n_steps, B, Cout, H, x0.device, events, extremes, spectrum, neighbourhoods, coherence)
     for s in _rollout_steps(net, x0, n_steps, coszen, n_invar, out, coff_of):
         tar = _truth_at(truth, s, x0.device)
         steps.add(s, scorer, out, tar, coff_of(s))
@@ -390,15 +408,17 @@ def ensemble_rollout(model, x0: torch.Tensor, truth, n_steps: int, n_members: in
 
 def lead_time_table(scores: RolloutScores, names, hours_per_step: float = 6.0, ensemble: EnsembleRolloutScores | None = None) -> str:
     """one line per lead time: RMSE (and ACC, and the batch-mean top-quantile error and small-scale power ratio when scored) of the named channels;
-    names: [(column title, channel index)].  ensemble: the crps_, spread_ and ens_rmse_ columns of an ensemble_rollout follow.  Scored
+    names: [(column title, channel index)]; lcoh_<name>, the batch-mean coherence scale, follows when the coherence was scored.  ensemble: the crps_, spread_ and ens_rmse_ columns of an ensemble_rollout follow.  Scored
     events add the equitable threat score of every threshold k, ets<k>_<name>, and -- for an ensemble -- its Brier score, bs<k>_<name>;
     scored neighbourhoods add the fractions skill score of every threshold k and scale r, fss<k>_r<r>_<name>, behind them; an ensemble's
     neighbourhoods add pfss<k>_r<r>_<name> and, with member scores, efss... and dfss... columns behind those."""
     rm, ac = scores.rmse.cpu().numpy(), None if scores.acc is None else scores.acc.cpu().numpy()
     tq = None if scores.tqe is None else scores.tqe.mean(dim=1).cpu().numpy()
     sr = None if scores.spectrum is None else scores.spectrum.ratio.mean(dim=1).cpu().numpy()
+    lc = None if scores.coherence is None else scores.coherence.scale.double().mean(dim=1).cpu().numpy()
     cols = [f"rmse_{n}" for n, _ in names] + ([f"acc_{n}" for n, _ in names] if ac is not None else []) + \
-        ([f"tqe_{n}" for n, _ in names] if tq is not None else []) + ([f"ssr_{n}" for n, _ in names] if sr is not None else [])
+        ([f"tqe_{n}" for n, _ in names] if tq is not None else []) + ([f"ssr_{n}" for n, _ in names] if sr is not None else []) + \
+        ([f"lcoh_{n}" for n, _ in names] if lc is not None else [])
     ens = [] if ensemble is None else [(k, getattr(ensemble, k).cpu().numpy()) for k in ("crps", "spread", "ens_rmse")]
     cols += [f"{k}_{n}" for k, _ in ens for n, _ in names]
     if scores.events is not None:
@@ -423,7 +443,7 @@ def lead_time_table(scores: RolloutScores, names, hours_per_step: float = 6.0, e
     for s in range(rm.shape[0]):
         vals = [rm[s, i] for _, i in names] + ([ac[s, i] for _, i in names] if ac is not None else []) + \
             ([tq[s, i] for _, i in names] if tq is not None else []) + ([sr[s, i] for _, i in names] if sr is not None else []) + \
-            [v[s, i] for _, v in ens for _, i in names] + [v[s, i, j] for _, v in evs for j in range(v.shape[2]) for _, i in names]
+            ([lc[s, i] for _, i in names] if lc is not None else []) + [v[s, i] for _, v in ens for _, i in names] + [v[s, i, j] for _, v in evs for j in range(v.shape[2]) for _, i in names]
         if fss is not None:
             vals += [fss[s, i, j, q] for j in range(fss.shape[2]) for q in range(fss.shape[3]) for _, i in names]
         vals += [v[s, i, j, q] for _, v in nbs for j in range(v.shape[2]) for q in range(v.shape[3]) for _, i in names]
@@ -438,6 +458,10 @@ class _Parser(argparse.ArgumentParser):
         a = super().parse_args(args, namespace)
         if a.spectrum_out and not a.spectrum:
             self.error("--spectrum-out needs --spectrum")
+        if a.coherence and not a.truth:
+            self.error("--coherence relates the forecast to the verifying analysis degree by degree: it needs --truth")
+        if a.coherence and a.score_grid is not None:
+            self.error("--score-grid scores on a coarser grid; --coherence is taken on the model's own grid: run them separately")
         if a.score_grid is not None:
             if not a.truth:
                 self.error("--score-grid names the grid the scores are taken on: it needs --truth")
@@ -486,6 +510,8 @@ class _Parser(argparse.ArgumentParser):
             self.error("--extremes is scored for a single forecast: run it without --ensemble")
         if a.spectrum:
             self.error("--spectrum is scored for a single forecast: run it without --ensemble")
+        if a.coherence:
+            self.error("--coherence is scored for a single forecast: run it without --ensemble")
         if not 2 <= a.ensemble <= 64:
             self.error("--ensemble: 2 .. 64 members")
         if a.perturbation is None:
@@ -511,6 +537,9 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--extremes", action="store_true", help="with --truth: also score the top-quantile error (tqe_<name> columns, \"tqe\" key)")
     ap.add_argument("--spectrum", action="store_true", help="with --truth: also the spherical-harmonic degree power of forecast and analysis; "
                                                             "ssr_<name> columns (small-scale power ratio), \"ssr\" key")
+    ap.add_argument("--coherence", action="store_true", help="with --truth: also the spectral coherence of forecast and analysis per degree and "
+                                                             "the degree down to which it stays at or above 0.5; lcoh_<name> columns, "
+                                                             "\"coherence\" key; with --spectrum-out a coherence array [steps, Cout, lmax]")
     ap.add_argument("--spectrum-out", default=None, metavar="FILE.npz", help="with --spectrum: write the arrays degree [lmax], pred and truth "
                                                                              "[steps, Cout, lmax] (batch-mean degree power)")
     ap.add_argument("--score-grid", type=float, default=None, metavar="DEG", help="with --truth: regrid forecast and analysis (first-order "
@@ -604,7 +633,7 @@ def _score_main(a, model, p, stats, x0, cz, n_invar):
         sc = ens.control
     else:
         sc = score_rollout(model, x0, truth_of, a.steps, cz, n_invar, scorer, keep_forecast=bool(a.out), extremes=a.extremes, spectrum=a.spectrum,
-                           events=spec, neighbourhoods=None if a.event_scales is None else tuple(a.event_scales))
+                           events=spec, neighbourhoods=None if a.event_scales is None else tuple(a.event_scales), coherence=a.coherence)
     if "track_channels" in p and "channel_names" in p:
         names = [(v, list(p["channel_names"]).index(v)) for v in p["track_channels"]]
     else:
@@ -623,6 +652,9 @@ def _score_main(a, model, p, stats, x0, cz, n_invar):
             doc["tqe"] = sc.tqe.mean(dim=1).cpu().tolist()
         if sc.spectrum is not None:
             doc["ssr"] = sc.spectrum.ratio.mean(dim=1).cpu().tolist()
+        if sc.coherence is not None:
+            # per lead time and channel: the batch mean of the degree down to which forecast and analysis cohere at `level` or better
+            doc["coherence"] = {"lcoh": sc.coherence.scale.double().mean(dim=1).cpu().tolist(), "level": sc.coherence.level}
         if ens is not None:
             doc["ensemble"] = {"members": a.ensemble, "crps": ens.crps.cpu().tolist(), "fair_crps": ens.fair_crps.cpu().tolist(),
                                "spread": ens.spread.cpu().tolist(), "ens_rmse": ens.ens_rmse.cpu().tolist(),
@@ -648,7 +680,8 @@ def _score_main(a, model, p, stats, x0, cz, n_invar):
         with open(a.scores_out, "w") as f:
             json.dump(doc, f)
     if a.spectrum_out:
-        np.savez(a.spectrum_out, degree=np.arange(H), pred=sc.spectrum.pred.cpu().numpy(), truth=sc.spectrum.truth.cpu().numpy())
+        more = {} if sc.coherence is None else {"coherence": sc.coherence.coherence.cpu().numpy()}
+        np.savez(a.spectrum_out, degree=np.arange(H), pred=sc.spectrum.pred.cpu().numpy(), truth=sc.spectrum.truth.cpu().numpy(), **more)
     if a.out:
         np.save(a.out, sc.forecast.cpu().numpy())
 

@@ -641,6 +641,38 @@ def sht_adjoint(table, coef, gpower):
     return dX
 
 
+def sht_cross_power(table, X, keep_coeffs: bool = False):
+    """spectra [3, pairs, lmax] = (P_aa, P_bb, C_ab) of the operand X [mmax, 4 pairs, nlat] whose planes are interleaved as pairs a_0, b_0,
+    a_1, b_1, ... (swv2_sht_cross_power); with keep_coeffs also the coefficients [mmax, 4 pairs, lmax] for sht_cross_adjoint, else None"""
+    _chk(table, torch.float32, "sht table"); _chk(X, torch.float32, "sht operand")
+    if table.dim() != 3 or X.dim() != 3 or X.shape[0] != table.shape[0] or X.shape[2] != table.shape[2] or X.shape[1] % 4:
+        raise L.Swv2Error(f"sht_cross_power: table {tuple(table.shape)} [mmax, lmax, nlat] against operand {tuple(X.shape)} [mmax, 4 pairs, nlat]")
+    mmax, lmax, nlat = table.shape
+    pairs = X.shape[1] // 4
+    lib = L.load()
+    nb = lib.swv2_sht_cross_ws_bytes(pairs, lmax, mmax)
+    ws = _scratch(nb, X.device, "sht_cross_power")
+    spectra = torch.empty(3, pairs, lmax, dtype=torch.float32, device=X.device)
+    coef = torch.empty(mmax, 4 * pairs, lmax, dtype=torch.float32, device=X.device) if keep_coeffs else None
+    L.check(_timed("sht_cross_power", lib.swv2_sht_cross_power, _p(table), _p(X), _p(spectra), _p(coef), pairs, nlat, lmax, mmax, _p(ws), nb,
+                   _stream()), "swv2_sht_cross_power")
+    return spectra, coef
+
+
+def sht_cross_adjoint(table, coef, gspectra):
+    """dX [mmax, 4 pairs, nlat]: the gradient of sht_cross_power's operand from gspectra [3, pairs, lmax] and the kept coefficients"""
+    for t, what in ((table, "sht table"), (coef, "sht coefficients"), (gspectra, "spectra gradient")):
+        _chk(t, torch.float32, what)
+    mmax, lmax, nlat = table.shape
+    pairs = coef.shape[1] // 4
+    if tuple(coef.shape) != (mmax, 4 * pairs, lmax) or tuple(gspectra.shape) != (3, pairs, lmax):
+        raise L.Swv2Error(f"sht_cross_adjoint: table {tuple(table.shape)}, coefficients {tuple(coef.shape)}, gradient {tuple(gspectra.shape)}")
+    dX = torch.empty(mmax, 4 * pairs, nlat, dtype=torch.float32, device=coef.device)
+    L.check(_timed("sht_cross_adjoint", L.load().swv2_sht_cross_adjoint, _p(table), _p(coef), _p(gspectra), _p(dX), pairs, nlat, lmax, mmax,
+                   _stream()), "swv2_sht_cross_adjoint")
+    return dX
+
+
 def sht_synth(table, rweights, coef, response=None, scales=(1.0, 1.0), *, nlon: int):
     """S [mmax, 2 planes, nlat] = rweights[k] sum_{l >= m} table[m, l, k] f_m h[plane, l] coef[m, n, l] (swv2_sht_synth): the synthesis from
     coefficients [mmax, 2 planes, lmax] back to the longitude transform of a field of nlon points per row.  response: None, [lmax] or

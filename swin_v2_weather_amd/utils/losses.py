@@ -17,6 +17,10 @@ Quadrature: the 'naive' rule, or Gauss-Legendre rows (utils/grids.py) when model
 string contains `geometric` (losses.py:102-120), for l1 and l2 alike: the kernels take per-row weights.
 pole-masked (an undefined name in the reference) raises, and so do the geometric h1 strings of LossHandler; the class behind them,
 GeometricH1Loss, is here on its own (utils/sht.py, csrc/sht.hip).
+
+amse: every string with the word amse and neither l2 nor l1 (those two keep their priority, as in the reference's if / elif) is the
+adjusted spectral MSE, GeometricAMSELoss below, per (sample, channel): loss = sum_bc chw[c] value[b, c] with the channel weights, the
+temp-std factor and the multistep weight of the l1 family.  `fused_with` is a no-op for it as for l1.
 """
 import math
 
@@ -96,6 +100,51 @@ class GeometricH1Loss(nn.Module):
 
     def forward(self, prd, tar, mask=None):
         return self.abs(prd, tar) if self.absolute else self.rel(prd, tar, mask)
+
+
+def amse_from_spectra(Px, Py, C, absolute=False):
+    """[..., lmax] degree powers of forecast and target and their cross spectrum -> [...]: the adjusted spectral MSE
+
+        A = sum_l [ (sqrt Px - sqrt Py)^2 + 2 max(Px, Py) (1 - C / sqrt(Px Py)) ]        (a degree with Px Py == 0: Px + Py - 2 C)
+
+    or, relative, A / sum_l Py.  Plain torch in the inputs' dtype; autograd differentiates it (the masked degrees are taken out before
+    the square roots, so no 0 * inf reaches a gradient)."""
+    zero = (Px * Py) == 0
+    one = torch.ones_like(Px)
+    px, py = torch.where(zero, one, Px), torch.where(zero, one, Py)
+    amp = (torch.sqrt(px) - torch.sqrt(py)) ** 2
+    coh = 2 * torch.maximum(px, py) * (1 - C / torch.sqrt(px * py))
+    A = torch.where(zero, Px + Py - 2 * C, amp + coh).sum(dim=-1)
+    return A if absolute else A / Py.sum(dim=-1)
+
+
+class GeometricAMSELoss(nn.Module):
+    """The adjusted spectral MSE on the sphere (Subich et al. 2025, "Fixing the double penalty in data-driven weather forecasting through
+    a modified spherical harmonic loss function"), per (sample, channel) plane: with P_x, P_y [b, c, l] the degree powers of prd and tar
+    and C their cross spectrum (utils/sht.py::cross_power; HIP kernels on fp32 CUDA tensors with contiguous planes),
+
+        A = sum_l [ (sqrt P_x - sqrt P_y)^2 + 2 max(P_x, P_y) (1 - C / sqrt(P_x P_y)) ]   (a degree with P_x P_y == 0: P_x + P_y - 2 C)
+        value[b, c] = A (absolute)   or   A / sum_l P_y[l] (relative)
+
+    The spectral MSE of a degree, P_x + P_y - 2 C, split into an amplitude term and a coherence term, the latter weighted by the larger
+    of the two powers and not by their geometric mean: a forecast is no longer rewarded for losing small-scale power.  forward returns
+    [B, C]; everything after cross_power is torch on [B, C, lmax].
+
+    Written from the paper's formula: the authors' code is not available to this project, so nothing here was compared with it.  The
+    loss is pinned by its identities (tests/test_cross_host.py): AMSE(x, x) = 0; AMSE(x, s x) = (1 - s)^2 sum P_x for s > 0; with max
+    replaced by sqrt(P_x P_y) it is sum degree_power(x - y), the spectral MSE, which it never falls below; and it equals it when P_x = P_y."""
+
+    def __init__(self, img_shape, absolute=False):
+        super().__init__()
+        self.img_shape = tuple(img_shape)
+        self.absolute = absolute
+
+    def forward(self, prd, tar):
+        from .sht import cross_power
+        if tuple(prd.shape[-2:]) != self.img_shape or prd.shape != tar.shape:
+            raise ValueError(f"GeometricAMSELoss for a {self.img_shape} grid got fields of {tuple(prd.shape)} and {tuple(tar.shape)}")
+        Px, Py, C = cross_power(prd, tar)
+        return amse_from_spectra(Px, Py, C, self.absolute)
 
 
 class _GeoL1(torch.autograd.Function):
@@ -289,6 +338,8 @@ class LossHandler(nn.Module):
             self.p = 2
         elif 'l1' in flags:
             self.p = 1
+        elif 'amse' in flags:
+            self.p = None                      # neither quadrature family: the spectral loss below
         else:
             raise ValueError(f"Unknown / unsupported loss function: {self.loss_type} (l2 and l1 families only)")
         if 'weighted' in flags:
@@ -319,6 +370,7 @@ class LossHandler(nn.Module):
         if getattr(params, 'model_grid_type', 'equiangular') == 'legendre_gauss' and 'geometric' in flags:
             rule = legendre_gauss_quadrature_weights
         self.register_buffer('quad_rows', rule(self.img_shape[0], self.img_shape[1], True).contiguous())
+        self.amse = GeometricAMSELoss(self.img_shape, absolute=self.absolute) if self.p is None else None
         self._l1_ws = {}                       # (device, B, C) -> the l1 kernels' workspace of that shape, made once and reused
         self._l2_ws = {}                       # the same for swv2_loss_sums
         ms = torch.ones(self.n_future + 1, dtype=torch.float32) / float(self.n_future + 1)
@@ -336,7 +388,7 @@ class LossHandler(nn.Module):
 
         @contextlib.contextmanager
         def cm():
-            # (l1: the head epilogue evaluates squared residuals -- no hand-over, the two-pass l1 kernels run)
+            # (l1, amse: the head epilogue evaluates squared residuals -- no hand-over, the two-pass l1 kernels / the spectral loss run)
             net = _core_net(model) if (self.p == 2 and self.training and os.environ.get("SWV2_LOSS_IN_HEAD", "1") != "0") else None
             # (rollouts: every step's head takes its channel block of the target; SWV2_LOSS_IN_HEAD_ROLLOUT=0 keeps the two-pass kernels)
             if net is None or (self.n_future != 0 and os.environ.get("SWV2_LOSS_IN_HEAD_ROLLOUT", "1") == "0"):
@@ -380,6 +432,8 @@ class LossHandler(nn.Module):
         lc, self._fused = self._fused, None
         if self.p == 1:
             return self._forward_l1(prd, tar)
+        if self.p is None:
+            return torch.sum(self._chw_now().to(prd.dtype) * self.amse(prd, tar))
         rsums = None
         if lc is not None and lc.steps and lc.tar is tar and self.training and prd.dtype == torch.float32:
             rsums = lc.rollout_sums(prd, prd.shape[1] // (self.n_future + 1))

@@ -18,6 +18,11 @@ csrc/sht.hip: torch's rfft for the longitudes, then one autograd node over swv2_
 operand layout [mmax, 2 planes, nlat], times 2 pi), swv2_sht_power and, in backward, swv2_sht_adjoint and the repack the other way.
 The node's input is the rfft's output, so autograd itself carries the gradient back through the rfft.
 
+Two fields degree by degree: `cross_power(a, b)` returns the degree powers of both and their cross spectrum
+C_ab[l] = sum_m w_m Re(c_a[l, m] conj(c_b[l, m])); `cross_power_torch` is its statement, and fp32 CUDA tensors with contiguous planes take
+swv2_sht_cross_power / swv2_sht_cross_adjoint on the pair stacked plane by plane (one rfft, one autograd node).  `spectral_coherence` is
+C_ab / sqrt(P_aa P_bb), the anomaly correlation of every degree, and `coherence_scale` the degree down to which it holds a level.
+
 The way back, stated the same way (pinned by its definition in fp64, tests/test_isht_host.py; never compared with torch_harmonics):
 
     S[..., k, m]  = sum_{l >= m} Pbar_l^m(cos theta_k) c[..., l, m]              Pbar = table / w_k
@@ -168,6 +173,73 @@ def degree_power(x: torch.Tensor) -> torch.Tensor:
     table = device_table(nlat, nlon, x.device)
     return _DegreePower.apply(longitude_transform(x), table).reshape(x.shape[:-2] + (nlat,))
 
+
+# ---- two fields degree by degree: cross spectrum, coherence -----------------------------------------------------------------------------
+def cross_power_torch(a: torch.Tensor, b: torch.Tensor, table: torch.Tensor):
+    """a, b [..., nlat, nlon] -> (P_aa, P_bb, C_ab), each [..., lmax]: the degree powers of both and the cross spectrum
+    C_ab[l] = Re(c_a[l, 0] conj(c_b[l, 0])) + 2 sum_{m >= 1} Re(c_a[l, m] conj(c_b[l, m])), every m >= 1 doubled as in degree_power_torch"""
+    ca, cb = torch.view_as_real(real_sht_torch(a, table)), torch.view_as_real(real_sht_torch(b, table))
+
+    def summed(t):
+        return t[..., :, 0] + 2 * torch.sum(t[..., :, 1:], dim=-1)
+
+    return (summed(ca[..., 0] ** 2 + ca[..., 1] ** 2), summed(cb[..., 0] ** 2 + cb[..., 1] ** 2),
+            summed(ca[..., 0] * cb[..., 0] + ca[..., 1] * cb[..., 1]))
+
+
+class _CrossPower(torch.autograd.Function):
+    """spectra [3, pairs, lmax] of F = rfft of the pair stacked as [pairs, 2, nlat, nlon], as longitude_transform leaves it (planes a_0,
+    b_0, a_1, ...): swv2_sht_repack (times 2 pi) and swv2_sht_cross_power; backward swv2_sht_cross_adjoint and the repack the other way.
+    Keeps the coefficients only when a gradient can be asked for.  As with _DegreePower autograd itself carries the gradient back
+    through the rfft and the stack, so an input that needs no gradient gets none."""
+
+    @staticmethod
+    def forward(ctx, F, table):
+        from .. import ops
+        planes, nlat, mmax, _ = F.shape
+        keep = F.requires_grad
+        spectra, coef = ops.sht_cross_power(table, ops.sht_repack(F, planes, nlat, mmax, 2.0 * math.pi), keep_coeffs=keep)
+        if keep:
+            ctx.save_for_backward(table, coef)
+        return spectra
+
+    @staticmethod
+    def backward(ctx, g):
+        from .. import ops
+        table, coef = ctx.saved_tensors
+        mmax, lmax, nlat = table.shape
+        dX = ops.sht_cross_adjoint(table, coef, g.contiguous().float())
+        return ops.sht_repack(dX, dX.shape[1] // 2, nlat, mmax, 2.0 * math.pi, backward=True), None
+
+
+def cross_power(a: torch.Tensor, b: torch.Tensor):
+    """a, b [..., nlat, nlon] of one shape -> (P_aa, P_bb, C_ab), each [..., lmax = nlat].  Two fp32 CUDA tensors with contiguous planes on
+    one device (at most 32767 planes each) run on csrc/sht.hip: the pair stacked, one rfft, one autograd node over swv2_sht_cross_power (a
+    failure there raises: nothing falls back); everything else takes cross_power_torch in a's dtype on a's device."""
+    if a.shape != b.shape:
+        raise ValueError(f"cross_power: {tuple(a.shape)} against {tuple(b.shape)}")
+    nlat, nlon = a.shape[-2:]
+    if not (on_kernels(a) and on_kernels(b) and a.device == b.device):
+        return cross_power_torch(a, b.to(device=a.device, dtype=a.dtype), device_table(nlat, nlon, a.device, _float_dtype(a)))
+    table = device_table(nlat, nlon, a.device)
+    pair = torch.stack((a, b), dim=-3)                       # [..., 2, nlat, nlon]: the one copy; views are read where they lie
+    s = _CrossPower.apply(longitude_transform(pair), table)
+    lead = a.shape[:-2] + (nlat,)
+    return s[0].reshape(lead), s[1].reshape(lead), s[2].reshape(lead)
+
+
+def spectral_coherence(P_aa: torch.Tensor, P_bb: torch.Tensor, C_ab: torch.Tensor) -> torch.Tensor:
+    """C_ab / sqrt(P_aa P_bb) in fp64: the anomaly correlation of every degree.  NaN where P_aa P_bb == 0; not clamped (rounding may
+    carry a value past +-1 by an ulp or so, and it is reported as it is)"""
+    den = P_aa.double() * P_bb.double()
+    return torch.where(den == 0, torch.full_like(den, float("nan")), C_ab.double() / torch.sqrt(den))
+
+
+def coherence_scale(coh: torch.Tensor, level: float = 0.5) -> torch.Tensor:
+    """coh [..., lmax] -> int64 [...]: the largest L >= 1 with coh[l] >= level for every 1 <= l <= L (the effective resolution, in
+    degrees of the expansion); 0 when coh[1] already fails.  A NaN counts as failing; degree 0 (the mean) is not looked at."""
+    ok = (coh[..., 1:] >= level).to(torch.int64)             # (NaN >= level is False)
+    return torch.cumprod(ok, dim=-1).sum(dim=-1)
 
 # ---- the way back: synthesis, filter, correlated noise ----------------------------------------------------------------------------------
 EARTH_RADIUS_KM = 6371.0

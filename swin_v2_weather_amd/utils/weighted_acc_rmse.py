@@ -360,6 +360,14 @@ class ForecastScorer:
         p, t = _channel_blocks("power_spectrum", self.C, self.H, self.W, prd, tar, coff_prd, coff_tar)
         return PowerSpectrum(degree_power(p), degree_power(t))
 
+    def spectral_coherence(self, prd, tar, coff_prd=0, coff_tar=0) -> torch.Tensor:
+        """the anomaly correlation of every degree, C / sqrt(P_prd P_tar) (utils/sht.py::cross_power and spectral_coherence: csrc/sht.hip on
+        CUDA fp32), of channels coff_prd .. + C of prd against channels coff_tar .. + C of tar, both read in place -> [B, C, lmax = H] in
+        fp64; NaN where a power is zero, not clamped"""
+        from .sht import cross_power, spectral_coherence
+        p, t = _channel_blocks("spectral_coherence", self.C, self.H, self.W, prd, tar, coff_prd, coff_tar)
+        return spectral_coherence(*cross_power(p, t))
+
     def quantile_error(self, prd, tar, coff_prd=0, coff_tar=0) -> torch.Tensor:
         """top_quantiles_error_torch of channels coff_prd .. + C of prd against channels coff_tar .. + C of tar (read in place) -> [B, C].
         The rank tensor and the workspace (one per B) are made once and reused."""
@@ -687,3 +695,6 @@ class RegriddedScorer:
 
     def power_spectrum(self, *args, **kwargs):
         raise ValueError("RegriddedScorer: degree spectra are taken on the model's own grid; use a ForecastScorer for power_spectrum")
+
+    def spectral_coherence(self, *args, **kwargs):
+        raise ValueError("RegriddedScorer: degree spectra are taken on the model's own grid; use a ForecastScorer for spectral_coherence")

@@ -1,16 +1,23 @@
 #!/usr/bin/env python3
 """Run a few optimisation steps of a named yaml config through the Trainer on one GPU and report ms/step (GPU box).
-   python tools/run_cfg.py bench_geo_depth24_e192_invar [local_batch] [steps]"""
-import os, sys, time, torch
+   python tools/run_cfg.py bench_geo_depth24_e192_invar [local_batch] [steps] [key=value ...]
+key=value overrides an entry of the config, the value read as yaml:
+   python tools/run_cfg.py bench_tiny 2 6 "loss='weighted amse'" channel_weights=auto          # the tiny config on the adjusted spectral MSE
+                                                                                               # ('weighted' needs the weights the base block leaves at 'none')"""
+import os, sys, time, torch, yaml
 from types import SimpleNamespace
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__))); sys.path.insert(0, ROOT)
 from swin_v2_weather_amd.utils.YParams import YParams
 from swin_v2_weather_amd.train import Trainer
 
-cfg = sys.argv[1]
-B = int(sys.argv[2]) if len(sys.argv) > 2 else 2
-steps = int(sys.argv[3]) if len(sys.argv) > 3 else 6
+over = dict(a.split("=", 1) for a in sys.argv[1:] if "=" in a)
+argv = [a for a in sys.argv if "=" not in a]
+cfg = argv[1]
+B = int(argv[2]) if len(argv) > 2 else 2
+steps = int(argv[3]) if len(argv) > 3 else 6
 p = YParams(os.path.join(ROOT, "swin_v2_weather_amd", "config", "swin.yaml"), cfg)
+for k, v in over.items():
+    p[k] = yaml.safe_load(v)
 p["batch_size"], p["max_epochs"] = B, 1
 p["synthetic_device_pool"], p["synthetic_steps_per_epoch"] = 2, steps + 3
 p["exp_dir"], p["save_checkpoint"], p["log_to_screen"], p["log_to_wandb"] = "/tmp/exp_run_cfg", False, False, False
@@ -24,5 +31,7 @@ for i in range(steps + 3):
     losses.append(float(tr.train_step(next(it))))
 torch.cuda.synchronize()
 dt = (time.perf_counter() - t0) / steps
-print(f"{cfg}: local batch {B}, {dt * 1e3:.1f} ms/step, {B / dt:.1f} samples/s, losses {losses[0]:.4f} -> {losses[-1]:.4f}, "
+print(f"{cfg}{''.join(f' {k}={v}' for k, v in over.items())}: local batch {B}, {dt * 1e3:.1f} ms/step, {B / dt:.1f} samples/s, losses {losses[0]:.4f} -> {losses[-1]:.4f}, "
       f"peak mem {torch.cuda.max_memory_allocated() / 2**30:.1f} GiB, params {tr.count_parameters() / 1e6:.1f} M")
+if over:
+    print("losses " + " ".join(f"{v:.5f}" for v in losses))
